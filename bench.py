@@ -85,6 +85,54 @@ def pmc_issue(kernel, samples, reads_per_s):
     return None
 
 
+DUMP_RECORDS_MAX = 1 << 20     # --dump-outputs: per-record arrays cover every read up to this many, a seeded sample beyond
+DUMP_SAMPLE_RECORDS = 2048     # records dumped byte for byte (a seeded sample) ...
+DUMP_SAMPLE_BYTES = 6 << 20    # ... up to this many bytes of them (24 MB as float32): 48 MB in all at most
+
+
+def dump_outputs(out_dir, stream_out, rec_off, n_reads, chunk=1 << 28):
+    """--dump-outputs: what the timed step hands its caller — the contiguous BLOW5 record stream and its index (rec_off, n + 1
+    offsets) — as float .npy files, the same for the same arguments on any build:
+        record_index.npy         read indices the next two files cover (all reads; a seeded sample past DUMP_RECORDS_MAX)  float64
+        record_bytes.npy         length of each of those records, 8-byte size prefix included                              float64
+        record_byte_sums.npy     sum of each of those records' bytes                                                        float64
+        sample_index.npy         read indices of the records dumped whole (a seeded sample)                                 float64
+        sample_record_bytes.npy  those records' bytes, concatenated in index order                                          float32"""
+    import numpy as np
+    import torch
+
+    if stream_out.is_cuda:
+        torch.cuda.synchronize(stream_out.device)
+    off_t = rec_off[: n_reads + 1]
+    off = off_t.cpu().numpy().astype(np.int64)
+    assert off[0] == 0 and (np.diff(off) > 0).all(), "record index is not a contiguous stream"
+    # byte sums from prefix sums at the record boundaries, on the device chunk by chunk (the stream is GBs)
+    pre = torch.zeros(n_reads + 1, dtype=torch.int64, device=off_t.device)
+    carry = 0
+    for c0 in range(0, int(off[-1]), chunk):
+        c1 = min(c0 + chunk, int(off[-1]))
+        cs = torch.cumsum(stream_out[c0:c1], 0, dtype=torch.int64)
+        lo, hi = int(np.searchsorted(off, c0, "right")), int(np.searchsorted(off, c1, "right"))
+        pre[lo:hi] = cs[off_t[lo:hi] - c0 - 1] + carry
+        carry += int(cs[-1].item())
+        del cs
+    lens = np.diff(off)
+    sums = (pre[1:] - pre[:-1]).cpu().numpy()
+    ids = np.arange(n_reads)
+    if n_reads > DUMP_RECORDS_MAX:
+        ids = np.sort(np.random.default_rng(1).choice(n_reads, DUMP_RECORDS_MAX, replace=False))
+    pick = np.sort(np.random.default_rng(2).choice(n_reads, min(n_reads, DUMP_SAMPLE_RECORDS), replace=False))
+    pick = pick[np.cumsum(lens[pick]) <= DUMP_SAMPLE_BYTES]
+    whole = torch.cat([stream_out[off[i]:off[i + 1]] for i in pick]) if len(pick) else stream_out[:0]
+    files = {"record_index": ids.astype(np.float64), "record_bytes": lens[ids].astype(np.float64),
+             "record_byte_sums": sums[ids].astype(np.float64), "sample_index": pick.astype(np.float64),
+             "sample_record_bytes": whole.cpu().numpy().astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {name: list(a.shape) for name, a in files.items()}}
+
+
 def make_events(L, _lib, count):
     evs = []
     for _ in range(count):
@@ -773,7 +821,13 @@ def main():
     ap.add_argument("--min-leg-seconds", type=float, default=1.2, help="every GPU leg keeps the device busy for about this long at least")
     ap.add_argument("--min-leg-steps-svb", type=int, default=300, help="configs[1] leg: steps (2.8 ms each on 1 M reads)")
     ap.add_argument("--min-leg-steps-long", type=int, default=40, help="configs[3] leg: steps (28 ms each on 65536 reads)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (the record stream and "
+                                                          "its index, a seeded sample of the records' bytes) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.long or args.decode):
+        ap.error("--dump-outputs covers the encode step of the default line (not --long / --decode)")
 
     # `python bench.py --gpus N` with no launcher around it (WORLD_SIZE unset): make the N ranks here — the same module the driver
     # uses (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`), this file and these
@@ -920,6 +974,8 @@ def main():
     cmp_ms = [elapsed_ms(L, _lib, evs[3 * k + 1], evs[3 * k + 2]) for k in range(K)]
     for e in evs:
         L.s5gpu_event_destroy(e)
+    # the last timed step's output, before anything else runs on the batch (every form of the step ends in stream_out / rec_off)
+    dumped = dump_outputs(args.dump_outputs, b.stream_out, b.rec_off, n_reads) if args.dump_outputs and rank == 0 else None
 
     default_shape = not (args.svb_only or args.mixed or args.two_pass) and n == 4000
     # the same step again for about a second (not what `value` is computed on: that is the K steps above)
@@ -1061,6 +1117,8 @@ def main():
         "pcie_inclusive": pcie_obj,
         "host_fed": host_fed,
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     # the other legs' headline numbers in ONE small object inside `roofline` (the driver's record keeps roofline / cpu_baseline / config whole and
     # only the NAMES of further top-level keys): every figure below is measured in this run, its full object is the top-level key of the same name
     def pick(d, *path):

@@ -9,6 +9,7 @@
 and the slow5lib-type-free hooks of include/slow5gpu_hooks.h."""
 import ctypes as C
 import os
+import shutil
 import struct
 import subprocess
 import sys
@@ -129,7 +130,9 @@ def test_open_with_checks_the_named_format(L):
 def test_rec_fwrite_binary_and_ascii_reproduce_the_reference_files(L, tmp_path):
     """src/get.c:89 — slow5_get then slow5_rec_fwrite in the output format: BLOW5 bytes equal the golden record, the ASCII line
     equals the golden .slow5 line"""
-    f = L.slow5_open(golden("exp_1_lossless_zlib_svb_v0.2.0.blow5").encode(), b"r")
+    src = tmp_path / "exp_1_lossless_zlib_svb_v0.2.0.blow5"          # a copy: slow5_idx_load writes the missing .idx beside the file
+    shutil.copy(golden(src.name), src)
+    f = L.slow5_open(str(src).encode(), b"r")
     assert L.slow5_idx_load(f) == 0
     rec = C.POINTER(Rec)()
     assert L.slow5_get(b"a649a4ae-c43d-492a-b6a1-a5b8b8076be4", C.byref(rec), f) == 0
