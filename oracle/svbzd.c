@@ -44,14 +44,14 @@ int s5o_svbzd_decode(const uint8_t *in, size_t in_len, int16_t *out, uint64_t *n
     const uint8_t *keys = in + 4;
     const uint8_t *data = keys + nkeys;
     const uint8_t *end = in + in_len;
-    int32_t prev = 0;
+    uint32_t prev = 0;   /* modulo 2^32: code-3 deltas can overflow int32, and only the low 16 bits are kept */
     for (uint32_t i = 0; i < n; i++) {
         unsigned code = (keys[i >> 2] >> (2 * (i & 3))) & 3;
         if ((size_t)(end - data) < code + 1) return -2;
         uint32_t z = 0;
         for (unsigned b = 0; b <= code; b++) z |= (uint32_t)data[b] << (8 * b);
         data += code + 1;
-        int32_t d = (int32_t)(z >> 1) ^ -(int32_t)(z & 1);
+        uint32_t d = (z >> 1) ^ (0u - (z & 1));
         prev += d;
         out[i] = (int16_t)prev;
     }

@@ -889,8 +889,8 @@ __device__ __forceinline__ int unpack_svbzd_wave(const s5gpu_decode_args_t &a, c
     const uint8_t *sigp = pay + hl + 8;
     const uint32_t avail = plen - hl - 8;
     if (L > avail || L < 4) return 7;
-    const uint32_t n = (uint32_t)ld_le(sigp, 4), nk = (n + 3) >> 2;
-    if ((uint64_t)4 + nk > L) return 7;
+    const uint32_t n = (uint32_t)ld_le(sigp, 4), nk = svb_key_bytes(n);
+    if (!svb_count_fits(n, L)) return 7;
     if (n > d.sig_cap) { if (lane_id() == 0) f.n_samples = n; return 6; }
     const uint8_t *keys = sigp + 4, *data = keys + nk, *dend = sigp + L;
     int16_t *out = a.sig_out + d.sig_off;
@@ -1040,7 +1040,8 @@ __device__ __forceinline__ uint32_t np_slot_adler(const uint8_t *pay, uint32_t n
 }
 // decode the svb-zd blob of the slot again — lane l the l-th 64th of the samples, scalar code per lane: its first data byte from a plain
 // sum over the keys in front of it, its first sample from the deltas in front of it (a wave prefix sum is the one primitive shared with the
-// unpack) — and compare with what the unpack stored
+// unpack) — and compare with what the unpack stored.  Called only on a record the unpack decoded (status 0): its count, keys and data
+// bytes are known to fit the blob, so the reads below stay inside it
 __device__ __forceinline__ int np_signal_check(const s5gpu_decode_args_t &a, const s5gpu_rec_desc_t &d, const uint8_t *pay, uint32_t plen) {
     const uint32_t idl = (uint32_t)ld_le(pay, 2), hl = 2 + idl + 4 + 32;
     const uint8_t *sigp = pay + hl + 8;
@@ -1374,8 +1375,8 @@ __device__ __forceinline__ void unpack_record_wg(const s5gpu_decode_args_t &a, u
     if (a.sig_method == S5GPU_SIG_SVB_ZD) {
         if (L > avail || L < 4) { if (tid == 0) f.status = 7; return; }
         n = (uint32_t)ld_le(sigp, 4);
-        const uint32_t nk = (n + 3) >> 2;
-        if ((uint64_t)4 + nk > L) { if (tid == 0) f.status = 7; return; }
+        const uint32_t nk = svb_key_bytes(n);
+        if (!svb_count_fits(n, L)) { if (tid == 0) f.status = 7; return; }
         sig_bytes = (uint32_t)L;
         if (n > d.sig_cap) { if (tid == 0) { f.status = 6; f.n_samples = n; } return; }
         const uint8_t *keys = sigp + 4, *data = keys + nk, *dend = sigp + L;
@@ -1463,8 +1464,8 @@ __global__ __launch_bounds__(NT) void k_svbzd_decode(s5gpu_decode_args_t a) {
     if (tid == 0) s_err = 0;
     __syncthreads();
     if (d.in_len < 4) { if (tid == 0) f.status = 7; return; }
-    const uint32_t n = (uint32_t)ld_le(blob, 4), nk = (n + 3) >> 2;
-    if ((uint64_t)4 + nk > d.in_len) { if (tid == 0) f.status = 7; return; }
+    const uint32_t n = (uint32_t)ld_le(blob, 4), nk = svb_key_bytes(n);
+    if (!svb_count_fits(n, d.in_len)) { if (tid == 0) f.status = 7; return; }
     if (n > d.sig_cap) { if (tid == 0) { f.status = 6; f.n_samples = n; } return; }
     const uint8_t *keys = blob + 4, *data = keys + nk, *dend = blob + d.in_len;
     int16_t *out = a.sig_out + d.sig_off;

@@ -164,6 +164,12 @@ __device__ __forceinline__ uint32_t svb_encode_tile(const int16_t *__restrict__ 
     return total;
 }
 
+// The key bytes of an n-value blob: ceil(n / 4), taken in 64 bits (in 32, n >= 0xFFFFFFFD wraps to 0).
+__device__ __forceinline__ uint32_t svb_key_bytes(uint32_t n) { return (uint32_t)(((uint64_t)n + 3u) >> 2); }
+// A blob of L bytes can hold n values only if it has room for the count, the keys and one data byte per value.  A count that fails this is
+// a malformed blob (status 7, as the CPU decoder has it), never a signal slot that is too small (6): the caller retries a 6 with a slot of n.
+__device__ __forceinline__ bool svb_count_fits(uint32_t n, uint64_t L) { return 4ull + svb_key_bytes(n) + n <= L; }
+
 // Decode values [t0, min(t0+SVB_TILE, n)) of one svb-zd blob.  keys: key area base + t0/4;
 // data: first data byte of this tile; data_end: end of blob.  `carry` = x[t0-1] (0 for the first tile).
 // Writes int16 samples to out[t0..].  Returns the tile's data byte count; updates carry (uniform).
@@ -188,8 +194,9 @@ __device__ __forceinline__ uint32_t svb_decode_tile(const uint8_t *keys, const u
         if (q < valid) nbytes += ((key >> (2 * q)) & 3) + 1;
     uint32_t total;
     const uint32_t off = block_excl_add(nbytes, ws, total);
-    {   // data[0 .. min(total, bytes left)) -> stage (total <= 4 * SVB_TILE)
-        const uint32_t have = (uint32_t)min((uint64_t)total, (uint64_t)(data_end - data));
+    {   // data[0 .. min(total, bytes left)) -> stage (total <= 4 * SVB_TILE); nothing once the keys of earlier tiles have claimed more
+        // bytes than the blob holds (data past data_end: the lanes below fail their test, no byte beyond the blob is loaded)
+        const uint32_t have = data < data_end ? (uint32_t)min((uint64_t)total, (uint64_t)(data_end - data)) : 0u;
         typedef uint32_t v4u __attribute__((ext_vector_type(4), aligned(1)));
         typedef uint32_t v4a __attribute__((ext_vector_type(4)));
         for (uint32_t k = 16u * tid; k < have; k += 16u * NT) {
@@ -275,8 +282,8 @@ __device__ __forceinline__ uint32_t svb_decode_tile_wave(const uint8_t *keys, co
     const uint32_t incl = wave_incl_add(nbytes);
     const uint32_t off = incl - nbytes;
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (STAGED) {   // data[0 .. min(total, bytes left)) -> stage
-        const uint32_t have = (uint32_t)min((uint64_t)total, (uint64_t)(data_end - data));
+    if (STAGED) {   // data[0 .. min(total, bytes left)) -> stage; nothing once data has run past data_end (as svb_decode_tile)
+        const uint32_t have = data < data_end ? (uint32_t)min((uint64_t)total, (uint64_t)(data_end - data)) : 0u;
         typedef uint32_t v4u __attribute__((ext_vector_type(4), aligned(1)));
         typedef uint32_t v4a __attribute__((ext_vector_type(4)));
         for (uint32_t k = 16u * (uint32_t)lane; k < have; k += 16u * 64u) {
