@@ -2,14 +2,20 @@
 """bench.py — BLOW5 record press throughput on N MI355X (BASELINE.json's metric: raw-signal GB/s and reads/s).
 
 Default run = BASELINE configs[2] as the headline value (1 M reads x 4000 samples per GPU, full encode svb-zd + DEFLATE,
-weak scaling) PLUS, in the same JSON line, one object per other GPU config of BASELINE.json:
+weak scaling) and nothing else: set up, warm up, time the K steps, write --dump-outputs, print the line.  Its kernel_ms and
+roofline come from events recorded inside the timed steps; every object that needs work of its own is null.
+
+--full adds, in the same JSON line, a "sustained" repeat of the step, the parity spot check against the CPU oracle, the CPU
+baseline, the mixed-read-lengths leg, the end-to-end / PCIe-inclusive / host-fed objects (bench_e2e.py) and one object per
+other GPU config of BASELINE.json:
     "configs1"  svb-zd encode alone on the same reads                                     (k_svbzd_encode, HBM-bound)
     "configs4"  decode for random `get` over the index of the records just written: K = 4096 batches (p50 / p99 latency) and
                 the whole index in one call, on our own records and on records written by stock zlib, every signal compared
                 with the generator; fields + signals only (S5GPU_DEC_NO_PAYLOAD), the full-record form beside it
     "configs3"  100 k-sample reads, a fixed read-index space sharded over the ranks with shard.shard_range (strong scaling)
-Every GPU leg runs for about a second of device time or more (the headline's K steps are what `value` is computed on; a
-"sustained" repeat of the same step follows it), so that a coarse utilisation sampler sees the legs.
+Every GPU leg runs for about a second of device time or more (the headline's K steps are what `value` is computed on; the
+"sustained" repeat follows them), so that a coarse utilisation sampler sees the legs.  --no-legs / --no-long / --no-mixed /
+--no-e2e take parts out of a --full line.
 
 A step = one pass of the hot path over one resident batch of synthetic reads, ending in the contiguous BLOW5 record
 stream the ordered fwrite loop emits:
@@ -21,7 +27,9 @@ Reads shard across ranks with no collective (RCCL carries the timing barrier and
 Prints ONE JSON line on rank 0.
 
 Other modes (one line each, for profiles/):  --svb-only (configs[1]), --long (configs[3] alone), --mixed (read lengths of a
-real run), --decode (configs[4] alone), --samples / --reads (any uniform shape).
+real run), --decode (configs[4] alone), --samples / --reads (any uniform shape).  --long and --decode make their leg the whole
+line, checks included; the other modes time their steps as the default run does, and --full adds the spot check (and, where
+it applies, the CPU baseline).
 """
 import argparse
 import ctypes as C
@@ -796,6 +804,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reads", type=int, default=1_000_000, help="reads per GPU per step")
     ap.add_argument("--samples", type=int, default=4000, help="int16 samples per read")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the sustained repeat, the parity spot check, the CPU baseline, "
+                                                        "the configs[1] / [3] / [4] and mixed-lengths legs, the e2e / PCIe-inclusive / host-fed objects")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline, reference-shaped point: seconds (0 = skip)")
     ap.add_argument("--cpu-sweep-seconds", type=float, default=5.0, help="CPU baseline: seconds per point of the -t / -K sweep (0 = skip)")
     ap.add_argument("--svb-only", action="store_true", help="configs[1] alone: svb-zd stage")
@@ -803,8 +813,8 @@ def main():
     ap.add_argument("--fused-cap", type=int, default=8192, help="--mixed: LDS payload budget of the fused kernel, bytes (longer payloads take the staged path)")
     ap.add_argument("--mixed", action="store_true", help="read lengths of a real run: log-normal, median 6000 samples (--reads reads, default 262144)")
     ap.add_argument("--long", action="store_true", help="configs[3] alone (the long-read leg as the whole line)")
-    ap.add_argument("--no-long", action="store_true", help="skip the configs[3] leg of the default run")
-    ap.add_argument("--no-legs", action="store_true", help="skip the configs[1] and configs[4] legs of the default run")
+    ap.add_argument("--no-long", action="store_true", help="skip the configs[3] leg of a --full run")
+    ap.add_argument("--no-legs", action="store_true", help="skip the configs[1] and configs[4] legs of a --full run")
     ap.add_argument("--long-reads", type=int, default=65536, help="configs[3] leg: size of the read-index space (all ranks together)")
     ap.add_argument("--long-samples", type=int, default=100_000)
     ap.add_argument("--long-chunk", type=int, default=16384, help="configs[3] leg: reads per launch (at most; a rank's shard is cut into >= 4 chunks)")
@@ -813,9 +823,9 @@ def main():
     ap.add_argument("--decode-batches-only", action="store_true", help="configs[4]: only the K-sized get batches (no bulk call, no stock-zlib records)")
     ap.add_argument("--get-reads", type=int, default=100_000, help="configs[4]: random read ids to fetch (seed 1)")
     ap.add_argument("--get-batch", type=int, default=4096, help="configs[4]: ids per batch (-K)")
-    ap.add_argument("--no-mixed", action="store_true", help="skip the mixed-read-lengths leg of the default run")
+    ap.add_argument("--no-mixed", action="store_true", help="skip the mixed-read-lengths leg of a --full run")
     ap.add_argument("--mixed-reads", type=int, default=262144, help="mixed leg: reads per GPU")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (file to file) object of the default run")
+    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (file to file) object of a --full run")
     ap.add_argument("--e2e-reads", type=int, default=1_000_000, help="e2e: reads in the files (4000 samples each; /dev/shm)")
     ap.add_argument("--e2e-cpu-reads", type=int, default=262_144, help="e2e: records of the same files the CPU twins convert per point")
     ap.add_argument("--min-leg-seconds", type=float, default=1.2, help="every GPU leg keeps the device busy for about this long at least")
@@ -978,9 +988,10 @@ def main():
     dumped = dump_outputs(args.dump_outputs, b.stream_out, b.rec_off, n_reads) if args.dump_outputs and rank == 0 else None
 
     default_shape = not (args.svb_only or args.mixed or args.two_pass) and n == 4000
+    legs = args.full and default_shape          # the line's other objects: --full only, and only for the default shape
     # the same step again for about a second (not what `value` is computed on: that is the K steps above)
     sustained = None
-    if default_shape and args.min_leg_seconds > 0:
+    if legs and args.min_leg_seconds > 0:
         reps = max(1, int(args.min_leg_seconds / max(dt / K, 1e-6)))
         reps = min(reps, 2000)
         dts = timed(shard, torch, dev, lambda: [(run_step(), second_half()) for _ in range(reps)])
@@ -989,7 +1000,7 @@ def main():
     main_out_len = b.out_len[:n_reads].cpu().numpy().astype(np.int64)
     main_recs = None
     sig_cpu_t = None
-    if rank == 0:
+    if rank == 0 and args.full:
         idx = [0, 1, n_reads // 2, n_reads - 1] if n_reads >= 4 else list(range(n_reads))
         main_recs = (idx, b.stream_records(idx) if single_pass else b.records(idx), b.stream_ok() if single_pass else True)
         if world == 1 and args.cpu_seconds > 0 and not args.svb_only and not args.mixed:   # the CPU baseline is an N = 1 figure
@@ -999,16 +1010,16 @@ def main():
 
     # ---- the other configs of BASELINE.json as legs of the same line (every rank takes part) ----
     leg1 = leg3 = leg4 = None
-    if default_shape and not args.no_legs:
+    if legs and not args.no_legs:
         if single_pass:     # configs[4] decodes the records the headline wrote; it runs before configs[1] reuses the stream buffer
             leg4 = decode_leg(args, L, _lib, shard, ob, b, n_reads, n, rank, world, dev, world == 1 and args.cpu_seconds > 0)
         leg1 = svb_leg(args, L, _lib, shard, ob, b, n_reads, n, rank, world, dev, K, args.warmup)
     del b                                       # free the main batch before the other legs allocate
     torch.cuda.empty_cache()
-    if default_shape and not args.no_long:
+    if legs and not args.no_long:
         leg3 = long_leg(args, L, _lib, press, shard, ob, rank, world, dev, K, args.warmup)
     leg_mixed = None
-    if default_shape and not args.no_mixed:
+    if legs and not args.no_mixed:
         leg_mixed = mixed_leg(args, L, _lib, press, shard, rank, world, dev)
 
     if rank != 0:
@@ -1016,7 +1027,7 @@ def main():
 
     # ---- N > 1: the HOST-FED curve beside the device-resident one (round 5): one process, one batch call, all N devices ----
     host_fed = None
-    if default_shape and world > 1 and not args.no_e2e:
+    if legs and world > 1 and not args.no_e2e:
         import bench_e2e
         # (every rank has left its legs — each ends on a barrier — and the other ranks are on their way out: rank 0 goes on alone)
         try:
@@ -1026,7 +1037,7 @@ def main():
 
     # ---- end to end through files + the host-buffer (PCIe-inclusive) batch call: N = 1 figures, like the CPU baseline ----
     e2e_obj = pcie_obj = None
-    if default_shape and world == 1 and not args.no_e2e:
+    if legs and world == 1 and not args.no_e2e:
         import bench_e2e
         torch.cuda.empty_cache()
         try:
@@ -1060,22 +1071,24 @@ def main():
         kernel = "k_pack+k_deflate_staged"
     traffic, traffic_src = (None, None) if args.mixed else pmc_traffic(kernel, n, n_reads)
 
-    # parity spot check of this very run (outside the timed region)
-    import zlib
+    # parity spot check of this very run (outside the timed region; --full)
+    parity = None
+    if main_recs is not None:
+        import zlib
 
-    idx, recs, parity = main_recs
-    if not args.mixed:
-        for i, rec in zip(idx, recs):
-            sig = ob.synth_read(0x5105, rank * n_reads + i, n)
-            if args.svb_only:
-                parity &= rec == ob.svbzd_encode(sig)
-            else:
-                r, keep = ob.make_rec(ob.synth_read_id(rank * n_reads + i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-                parity &= zlib.decompress(rec[8:]) == ob.rec_pack(r, ob.SIG_SVB_ZD)
-    else:
-        for i, rec in zip(idx, recs):          # mixed lengths: stock zlib must inflate every sampled record to a payload of the right shape
-            pay = zlib.decompress(rec[8:])
-            parity &= len(pay) > 82 and int.from_bytes(pay[82:86], "little") == int(ns[i])
+        idx, recs, parity = main_recs
+        if not args.mixed:
+            for i, rec in zip(idx, recs):
+                sig = ob.synth_read(0x5105, rank * n_reads + i, n)
+                if args.svb_only:
+                    parity &= rec == ob.svbzd_encode(sig)
+                else:
+                    r, keep = ob.make_rec(ob.synth_read_id(rank * n_reads + i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
+                    parity &= zlib.decompress(rec[8:]) == ob.rec_pack(r, ob.SIG_SVB_ZD)
+        else:
+            for i, rec in zip(idx, recs):          # mixed lengths: stock zlib must inflate every sampled record to a payload of the right shape
+                pay = zlib.decompress(rec[8:])
+                parity &= len(pay) > 82 and int.from_bytes(pay[82:86], "little") == int(ns[i])
 
     cpu = None
     if sig_cpu_t is not None:
@@ -1091,14 +1104,14 @@ def main():
         "metric": "blow5_encode_raw_signal_throughput" if not args.svb_only else "svbzd_encode_raw_signal_throughput",
         "value": round(value, 3), "unit": "GB/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
         "ms_per_step": round(dt / K * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "int16->u8", "data": "synthetic",
+        "dtype": "int16->u8", "data": "synthetic", "full": args.full,
         "config": {"workload": workload, "reads_per_gpu": n_reads, "samples_per_read": n if not args.mixed else "mixed",
                    "record_press": "none" if args.svb_only else "zlib",
                    "signal_press": "svb-zd", "parallelism": "reads sharded over %d GPU(s), no collective" % world},
         "ranks_seen": ranks_seen,
         "reads_per_s": round(reads_per_s, 1),
         "bytes_per_sample": round(z_bytes / (raw_bytes / 2), 4),
-        "parity_spot_check": bool(parity),
+        "parity_spot_check": bool(parity) if parity is not None else None,
         "kernel_ms": {"encode": round(float(np.mean(enc_ms)), 3), "compact": round(float(np.mean(cmp_ms)), 3) if not single_pass else 0.0},
         "output": "ordered single-pass record stream (k_encode_stream)" if single_pass else "worst-case slots + compaction pass",
         "roofline": {"bound": "hbm", "kernel": kernel,

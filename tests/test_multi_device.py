@@ -210,7 +210,7 @@ def test_bench_two_ranks_preflight_on_one_gpu(tmp_path):
         env.pop(k, None)
     # round 6: PLAIN `python bench.py --gpus 2` — no launcher around it: bench.py makes its own ranks (torch.distributed.run, the driver's
     # module) when WORLD_SIZE is unset, so `--gpus N` can never end as N copies' worth of one rank with `n_gpus: 1`
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--reads", "20000", "--long-reads", "512", "--cpu-seconds", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--reads", "20000", "--long-reads", "512", "--cpu-seconds", "0",
            "--get-reads", "20000", "--min-leg-seconds", "0.2", "--min-leg-steps-svb", "4", "--min-leg-steps-long", "2", "--mixed-reads", "8192"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -11,9 +11,9 @@ PROBE=$PWD/slow5tools_amd/_variants/libs5_probe.so     # tools/variant.sh probe 
 bash tools/pmc_traffic_all.sh $PWD/$O/pmc > $O/pmc_traffic.txt 2>&1
 cp $O/pmc/pmc_traffic.json profiles/pmc_traffic.json          # (so that the bench lines below carry roofline.traffic)
 cp $O/pmc/pmc_traffic.json $O/pmc_traffic.json.txt
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --decode > $O/bench_decode.json 2> $O/bench_decode.err
-tools/kstats.sh r04p/enc python bench.py --no-long --no-mixed --no-e2e --cpu-seconds 0
+tools/kstats.sh r04p/enc python bench.py --full --no-long --no-mixed --no-e2e --cpu-seconds 0
 tools/kstats.sh r04p/svb python bench.py --svb-only --cpu-seconds 0
 tools/kstats.sh r04p/long python bench.py --long --cpu-seconds 0
 tools/kstats.sh r04p/long_one_stream python bench.py --long --long-streams 1 --cpu-seconds 0

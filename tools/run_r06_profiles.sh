@@ -9,9 +9,9 @@ rm -rf $O; mkdir -p $O
 bash tools/pmc_traffic_all.sh $PWD/$O/pmc > $O/pmc_traffic.txt 2>&1
 cp $O/pmc/pmc_traffic.json profiles/pmc_traffic.json          # (so that the bench lines below carry roofline.traffic)
 cp $O/pmc/pmc_traffic.json $O/pmc_traffic.json.txt
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 python bench.py --decode > $O/bench_decode.json 2> $O/bench_decode.err
-tools/kstats.sh r06p/enc python bench.py --no-long --no-mixed --no-e2e --cpu-seconds 0
+tools/kstats.sh r06p/enc python bench.py --full --no-long --no-mixed --no-e2e --cpu-seconds 0
 tools/kstats.sh r06p/svb python bench.py --svb-only --cpu-seconds 0
 tools/kstats.sh r06p/long python bench.py --long --cpu-seconds 0
 tools/kstats.sh r06p/long_one_stream python bench.py --long --long-streams 1 --cpu-seconds 0
