@@ -13,6 +13,10 @@
  *        tune it, S5VIEW_PER_RECORD=1 forces the per-record pipeline the tests compare it with).
  *   s5view --index in.blow5          writes in.blow5.idx (slow5tools index)
  *   s5view --get in.blow5 read_id    prints len_raw_signal and the first samples of one read (slow5tools get)
+ *   s5view --degrade BITS in out [record] [signal] [K] [workers]
+ *                                    slow5tools degrade: the same loop with every sample rounded to a multiple of 2^BITS (BITS 1..16;
+ *                                    include/slow5gpu.h, s5gpu_qts_round_dev) on the device; the output press defaults to zlib ex-zd
+ *                                    (src/degrade.c:302).  Every pipeline above takes it.
  */
 #define _GNU_SOURCE
 #include <pthread.h>
@@ -34,6 +38,8 @@ static double now_s(void);
 static void stamp(const char *what) { if (g_timing) fprintf(stderr, "s5view[t] %8.3f  %s\n", now_s() - g_t_main, what); }
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
+static uint8_t g_qts;   /* --degrade BITS (1..16); 0: plain view */
+
 static int die(const char *what) {
     fprintf(stderr, "s5view: %s (slow5_errno %d; %s)\n", what, slow5_errno, s5gpu_last_error());
     return EXIT_FAILURE;
@@ -115,8 +121,10 @@ static void *worker_main(void *arg) {                               /* compute p
         P->next_work = s + 1;
         b->state = ST_BUSY;
         pthread_mutex_unlock(&P->mu);
-        if (slow5_gpu_convert_batch(b->n, b->mem, b->bytes, P->in->format, P->from, P->in->header->aux_meta, P->fmt_out, P->to, NULL, 0, b->bufs,
-                                    b->lens) != 0) {
+        if ((g_qts ? slow5_gpu_convert_batch_qts(b->n, b->mem, b->bytes, P->in->format, P->from, P->in->header->aux_meta, P->fmt_out, P->to, NULL, 0,
+                                                 b->bufs, b->lens, g_qts)
+                   : slow5_gpu_convert_batch(b->n, b->mem, b->bytes, P->in->format, P->from, P->in->header->aux_meta, P->fmt_out, P->to, NULL, 0, b->bufs,
+                                             b->lens)) != 0) {
             pipe_fail(P, "GPU press path failed");
             return NULL;
         }
@@ -327,7 +335,17 @@ static void *fworker_main(void *arg) {
         pthread_mutex_unlock(&P->mu);
         const double tg0 = now_s();
         for (int attempt = 0;; attempt++) {
-            const int rc = P->ascii_out
+            const int rc = g_qts
+                ? (P->ascii_out
+                   ? s5gpu_blow5_to_ascii_stream_qts(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, rec_code_of(P->from.record_method),
+                                                     sig_code_of(P->from.signal_method), P->n_aux, P->aux_type, NULL, 0, b->out, b->out_cap, b->out_off, NULL, g_qts)
+                   : P->ascii
+                   ? s5gpu_ascii_to_blow5_stream_qts(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, P->n_aux, P->aux_type, rec_code_of(P->to.record_method),
+                                                     sig_code_of(P->to.signal_method), NULL, 0, b->out, b->out_cap, b->out_off, NULL, g_qts)
+                   : s5gpu_recompress_stream_qts(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, rec_code_of(P->from.record_method),
+                                                 sig_code_of(P->from.signal_method), rec_code_of(P->to.record_method), sig_code_of(P->to.signal_method), NULL, 0,
+                                                 b->out, b->out_cap, b->out_off, NULL, g_qts))
+                : P->ascii_out
                 ? s5gpu_blow5_to_ascii_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, rec_code_of(P->from.record_method), sig_code_of(P->from.signal_method),
                                               P->n_aux, P->aux_type, NULL, 0, b->out, b->out_cap, b->out_off, NULL)
                 : P->ascii
@@ -598,11 +616,22 @@ int main(int argc, char **argv) {
         slow5_close(s);
         return EXIT_SUCCESS;
     }
+    if (argc >= 2 && strcmp(argv[1], "--degrade") == 0) {
+        char *end = NULL;
+        const long b = argc >= 3 ? strtol(argv[2], &end, 10) : 0;
+        if (argc < 5 || end == argv[2] || *end || b < 1 || b > 16) {   /* ("auto", the reference's dataset detection, is not offered) */
+            fprintf(stderr, "usage: s5view --degrade BITS(1..16) in.[b|s]low5 out.[b|s]low5 [none|zlib|zstd] [none|svb-zd|ex-zd] [K] [workers]\n");
+            return EXIT_FAILURE;
+        }
+        g_qts = (uint8_t)b;
+        argv += 2;
+        argc -= 2;
+    }
     if (argc < 3) {
         fprintf(stderr, "usage: s5view in.blow5 out.blow5 [none|zlib|zstd] [none|svb-zd|ex-zd] [K]\n");
         return EXIT_FAILURE;
     }
-    slow5_press_method_t to = {SLOW5_COMPRESS_ZLIB, SLOW5_COMPRESS_SVB_ZD};
+    slow5_press_method_t to = {SLOW5_COMPRESS_ZLIB, g_qts ? SLOW5_COMPRESS_EX_ZD : SLOW5_COMPRESS_SVB_ZD};   /* degrade: src/degrade.c:302 */
     if (argc > 3) to.record_method = strcmp(argv[3], "none") == 0 ? SLOW5_COMPRESS_NONE : strcmp(argv[3], "zstd") == 0 ? SLOW5_COMPRESS_ZSTD : SLOW5_COMPRESS_ZLIB;
     if (argc > 4) to.signal_method = strcmp(argv[4], "none") == 0 ? SLOW5_COMPRESS_NONE : strcmp(argv[4], "ex-zd") == 0 ? SLOW5_COMPRESS_EX_ZD : SLOW5_COMPRESS_SVB_ZD;
     const int64_t K = argc > 5 ? atoll(argv[5]) : 4096;
@@ -696,7 +725,8 @@ int main(int argc, char **argv) {
             }
             if (n == 0) break;
             /* compute phase: the work_db() of src/view.c:292, one call for the whole batch */
-            if (slow5_gpu_convert_batch(n, mem, bytes, in->format, from, in->header->aux_meta, fmt_out, to, NULL, 0, bufs, lens) != 0)
+            if ((g_qts ? slow5_gpu_convert_batch_qts(n, mem, bytes, in->format, from, in->header->aux_meta, fmt_out, to, NULL, 0, bufs, lens, g_qts)
+                       : slow5_gpu_convert_batch(n, mem, bytes, in->format, from, in->header->aux_meta, fmt_out, to, NULL, 0, bufs, lens)) != 0)
                 return die("GPU press path failed");
             for (int64_t i = 0; i < n; i++) {                           /* ordered write phase, src/view.c:296-299 */
                 if (fwrite(bufs[i], 1, lens[i], out) != lens[i]) return die("write failed");

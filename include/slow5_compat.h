@@ -184,6 +184,14 @@ int slow5_gpu_recompress_batch(int64_t n, char **mem, size_t *bytes, slow5_press
 int slow5_gpu_convert_batch(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
                             const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
                             const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len);
+/* degrade's worker (src/degrade.c:235-271): slow5_gpu_convert_batch with every sample qts-rounded to `bits` (1..16, else -1 with
+ * SLOW5_ERR_ARG) on the device, between the decode (or text parse) and the encode (or text format); ASCII -> ASCII rounds in its first
+ * half.  The rule: include/slow5gpu.h, s5gpu_qts_round_dev. */
+int slow5_gpu_convert_batch_qts(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
+                                const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
+                                const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits);
+/* slow5lib's per-record form (src/degrade.c:255): the same rule over read->raw_signal, on the host; bits outside 1..16 change nothing */
+void slow5_rec_qts_round(struct slow5_rec *read, uint8_t bits);
 /* get worker (src/get.c:37-66) after the pread: decode n records into slow5_rec_t's */
 int slow5_gpu_depress_parse_batch(int64_t n, char **mem, size_t *bytes, slow5_press_method_t from,
                                   struct slow5_rec **reads);

@@ -226,6 +226,11 @@ int s5gpu_compact_dev(uint32_t n_reads, const s5gpu_read_desc_t *desc, const uin
                       uint64_t *rec_off, uint8_t *stream, uint64_t *tmp, void *hip_stream);
 /* write val[i] (little-endian u32) at base + off[i]: the read_group rewrite of merge (src/merge.c:51) on device */
 int s5gpu_patch_u32_dev(uint8_t *base, const uint64_t *off, const uint32_t *val, uint32_t n, void *hip_stream);
+/* qts rounding in place (slow5tools degrade, slow5_rec_qts_round): every sample x of record i, sig[sig_off[i] .. + n_samples[i]), becomes
+ *     y = ((x + 2^(bits-1)) >> bits) << bits   in int32 (nearest multiple of 2^bits, ties toward +inf);  y > 32767: y -= 2^bits
+ * bits 1..16 (else S5GPU_ERR_ARG).  sig_off / n_samples: device arrays of n entries, the records in order and apart
+ * (sig_off[i] + n_samples[i] <= sig_off[i + 1]), every sig_off a multiple of 8.  Nothing outside the records' samples is touched. */
+int s5gpu_qts_round_dev(int16_t *sig, uint32_t n, const uint64_t *sig_off, const uint32_t *n_samples, uint32_t bits, void *hip_stream);
 /* synthetic reads on device (bench/test workload; bit-identical to oracle/synth.c) */
 int s5gpu_synth_dev(int16_t *sig, uint64_t n_reads, uint64_t n_samples, uint64_t stride_samples, uint64_t seed,
                     uint64_t first_read_idx, void *hip_stream);
@@ -381,6 +386,28 @@ int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_byte
 int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
                                const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
                                int32_t *status);
+
+/* _qts twins of the convert calls (slow5tools degrade, src/degrade.c:235-271): the same arguments and results, with every sample
+ * qts-rounded to qts_bits (1..16, else S5GPU_ERR_ARG; the rule at s5gpu_qts_round_dev) on the device between the stage that makes the
+ * signals (decode / text parse) and the one that takes them (encode / text format).  The plain calls round nothing. */
+int s5gpu_recompress_batch_qts(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
+                               int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                               int32_t *status, uint32_t qts_bits);
+int s5gpu_recompress_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                int from_sig, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void *out_buf,
+                                size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits);
+int s5gpu_ascii_to_blow5_batch_qts(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+                                   int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                   int32_t *status, uint32_t qts_bits);
+int s5gpu_ascii_to_blow5_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+                                    uint32_t n_aux, const uint8_t *aux_type, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux,
+                                    void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits);
+int s5gpu_blow5_to_ascii_batch_qts(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
+                                   const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                   int32_t *status, uint32_t qts_bits);
+int s5gpu_blow5_to_ascii_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                    int from_sig, uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
+                                    void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,11 @@ int slow5_gpu_hook_convert(int64_t n, char **mem, size_t *bytes, int from_fmt, i
                            const char *aux_types_line, int to_fmt, int to_record_method, int to_signal_method,
                            const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len);
 
+/* degrade's work_db (src/degrade.c:235-271): slow5_gpu_hook_convert with every sample qts-rounded to `bits` (1..16) before the encode. */
+int slow5_gpu_hook_convert_qts(int64_t n, char **mem, size_t *bytes, int from_fmt, int from_record_method, int from_signal_method,
+                               const char *aux_types_line, int to_fmt, int to_record_method, int to_signal_method,
+                               const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits);
+
 /* One decoded read, for callers that fill their own slow5_rec_t (get --benchmark src/get.c:52, skim src/skim.c:320, split).
  * read_id and aux point INTO the uncompressed record that replaced mem[i] (the caller frees mem[i], as after
  * slow5_rec_depress_parse, src/view.c:41); raw_signal is a malloc'd buffer the caller owns. */

@@ -276,9 +276,9 @@ extern "C" int s5gpu_aux_types_parse(const char *types_line, size_t len, uint8_t
     return (int)n_aux;
 }
 
-extern "C" int s5gpu_ascii_to_blow5_batch(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+static int ascii_to_blow5_batch_any(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
                                           int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
-                                          int32_t *status) {
+                                          int32_t *status, uint32_t qts_bits) {
     if (n == 0) return S5GPU_OK;
     if (!line || !line_len || !out || !out_len || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_ascii_to_blow5_batch: NULL argument"); return S5GPU_ERR_ARG; }
     s5host::CtxHold hold;
@@ -348,6 +348,9 @@ extern "C" int s5gpu_ascii_to_blow5_batch(uint32_t n, const char *const *line, c
     for (uint32_t i = 0; i < n; i++)
         if (hs[i]) { bad = true; if (status) status[i] = hs[i]; }
     if (bad) { s5gpu_set_error("s5gpu_ascii_to_blow5_batch: raw_signal text of at least one line is malformed (see status[i])"); return S5GPU_ERR_DATA; }
+    if (qts_bits && (rc = s5_qts_round_strided((int16_t *)c->d_sig.p, n, (const uint8_t *)c->d_desc.p + offsetof(s5gpu_read_desc_t, sig_off), sizeof(s5gpu_read_desc_t),
+                                               (const uint8_t *)c->d_desc.p + offsetof(s5gpu_read_desc_t, n_samples), sizeof(s5gpu_read_desc_t), qts_bits, c->st)))
+        return rc;
     s5gpu_encode_args_t a;
     memset(&a, 0, sizeof a);
     a.n_reads = n; a.rec_method = to_rec; a.sig_method = to_sig;
@@ -359,9 +362,9 @@ extern "C" int s5gpu_ascii_to_blow5_batch(uint32_t n, const char *const *line, c
 
 // The same for a CHUNK of a .slow5 file: lines framed in place, the chunk uploaded as it is, one contiguous record stream back
 // (the ASCII twin of s5gpu_recompress_stream; /root/reference/src/view.c:35-57 with a .slow5 input, configs[0] of BASELINE.json).
-extern "C" int s5gpu_ascii_to_blow5_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+static int ascii_to_blow5_stream_any(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
                                            uint32_t n_aux, const uint8_t *aux_type, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux,
-                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
+                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !line_pos || !line_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_ascii_to_blow5_stream: NULL argument"); return S5GPU_ERR_ARG; }
     for (uint32_t i = 0; i < n; i++) {
@@ -450,6 +453,9 @@ extern "C" int s5gpu_ascii_to_blow5_stream(uint32_t n, const void *chunk, size_t
         for (uint32_t i = 0; i < m; i++)
             if (hs[i]) { bad = true; if (status) status[lo + i] = hs[i]; }
         if (bad) { s5gpu_set_error("s5gpu_ascii_to_blow5_stream: raw_signal text of at least one line is malformed (see status[i])"); return sg.fail(S5GPU_ERR_DATA, slot); }
+        if (qts_bits && (r = s5_qts_round_strided((int16_t *)c->d_sig.p, m, (const uint8_t *)c->d_desc.p + offsetof(s5gpu_read_desc_t, sig_off), sizeof(s5gpu_read_desc_t),
+                                                  (const uint8_t *)c->d_desc.p + offsetof(s5gpu_read_desc_t, n_samples), sizeof(s5gpu_read_desc_t), qts_bits, c->st)))
+            return sg.fail(r, slot);
         s5gpu_encode_args_t a;
         memset(&a, 0, sizeof a);
         a.n_reads = m; a.rec_method = to_rec; a.sig_method = to_sig;
@@ -482,9 +488,9 @@ extern "C" int s5gpu_ascii_to_blow5_stream(uint32_t n, const void *chunk, size_t
     return S5GPU_OK;
 }
 
-extern "C" int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
+static int blow5_to_ascii_batch_any(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
                                           const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
-                                          int32_t *status) {
+                                          int32_t *status, uint32_t qts_bits) {
     if (n == 0) return S5GPU_OK;
     if (!rec || !rec_len || !out || !out_len || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_blow5_to_ascii_batch: NULL argument"); return S5GPU_ERR_ARG; }
     s5host::CtxHold hold;
@@ -495,6 +501,7 @@ extern "C" int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, co
     std::vector<s5gpu_rec_desc_t> rd;
     std::vector<s5gpu_rec_fields_t> ff;
     if ((rc = s5host::decode_resident(c, n, rec, rec_len, from_rec, from_sig, rd, ff, status))) return rc;
+    if (qts_bits && (rc = s5host::qts_round_decoded(c, n, qts_bits))) return rc;
     // text slots (worst case 7 bytes / sample) + the read_id and aux ranges the host needs
     std::vector<s5gpu_read_desc_t> td_slots(n);      // reused by the compaction: out_off / slot_cap
     std::vector<s5gpu_txt_desc_t> td(n);
@@ -599,9 +606,9 @@ extern "C" int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, co
 // are printed on the host from the decoded fields (ids and aux bytes gathered on the device, one small D2H) into a prefix
 // ("id \t rg \t ... \t n \t") and a suffix ("\t aux ... \n") per line; the device then puts prefix | signal text | suffix of every
 // line at its place in the output block (offsets = prefix sums of the three lengths), and ONE D2H brings the block back.
-extern "C" int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+static int blow5_to_ascii_stream_any(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
                                            int from_sig, uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
-                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
+                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_blow5_to_ascii_stream: NULL argument"); return S5GPU_ERR_ARG; }
     for (uint32_t i = 0; i < n; i++) {
@@ -631,6 +638,7 @@ extern "C" int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t
         if ((r = s5host::decode_resident_framed(c, m, rec.data(), len.data(), from_rec, from_sig, rd, ff, status ? status + lo : nullptr,
                                                 (const uint8_t *)chunk + b0, (size_t)(e1 - b0))))
             return sg.fail(r, slot);
+        if (qts_bits && (r = s5host::qts_round_decoded(c, m, qts_bits))) return sg.fail(r, slot);
         auto hip = [&](hipError_t e, const char *what) -> int {
             if (e == hipSuccess) return 0;
             s5gpu_set_error("%s failed: %s", what, hipGetErrorString(e));
@@ -755,4 +763,51 @@ extern "C" int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t
         return S5GPU_ERR_NOMEM;
     }
     return S5GPU_OK;
+}
+
+// The four calls above, and their _qts twins (slow5tools degrade): every sample qts-rounded to qts_bits (1..16) in HBM between the stage that
+// makes the int16 signals (text parse / decode) and the one that takes them (encode / text format).  The plain calls round nothing.
+extern "C" int s5gpu_ascii_to_blow5_batch(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+                                          int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                          int32_t *status) {
+    return ascii_to_blow5_batch_any(n, line, line_len, n_aux, aux_type, to_rec, to_sig, new_read_group, drop_aux, out, out_len, status, 0);
+}
+extern "C" int s5gpu_ascii_to_blow5_batch_qts(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+                                              int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                              int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_ascii_to_blow5_batch_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return ascii_to_blow5_batch_any(n, line, line_len, n_aux, aux_type, to_rec, to_sig, new_read_group, drop_aux, out, out_len, status, qts_bits);
+}
+extern "C" int s5gpu_ascii_to_blow5_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+                                           uint32_t n_aux, const uint8_t *aux_type, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux,
+                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
+    return ascii_to_blow5_stream_any(n, chunk, chunk_bytes, line_pos, line_len, n_aux, aux_type, to_rec, to_sig, new_read_group, drop_aux, out_buf, out_cap, out_off, status, 0);
+}
+extern "C" int s5gpu_ascii_to_blow5_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+                                               uint32_t n_aux, const uint8_t *aux_type, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux,
+                                               void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_ascii_to_blow5_stream_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return ascii_to_blow5_stream_any(n, chunk, chunk_bytes, line_pos, line_len, n_aux, aux_type, to_rec, to_sig, new_read_group, drop_aux, out_buf, out_cap, out_off, status, qts_bits);
+}
+extern "C" int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
+                                          const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                          int32_t *status) {
+    return blow5_to_ascii_batch_any(n, rec, rec_len, from_rec, from_sig, n_aux, aux_type, new_read_group, drop_aux, out, out_len, status, 0);
+}
+extern "C" int s5gpu_blow5_to_ascii_batch_qts(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
+                                              const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                              int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_blow5_to_ascii_batch_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return blow5_to_ascii_batch_any(n, rec, rec_len, from_rec, from_sig, n_aux, aux_type, new_read_group, drop_aux, out, out_len, status, qts_bits);
+}
+extern "C" int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                           int from_sig, uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
+                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
+    return blow5_to_ascii_stream_any(n, chunk, chunk_bytes, rec_pos, rec_len, from_rec, from_sig, n_aux, aux_type, new_read_group, drop_aux, out_buf, out_cap, out_off, status, 0);
+}
+extern "C" int s5gpu_blow5_to_ascii_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                               int from_sig, uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
+                                               void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_blow5_to_ascii_stream_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return blow5_to_ascii_stream_any(n, chunk, chunk_bytes, rec_pos, rec_len, from_rec, from_sig, n_aux, aux_type, new_read_group, drop_aux, out_buf, out_cap, out_off, status, qts_bits);
 }

@@ -990,13 +990,21 @@ static int decode_resident_impl(Ctx *c, uint32_t n, const void *const *rec, cons
     return S5GPU_OK;
 }
 
+// qts rounding of what decode_resident left in c->d_sig2: record i's samples start at d_desc2[i].sig_off, d_fields[i].n_samples of them (both
+// tables already on the device, in record order, the slots apart)
+int s5host::qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits) {
+    return s5_qts_round_strided((int16_t *)c->d_sig2.p, n, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off), sizeof(s5gpu_rec_desc_t),
+                                (const uint8_t *)c->d_fields.p + offsetof(s5gpu_rec_fields_t, n_samples), sizeof(s5gpu_rec_fields_t), bits, c->st);
+}
+
 // ---- view / merge worker for a whole batch, device-resident between decode and encode ----
 static int recompress_batch_dev(int slot, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
-                                int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status, s5host::Arena *ar);
+                                int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status, s5host::Arena *ar,
+                                uint32_t qts_bits);
 
 static int recompress_batch_any(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
                                 int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
-                                int32_t *status, void **arena) {
+                                int32_t *status, void **arena, uint32_t qts_bits = 0) {
     if (arena) *arena = NULL;
     if (n == 0) return S5GPU_OK;
     if (!rec || !rec_len || !out || !out_len) { s5gpu_set_error("s5gpu_recompress_batch: NULL argument"); return S5GPU_ERR_ARG; }
@@ -1010,7 +1018,8 @@ static int recompress_batch_any(uint32_t n, const void *const *rec, const size_t
     }
     const int rc = s5host::for_each_device_range(n, [&](int slot, uint32_t lo, uint32_t hi) {
         return recompress_batch_dev(slot, hi - lo, rec + lo, rec_len + lo, from_rec, from_sig, to_rec, to_sig,
-                                    new_read_group ? new_read_group + lo : nullptr, drop_aux, out + lo, out_len + lo, status ? status + lo : nullptr, ar);
+                                    new_read_group ? new_read_group + lo : nullptr, drop_aux, out + lo, out_len + lo, status ? status + lo : nullptr, ar,
+                                    qts_bits);
     });
     if (rc) {
         for (uint32_t i = 0; i < n; i++) { if (!ar) free(out[i]); out[i] = NULL; }
@@ -1024,6 +1033,13 @@ extern "C" int s5gpu_recompress_batch(uint32_t n, const void *const *rec, const 
                                       int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
                                       int32_t *status) {
     return recompress_batch_any(n, rec, rec_len, from_rec, from_sig, to_rec, to_sig, new_read_group, drop_aux, out, out_len, status, nullptr);
+}
+// degrade's worker (src/degrade.c:235-271): the same, with every decoded sample qts-rounded to qts_bits (1..16) in HBM before the encode
+extern "C" int s5gpu_recompress_batch_qts(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
+                                          int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
+                                          int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_recompress_batch_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return recompress_batch_any(n, rec, rec_len, from_rec, from_sig, to_rec, to_sig, new_read_group, drop_aux, out, out_len, status, nullptr, qts_bits);
 }
 extern "C" int s5gpu_recompress_batch_arena(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
                                             int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
@@ -1149,7 +1165,8 @@ static int recompress_encode_half(Ctx *c, uint32_t n, const std::vector<s5gpu_re
                                   const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, std::vector<uint64_t> *stream_off, s5host::Arena *ar = nullptr);
 
 static int recompress_batch_dev(int slot, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, int to_rec,
-                                int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status, s5host::Arena *ar) {
+                                int to_sig, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status, s5host::Arena *ar,
+                                uint32_t qts_bits) {
     s5host::CtxHold hold;
     int rc = hold.acquire(slot);
     if (rc) return rc;
@@ -1157,6 +1174,7 @@ static int recompress_batch_dev(int slot, uint32_t n, const void *const *rec, co
     std::vector<s5gpu_rec_desc_t> rd;
     std::vector<s5gpu_rec_fields_t> ff;
     if ((rc = s5host::decode_resident(c, n, rec, rec_len, from_rec, from_sig, rd, ff, status))) return rc;
+    if (qts_bits && (rc = s5host::qts_round_decoded(c, n, qts_bits))) return rc;
     return recompress_encode_half(c, n, rd, ff, to_rec, to_sig, new_read_group, drop_aux, out, out_len, nullptr, ar);
 }
 
@@ -1385,9 +1403,9 @@ extern "C" void s5gpu_host_free(void *p) { if (p) (void)s5_pinned_free(p); }
 // read from disk, and the re-encoded records come back as one contiguous stream, exactly as the ordered write loop would emit
 // them — no per-record malloc or memcpy on either side (the reader thread of the reference's loop, src/view.c:265-278, spends
 // its time in exactly those).  Device g of G takes the g-th contiguous share of the records.
-extern "C" int s5gpu_recompress_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
-                                       int from_sig, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void *out_buf,
-                                       size_t out_cap, uint64_t *out_off, int32_t *status) {
+static int recompress_stream_any(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                 int from_sig, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void *out_buf,
+                                 size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !out_buf || !out_off) { s5gpu_set_error("s5gpu_recompress_stream: NULL argument"); return S5GPU_ERR_ARG; }
     for (uint32_t i = 0; i < n; i++) {
@@ -1417,6 +1435,7 @@ extern "C" int s5gpu_recompress_stream(uint32_t n, const void *chunk, size_t chu
         std::vector<s5gpu_rec_fields_t> ff;
         std::vector<uint64_t> off;
         if ((r = decode_resident_impl(c, m, rec.data(), len.data(), from_rec, from_sig, rd, ff, status ? status + lo : nullptr, &fs))) return sg.fail(r, slot);
+        if (qts_bits && (r = s5host::qts_round_decoded(c, m, qts_bits))) return sg.fail(r, slot);
         if ((r = recompress_encode_half(c, m, rd, ff, to_rec, to_sig, new_read_group ? new_read_group + lo : nullptr, drop_aux, nullptr, nullptr, &off))) return sg.fail(r, slot);
         uint64_t base = 0;
         bool copy = false;
@@ -1438,4 +1457,17 @@ extern "C" int s5gpu_recompress_stream(uint32_t n, const void *chunk, size_t chu
         return S5GPU_ERR_NOMEM;
     }
     return S5GPU_OK;
+}
+extern "C" int s5gpu_recompress_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                       int from_sig, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void *out_buf,
+                                       size_t out_cap, uint64_t *out_off, int32_t *status) {
+    return recompress_stream_any(n, chunk, chunk_bytes, rec_pos, rec_len, from_rec, from_sig, to_rec, to_sig, new_read_group, drop_aux, out_buf,
+                                 out_cap, out_off, status, 0);
+}
+extern "C" int s5gpu_recompress_stream_qts(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int from_rec,
+                                           int from_sig, int to_rec, int to_sig, const uint32_t *new_read_group, int drop_aux, void *out_buf,
+                                           size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
+    if (qts_bits < 1 || qts_bits > 16) { s5gpu_set_error("s5gpu_recompress_stream_qts: bits %u outside 1..16", qts_bits); return S5GPU_ERR_ARG; }
+    return recompress_stream_any(n, chunk, chunk_bytes, rec_pos, rec_len, from_rec, from_sig, to_rec, to_sig, new_read_group, drop_aux, out_buf,
+                                 out_cap, out_off, status, qts_bits);
 }

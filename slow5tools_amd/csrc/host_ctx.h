@@ -109,6 +109,8 @@ int encode_and_collect(Ctx *c, uint32_t n, const std::vector<s5gpu_read_desc_t> 
 // decode host records, results resident in c->d_pay / c->d_sig2 (host_api.hip)
 int decode_resident(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig,
                     std::vector<s5gpu_rec_desc_t> &rd, std::vector<s5gpu_rec_fields_t> &ff, int32_t *status);
+// qts-round (slow5tools degrade) the signals decode_resident left in c->d_sig2, on c->st; bits 1..16 (host_api.hip)
+int qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits);
 // ... the records sitting framed in one host buffer (a file chunk): [base, base + bytes) is uploaded as it is, rec[i] point into it
 int decode_resident_framed(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig,
                            std::vector<s5gpu_rec_desc_t> &rd, std::vector<s5gpu_rec_fields_t> &ff, int32_t *status, const uint8_t *base, size_t bytes);
@@ -175,6 +177,11 @@ struct ShareGather {
     }
 };
 }  // namespace s5host
+
+// k_qts_round over n records in order: sig_off (u64) of record i at sig_off + i * off_stride, n_samples (u32) at n_samples + i * len_stride,
+// all on the device (kernels.hip; s5gpu_qts_round_dev is its plain-array form)
+int s5_qts_round_strided(int16_t *sig, uint32_t n, const void *sig_off, uint32_t off_stride, const void *n_samples, uint32_t len_stride,
+                         uint32_t bits, hipStream_t st);
 
 static inline uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 

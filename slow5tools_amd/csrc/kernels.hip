@@ -1499,6 +1499,87 @@ __global__ __launch_bounds__(NT) void k_patch_u32(uint8_t *base, const uint64_t 
 }
 
 // ------------------------------------------------------------------------------------------------
+// qts rounding of decoded signals in place (slow5tools degrade: slow5_rec_qts_round, src/degrade.c:255)
+// ------------------------------------------------------------------------------------------------
+// y = round x to the nearest multiple of 2^b, ties toward +inf, in int32; a y past 32767 steps down by 2^b (it keeps its b trailing
+// zeros and stays an int16).  The fixtures pin the non-negative samples only (every sample of tests/golden/ref/raw/degrade lies in
+// 271..1464, where round-half-up and round-half-away-from-zero agree).  Negative ties and the top clamp are OUR CHOICE: ties go toward
+// +inf on both sides of zero (-6 at b = 2 gives -4), and 32767 at b = 1 gives 32766, not -32768.
+__device__ __forceinline__ int32_t qts1(int32_t x, int32_t half, int32_t keep, int32_t step) {
+    int32_t y = (x + half) & keep;   // == ((x + half) >> b) << b in two's complement
+    if (y > 32767) y -= step;
+    return y;
+}
+__device__ __forceinline__ uint32_t qts2(uint32_t w, int32_t half, int32_t keep, int32_t step) {
+    const int32_t lo = qts1((int32_t)(int16_t)(w & 0xFFFFu), half, keep, step), hi = qts1((int32_t)w >> 16, half, keep, step);
+    return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16);
+}
+__device__ __forceinline__ uint4 qts8(uint4 v, int32_t half, int32_t keep, int32_t step) {
+    v.x = qts2(v.x, half, keep, step); v.y = qts2(v.y, half, keep, step);
+    v.z = qts2(v.z, half, keep, step); v.w = qts2(v.w, half, keep, step);
+    return v;
+}
+// Where the records' samples are: sig_off (u64) and n_samples (u32) of record i at off + i * off_stride / len + i * len_stride, so
+// the same kernel reads plain arrays (s5gpu_qts_round_dev) and the descriptor tables the pipelines already hold on the device.
+struct QtsRecs {
+    const uint8_t *off, *len;
+    uint32_t off_stride, len_stride, n;
+    __device__ __forceinline__ uint64_t o(uint32_t i) const { return *(const uint64_t *)(off + (uint64_t)i * off_stride); }
+    __device__ __forceinline__ uint32_t l(uint32_t i) const { return *(const uint32_t *)(len + (uint64_t)i * len_stride); }
+};
+// The records lie in order (sig_off[i] + n_samples[i] <= sig_off[i + 1], every sig_off a multiple of 8).  The samples between the first
+// record's start and the last one's end are cut into as many equal runs of whole 8-sample chunks as the grid has waves, whatever the
+// records' lengths: one 2 M-sample read is spread over the whole GPU as evenly as a batch of thousands of 4 k-sample reads.  A wave finds
+// the record under its run's start by a 64-way search (each lane probes one point), then walks the records of its run: 16-byte loads and
+// stores over the whole chunks, one 2-byte load / store per sample of a record's last partial chunk.  Nothing outside [sig_off,
+// sig_off + n_samples) of a record is read or written.
+constexpr int QTS_UNROLL = 4;
+__global__ __launch_bounds__(NT) void k_qts_round(int16_t *__restrict__ sig, QtsRecs R, uint32_t bits) {
+    const uint32_t lane = lane_id();
+    const int32_t step = 1 << bits, half = step >> 1, keep = -step;
+    const uint64_t nwaves = (uint64_t)gridDim.x * NW, w = (uint64_t)blockIdx.x * NW + wave_id();
+    const uint64_t s0 = R.o(0), s1 = R.o(R.n - 1) + R.l(R.n - 1);
+    const uint64_t chunks = s1 > s0 ? (s1 - s0 + 7) / 8 : 0;
+    const uint64_t A = s0 + 8 * (w * chunks / nwaves), B = s0 + 8 * ((w + 1) * chunks / nwaves);
+    if (A >= B) return;
+    // the last record that starts at or before A: off[lo] <= A < off[hi] (hi = n: past the end)
+    uint32_t lo = 0, hi = R.n;
+    while (hi - lo > 1) {
+        const uint32_t span = hi - lo;
+        const uint32_t p = lo + (uint32_t)((uint64_t)span * lane / 64);            // lane 0 probes lo itself (true)
+        const bool le = R.o(p) <= A;
+        const uint64_t m = __ballot(le);                                            // monotone in the lane: lanes 0..k set
+        const uint32_t k = 63 - __builtin_clzll(m);
+        const uint32_t nlo = __shfl(p, k);
+        const uint32_t nhi = k == 63 ? hi : __shfl(p, k + 1);
+        lo = nlo; hi = nhi;
+    }
+    for (uint32_t r = lo; r < R.n; r++) {
+        const uint64_t o = R.o(r);
+        if (o >= B) break;
+        const uint64_t e = o + R.l(r);
+        const uint64_t a = o > A ? o : A, z = e < B ? e : B;
+        if (a >= z) continue;
+        uint4 *p = (uint4 *)(sig + a);
+        const uint64_t nf = (z - a) / 8;
+        uint64_t k = lane;
+        for (; k + 64 * (QTS_UNROLL - 1) < nf; k += 64 * QTS_UNROLL) {   // all loads in flight before the first store
+            uint4 v[QTS_UNROLL];
+#pragma unroll
+            for (int u = 0; u < QTS_UNROLL; u++) v[u] = p[k + 64 * u];
+#pragma unroll
+            for (int u = 0; u < QTS_UNROLL; u++) p[k + 64 * u] = qts8(v[u], half, keep, step);
+        }
+        for (; k < nf; k += 64) p[k] = qts8(p[k], half, keep, step);
+        const uint32_t t = (uint32_t)((z - a) & 7);                     // only at a record's end (A and B are whole chunks)
+        if (lane < t) {
+            int16_t *q = sig + a + 8 * nf + lane;
+            *q = (int16_t)qts1(*q, half, keep, step);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // compaction: slots -> contiguous record stream (the ordered fwrite of src/view.c:296-299)
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_CH = NT * 4;
@@ -2369,6 +2450,30 @@ extern "C" int s5gpu_patch_u32_dev(uint8_t *base, const uint64_t *off, const uin
     hipLaunchKernelGGL(k_patch_u32, dim3((n + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream_, base, off, val, n);
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
+}
+
+// k_qts_round: four workgroups of four waves per CU of the current device (the runs are equal, so a wave that is done leaves nothing behind)
+int s5_qts_round_strided(int16_t *sig, uint32_t n, const void *sig_off, uint32_t off_stride, const void *n_samples, uint32_t len_stride,
+                         uint32_t bits, hipStream_t st) {
+    if (bits < 1 || bits > 16) { s5gpu_set_error("qts rounding: bits %u outside 1..16", bits); return S5GPU_ERR_ARG; }
+    if (n == 0) return S5GPU_OK;
+    if (!sig || !sig_off || !n_samples) { s5gpu_set_error("qts rounding: NULL argument"); return S5GPU_ERR_ARG; }
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    int cu = dev >= 0 && dev < 64 ? cus[dev].load() : 0;
+    if (cu <= 0) {
+        HIP_TRY(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
+        if (cu <= 0) cu = 256;
+        if (dev >= 0 && dev < 64) cus[dev].store(cu);
+    }
+    QtsRecs R = {(const uint8_t *)sig_off, (const uint8_t *)n_samples, off_stride, len_stride, n};
+    hipLaunchKernelGGL(k_qts_round, dim3(4 * cu), dim3(NT), 0, st, sig, R, bits);
+    HIP_TRY(hipGetLastError());
+    return S5GPU_OK;
+}
+extern "C" int s5gpu_qts_round_dev(int16_t *sig, uint32_t n, const uint64_t *sig_off, const uint32_t *n_samples, uint32_t bits, void *stream_) {
+    return s5_qts_round_strided(sig, n, sig_off, sizeof(uint64_t), n_samples, sizeof(uint32_t), bits, (hipStream_t)stream_);
 }
 
 // ---- s5gpu_warmup: the code objects of this file and of ascii_kernels.hip are loaded by their first launch ----

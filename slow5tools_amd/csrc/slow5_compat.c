@@ -289,11 +289,23 @@ int slow5_decode(char **mem, size_t *bytes, struct slow5_rec **read, struct slow
     return 0;
 }
 
-int slow5_gpu_convert_batch(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
-                            const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
-                            const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len) {
-    if (from_fmt == SLOW5_FORMAT_BINARY && to_fmt == SLOW5_FORMAT_BINARY)
-        return slow5_gpu_recompress_batch(n, mem, bytes, from, to, new_read_group, drop_aux, out, out_len);
+/* bits 0: no rounding (the plain calls); 1..16: the _qts twins */
+static int convert_batch_any(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
+                             const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
+                             const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits) {
+    if (from_fmt == SLOW5_FORMAT_BINARY && to_fmt == SLOW5_FORMAT_BINARY) {
+        if (!bits) return slow5_gpu_recompress_batch(n, mem, bytes, from, to, new_read_group, drop_aux, out, out_len);
+        const int fr = rec_code(from.record_method), fs = sig_code(from.signal_method);
+        const int tr = rec_code(to.record_method), ts = sig_code(to.signal_method);
+        if (n < 0 || fr < 0 || fs < 0 || tr < 0 || ts < 0) { slow5_errno = SLOW5_ERR_PRESS; return -1; }
+        if (n == 0) return 0;
+        if (s5gpu_recompress_batch_qts((uint32_t)n, (const void *const *)mem, bytes, fr, fs, tr, ts, new_read_group, drop_aux, out, out_len, NULL, bits) != S5GPU_OK) {
+            slow5_errno = SLOW5_ERR_RECPARSE;
+            return -1;
+        }
+        for (int64_t i = 0; i < n; i++) { free(mem[i]); mem[i] = NULL; }
+        return 0;
+    }
     const uint32_t n_aux = aux_meta ? aux_meta->num : 0;
     const uint8_t *types = aux_meta ? aux_meta->types : NULL;
     if (n < 0 || (from_fmt != SLOW5_FORMAT_ASCII && from_fmt != SLOW5_FORMAT_BINARY) || (to_fmt != SLOW5_FORMAT_ASCII && to_fmt != SLOW5_FORMAT_BINARY)) {
@@ -305,18 +317,23 @@ int slow5_gpu_convert_batch(int64_t n, char **mem, size_t *bytes, enum slow5_fmt
     if (from_fmt == SLOW5_FORMAT_ASCII && to_fmt == SLOW5_FORMAT_BINARY) {
         const int tr = rec_code(to.record_method), ts = sig_code(to.signal_method);
         if (tr < 0 || ts < 0) { slow5_errno = SLOW5_ERR_PRESS; return -1; }
-        rc = s5gpu_ascii_to_blow5_batch((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, tr, ts, new_read_group, drop_aux, out, out_len, NULL);
+        rc = bits ? s5gpu_ascii_to_blow5_batch_qts((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, tr, ts, new_read_group, drop_aux, out, out_len, NULL, bits)
+                  : s5gpu_ascii_to_blow5_batch((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, tr, ts, new_read_group, drop_aux, out, out_len, NULL);
     } else if (from_fmt == SLOW5_FORMAT_BINARY) {
         const int fr = rec_code(from.record_method), fs = sig_code(from.signal_method);
         if (fr < 0 || fs < 0) { slow5_errno = SLOW5_ERR_PRESS; return -1; }
-        rc = s5gpu_blow5_to_ascii_batch((uint32_t)n, (const void *const *)mem, bytes, fr, fs, n_aux, types, new_read_group, drop_aux, out, out_len, NULL);
+        rc = bits ? s5gpu_blow5_to_ascii_batch_qts((uint32_t)n, (const void *const *)mem, bytes, fr, fs, n_aux, types, new_read_group, drop_aux, out, out_len, NULL, bits)
+                  : s5gpu_blow5_to_ascii_batch((uint32_t)n, (const void *const *)mem, bytes, fr, fs, n_aux, types, new_read_group, drop_aux, out, out_len, NULL);
     } else {
-        /* ASCII -> ASCII: the reference parses and prints again; through BLOW5 (none, none) gives the same canonical text */
+        /* ASCII -> ASCII: the reference parses and prints again; through BLOW5 (none, none) gives the same canonical text (degrade: rounded
+         * in the first half) */
         void **mid = (void **)calloc((size_t)n, sizeof *mid);
         size_t *mid_len = (size_t *)calloc((size_t)n, sizeof *mid_len);
         if (!mid || !mid_len) { free(mid); free(mid_len); slow5_errno = SLOW5_ERR_MEM; return -1; }
-        rc = s5gpu_ascii_to_blow5_batch((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, S5GPU_REC_NONE, S5GPU_SIG_NONE, new_read_group,
-                                        drop_aux, mid, mid_len, NULL);
+        rc = bits ? s5gpu_ascii_to_blow5_batch_qts((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, S5GPU_REC_NONE, S5GPU_SIG_NONE,
+                                                   new_read_group, drop_aux, mid, mid_len, NULL, bits)
+                  : s5gpu_ascii_to_blow5_batch((uint32_t)n, (const char *const *)mem, bytes, n_aux, types, S5GPU_REC_NONE, S5GPU_SIG_NONE, new_read_group,
+                                               drop_aux, mid, mid_len, NULL);
         if (rc == S5GPU_OK) {
             for (int64_t i = 0; i < n; i++) { memmove(mid[i], (char *)mid[i] + 8, mid_len[i] - 8); mid_len[i] -= 8; }   /* drop the u64 prefix */
             rc = s5gpu_blow5_to_ascii_batch((uint32_t)n, (const void *const *)mid, mid_len, S5GPU_REC_NONE, S5GPU_SIG_NONE, drop_aux ? 0 : n_aux, types, NULL,
@@ -328,6 +345,31 @@ int slow5_gpu_convert_batch(int64_t n, char **mem, size_t *bytes, enum slow5_fmt
     if (rc != S5GPU_OK) { slow5_errno = SLOW5_ERR_RECPARSE; return -1; }
     for (int64_t i = 0; i < n; i++) { free(mem[i]); mem[i] = NULL; }
     return 0;
+}
+
+int slow5_gpu_convert_batch(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
+                            const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
+                            const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len) {
+    return convert_batch_any(n, mem, bytes, from_fmt, from, aux_meta, to_fmt, to, new_read_group, drop_aux, out, out_len, 0);
+}
+
+int slow5_gpu_convert_batch_qts(int64_t n, char **mem, size_t *bytes, enum slow5_fmt from_fmt, slow5_press_method_t from,
+                                const struct slow5_aux_meta *aux_meta, enum slow5_fmt to_fmt, slow5_press_method_t to,
+                                const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits) {
+    if (bits < 1 || bits > 16) { slow5_errno = SLOW5_ERR_ARG; return -1; }
+    return convert_batch_any(n, mem, bytes, from_fmt, from, aux_meta, to_fmt, to, new_read_group, drop_aux, out, out_len, bits);
+}
+
+/* slow5lib's per-record rounding (called at src/degrade.c:255): the rule of s5gpu_qts_round_dev, in plain C over one record.  bits outside
+ * 1..16 leave the record as it is. */
+void slow5_rec_qts_round(struct slow5_rec *r, uint8_t bits) {
+    if (!r || !r->raw_signal || bits < 1 || bits > 16) return;
+    const int32_t step = (int32_t)1 << bits, half = step >> 1;
+    for (uint64_t i = 0; i < r->len_raw_signal; i++) {
+        int32_t y = ((int32_t)r->raw_signal[i] + half) & -step;
+        if (y > 32767) y -= step;
+        r->raw_signal[i] = (int16_t)y;
+    }
 }
 
 int slow5_gpu_recompress_batch(int64_t n, char **mem, size_t *bytes, slow5_press_method_t from, slow5_press_method_t to,
@@ -442,6 +484,22 @@ int slow5_gpu_hook_convert(int64_t n, char **mem, size_t *bytes, int from_fmt, i
     }
     return slow5_gpu_convert_batch(n, mem, bytes, (enum slow5_fmt)from_fmt, from, am.num ? &am : NULL, (enum slow5_fmt)to_fmt, to, new_read_group,
                                    drop_aux, out, out_len);
+}
+
+int slow5_gpu_hook_convert_qts(int64_t n, char **mem, size_t *bytes, int from_fmt, int from_record_method, int from_signal_method,
+                               const char *aux_types_line, int to_fmt, int to_record_method, int to_signal_method,
+                               const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits) {
+    slow5_press_method_t from = {(enum slow5_press_method)from_record_method, (enum slow5_press_method)from_signal_method};
+    slow5_press_method_t to = {(enum slow5_press_method)to_record_method, (enum slow5_press_method)to_signal_method};
+    uint8_t types[1024];
+    struct slow5_aux_meta am = {0, types};
+    if (aux_types_line) {
+        const int k = s5gpu_aux_types_parse(aux_types_line, strlen(aux_types_line), types, sizeof types);
+        if (k < 0) { slow5_errno = SLOW5_ERR_TYPE; return -1; }
+        am.num = (uint32_t)k;
+    }
+    return slow5_gpu_convert_batch_qts(n, mem, bytes, (enum slow5_fmt)from_fmt, from, am.num ? &am : NULL, (enum slow5_fmt)to_fmt, to, new_read_group,
+                                       drop_aux, out, out_len, bits);
 }
 
 int slow5_gpu_hook_depress_parse(int64_t n, char **mem, size_t *bytes, int from_record_method, int from_signal_method, slow5_gpu_read_t *reads) {

@@ -96,6 +96,32 @@ def decode_records(records, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, raise_on
     return out
 
 
+def degrade_records(records, bits, from_rec=REC_ZLIB, from_sig=SIG_SVB_ZD, to_rec=REC_ZLIB, to_sig=SIG_EX_ZD):
+    """slow5tools degrade's worker for a batch (src/degrade.c:235-271) through s5gpu_recompress_batch_qts: records (bytes without the
+    u64 prefix) decoded, every sample rounded to a multiple of 2**bits (include/slow5gpu.h, s5gpu_qts_round_dev), re-encoded with
+    (to_rec, to_sig).  Returns list of bytes, each [u64 size][record]."""
+    L = _lib.lib()
+    n = len(records)
+    if n == 0:
+        return []
+    vp = C.c_void_p
+    rb = [bytes(r) for r in records]
+    rbuf = [C.create_string_buffer(r, max(len(r), 1)) for r in rb]
+    rec_p = (vp * n)(*[C.addressof(b) for b in rbuf])
+    rl = (C.c_size_t * n)(*[len(r) for r in rb])
+    out = (vp * n)()
+    out_len = (C.c_size_t * n)()
+    check(L.s5gpu_recompress_batch_qts(n, rec_p, rl, from_rec, from_sig, to_rec, to_sig, None, 0, out, out_len, None, bits),
+          "s5gpu_recompress_batch_qts")
+    libc = C.CDLL(None)
+    libc.free.argtypes = [vp]
+    res = []
+    for i in range(n):
+        res.append(C.string_at(out[i], out_len[i]))
+        libc.free(out[i])
+    return res
+
+
 def decode_signals_dev(records, rec_method=REC_ZLIB, max_pay_cap=None, sig_caps=None, scratch_bytes=None, device="cuda:0", sig_method=SIG_SVB_ZD,
                        max_in_len=None):
     """s5gpu_decode_dev with S5GPU_DEC_NO_PAYLOAD: fields + signals only, the uncompressed records stay in reused scratch slots
