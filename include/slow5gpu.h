@@ -409,6 +409,56 @@ int s5gpu_blow5_to_ascii_stream_qts(uint32_t n, const void *chunk, size_t chunk_
                                     int from_sig, uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
                                     void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits);
 
+/* ---- skim (slow5tools skim, src/skim.c): every field of every read but the raw signal, one text line per record ----
+ * The line: read_id \t read_group \t digitisation \t offset \t range \t sampling_rate \t len_raw_signal \t . [\t aux]... \n, doubles as
+ * "%f" with trailing zeros and a bare '.' trimmed, len_raw_signal the SAMPLE count (read from the signal blob's head: the signal is never
+ * decoded), each aux field printed by the role its NAME gives it (src/skim.c:227-260; docs/codecs.md §4.9). */
+enum { S5GPU_SKIM_DOT = 0,      /* a field skim does not handle (arrays included): "."                            */
+       S5GPU_SKIM_STRING,       /* channel_number (char*): the string, "." when empty                             */
+       S5GPU_SKIM_DOUBLE,       /* median_before: "%f"-trimmed, NaN "."                                           */
+       S5GPU_SKIM_FLOAT,        /* tracked_scaling_shift / _scale, predicted_scaling_shift / _scale, time_since_mux_change */
+       S5GPU_SKIM_INT32,        /* read_number; "." for INT32_MAX                                                 */
+       S5GPU_SKIM_UINT8,        /* start_mux; "." for 255                                                         */
+       S5GPU_SKIM_UINT32,       /* num_reads_since_mux_change; "." for UINT32_MAX                                 */
+       S5GPU_SKIM_UINT64,       /* start_time, num_minknow_events; "." for UINT64_MAX                             */
+       S5GPU_SKIM_ENUM };       /* end_reason: its label from the header's enum{...}; "." for 255                 */
+#define S5GPU_SKIM_MAX_AUX 64
+#define S5GPU_SKIM_MAX_LABELS 1024
+#define S5GPU_SKIM_TEXT 16384
+/* record status of the skim calls beside 1-5 and 7 (s5gpu_rec_fields_t): an enum value at or past the label count */
+#define S5GPU_STATUS_BAD_ENUM 8
+/* What skim needs of a header, parsed once per file.  Field a's name and enum labels sit in text[]. */
+typedef struct s5gpu_skim_layout {
+    uint32_t n_aux;                              /* aux fields, header order                                  */
+    uint32_t n_labels_total;
+    uint32_t text_len;
+    uint32_t n_unhandled;                        /* fields with role S5GPU_SKIM_DOT (s5skim warns once each)  */
+    uint8_t type[S5GPU_SKIM_MAX_AUX];            /* S5GPU_AUX_* code: how the field's bytes are laid out      */
+    uint8_t role[S5GPU_SKIM_MAX_AUX];            /* S5GPU_SKIM_*: how it prints                               */
+    uint16_t n_labels[S5GPU_SKIM_MAX_AUX];       /* enum fields: label count                                  */
+    uint16_t label_first[S5GPU_SKIM_MAX_AUX];    /* enum fields: index of the first label in label_off / len  */
+    uint32_t name_off[S5GPU_SKIM_MAX_AUX];       /* field name at text + name_off, name_len bytes             */
+    uint32_t name_len[S5GPU_SKIM_MAX_AUX];
+    uint32_t label_off[S5GPU_SKIM_MAX_LABELS];   /* label l at text + label_off[l], label_len[l] bytes        */
+    uint16_t label_len[S5GPU_SKIM_MAX_LABELS];
+    char text[S5GPU_SKIM_TEXT];
+} s5gpu_skim_layout_t;
+/* header text (as stored in a BLOW5 header: the '@' lines, the types line "#char*\t...", the names line "#read_id\t...") -> layout.
+ * S5GPU_ERR_DATA when a field skim prints by name is declared with another type (slow5lib's slow5_aux_get_<type> fails on it) or the
+ * two '#' lines are missing or disagree; S5GPU_ERR_ARG when the header has more fields, labels or name bytes than the layout holds. */
+int s5gpu_skim_layout_parse(const char *header, size_t len, s5gpu_skim_layout_t *layout);
+/* The skim worker on a CHUNK of a BLOW5 file (records framed as for s5gpu_recompress_stream): the lines of the n records come back as ONE
+ * contiguous block of text in out_buf, out_off[i] = start of line i, out_off[n] = total.  Records are inflated on the device (zlib, zstd)
+ * or taken as they are (record press none), the lines formatted there (k_skim_format), one D2H of finished text.  Too little room:
+ * S5GPU_ERR_NOMEM and out_off[0] = the bytes needed.  A bad record fails the call with S5GPU_ERR_DATA; status[i] (may be NULL) says which:
+ * 1-5 as in s5gpu_rec_fields_t, 7 malformed record, S5GPU_STATUS_BAD_ENUM.  Several devices split the records as the other chunk calls do. */
+int s5gpu_skim_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+                      int sig_method, const s5gpu_skim_layout_t *layout, void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status);
+/* ... on n records anywhere in host memory (bytes without the u64 prefix): out[i] = line i, malloc'd and NUL-terminated (a C string, as the
+ * reference's print loop takes it: src/skim.c:416-420), out_len[i] its length without the NUL */
+int s5gpu_skim_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, const s5gpu_skim_layout_t *layout,
+                     void **out, size_t *out_len, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,14 @@ int slow5_gpu_hook_convert_qts(int64_t n, char **mem, size_t *bytes, int from_fm
                                const char *aux_types_line, int to_fmt, int to_record_method, int to_signal_method,
                                const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, uint8_t bits);
 
+/* skim's work_db (src/skim.c:410, worker process_read :316-335): out[i] = the skim line of record mem[i], malloc'd, ending in '\n' and
+ * NUL-terminated; out_len[i] = its length without the NUL.  The ordered print loop (printf("%s") + free, src/skim.c:416-420) is
+ * unchanged.  header / header_len: the file's header text (the '@' lines and the two '#' lines) — the aux fields and the enum labels
+ * are read from it.  mem[i] are freed and set NULL like the reference's worker does
+ * (src/skim.c:323).  The lines are formatted on the GPU; the raw signal is never decoded. */
+int slow5_gpu_hook_skim(int64_t n, char **mem, size_t *bytes, int record_method, int signal_method, const char *header, size_t header_len,
+                        void **out, size_t *out_len);
+
 /* One decoded read, for callers that fill their own slow5_rec_t (get --benchmark src/get.c:52, skim src/skim.c:320, split).
  * read_id and aux point INTO the uncompressed record that replaced mem[i] (the caller frees mem[i], as after
  * slow5_rec_depress_parse, src/view.c:41); raw_signal is a malloc'd buffer the caller owns. */

@@ -45,6 +45,19 @@ class DecodeArgs(C.Structure):
 assert C.sizeof(DecodeArgs) == 72
 
 
+SKIM_MAX_AUX, SKIM_MAX_LABELS, SKIM_TEXT = 64, 1024, 16384
+SKIM_DOT, SKIM_STRING, SKIM_DOUBLE, SKIM_FLOAT, SKIM_INT32, SKIM_UINT8, SKIM_UINT32, SKIM_UINT64, SKIM_ENUM = range(9)
+STATUS_BAD_ENUM = 8
+
+
+class SkimLayout(C.Structure):
+    """s5gpu_skim_layout_t"""
+    _fields_ = [("n_aux", C.c_uint32), ("n_labels_total", C.c_uint32), ("text_len", C.c_uint32), ("n_unhandled", C.c_uint32),
+                ("type", C.c_uint8 * SKIM_MAX_AUX), ("role", C.c_uint8 * SKIM_MAX_AUX), ("n_labels", C.c_uint16 * SKIM_MAX_AUX),
+                ("label_first", C.c_uint16 * SKIM_MAX_AUX), ("name_off", C.c_uint32 * SKIM_MAX_AUX), ("name_len", C.c_uint32 * SKIM_MAX_AUX),
+                ("label_off", C.c_uint32 * SKIM_MAX_LABELS), ("label_len", C.c_uint16 * SKIM_MAX_LABELS), ("text", C.c_char * SKIM_TEXT)]
+
+
 class S5GpuError(RuntimeError):
     pass
 
@@ -113,6 +126,10 @@ def lib():
     L.s5gpu_ascii_to_blow5_stream_qts.argtypes = [u32, vp, C.c_size_t, vp, vp, u32, vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, u32]
     L.s5gpu_blow5_to_ascii_batch_qts.argtypes = [u32, vp, vp, i32, i32, u32, vp, vp, i32, vp, vp, vp, u32]
     L.s5gpu_blow5_to_ascii_stream_qts.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, u32, vp, vp, i32, vp, C.c_size_t, vp, vp, u32]
+    # skim: the header's layout, the chunk call and the pointer-array call
+    L.s5gpu_skim_layout_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(SkimLayout)]
+    L.s5gpu_skim_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, C.POINTER(SkimLayout), vp, C.c_size_t, vp, vp]
+    L.s5gpu_skim_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(SkimLayout), vp, vp, vp]
     _LIB = L
     return L
 

@@ -647,6 +647,8 @@ static uint64_t payload_guess(int rec_method, const void *rec, size_t len) {
     return len;
 }
 
+uint64_t s5host::payload_guess_of(int rec_method, const void *rec, size_t len) { return payload_guess(rec_method, rec, len); }
+
 static int decode_batch_dev(int slot, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
                             void **payload, int16_t **sig, s5gpu_rec_fields_t *fields);
 

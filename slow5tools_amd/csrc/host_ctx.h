@@ -109,6 +109,8 @@ int encode_and_collect(Ctx *c, uint32_t n, const std::vector<s5gpu_read_desc_t> 
 // decode host records, results resident in c->d_pay / c->d_sig2 (host_api.hip)
 int decode_resident(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig,
                     std::vector<s5gpu_rec_desc_t> &rd, std::vector<s5gpu_rec_fields_t> &ff, int32_t *status);
+// first guess at a record's uncompressed size (a zstd frame may say it; zlib: 4x + 4 KiB) (host_api.hip)
+uint64_t payload_guess_of(int rec_method, const void *rec, size_t len);
 // qts-round (slow5tools degrade) the signals decode_resident left in c->d_sig2, on c->st; bits 1..16 (host_api.hip)
 int qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits);
 // ... the records sitting framed in one host buffer (a file chunk): [base, base + bytes) is uploaded as it is, rec[i] point into it

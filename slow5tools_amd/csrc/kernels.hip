@@ -2423,6 +2423,17 @@ extern "C" int s5gpu_compact_dev(uint32_t n, const s5gpu_read_desc_t *desc, cons
     return S5GPU_OK;
 }
 
+// the scan of s5gpu_compact_dev alone: off[i] = len[0] + ... + len[i-1], off[n] = total (the line offsets of skim_api.hip)
+int s5_scan_lengths(const uint32_t *len, uint32_t n, uint64_t *off, uint64_t *tmp, hipStream_t st) {
+    if (n == 0) return S5GPU_OK;
+    const uint32_t nb = (n + SCAN_CH - 1) / SCAN_CH;
+    hipLaunchKernelGGL(k_scan_partial, dim3(nb), dim3(NT), 0, st, len, n, tmp);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(NT), 0, st, tmp, nb);
+    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(NT), 0, st, len, n, tmp, off);
+    HIP_TRY(hipGetLastError());
+    return S5GPU_OK;
+}
+
 // slot r (desc[r].out_off in `slots`, len[r] bytes) -> dst + off[r]: k_compact with the destinations given (the text assembly of ascii_api.hip)
 extern "C" int s5gpu_scatter_slots_dev(uint32_t n, const s5gpu_read_desc_t *desc, const uint8_t *slots, const uint32_t *len, const uint64_t *off, uint8_t *dst,
                                        void *stream_) {

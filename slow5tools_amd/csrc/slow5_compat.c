@@ -502,6 +502,21 @@ int slow5_gpu_hook_convert_qts(int64_t n, char **mem, size_t *bytes, int from_fm
                                        drop_aux, out, out_len, bits);
 }
 
+int slow5_gpu_hook_skim(int64_t n, char **mem, size_t *bytes, int record_method, int signal_method, const char *header, size_t header_len,
+                        void **out, size_t *out_len) {
+    if (n < 0 || n > 0xFFFFFFFFll || !hook_method_ok(record_method, signal_method) || !header) { slow5_errno = SLOW5_ERR_ARG; return -1; }
+    if (n == 0) return 0;
+    s5gpu_skim_layout_t *layout = (s5gpu_skim_layout_t *)malloc(sizeof *layout);
+    if (!layout) { slow5_errno = SLOW5_ERR_MEM; return -1; }
+    if (s5gpu_skim_layout_parse(header, header_len, layout) != S5GPU_OK) { free(layout); slow5_errno = SLOW5_ERR_TYPE; return -1; }
+    const int rc = s5gpu_skim_batch((uint32_t)n, (const void *const *)mem, bytes, rec_code((enum slow5_press_method)record_method),
+                                    sig_code((enum slow5_press_method)signal_method), layout, out, out_len, NULL);
+    free(layout);
+    if (rc != S5GPU_OK) { slow5_errno = SLOW5_ERR_RECPARSE; return -1; }
+    for (int64_t i = 0; i < n; i++) { free(mem[i]); mem[i] = NULL; }   /* the reference's worker frees the input record (src/skim.c:323) */
+    return 0;
+}
+
 int slow5_gpu_hook_depress_parse(int64_t n, char **mem, size_t *bytes, int from_record_method, int from_signal_method, slow5_gpu_read_t *reads) {
     if (n < 0 || !hook_method_ok(from_record_method, from_signal_method)) { slow5_errno = SLOW5_ERR_PRESS; return -1; }
     if (n == 0) return 0;
