@@ -13,12 +13,17 @@
  *        get --benchmark (get.c:52): fetch + decode only, nothing written; prints reads/s and the batch latencies of the decode call
  *   s5get --random in.blow5 N seed out_ids.txt
  *        N ids drawn uniformly (with replacement) from the index: the id list of BASELINE configs[4] (100 k ids, seed 1)
+ *   s5get [--to slow5|blow5] [-o out] [-l ids.txt] [--skip] [--index in.idx] [-c rec] [-s sig] [-K K] [-t readers] in.[sb]low5 [read_id ...]
+ *        slow5tools get's own command line (src/get.c:110-330), taken whenever an option is given or fewer than three positional arguments:
+ *        SLOW5 or BLOW5 in, SLOW5 (default, on stdout) or BLOW5 out; ids from the arguments, else the list, else stdin.
  */
 #define _GNU_SOURCE
+#include <getopt.h>
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -62,10 +67,13 @@ typedef struct {
     uint64_t n_ids;
     int64_t K, n_batches, next_fill, next_work;
     slow5_press_method_t from, to;
-    int benchmark, skip, failed;
+    enum slow5_fmt in_fmt, out_fmt;  /* SLOW5 ASCII or BLOW5 on either side (the positional forms: BLOW5 -> BLOW5) */
+    const struct slow5_aux_meta *aux; /* the input header's aux column types (NULL: none) */
+    int benchmark, skip, warn_skip, failed;
     char why[320];
-    uint64_t missing;
+    uint64_t missing, in_size;
 } gpipe_t;
+static gpipe_t P;                    /* the pipeline of the process: set up by main or get_main, driven by run() */
 
 static void gfail(gpipe_t *P, const char *what, const char *arg) {
     pthread_mutex_lock(&P->mu);
@@ -118,7 +126,11 @@ static void *greader_main(void *arg) {
         for (uint64_t i = i0; i < i1; i++) {
             struct slow5_rec_idx e;
             if (slow5_idx_get(P->in->index, P->ids[i], &e) != 0) {
-                if (P->skip) { __sync_fetch_and_add(&P->missing, 1); continue; }
+                if (P->skip) {
+                    __sync_fetch_and_add(&P->missing, 1);
+                    if (P->warn_skip) fprintf(stderr, "s5get: warning: read id '%s' not found, skipped\n", P->ids[i]);
+                    continue;
+                }
                 gfail(P, "read id not in the index:", P->ids[i]);
                 return NULL;
             }
@@ -136,11 +148,15 @@ static void *greader_main(void *arg) {
                 if (r <= 0) { gfail(P, "pread failed for", P->ids[i]); return NULL; }
                 got += (size_t)r;
             }
-            uint64_t sz;
-            memcpy(&sz, b->in + at, 8);
-            if (sz + 8 != e.size) { gfail(P, "the index does not match the file at", P->ids[i]); return NULL; }
-            b->rec_pos[n] = at + 8;
-            b->rec_len[n] = (uint32_t)sz;
+            const int line = P->in_fmt == SLOW5_FORMAT_ASCII;           /* SLOW5: the record line itself, its newline included */
+            uint64_t sz = e.size - 8;
+            if (!line) memcpy(&sz, b->in + at, 8);
+            if (line ? e.size > 0xFFFFFFFFull || (b->in[at + e.size - 1] != '\n' && e.offset + e.size != P->in_size) : sz + 8 != e.size) {
+                gfail(P, "the index does not match the file at", P->ids[i]);   /* (only the file's last line may lack its newline) */
+                return NULL;
+            }
+            b->rec_pos[n] = line ? at : at + 8;
+            b->rec_len[n] = (uint32_t)(line ? e.size : sz);
             n++;
             at = (at + e.size + 15) & ~(size_t)15;
         }
@@ -150,6 +166,19 @@ static void *greader_main(void *arg) {
         pthread_cond_broadcast(&P->cv);
         pthread_mutex_unlock(&P->mu);
     }
+}
+
+/* a batch with SLOW5 text on either side: the stream call of its input / output pair */
+static int convert_stream(const gpipe_t *P, gslot_t *b) {
+    const uint32_t na = P->aux ? P->aux->num : 0;
+    const uint8_t *at = P->aux ? P->aux->types : NULL;
+    const int fr = rec_code_of(P->from.record_method), fs = sig_code_of(P->from.signal_method);
+    const int tr = rec_code_of(P->to.record_method), ts = sig_code_of(P->to.signal_method);
+    if (P->in_fmt == SLOW5_FORMAT_BINARY)
+        return s5gpu_blow5_to_ascii_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, fr, fs, na, at, NULL, 0, b->out, b->out_cap, b->off, NULL);
+    if (P->out_fmt == SLOW5_FORMAT_BINARY)
+        return s5gpu_ascii_to_blow5_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, na, at, tr, ts, NULL, 0, b->out, b->out_cap, b->off, NULL);
+    return s5gpu_ascii_to_ascii_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, na, at, NULL, 0, b->out, b->out_cap, b->off, NULL);
 }
 
 /* compute phase: the work_db() of get.c:364, one call per batch */
@@ -175,6 +204,8 @@ static void *gworker_main(void *arg) {
             if (P->benchmark)
                 rc = s5gpu_decode_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, rec_code_of(P->from.record_method), sig_code_of(P->from.signal_method),
                                          (int16_t *)b->out, b->out_cap / 2, b->off, b->fields);
+            else if (P->in_fmt == SLOW5_FORMAT_ASCII || P->out_fmt == SLOW5_FORMAT_ASCII)
+                rc = convert_stream(P, b);
             else
                 rc = s5gpu_recompress_stream(b->n, b->in, b->in_have, b->rec_pos, b->rec_len, rec_code_of(P->from.record_method), sig_code_of(P->from.signal_method),
                                              rec_code_of(P->to.record_method), sig_code_of(P->to.signal_method), NULL, 0, b->out, b->out_cap, b->off, NULL);
@@ -202,7 +233,7 @@ static void *gworker_main(void *arg) {
 static int cmp_d(const void *a, const void *b) { const double x = *(const double *)a, y = *(const double *)b; return x < y ? -1 : x > y; }
 
 static char **read_ids(const char *path, uint64_t *n_out) {
-    FILE *f = fopen(path, "r");
+    FILE *f = path ? fopen(path, "r") : stdin;
     if (!f) return NULL;
     uint64_t n = 0, cap = 1024;
     char **ids = (char **)malloc(sizeof(char *) * cap), *line = NULL;
@@ -215,7 +246,7 @@ static char **read_ids(const char *path, uint64_t *n_out) {
         ids[n++] = strdup(line);
     }
     free(line);
-    fclose(f);
+    if (f != stdin) fclose(f);
     *n_out = n;
     return ids;
 }
@@ -240,6 +271,98 @@ static int leave(void) {
     if (e && atoi(e)) { s5gpu_shutdown(); return EXIT_SUCCESS; }
     _exit(EXIT_SUCCESS);
 }
+static int run(FILE *out, int readers, double t_idx);
+
+/* several GPUs: S5VIEW_DEV_MASK (bit d = HIP device d) — every batch call then splits its records over them */
+static int init_dev_mask(void) {
+    const char *dm = getenv("S5VIEW_DEV_MASK");
+    return dm && strtoull(dm, NULL, 0) && s5gpu_init_mask(strtoull(dm, NULL, 0)) != S5GPU_OK ? -1 : 0;
+}
+static void set_batches(long long K) {
+    P.K = K < 1 ? 1 : K;
+    P.n_batches = (int64_t)((P.n_ids + (uint64_t)P.K - 1) / (uint64_t)P.K);
+    /* Round 5: eight slots of K x (4 KiB in + 16 KiB out) are 670 MB of pinned memory — 150 ms of page pinning for a job whose 24 batches
+     * take 35 ms of GPU time.  A job gets one slot per six batches (2 .. 8), and no more reader threads than slots. */
+    P.nslot = P.n_batches / 6 < 2 ? 2 : P.n_batches / 6 > GSLOT ? GSLOT : (int)(P.n_batches / 6);
+}
+
+/* slow5tools get's command line: any option, or fewer than three positional arguments (every case of the reference's test/test_get.sh
+ * carries an option); `in ids.txt out [...]` and --benchmark stay what they were */
+static int get_form(int argc, char **argv) {
+    int positional = 0;
+    if (argc >= 2 && strcmp(argv[1], "--benchmark") == 0) return 0;
+    for (int k = 1; k < argc; k++) {
+        if (argv[k][0] == '-' && argv[k][1]) return 1;
+        positional++;
+    }
+    return positional < 3;
+}
+static int get_fail(const char *what, const char *arg) {
+    fprintf(stderr, "s5get: %s %s\n", what, arg ? arg : "");
+    return EXIT_FAILURE;
+}
+static int press_of(const char *s, enum slow5_press_method *m) {
+    static const char *const name[] = {"none", "zlib", "svb-zd", "zstd", "ex-zd"};   /* enum slow5_press_method order */
+    for (int k = 0; k < 5; k++) if (strcmp(s, name[k]) == 0) { *m = (enum slow5_press_method)k; return 0; }
+    return -1;
+}
+static int get_main(int argc, char **argv) {
+    static const struct option lo[] = {{"to", 1, NULL, 'b'}, {"compress", 1, NULL, 'c'}, {"sig-compress", 1, NULL, 's'}, {"batchsize", 1, NULL, 'K'},
+                                       {"output", 1, NULL, 'o'}, {"list", 1, NULL, 'l'}, {"skip", 0, NULL, 'k'}, {"threads", 1, NULL, 't'},
+                                       {"index", 1, NULL, 'x'}, {NULL, 0, NULL, 0}};
+    const char *to = NULL, *out_path = NULL, *list = NULL, *index = NULL, *ext;
+    long long K = 4096;
+    int readers = 8, opt;
+    P.to.record_method = SLOW5_COMPRESS_ZLIB; P.to.signal_method = SLOW5_COMPRESS_SVB_ZD;
+    while ((opt = getopt_long(argc, argv, "o:b:c:s:K:l:t:", lo, NULL)) != -1) {
+        switch (opt) {
+        case 'b': to = optarg; break;
+        case 'c': if (press_of(optarg, &P.to.record_method) != 0) return get_fail("unknown record compression", optarg); break;
+        case 's': if (press_of(optarg, &P.to.signal_method) != 0) return get_fail("unknown signal compression", optarg); break;
+        case 'K': K = atoll(optarg); break;
+        case 'o': out_path = optarg; break;
+        case 'l': list = optarg; break;
+        case 'k': P.skip = P.warn_skip = 1; break;
+        case 't': readers = atoi(optarg); break;
+        case 'x': index = optarg; break;
+        default: return get_fail("usage: s5get [--to slow5|blow5] [-o out] [-l ids.txt] [--skip] [--index in.idx] [-c rec] [-s sig] [-K K] [-t readers]",
+                                 "in.[sb]low5 [read_id ...]");
+        }
+    }
+    if (optind >= argc) return get_fail("missing slow5 or blow5 file", NULL);
+    /* the output format: the -o extension, else --to, else SLOW5 (on stdout without -o) */
+    enum slow5_fmt fmt_to = !to ? SLOW5_FORMAT_UNKNOWN : strcmp(to, "slow5") == 0 ? SLOW5_FORMAT_ASCII : strcmp(to, "blow5") == 0 ? SLOW5_FORMAT_BINARY : -1;
+    enum slow5_fmt fmt_ext = !out_path || !(ext = strrchr(out_path, '.')) ? SLOW5_FORMAT_UNKNOWN
+                           : strcmp(ext, ".slow5") == 0 ? SLOW5_FORMAT_ASCII : strcmp(ext, ".blow5") == 0 ? SLOW5_FORMAT_BINARY : SLOW5_FORMAT_UNKNOWN;
+    if ((int)fmt_to < 0) return get_fail("--to takes slow5 or blow5, not", to);
+    if (fmt_ext && fmt_to && fmt_ext != fmt_to) return get_fail("--to does not match the extension of", out_path);
+    if (out_path && !fmt_ext && !fmt_to) return get_fail("no output format (use --to) for", out_path);
+    P.out_fmt = fmt_ext ? fmt_ext : fmt_to ? fmt_to : SLOW5_FORMAT_ASCII;
+    if (init_dev_mask() != 0) return die("cannot initialise the devices of S5VIEW_DEV_MASK");
+    pthread_mutex_init(&P.mu, NULL);
+    pthread_cond_init(&P.cv, NULL);
+    if (optind + 1 < argc) { P.ids = argv + optind + 1; P.n_ids = (uint64_t)(argc - optind - 1); }   /* ids: the arguments, the list, stdin */
+    else if (!(P.ids = read_ids(list, &P.n_ids))) return get_fail("cannot read the read id list", list);
+    set_batches(K);
+    pthread_t init_th;
+    const int early_init = !(getenv("S5VIEW_DEV_MASK") && strtoull(getenv("S5VIEW_DEV_MASK"), NULL, 0));
+    const int early_init_started = early_init && pthread_create(&init_th, NULL, early_init_main, &P) == 0;
+    struct stat st;
+    if (!(P.in = slow5_open(argv[optind], "r")) || fstat(fileno(P.in->fp), &st) != 0) return get_fail("cannot open", argv[optind]);
+    P.in_size = (uint64_t)st.st_size;
+    P.in_fmt = P.in->format;
+    P.aux = P.in->header->aux_meta;
+    P.from.record_method = P.in->compress->record_press->method; P.from.signal_method = P.in->compress->signal_press->method;
+    FILE *out = out_path ? fopen(out_path, "wb") : stdout;            /* the header goes out before the index is loaded (src/get.c:276-283) */
+    if (!out) return get_fail("cannot open the output", out_path);
+    if (slow5_hdr_fwrite(out, P.in->header, P.out_fmt, P.to) < 0 || fflush(out) != 0) return die("header write failed");
+    const double t_idx0 = now_s();
+    if ((index ? slow5_idx_load_with(P.in, index) : slow5_idx_load(P.in)) != 0) return die("cannot load the index");
+    const double t_idx = now_s() - t_idx0;
+    if (early_init_started) pthread_join(init_th, NULL);
+    return run(out, readers < 1 ? 1 : readers, t_idx);
+}
+
 int main(int argc, char **argv) {
     if (argc >= 6 && strcmp(argv[1], "--random") == 0) {
         slow5_file_t *s = slow5_open(argv[2], "r");
@@ -261,6 +384,7 @@ int main(int argc, char **argv) {
     }
     g_t_main = now_s();
     { const char *e = getenv("S5VIEW_TIMING"); g_timing = e && atoi(e); }
+    if (get_form(argc, argv)) return get_main(argc, argv);
     const int benchmark = argc >= 2 && strcmp(argv[1], "--benchmark") == 0;
     char **av = argv + (benchmark ? 1 : 0);
     const int ac = argc - (benchmark ? 1 : 0);
@@ -269,12 +393,7 @@ int main(int argc, char **argv) {
                         "       s5get --benchmark in.blow5 ids.txt [K] [readers]\n       s5get --random in.blow5 N seed out_ids.txt\n");
         return EXIT_FAILURE;
     }
-    {   /* several GPUs: S5VIEW_DEV_MASK (bit d = HIP device d) — every batch call then splits its records over them */
-        const char *dm = getenv("S5VIEW_DEV_MASK");
-        if (dm && strtoull(dm, NULL, 0) && s5gpu_init_mask(strtoull(dm, NULL, 0)) != S5GPU_OK) return die("cannot initialise the devices of S5VIEW_DEV_MASK");
-    }
-    gpipe_t P;
-    memset(&P, 0, sizeof P);
+    if (init_dev_mask() != 0) return die("cannot initialise the devices of S5VIEW_DEV_MASK");
     pthread_mutex_init(&P.mu, NULL);
     pthread_cond_init(&P.cv, NULL);
     P.benchmark = benchmark;
@@ -282,15 +401,7 @@ int main(int argc, char **argv) {
     P.ids = read_ids(av[2], &P.n_ids);
     if (!P.ids) return die("cannot read the id list");
     stamp("id list read");
-    {
-        const int argk0 = benchmark ? 3 : 6;
-        P.K = ac > argk0 ? atoll(av[argk0]) : 4096;
-        if (P.K < 1) P.K = 1;
-        P.n_batches = (int64_t)((P.n_ids + (uint64_t)P.K - 1) / (uint64_t)P.K);
-        /* Round 5: eight slots of K x (4 KiB in + 16 KiB out) are 670 MB of pinned memory — 150 ms of page pinning for a job whose 24 batches
-         * take 35 ms of GPU time.  A job gets one slot per six batches (2 .. 8), and no more reader threads than slots. */
-        P.nslot = P.n_batches / 6 < 2 ? 2 : P.n_batches / 6 > GSLOT ? GSLOT : (int)(P.n_batches / 6);
-    }
+    set_batches(ac > (benchmark ? 3 : 6) ? atoll(av[benchmark ? 3 : 6]) : 4096);
     /* the HIP runtime and the device context come up (~0.15 s), and the batch slots are pinned, while the index is loaded (~0.13 s per million reads) */
     pthread_t init_th;
     const int early_init = !(getenv("S5VIEW_DEV_MASK") && strtoull(getenv("S5VIEW_DEV_MASK"), NULL, 0));     /* (a device mask has initialised the library already) */
@@ -317,6 +428,13 @@ int main(int argc, char **argv) {
     }
     const int readers = ac > argk + 1 ? atoi(av[argk + 1]) : 8;
     { const char *e = getenv("S5GET_SKIP"); P.skip = e && atoi(e); }
+    P.in_fmt = P.out_fmt = SLOW5_FORMAT_BINARY;
+    return run(out, readers, t_idx);
+}
+
+/* read, GPU and write phases of both command lines; out = the output with its header written (NULL: --benchmark) */
+static int run(FILE *out, int readers, double t_idx) {
+    const int benchmark = P.benchmark;
     P.fd = fileno(P.in->fp);
     for (int i = 0; i < P.nslot; i++) P.slot[i].seq = (int64_t)i - P.nslot;     /* (a slot's buffers are pinned by the reader that first fills it: gslot_alloc) */
     double *lat = (double *)malloc(sizeof(double) * (size_t)(P.n_batches ? P.n_batches : 1));
@@ -363,10 +481,10 @@ int main(int argc, char **argv) {
     const double dt = now_s() - t0;
     stamp("last batch done");
     if (P.failed) { fprintf(stderr, "s5get: %s\n", P.why); return EXIT_FAILURE; }
-    if (out) {
-        if (fseek(out, 0, SEEK_END) != 0 || slow5_eof_fwrite(out) < 0) return die("eof write failed");
-        if (fclose(out) != 0) return die("closing the output failed (its last bytes may not be on disk)");
+    if (out && P.out_fmt == SLOW5_FORMAT_BINARY) {   /* (the batches went out by write(2): the FILE's position first, unless it is a pipe) */
+        if ((lseek(fileno(out), 0, SEEK_CUR) >= 0 && fseek(out, 0, SEEK_END) != 0) || slow5_eof_fwrite(out) < 0) return die("eof write failed");
     }
+    if (out && (out == stdout ? fflush(out) : fclose(out)) != 0) return die("closing the output failed (its last bytes may not be on disk)");
     int64_t nl = P.n_batches;
     if (nl > 1 && (uint64_t)P.K * (uint64_t)nl != P.n_ids) nl--;       /* the last batch is a short one */
     qsort(lat, (size_t)nl, sizeof(double), cmp_d);

@@ -143,7 +143,8 @@ void slow5_rec_free(struct slow5_rec *read);
  * Only what view / merge / get need around the press path: open + header, sequential record framing, header and
  * EOF writers, and the read_id index.  slow5_open tells BLOW5 from SLOW5 ASCII by the file's first bytes; for ASCII,
  * slow5_get_next_mem returns one record line (without its newline) and slow5_hdr_fwrite prints the two '#' version lines
- * followed by the same header text.  The index calls are BLOW5 only. */
+ * followed by the same header text.  The index calls take both formats: a SLOW5 entry is one record line (offset = its first byte, size = its
+ * length with the line end), and slow5_get_mem returns that line without its line end. */
 slow5_file_t *slow5_open(const char *pathname, const char *mode);                 /* "r" only */
 /* the same with the format the caller parsed from --from / the extension (/root/reference/src/view.c:192, src/degrade.c:423):
  * SLOW5_FORMAT_UNKNOWN = look at the file; a named format must match what the file's first bytes say */
@@ -160,6 +161,7 @@ int slow5_hdr_fwrite(FILE *fp, struct slow5_hdr *header, enum slow5_fmt format, 
 long slow5_eof_fwrite(FILE *fp);                                                  /* "5WOLB", src/view.c:313 */
 int slow5_idx_create(slow5_file_t *s5p);   /* writes <pathname>.idx (slow5tools index, src/index.c) */
 int slow5_idx_load(slow5_file_t *s5p);     /* loads <pathname>.idx, building it first if absent (src/get.c:286) */
+int slow5_idx_load_with(slow5_file_t *s5p, const char *pathname);   /* the same with the index at `pathname`, NULL = default (get --index, src/get.c:294) */
 void slow5_idx_unload(slow5_file_t *s5p);
 /* where read_id's record sits in the file: offset of its u64 size prefix, size = 8 + record bytes (slow5lib's slow5_idx_get [RECALLED]); 0, or
  * -1 when the id is not in the index.  For loops that pread many records into one buffer (examples/s5get.c). */
@@ -167,7 +169,9 @@ struct slow5_rec_idx { uint64_t offset, size; };
 int slow5_idx_get(struct slow5_idx *index, const char *read_id, struct slow5_rec_idx *read_index);
 /* the ids of the index in file order (slow5_get_rids, /root/reference/src/skim.c): *n of them; the array and the strings stay the index's */
 char **slow5_get_rids(const slow5_file_t *s5p, uint64_t *n);
-/* raw record bytes of read_id (pread by index), malloc'd; the decode half of slow5_get goes through the batch hooks */
+/* raw record bytes of read_id (pread by index), malloc'd; the decode half of slow5_get goes through the batch hooks.  SLOW5: the record line
+ * without its line end ("\n" or "\r\n"), NUL-terminated; *n excludes the line end.  slow5_get parses such a line through the ASCII -> BLOW5
+ * (none, none) route. */
 void *slow5_get_mem(const char *read_id, size_t *n, const slow5_file_t *s5p);
 int slow5_get(const char *read_id, struct slow5_rec **read, slow5_file_t *s5p);   /* src/get.c:45 */
 

@@ -386,6 +386,15 @@ int s5gpu_blow5_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_byte
 int s5gpu_blow5_to_ascii_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig, uint32_t n_aux,
                                const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len,
                                int32_t *status);
+/* SLOW5 -> SLOW5 (get --to slow5 on a .slow5): every line printed again, byte for byte what slow5_gpu_convert_batch(ASCII -> ASCII) gives.
+ * Arguments, status[i] and the NOMEM protocol of s5gpu_ascii_to_blow5_stream without the press methods; the lines come back as ONE block
+ * laid out as by s5gpu_blow5_to_ascii_stream. */
+int s5gpu_ascii_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+                                uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
+                                void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status);
+/* its batch twin: lines (with or without the newline) -> lines ending in a newline, out[i] malloc'd */
+int s5gpu_ascii_to_ascii_batch(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+                               const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status);
 
 /* _qts twins of the convert calls (slow5tools degrade, src/degrade.c:235-271): the same arguments and results, with every sample
  * qts-rounded to qts_bits (1..16, else S5GPU_ERR_ARG; the rule at s5gpu_qts_round_dev) on the device between the stage that makes the

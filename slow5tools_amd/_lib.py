@@ -118,6 +118,8 @@ def lib():
     L.s5gpu_aux_types_parse.argtypes = [C.c_char_p, C.c_size_t, vp, u32]
     L.s5gpu_ascii_to_blow5_batch.argtypes = [u32, vp, vp, u32, vp, i32, i32, vp, i32, vp, vp, vp]
     L.s5gpu_blow5_to_ascii_batch.argtypes = [u32, vp, vp, i32, i32, u32, vp, vp, i32, vp, vp, vp]
+    L.s5gpu_ascii_to_ascii_batch.argtypes = [u32, vp, vp, u32, vp, vp, i32, vp, vp, vp]
+    L.s5gpu_ascii_to_ascii_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp]
     # degrade (qts rounding): the device entry and the _qts twins of the convert calls (trailing uint32_t qts_bits)
     L.s5gpu_qts_round_dev.argtypes = [vp, u32, vp, vp, u32, vp]
     L.s5gpu_recompress_batch_qts.argtypes = [u32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, u32]

@@ -1,4 +1,4 @@
-"""SLOW5 ASCII <-> BLOW5 for whole batches of records — thin ctypes wrappers.
+"""SLOW5 ASCII <-> BLOW5, and SLOW5 ASCII -> SLOW5 ASCII, for whole batches of records — thin ctypes wrappers.
 
 The reference does this inside slow5_rec_depress_parse / slow5_rec_to_mem when one side of `view` is a .slow5 file
 (/root/reference/src/view.c:35-57).  Here the raw_signal column is parsed / printed on the GPU."""
@@ -80,4 +80,23 @@ def blow5_to_ascii(records, types=b"", rec_method=REC_ZLIB, sig_method=SIG_SVB_Z
     if status is not None:
         status[:] = list(st)
     check(rc, "s5gpu_blow5_to_ascii_batch")
+    return _collect(out, out_len, n)
+
+
+def ascii_to_ascii(lines, types=b"", new_read_group=None, drop_aux=False, status=None):
+    """Record lines -> the same records printed again (the canonical SLOW5 text), each line ending in a newline."""
+    L = _lib.lib()
+    n = len(lines)
+    if n == 0:
+        return []
+    keep, ptr, lens = _ptrs(lines)
+    tb = (C.c_uint8 * max(len(types), 1))(*types)
+    rg = None if new_read_group is None else np.ascontiguousarray(new_read_group, dtype=np.uint32)
+    out = (C.c_void_p * n)()
+    out_len = (C.c_size_t * n)()
+    st = (C.c_int32 * n)()
+    rc = L.s5gpu_ascii_to_ascii_batch(n, ptr, lens, len(types), tb, rg.ctypes.data if rg is not None else None, int(drop_aux), out, out_len, st)
+    if status is not None:
+        status[:] = list(st)
+    check(rc, "s5gpu_ascii_to_ascii_batch")
     return _collect(out, out_len, n)

@@ -765,6 +765,206 @@ static int blow5_to_ascii_stream_any(uint32_t n, const void *chunk, size_t chunk
     return S5GPU_OK;
 }
 
+// SLOW5 -> SLOW5 on a CHUNK (get --to slow5 on a .slow5): the re-print of slow5_gpu_convert_batch(ASCII -> ASCII) without its BLOW5 record.
+// Scalar and aux columns parsed and printed back on the host into a prefix and a suffix per line; one H2D of the chunk; k_ascii_parse then
+// k_ascii_format on the raw_signal columns; prefix | signal | suffix put in place on the device as in s5gpu_blow5_to_ascii_stream; one D2H.
+extern "C" int s5gpu_ascii_to_ascii_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *line_pos, const uint32_t *line_len,
+                                           uint32_t n_aux, const uint8_t *aux_type, const uint32_t *new_read_group, int drop_aux,
+                                           void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
+    if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
+    if (!chunk || !line_pos || !line_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_ascii_to_ascii_stream: NULL argument"); return S5GPU_ERR_ARG; }
+    for (uint32_t i = 0; i < n; i++) {
+        if (status) status[i] = 0;
+        if (line_pos[i] > chunk_bytes || line_len[i] > chunk_bytes - line_pos[i]) { s5gpu_set_error("line %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
+    }
+    const int G = s5host::n_devices();
+    if (G == 0) return S5GPU_ERR_NODEV;
+    s5host::ShareGather sg(G);
+    auto share = [&](int slot, uint32_t lo, uint32_t hi) -> int {
+        s5host::CtxHold hold;
+        int r = hold.acquire(slot);
+        if (r) return sg.fail(r, slot);
+        Ctx *c = hold.c;
+        const uint32_t m = hi - lo;
+        const char *base_p = (const char *)chunk;
+        // 1. the scalar and aux columns on the host: parsed, then printed back into the prefix and suffix of the line
+        std::vector<Line> L(m);
+        std::vector<std::string> pre(m), suf(m);
+        uint64_t text_bytes = 0, b0 = UINT64_MAX, e1 = 0;
+        for (uint32_t i = lo; i < hi; i++) {
+            text_bytes += line_len[i];
+            b0 = b0 < line_pos[i] ? b0 : line_pos[i];
+            e1 = e1 > line_pos[i] + line_len[i] ? e1 : line_pos[i] + line_len[i];
+        }
+        b0 &= ~15ull;
+        const uint32_t out_aux = drop_aux ? 0 : n_aux;
+        parallel_for(m, text_bytes, [&](uint32_t a, uint32_t b) {
+            for (uint32_t i = a; i < b; i++) {
+                Line &l = L[i];
+                parse_line(base_p + line_pos[lo + i], line_len[lo + i], n_aux, aux_type, new_read_group ? new_read_group + lo + i : nullptr, drop_aux, l);
+                if (l.status) continue;
+                // head = u16 id_len | id | u32 rg | 4 x f64, as the BLOW5 record carries them
+                const uint8_t *h = (const uint8_t *)l.head.data();
+                uint16_t idl; uint32_t rg; double dv[4];
+                memcpy(&idl, h, 2); memcpy(&rg, h + 2 + idl, 4); memcpy(dv, h + 6 + idl, 32);
+                std::string &s = pre[i];
+                s.reserve(idl + 96);
+                s.append((const char *)h + 2, idl);
+                s.push_back('\t'); fmt_u64(s, rg);
+                for (int j = 0; j < 4; j++) { s.push_back('\t'); fmt_f64(s, dv[j]); }
+                s.push_back('\t'); fmt_u64(s, l.n_samples);
+                s.push_back('\t');
+                if (out_aux && !aux_to_text((const uint8_t *)l.aux.data(), l.aux.size(), out_aux, aux_type, suf[i])) l.status = 16;
+                suf[i].push_back('\n');
+            }
+        });
+        bool bad = false;
+        for (uint32_t i = 0; i < m; i++)
+            if (L[i].status) { bad = true; if (status) status[lo + i] = L[i].status; }
+        if (bad) { s5gpu_set_error("s5gpu_ascii_to_ascii_stream: at least one line is malformed (see status[i])"); return sg.fail(S5GPU_ERR_DATA, slot); }
+        // 2. layout: parse descriptors into the uploaded chunk, format descriptors into worst-case text slots (7 bytes / sample)
+        std::vector<s5gpu_txt_desc_t> tp(m), tf(m);
+        std::vector<s5gpu_read_desc_t> slots(m);
+        uint64_t so = 0, to = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            const uint64_t cap = up(7ull * L[i].n_samples + 16, 16);
+            if (cap > 0xFFFFFF00ull) { s5gpu_set_error("read %u: signal text larger than 4 GiB", lo + i); return sg.fail(S5GPU_ERR_ARG, slot); }
+            memset(&tp[i], 0, sizeof tp[i]);
+            tp[i].txt_off = (uint64_t)(L[i].sig - base_p) - b0; tp[i].sig_off = so; tp[i].txt_len = L[i].sig_len; tp[i].n_samples = L[i].n_samples;
+            memset(&tf[i], 0, sizeof tf[i]);
+            tf[i].txt_off = to; tf[i].sig_off = so; tf[i].txt_len = (uint32_t)cap; tf[i].n_samples = L[i].n_samples;
+            memset(&slots[i], 0, sizeof slots[i]);
+            slots[i].out_off = to; slots[i].slot_cap = (uint32_t)cap;
+            so += up(L[i].n_samples, 8);
+            to += cap;
+        }
+        const size_t b_td = up(sizeof(s5gpu_txt_desc_t) * m, 64), b_rd = up(sizeof(s5gpu_read_desc_t) * m, 64), b_g8 = up(8ull * m, 64), b_4 = up(4ull * m, 64);
+        // d_tdesc: parse desc | format desc | slot desc | parse status | txt_len | format status | (step 3) piece src | piece dst | piece len | sig dst
+        const size_t o_tf = b_td, o_rd = o_tf + b_td, o_ps = o_rd + b_rd, o_tl = o_ps + b_4, o_fs = o_tl + b_4, o_p = o_fs + b_4;
+        const size_t b_all = o_p + 2 * (2 * b_g8) + up(8ull * m, 64) + b_g8;
+        const uint64_t tbytes = e1 - b0;
+        if ((r = c->d_tdesc.reserve(b_all)) || (r = c->d_txt.reserve(tbytes + 64)) || (r = c->d_sig.reserve(so * 2 + 64)) || (r = c->d_gather.reserve(to + 64)) ||
+            (r = c->h_in.reserve(b_all)) || (r = c->h_out.reserve(3 * b_4 + 64)))
+            return sg.fail(r, slot);
+        uint8_t *h = (uint8_t *)c->h_in.p, *dv = (uint8_t *)c->d_tdesc.p;
+        memcpy(h, tp.data(), sizeof(s5gpu_txt_desc_t) * m);
+        memcpy(h + o_tf, tf.data(), sizeof(s5gpu_txt_desc_t) * m);
+        memcpy(h + o_rd, slots.data(), sizeof(s5gpu_read_desc_t) * m);
+        auto hip = [&](hipError_t e, const char *what) -> int {
+            if (e == hipSuccess) return 0;
+            s5gpu_set_error("%s failed: %s", what, hipGetErrorString(e));
+            return sg.fail(S5GPU_ERR_HIP, slot);
+        };
+        if ((r = hip(hipMemcpyAsync(c->d_txt.p, (const uint8_t *)chunk + b0, tbytes, hipMemcpyHostToDevice, c->st), "upload of the chunk"))) return r;
+        if ((r = hip(hipMemcpyAsync(dv, h, o_ps, hipMemcpyHostToDevice, c->st), "upload"))) return r;
+        int32_t *d_ps = (int32_t *)(dv + o_ps), *d_fs = (int32_t *)(dv + o_fs);
+        uint32_t *d_tl = (uint32_t *)(dv + o_tl);
+        if ((r = s5gpu_ascii_parse_dev(m, (const s5gpu_txt_desc_t *)dv, (const uint8_t *)c->d_txt.p, (int16_t *)c->d_sig.p, d_ps, c->st))) return sg.fail(r, slot);
+        if ((r = s5gpu_ascii_format_dev(m, (const s5gpu_txt_desc_t *)(dv + o_tf), (const int16_t *)c->d_sig.p, (uint8_t *)c->d_gather.p, d_tl, d_fs, c->st)))
+            return sg.fail(r, slot);
+        if ((r = hip(hipMemcpyAsync(c->h_out.p, d_ps, 3 * b_4, hipMemcpyDeviceToHost, c->st), "status download"))) return r;   // parse status | txt_len | format status
+        if ((r = hip(hipStreamSynchronize(c->st), "synchronise"))) return r;
+        s5_trace("ascii_to_ascii_stream: chunk uploaded, raw_signal parsed and printed again on the device");
+        const int32_t *hps = (const int32_t *)c->h_out.p, *hfs = (const int32_t *)((const uint8_t *)c->h_out.p + 2 * b_4);
+        const uint32_t *htl = (const uint32_t *)((const uint8_t *)c->h_out.p + b_4);
+        for (uint32_t i = 0; i < m; i++)
+            if (hps[i]) { bad = true; if (status) status[lo + i] = hps[i]; }
+        if (bad) { s5gpu_set_error("s5gpu_ascii_to_ascii_stream: raw_signal text of at least one line is malformed (see status[i])"); return sg.fail(S5GPU_ERR_DATA, slot); }
+        std::vector<uint32_t> tl(m);
+        for (uint32_t i = 0; i < m; i++) {
+            if (hfs[i] || htl[i] > tf[i].txt_len) { s5gpu_set_error("read %u: signal formatting failed (status %d)", lo + i, hfs[i]); return sg.fail(S5GPU_ERR_HIP, slot); }
+            tl[i] = htl[i];
+        }
+        // 3. prefix | signal text | suffix of every line to its place in the output block on the device, one D2H
+        std::vector<uint64_t> off(m + 1), p_src(2ull * m), p_dst(2ull * m), s_dst(m);
+        std::vector<uint32_t> p_len(2ull * m);
+        uint64_t bo = 0;
+        off[0] = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            p_src[2 * i] = bo; p_len[2 * i] = (uint32_t)pre[i].size(); p_dst[2 * i] = off[i]; bo += pre[i].size();
+            s_dst[i] = off[i] + pre[i].size();
+            p_src[2 * i + 1] = bo; p_len[2 * i + 1] = (uint32_t)suf[i].size(); p_dst[2 * i + 1] = s_dst[i] + tl[i]; bo += suf[i].size();
+            off[i + 1] = p_dst[2 * i + 1] + suf[i].size();
+        }
+        uint64_t base = 0;
+        bool copy = false;
+        if ((r = sg.place(slot, off[m], out_cap, &base, &copy))) return r;
+        if (!copy) return S5GPU_OK;
+        if ((r = c->d_stream.reserve(off[m] + 64)) || (r = c->d_aux.reserve(bo + 64)) || (r = c->h_in.reserve(b_all + bo + 64))) return r;
+        h = (uint8_t *)c->h_in.p;
+        uint8_t *hb = h + b_all;
+        for (uint32_t i = 0; i < m; i++) {
+            memcpy(hb + p_src[2 * i], pre[i].data(), pre[i].size());
+            memcpy(hb + p_src[2 * i + 1], suf[i].data(), suf[i].size());
+        }
+        const size_t o_pd = o_p + 2 * b_g8, o_pl = o_pd + 2 * b_g8, o_sd = o_pl + up(8ull * m, 64);
+        memcpy(h + o_p, p_src.data(), 16ull * m);
+        memcpy(h + o_pd, p_dst.data(), 16ull * m);
+        memcpy(h + o_pl, p_len.data(), 8ull * m);
+        memcpy(h + o_sd, s_dst.data(), 8ull * m);
+        HIP_TRY(hipMemcpyAsync(dv + o_p, h + o_p, b_all - o_p, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->d_aux.p, hb, bo, hipMemcpyHostToDevice, c->st));
+        if ((r = s5gpu_gather_dev(2 * m, (const uint64_t *)(dv + o_p), (const uint32_t *)(dv + o_pl), (const uint64_t *)(dv + o_pd),
+                                  (const uint8_t *)c->d_aux.p, (uint8_t *)c->d_stream.p, c->st)))
+            return r;
+        if ((r = s5gpu_scatter_slots_dev(m, (const s5gpu_read_desc_t *)(dv + o_rd), (const uint8_t *)c->d_gather.p, d_tl, (const uint64_t *)(dv + o_sd),
+                                         (uint8_t *)c->d_stream.p, c->st)))
+            return r;
+        HIP_TRY(hipMemcpyAsync((uint8_t *)out_buf + base, c->d_stream.p, off[m], hipMemcpyDeviceToHost, c->st));
+        for (uint32_t i = 0; i < m; i++) out_off[lo + i] = base + off[i];
+        if (hi == n) out_off[n] = base + off[m];
+        HIP_TRY(hipStreamSynchronize(c->st));
+        s5_trace("lines placed, block downloaded");
+        return S5GPU_OK;
+    };
+    // any way a share gives up releases the shares waiting behind it (ShareGather::place)
+    const int rc = s5host::for_each_device_range(n, [&](int slot, uint32_t lo, uint32_t hi) -> int { const int r = share(slot, lo, hi); if (r) sg.fail(r, slot); return r; });
+    if (rc) return sg.report(rc);   // the share that failed first, not the lowest slot that noticed
+    if (sg.overflow) {
+        const uint64_t need = sg.need();
+        out_off[0] = need;
+        s5gpu_set_error("s5gpu_ascii_to_ascii_stream: output buffer too small (%llu bytes needed)", (unsigned long long)need);
+        return S5GPU_ERR_NOMEM;
+    }
+    return S5GPU_OK;
+}
+
+// The batch twin: the lines framed back to back in one buffer, the stream call above, its block cut into one malloc'd line per record.  The
+// block's size is known once the signals are printed: a first guess, and on S5GPU_ERR_NOMEM one more call with the size reported.
+extern "C" int s5gpu_ascii_to_ascii_batch(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,
+                                          const uint32_t *new_read_group, int drop_aux, void **out, size_t *out_len, int32_t *status) {
+    if (n == 0) return S5GPU_OK;
+    if (!line || !line_len || !out || !out_len) { s5gpu_set_error("s5gpu_ascii_to_ascii_batch: NULL argument"); return S5GPU_ERR_ARG; }
+    std::vector<uint64_t> pos(n), off(n + 1);
+    std::vector<uint32_t> len(n);
+    std::string buf;
+    for (uint32_t i = 0; i < n; i++) {
+        out[i] = NULL; out_len[i] = 0;
+        if (line_len[i] > 0xFFFFFFFFull || (line_len[i] && !line[i])) { s5gpu_set_error("s5gpu_ascii_to_ascii_batch: line %u", i); return S5GPU_ERR_ARG; }
+        pos[i] = buf.size(); len[i] = (uint32_t)line_len[i];
+        if (len[i]) buf.append(line[i], len[i]);
+    }
+    const size_t at = buf.size();
+    buf.append(32, '\0');                                               // the parse kernel's look-ahead
+    std::vector<char> block(at + at / 8 + 256ull * n + 4096);
+    int rc = s5gpu_ascii_to_ascii_stream(n, buf.data(), at, pos.data(), len.data(), n_aux, aux_type, new_read_group, drop_aux, block.data(), block.size(), off.data(), status);
+    if (rc == S5GPU_ERR_NOMEM) {
+        block.resize(off[0]);
+        rc = s5gpu_ascii_to_ascii_stream(n, buf.data(), at, pos.data(), len.data(), n_aux, aux_type, new_read_group, drop_aux, block.data(), block.size(), off.data(), status);
+    }
+    if (rc != S5GPU_OK) return rc;
+    for (uint32_t i = 0; i < n; i++) {
+        const size_t l = (size_t)(off[i + 1] - off[i]);
+        if (!(out[i] = malloc(l ? l : 1))) {
+            for (uint32_t j = 0; j <= i; j++) { free(out[j]); out[j] = NULL; out_len[j] = 0; }
+            return S5GPU_ERR_NOMEM;
+        }
+        memcpy(out[i], block.data() + off[i], l);
+        out_len[i] = l;
+    }
+    return S5GPU_OK;
+}
+
 // The four calls above, and their _qts twins (slow5tools degrade): every sample qts-rounded to qts_bits (1..16) in HBM between the stage that
 // makes the int16 signals (text parse / decode) and the one that takes them (encode / text format).  The plain calls round nothing.
 extern "C" int s5gpu_ascii_to_blow5_batch(uint32_t n, const char *const *line, const size_t *line_len, uint32_t n_aux, const uint8_t *aux_type,

@@ -5,7 +5,8 @@
  * from /root/reference/src/view.c:192,246,265-278,313, src/get.c:286,45 and src/index.c.  slow5lib is an
  * absent submodule, so the layouts follow SURVEY.md Appendix A (verified on the golden files) and the
  * reference's own literal statement in test/misc/make_blow5.c:11-101.  Header attributes are kept as the opaque
- * text blob; SLOW5 ASCII files (same text after two '#' version lines, one record per line) are framed here too.  No codec work happens here: read ids for the index come from the GPU batch decode.
+ * text blob; SLOW5 ASCII files (same text after two '#' version lines, one record per line) are framed here too.  No codec work happens here: read ids for the index come from the GPU batch decode
+ * (BLOW5) or are the text up to a line's first tab (SLOW5).
  */
 #define _GNU_SOURCE
 #include <fcntl.h>
@@ -481,6 +482,71 @@ static struct slow5_idx *idx_scan(slow5_file_t *s) {
     return ix;
 }
 
+/* SLOW5 ASCII: one entry per record line, offset = its first byte, size = its length with the newline, id = the text up to the first tab;
+ * '#' / '@' lines get none.  Framed on the host, memchr over large pread chunks (a line the chunk's end cuts is carried into the next one, a
+ * line longer than the chunk grows it).  The edge cases (no final newline, "\r\n", no tab): docs/codecs.md §4.10. */
+static struct slow5_idx *idx_scan_ascii(slow5_file_t *s) {
+    struct slow5_idx *ix = (struct slow5_idx *)calloc(1, sizeof *ix);
+    if (!ix) { slow5_errno = SLOW5_ERR_MEM; return NULL; }
+    ix->version = s->header->version;
+    struct stat fst;
+    const int fd = fileno(s->fp);
+    if (fstat(fd, &fst) != 0 || (uint64_t)fst.st_size < s->meta.start_rec_offset) { idx_free(ix); slow5_errno = SLOW5_ERR_TRUNC; return NULL; }
+    const char *ce = getenv("SLOW5_IDX_CHUNK_KB");                       /* tests: chunks smaller than a line */
+    size_t chunk = ce && atoi(ce) > 0 ? (size_t)atoi(ce) << 10 : (size_t)64 << 20;
+    uint64_t pos = s->meta.start_rec_offset;
+    const uint64_t end = (uint64_t)fst.st_size;
+    if (chunk > end - pos) chunk = (size_t)(end - pos) > 4096 ? (size_t)(end - pos) : 4096;
+    char *buf = (char *)malloc(chunk);
+    int err = buf ? 0 : SLOW5_ERR_MEM;
+    size_t carry = 0;
+    while (!err && (pos < end || carry)) {
+        if (carry == chunk) {                                             /* one line fills the whole chunk: a bigger chunk */
+            char *nb = (char *)realloc(buf, chunk * 2);
+            if (!nb) { err = SLOW5_ERR_MEM; break; }
+            buf = nb; chunk *= 2;
+        }
+        size_t want = chunk - carry;
+        if (want > end - pos) want = (size_t)(end - pos);
+        size_t got = 0;
+        while (got < want) {
+            ssize_t r = pread(fd, buf + carry + got, want - got, (off_t)(pos + got));
+            if (r <= 0) { err = SLOW5_ERR_IO; break; }
+            got += (size_t)r;
+        }
+        if (err) break;
+        const uint64_t file_base = pos - carry;                          /* file offset of buf[0] */
+        pos += want;
+        const size_t have = carry + want;
+        size_t p = 0;
+        while (p < have) {
+            const char *nl = (const char *)memchr(buf + p, '\n', have - p);
+            if (!nl && pos < end) break;                                  /* cut by the chunk's end: carried */
+            const size_t len = nl ? (size_t)(nl - (buf + p)) + 1 : have - p;   /* (no newline: the file's last line) */
+            const char *line = buf + p;
+            if (line[0] != '#' && line[0] != '@') {
+                const char *tab = (const char *)memchr(line, '\t', len);
+                const size_t idl = tab ? (size_t)(tab - line) : 0;
+                if (!tab || idl == 0 || idl > 0xFFFF) { err = SLOW5_ERR_RECPARSE; break; }
+                if (idx_push(ix, line, (uint16_t)idl, file_base + p, len) != 0) { err = SLOW5_ERR_MEM; break; }
+            }
+            p += len;
+        }
+        if (err) break;
+        carry = have - p;
+        if (carry && p) memmove(buf, buf + p, carry);
+    }
+    free(buf);
+    if (!err && idx_build_table(ix) != 0) err = SLOW5_ERR_MEM;
+    if (err) {
+        if (err == SLOW5_ERR_RECPARSE) slow5_compat_error("'%s': a record line has no read id (no tab) at entry %llu", s->meta.pathname, (unsigned long long)ix->n);
+        idx_free(ix);
+        slow5_errno = err;
+        return NULL;
+    }
+    return ix;
+}
+
 static int idx_write(const struct slow5_idx *ix, const char *path) {
     FILE *fp = fopen(path, "wb");
     if (!fp) return -1;
@@ -546,11 +612,14 @@ static struct slow5_idx *idx_read(const char *path) {
     return ix;
 }
 
-int slow5_idx_create(slow5_file_t *s) {
-    if (!s || !s->fp || s->format != SLOW5_FORMAT_BINARY) { slow5_errno = SLOW5_ERR_ARG; return -1; }   /* BLOW5 only here */
-    struct slow5_idx *ix = idx_scan(s);
+static int idx_file_ok(const slow5_file_t *s) { return s && s->fp && (s->format == SLOW5_FORMAT_BINARY || s->format == SLOW5_FORMAT_ASCII); }
+
+/* writes the index to path (NULL: <pathname>.idx) */
+static int idx_create_at(slow5_file_t *s, const char *path) {
+    if (!idx_file_ok(s)) { slow5_errno = SLOW5_ERR_ARG; return -1; }
+    struct slow5_idx *ix = s->format == SLOW5_FORMAT_ASCII ? idx_scan_ascii(s) : idx_scan(s);
     if (!ix) return -1;
-    char *p = idx_path(s);
+    char *p = path ? strdup(path) : idx_path(s);
     int rc = p ? idx_write(ix, p) : -1;
     free(p);
     idx_free(ix);
@@ -558,16 +627,19 @@ int slow5_idx_create(slow5_file_t *s) {
     return rc;
 }
 
-int slow5_idx_load(slow5_file_t *s) {
-    if (!s || !s->fp || s->format != SLOW5_FORMAT_BINARY) { slow5_errno = SLOW5_ERR_ARG; return -1; }
+int slow5_idx_create(slow5_file_t *s) { return idx_create_at(s, NULL); }
+int slow5_idx_load(slow5_file_t *s) { return slow5_idx_load_with(s, NULL); }
+
+int slow5_idx_load_with(slow5_file_t *s, const char *path) {
+    if (!idx_file_ok(s)) { slow5_errno = SLOW5_ERR_ARG; return -1; }
     if (s->index) return 0;
-    char *p = idx_path(s);
+    char *p = path ? strdup(path) : idx_path(s);
     if (!p) { slow5_errno = SLOW5_ERR_MEM; return -1; }
-    if (access(p, R_OK) != 0 && slow5_idx_create(s) != 0) { free(p); return -1; }
+    if (access(p, R_OK) != 0 && idx_create_at(s, p) != 0) { free(p); return -1; }
     s->index = idx_read(p);
     if (s->index) {
-        /* an index is only as good as the file it was made from: same version, every entry inside the file (size covers the
-         * u64 prefix).  An index OLDER than the BLOW5 is only warned about and still used, as slow5lib does: mtimes have one-second
+        /* an index is only as good as the file it was made from: same version, every entry inside the file (a BLOW5 size covers the
+         * u64 prefix, a SLOW5 line has a byte at least).  An index OLDER than the BLOW5 is only warned about and still used, as slow5lib does: mtimes have one-second
          * granularity and get reordered by cp / rsync, the directory may be read-only, and the index is the user's file */
         struct stat fs, is;
         int stale = 0;
@@ -577,7 +649,7 @@ int slow5_idx_load(slow5_file_t *s) {
             const uint64_t fsz = (uint64_t)fs.st_size;
             for (uint64_t i = 0; i < s->index->n && !stale; i++) {
                 const struct idx_ent *e = &s->index->ents[i];
-                if (e->size < 8 || e->offset < s->meta.start_rec_offset || e->offset > fsz || e->size > fsz - e->offset) stale = 1;   /* (no sum: it could wrap) */
+                if (e->size < (s->format == SLOW5_FORMAT_ASCII ? 1u : 8u) || e->offset < s->meta.start_rec_offset || e->offset > fsz || e->size > fsz - e->offset) stale = 1;   /* (no sum: it could wrap) */
             }
             if (!stale && stat(p, &is) == 0 && is.st_mtime < fs.st_mtime)
                 slow5_compat_warn("index '%s' is older than '%s'; using it all the same (re-create it with slow5_idx_create if the file was rewritten)", p, s->meta.pathname);
@@ -621,10 +693,13 @@ void *slow5_get_mem(const char *read_id, size_t *n, const slow5_file_t *s) {
         if (!slow5_compat_skip_rid) slow5_compat_error("read id '%s' is not in the index", read_id);
         return NULL;
     }
-    const size_t sz = (size_t)(e->size - 8);
-    void *mem = malloc(sz ? sz : 1);
+    const size_t at = s->format == SLOW5_FORMAT_ASCII ? 0 : 8;       /* SLOW5: the line, returned without its line end, NUL-terminated */
+    size_t sz = (size_t)(e->size - at);
+    char *mem = (char *)malloc(sz + 1);
     if (!mem) { slow5_errno = SLOW5_ERR_MEM; return NULL; }
-    if (pread(fileno(s->fp), mem, sz, (off_t)(e->offset + 8)) != (ssize_t)sz) { free(mem); slow5_errno = SLOW5_ERR_IO; return NULL; }   /* thread-safe like slow5_get */
+    if (pread(fileno(s->fp), mem, sz, (off_t)(e->offset + at)) != (ssize_t)sz) { free(mem); slow5_errno = SLOW5_ERR_IO; return NULL; }   /* thread-safe like slow5_get */
+    if (!at && sz && mem[sz - 1] == '\n' && --sz && mem[sz - 1] == '\r') sz--;
+    mem[sz] = '\0';
     if (n) *n = sz;
     return mem;
 }
@@ -633,6 +708,21 @@ int slow5_get(const char *read_id, struct slow5_rec **read, slow5_file_t *s) {
     size_t n = 0;
     char *mem = (char *)slow5_get_mem(read_id, &n, s);
     if (!mem) return slow5_errno;
+    if (s->format == SLOW5_FORMAT_ASCII) {   /* the line through the ASCII -> BLOW5 (none, none) route, then the record decode */
+        const struct slow5_aux_meta *am = s->header->aux_meta;
+        const char *line = mem;
+        void *rec = NULL;
+        size_t rl = 0;
+        const int rc = s5gpu_ascii_to_blow5_batch(1, &line, &n, am ? am->num : 0, am ? am->types : NULL, S5GPU_REC_NONE, S5GPU_SIG_NONE, NULL, 0, &rec, &rl, NULL);
+        free(mem);
+        if (rc != S5GPU_OK) { slow5_errno = SLOW5_ERR_RECPARSE; return slow5_errno; }
+        mem = (char *)rec;
+        memmove(mem, mem + 8, n = rl - 8);                                  /* without its u64 prefix, as slow5_get_next_mem hands records out */
+        slow5_press_method_t none = {SLOW5_COMPRESS_NONE, SLOW5_COMPRESS_NONE};
+        const int rc2 = slow5_gpu_depress_parse_batch(1, &mem, &n, none, read);
+        free(mem);
+        return rc2 == 0 ? 0 : (slow5_errno ? slow5_errno : SLOW5_ERR_RECPARSE);
+    }
     int rc = slow5_rec_depress_parse(&mem, &n, read_id, read, s);
     free(mem);
     return rc == 0 ? 0 : (slow5_errno ? slow5_errno : SLOW5_ERR_RECPARSE);
