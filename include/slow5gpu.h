@@ -468,6 +468,45 @@ int s5gpu_skim_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const u
 int s5gpu_skim_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, const s5gpu_skim_layout_t *layout,
                      void **out, size_t *out_len, int32_t *status);
 
+/* ---- signals: per-read order statistics and normalised tensors of DECODED reads, on the device (docs/codecs.md §4.11) ----
+ * The input is what s5gpu_decode_dev left behind: `sig`, and per record its sig_off (a multiple of 8 samples), the sig_cap the decoder was
+ * given for it, and its parsed fields.  The samples a kernel may touch of record i are
+ *     n_eff = fields[i].status == 0 ? min(fields[i].n_samples, sig_cap[i]) : 0
+ * never n_samples as it stands (a record that failed with status 6 holds the count it NEEDED there).  Every statistic is an integer. */
+typedef struct s5gpu_sig_stats {
+    uint32_t n;            /* n_eff; 0: every other member but status is 0                                         */
+    int32_t status;        /* 0 ok, else the record's decode status (s5gpu_rec_fields_t)                           */
+    int64_t sum;
+    uint64_t sumsq;        /* exact: x^2 <= 2^30, n < 2^32                                                         */
+    int32_t med2;          /* 2 x median: s[(n-1)/2] + s[n/2] of the sorted samples s                              */
+    uint32_t mad4;         /* 4 x MAD: ks[(n-1)/2] + ks[n/2] of the sorted keys |2x - med2| (0 .. 131070)          */
+    int16_t min, max;
+    int16_t q[4];          /* q[k] = s[floor(q_k * (n-1))] (the "lower" order statistic; product in double); unused: 0 */
+    uint32_t reserved;     /* 0 */
+} s5gpu_sig_stats_t;
+/* n records -> stats[i].  q: n_q (<= 4) quantiles in [0, 1], a HOST array (may be NULL when n_q == 0).  sig_off / sig_cap / fields / stats:
+ * device arrays of n entries.  Asynchronous on hip_stream. */
+int s5gpu_signal_stats_dev(uint32_t n, const int16_t *sig, const uint64_t *sig_off, const uint32_t *sig_cap, const s5gpu_rec_fields_t *fields,
+                           uint32_t n_q, const double *q, s5gpu_sig_stats_t *stats, void *hip_stream);
+enum { S5GPU_NORM_RAW = 0,      /* float(x)                                                                                  */
+       S5GPU_NORM_PA,           /* float32((double(x) + offset) * (range / digitisation)), in double from the read's fields  */
+       S5GPU_NORM_MEDMAD,       /* (2x - med2) / (0.7413f * mad4) = (x - med) / (1.4826 MAD); scale 1 when mad4 == 0         */
+       S5GPU_NORM_QUANT };      /* (x - a (q[0] + q[1])) / max(b (q[1] - q[0]), 1), in double, rounded to float32 once       */
+enum { S5GPU_SIG_F32 = 0, S5GPU_SIG_F16 = 1 };   /* float16 = the float32 result rounded to nearest even */
+/* A dense [n_windows, W] tensor of normalised samples at `out` (16-byte aligned).  Window w = (read win_read[w], start win_start[w]), device
+ * arrays: element j of its row is sample win_start[w] + j of that read where that lies below n_eff, and 0 otherwise.  A window whose read is
+ * >= n or failed, or whose start is > n_eff, is a row of zeros and win_status[w] = 1 (else 0): it is never loaded from.  stats: what
+ * s5gpu_signal_stats_dev wrote for the same records (MEDMAD, QUANT; may be NULL for RAW and PA).  a, b: QUANT only. */
+int s5gpu_signal_windows_dev(uint32_t n, const int16_t *sig, const uint64_t *sig_off, const uint32_t *sig_cap, const s5gpu_rec_fields_t *fields,
+                             const s5gpu_sig_stats_t *stats, uint32_t n_windows, const uint32_t *win_read, const uint32_t *win_start, uint32_t W,
+                             int mode, double a, double b, int dtype, void *out, int32_t *win_status, void *hip_stream);
+/* Statistics of the n records of a file chunk (framed as for s5gpu_decode_stream): one upload, the decode (fields + signals only where the
+ * methods allow S5GPU_DEC_NO_PAYLOAD, the full form otherwise), the statistics kernel, and one small download of stats_out[i] and fields_out[i]
+ * (may be NULL): the signals never leave the device.  Runs on the FIRST device in use, whatever s5gpu_init_mask named.  A corrupt record
+ * fails the call with S5GPU_ERR_DATA; stats_out[i].status / fields_out[i].status say which, the other records' results are valid. */
+int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+                              int sig_method, uint32_t n_q, const double *q, s5gpu_sig_stats_t *stats_out, s5gpu_rec_fields_t *fields_out);
+
 #ifdef __cplusplus
 }
 #endif

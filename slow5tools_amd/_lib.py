@@ -49,6 +49,9 @@ SKIM_MAX_AUX, SKIM_MAX_LABELS, SKIM_TEXT = 64, 1024, 16384
 SKIM_DOT, SKIM_STRING, SKIM_DOUBLE, SKIM_FLOAT, SKIM_INT32, SKIM_UINT8, SKIM_UINT32, SKIM_UINT64, SKIM_ENUM = range(9)
 STATUS_BAD_ENUM = 8
 
+NORM_RAW, NORM_PA, NORM_MEDMAD, NORM_QUANT = range(4)
+SIG_F32, SIG_F16 = 0, 1
+
 
 class SkimLayout(C.Structure):
     """s5gpu_skim_layout_t"""
@@ -132,6 +135,10 @@ def lib():
     L.s5gpu_skim_layout_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(SkimLayout)]
     L.s5gpu_skim_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, C.POINTER(SkimLayout), vp, C.c_size_t, vp, vp]
     L.s5gpu_skim_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(SkimLayout), vp, vp, vp]
+    # signals: statistics and normalised windows of decoded reads on the device, and the chunk call (q: a host array of doubles)
+    L.s5gpu_signal_stats_dev.argtypes = [u32, vp, vp, vp, vp, u32, vp, vp, vp]
+    L.s5gpu_signal_windows_dev.argtypes = [u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, i32, C.c_double, C.c_double, i32, vp, vp, vp]
+    L.s5gpu_signal_stats_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, u32, vp, vp, vp]
     _LIB = L
     return L
 
@@ -149,4 +156,5 @@ EXPORTS = [
     "s5gpu_encode_batch", "s5gpu_decode_batch", "s5gpu_solo_batch", "s5gpu_deflate_parked_dev", "s5gpu_inflate_dev",
     "s5gpu_svbzd_decode_dev", "s5gpu_set_option", "s5gpu_recompress_batch", "s5gpu_patch_u32_dev", "s5gpu_encode_stream_dev",
     "s5gpu_svbzd_encode_stream_dev", "s5gpu_pack_parked_dev", "s5gpu_warmup",
+    "s5gpu_signal_stats_dev", "s5gpu_signal_windows_dev", "s5gpu_signal_stats_stream",
 ]

@@ -122,11 +122,21 @@ def degrade_records(records, bits, from_rec=REC_ZLIB, from_sig=SIG_SVB_ZD, to_re
     return res
 
 
-def decode_signals_dev(records, rec_method=REC_ZLIB, max_pay_cap=None, sig_caps=None, scratch_bytes=None, device="cuda:0", sig_method=SIG_SVB_ZD,
-                       max_in_len=None):
-    """s5gpu_decode_dev with S5GPU_DEC_NO_PAYLOAD: fields + signals only, the uncompressed records stay in reused scratch slots
-    (what `get` needs of /root/reference/src/get.c:37-66 when the caller holds the read ids).  records: bytes without the u64 prefix.
-    Returns (fields as a numpy REC_FIELDS array, list of int16 arrays — empty where status != 0)."""
+def no_payload_methods(rec_method, sig_method):
+    """the pairs of methods s5gpu_decode_dev serves with S5GPU_DEC_NO_PAYLOAD (include/slow5gpu.h)"""
+    return (sig_method == SIG_SVB_ZD and rec_method in (REC_ZLIB, REC_ZSTD)) or (sig_method == SIG_EX_ZD and rec_method == REC_ZLIB)
+
+
+class DecodedDev:
+    """What decode_to_device leaves on the device: t_sig (int16), t_fields (uint8, 64 B per record), and on the host the descriptors' sig_off /
+    sig_cap (numpy int64) the decoder was given.  The tensors are kept alive by this object."""
+
+
+def decode_to_device(records, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, max_pay_cap=None, sig_caps=None, scratch_bytes=None, device="cuda:0",
+                     max_in_len=None, no_payload=True):
+    """The upload + s5gpu_decode_dev part shared by decode_signals_dev and signals.read_signals: records (bytes without the u64 prefix) are
+    decoded into one int16 tensor that STAYS on the device.  no_payload: fields + signals only (S5GPU_DEC_NO_PAYLOAD); False: every record
+    gets a payload slot of max_pay_cap bytes as well (any pair of methods).  Returns a DecodedDev; the stream is synchronised."""
     import torch
 
     L = _lib.lib()
@@ -145,24 +155,43 @@ def decode_signals_dev(records, rec_method=REC_ZLIB, max_pay_cap=None, sig_caps=
     d = np.zeros(n, dtype=_lib.REC_DESC)
     d["in_off"], d["in_len"], d["sig_off"], d["sig_cap"] = offs[:-1], lens, so[:-1], sig_caps
     dev = torch.device(device)
-    t_in = torch.from_numpy(blob).to(dev)
-    t_desc = torch.from_numpy(d.view(np.uint8).copy()).to(dev)
-    t_sig = torch.zeros(int(so[-1]) + 64, dtype=torch.int16, device=dev)
-    t_fields = torch.zeros(max(n, 1) * 64, dtype=torch.uint8, device=dev)
-    if scratch_bytes is None:
-        L.s5gpu_decode_scratch_bytes.restype = C.c_uint64
-        L.s5gpu_decode_scratch_bytes.argtypes = [C.c_uint32]
-        scratch_bytes = int(L.s5gpu_decode_scratch_bytes(max_pay_cap))
-    t_scr = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+    r = DecodedDev()
+    r.n, r.dev, r.sig_off, r.sig_cap = n, dev, so[:-1].copy(), sig_caps.copy()
     a = _lib.DecodeArgs()
-    a.n_recs, a.rec_method, a.sig_method, a.flags = n, rec_method, sig_method, _lib.DEC_NO_PAYLOAD
-    a.desc, a.in_, a.payload, a.sig_out, a.fields = t_desc.data_ptr(), t_in.data_ptr(), t_scr.data_ptr(), t_sig.data_ptr(), t_fields.data_ptr()
-    a.payload_bytes, a.max_pay_cap = scratch_bytes, max_pay_cap
+    a.n_recs, a.rec_method, a.sig_method = n, rec_method, sig_method
+    if no_payload:
+        if scratch_bytes is None:
+            L.s5gpu_decode_scratch_bytes.restype = C.c_uint64
+            L.s5gpu_decode_scratch_bytes.argtypes = [C.c_uint32]
+            scratch_bytes = int(L.s5gpu_decode_scratch_bytes(max_pay_cap))
+        r.t_scr = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        a.flags, a.payload_bytes = _lib.DEC_NO_PAYLOAD, scratch_bytes
+    else:
+        pay_slot = (max_pay_cap + 16 + 15) // 16 * 16
+        d["pay_off"], d["pay_cap"] = np.arange(n, dtype=np.int64) * pay_slot, max_pay_cap
+        r.t_scr = torch.empty(n * pay_slot + 64, dtype=torch.uint8, device=dev)
+    r.t_in = torch.from_numpy(blob).to(dev)
+    r.t_desc = torch.from_numpy(d.view(np.uint8).copy()).to(dev)
+    r.t_sig = torch.zeros(int(so[-1]) + 64, dtype=torch.int16, device=dev)
+    r.t_fields = torch.zeros(max(n, 1) * 64, dtype=torch.uint8, device=dev)
+    a.desc, a.in_, a.payload, a.sig_out, a.fields = r.t_desc.data_ptr(), r.t_in.data_ptr(), r.t_scr.data_ptr(), r.t_sig.data_ptr(), r.t_fields.data_ptr()
+    a.max_pay_cap = max_pay_cap
     a.max_in_len = int(lens.max()) if (max_in_len is None and n) else int(max_in_len or 0)   # (a hint: short records stay in LDS, include/slow5gpu.h)
     check(L.s5gpu_decode_dev(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_decode_dev")
     torch.cuda.synchronize(dev)
-    f = t_fields.cpu().numpy().view(_lib.REC_FIELDS)[:n].copy()
-    sig = t_sig.cpu().numpy()
+    return r
+
+
+def decode_signals_dev(records, rec_method=REC_ZLIB, max_pay_cap=None, sig_caps=None, scratch_bytes=None, device="cuda:0", sig_method=SIG_SVB_ZD,
+                       max_in_len=None):
+    """s5gpu_decode_dev with S5GPU_DEC_NO_PAYLOAD: fields + signals only, the uncompressed records stay in reused scratch slots
+    (what `get` needs of /root/reference/src/get.c:37-66 when the caller holds the read ids).  records: bytes without the u64 prefix.
+    Returns (fields as a numpy REC_FIELDS array, list of int16 arrays — empty where status != 0)."""
+    n = len(records)
+    r = decode_to_device(records, rec_method, sig_method, max_pay_cap, sig_caps, scratch_bytes, device, max_in_len)
+    so = r.sig_off
+    f = r.t_fields.cpu().numpy().view(_lib.REC_FIELDS)[:n].copy()
+    sig = r.t_sig.cpu().numpy()
     out = [sig[int(so[i]):int(so[i]) + int(f["n_samples"][i])].copy() if f["status"][i] == 0 else np.zeros(0, np.int16) for i in range(n)]
     return f, out
 
