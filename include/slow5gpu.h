@@ -168,8 +168,6 @@ int s5gpu_device_count(void);
  * inflate kernel (throughput), smaller ones the wave-per-record kernel (latency); default 24576.
  * "inflate_route" (0/1, default 1): such batches are first counting-sorted by compressed length on the device, and records
  * of >= 32 KiB go to the wave-per-record kernel beside the lane kernel (real runs have read lengths spread over two decades).
- * In inflate-only calls fields[i].reserved, fields[0..128].read_group and fields[128].aux_len are then left holding routing
- * scratch (s5gpu_decode_dev overwrites all of them with the parsed fields).
  * "multi_min_per_device" (default 1024): a host batch of fewer than this many records per device stays on the first device.
  * "unpack_fused" (0/1, default 1): s5gpu_decode_dev on zlib / zstd + svb-zd records lets the wave that decompressed a record parse it and decode
  * its signal as well (fields.reserved is scratch on the way and 0 at the end); 0 = always the separate unpack kernel.
@@ -180,7 +178,8 @@ int s5gpu_device_count(void);
  * the HBM-staged kernels take the rest; measured on real-run read lengths it gains nothing (profiles/r04_mixed_tier2.txt).
  * "order_min" (default 8192; 0 = never): batches of at least this many zlib / zstd records are DECODED longest record first (a counting sort
  * by compressed length on the device builds the launch order), and the overflow list of a mixed ENCODE batch (the reads the staged kernels
- * redo) is taken longest read first.  Costs 4 bytes per record of scratch per (device, stream), kept until s5gpu_shutdown.
+ * redo) is taken longest read first.  Costs 4 bytes per record of scratch per (device, stream), kept until s5gpu_shutdown; the sorted list of
+ * "inflate_route" (batches of >= 1024 records, whatever order_min says) lives in the same scratch at the same cost.
  * "zstd_pre_min" (default 256; 0 = never): zstd batches of at least this many frames run a first pass that reads every frame's first tree
  * description, a frame per lane, in front of the decoder.  Costs 144 bytes per record in the same per-(device, stream) scratch
  * (144 MB for a million frames); a process that decodes on many short-lived streams should reuse streams or set this to 0. */

@@ -22,6 +22,7 @@
 #include "zstd_enc_dev.h"
 #include "svb_dev.h"
 #include "exzd_dev.h"
+#include "order_dev.h"
 
 using namespace s5;
 
@@ -277,45 +278,6 @@ __global__ __launch_bounds__(NT, S5_FUSED_WG_PER_CU) void k_encode_stream(EncPar
 // is in LDS before its output is written, so the writer never catches the reader.
 __device__ __forceinline__ uint32_t park_offset(const s5gpu_read_desc_t &d, int sig_method) {
     return (d.slot_cap - payload_bound_dev(d, sig_method)) & ~15u;
-}
-
-constexpr uint32_t ORD_FLAG = 129, ORD_LIST = 132;
-__device__ __forceinline__ uint32_t order_at(const uint32_t *ord, uint32_t i) {
-    return ord && !ord[ORD_FLAG] ? ord[ORD_LIST + i] : i;
-}
-__device__ __forceinline__ uint32_t order_bucket(uint32_t len) {
-    if (len < 4) return len;
-    const uint32_t hb = 31u - (uint32_t)__clz((int)len);
-    return hb * 4 + ((len >> (hb - 2)) & 3u);
-}
-// ... and for the ENCODE side (round 4): the reads on the overflow list of a mixed batch (the ones the staged kernels redo) by their
-// number of samples, longest first — a 300 k-sample read keeps one workgroup busy for most of a millisecond, and in list order (the order
-// in which the fused kernel's workgroups happened to give up) it starts wherever it stands.  The list holds read indices.
-__global__ __launch_bounds__(NT) void k_eorder_count(const s5gpu_read_desc_t *desc, const uint32_t *ovf, uint32_t *ord) {
-    __shared__ uint32_t h[128];
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i < ovf[0]) atomicAdd(&h[order_bucket(desc[ovf[1 + i]].n_samples)], 1u);
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(&ord[threadIdx.x], h[threadIdx.x]);
-}
-__global__ __launch_bounds__(NT) void k_eorder_scatter(const s5gpu_read_desc_t *desc, const uint32_t *ovf, uint32_t *ord) {
-    __shared__ uint32_t h[128], base[128];
-    if (ord[ORD_FLAG]) return;
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    uint32_t b = 0, rank = 0, r = 0;
-    if (i < ovf[0]) { r = ovf[1 + i]; b = order_bucket(desc[r].n_samples); rank = atomicAdd(&h[b], 1u); }
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) base[threadIdx.x] = atomicAdd(&ord[threadIdx.x], h[threadIdx.x]);
-    __syncthreads();
-    if (i < ovf[0]) ord[ORD_LIST + base[b] + rank] = r;
-}
-// entry `it` of the overflow list, in launch order when there is one
-__device__ __forceinline__ uint32_t ovf_at(const uint32_t *ovf, const uint32_t *ord, uint32_t it) {
-    return ord && !ord[ORD_FLAG] ? ord[ORD_LIST + it] : ovf[1 + it];
 }
 
 // Staged path, step 1: payload straight to HBM.  mode 0: all reads, parked for k_deflate_staged;
@@ -816,61 +778,6 @@ __global__ __launch_bounds__(64) void k_inflate_head(s5gpu_decode_args_t a) {
     }
 }
 
-// ---- launch order of the wave-per-record kernels: the longest records first (round 3) ----
-// One wave decodes one record, so a batch ends when its longest record does — and a record of 300 k samples takes a wave ~15 ms however
-// idle the rest of the device is.  In file order it starts wherever it happens to stand: 262 144 records with the read lengths of a real
-// run decode in 23.7 ms, 16.6 ms with the longest first (tools/mixed_lengths.py: the rate per sample of a batch of equal reads).  So batches
-// larger than the device holds at once are counting-sorted by compressed length first — 128 buckets, four per octave, descending; the
-// k_route_* kernels' scheme with its scratch in a buffer of the library's own: ord[0..127] bucket counts, then cursors; ord[129] != 0: one
-// length class, no list (file order is as good); the list from ord[132] on.
-__global__ __launch_bounds__(NT) void k_order_zero(uint32_t *ord) {
-    if (threadIdx.x < ORD_LIST) ord[threadIdx.x] = 0;
-}
-__global__ __launch_bounds__(NT) void k_order_count(const s5gpu_rec_desc_t *desc, uint32_t n, uint32_t *ord) {
-    __shared__ uint32_t h[128];
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i < n) atomicAdd(&h[order_bucket(desc[i].in_len)], 1u);
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(&ord[threadIdx.x], h[threadIdx.x]);
-}
-__global__ __launch_bounds__(128) void k_order_scan(uint32_t *ord) {   // one workgroup of 128: thread t owns bucket 127 - t
-    __shared__ uint32_t ws[2];
-    __shared__ uint64_t su[2];
-    const uint32_t b = 127u - threadIdx.x;
-    const uint32_t c = ord[b];
-    const uint32_t incl = wave_incl_add(c);
-    if (lane_id() == 63) ws[wave_id()] = incl;
-    const uint64_t used = __ballot(c != 0);
-    if (lane_id() == 0) su[wave_id()] = used;
-    __syncthreads();
-    ord[b] = incl - c + (wave_id() ? ws[0] : 0u);                       // cursor of the bucket in the descending list
-    if (threadIdx.x == 0) {
-        // su[0] bit i = bucket 127 - i, su[1] bit i = bucket 63 - i: at most three neighbouring buckets in use = one length class
-        const int nb = __popcll((unsigned long long)su[0]) + __popcll((unsigned long long)su[1]);
-        int first = -1, last = -1;
-        for (int t = 0; t < 128; t++) {
-            const bool u = ((t < 64 ? su[0] >> t : su[1] >> (t - 64)) & 1ull) != 0;
-            if (u) { if (first < 0) first = t; last = t; }
-        }
-        ord[ORD_FLAG] = nb == 0 || last - first <= 2 ? 1u : 0u;
-    }
-}
-__global__ __launch_bounds__(NT) void k_order_scatter(const s5gpu_rec_desc_t *desc, uint32_t n, uint32_t *ord) {   // a workgroup reserves one range per bucket
-    __shared__ uint32_t h[128], base[128];
-    if (ord[ORD_FLAG]) return;
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    uint32_t b = 0, rank = 0;
-    if (i < n) { b = order_bucket(desc[i].in_len); rank = atomicAdd(&h[b], 1u); }
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) base[threadIdx.x] = atomicAdd(&ord[threadIdx.x], h[threadIdx.x]);
-    __syncthreads();
-    if (i < n) ord[ORD_LIST + base[b] + rank] = i;
-}
-
 // K4, parallel inside the record (inflate_par_dev.h): one record per wave64, 64 self-synchronising segment decoders.  Default for
 // every batch size; what it declines (status INF_NEED_FALLBACK) the wave-per-record decoder redoes right behind it.
 // UNPACK (s5gpu_decode_dev on svb-zd records): the wave that inflated a record also parses it and decodes its signal — the payload
@@ -1249,15 +1156,20 @@ __global__ __launch_bounds__(64, S5_ZI_W) void k_zstd_inflate(s5gpu_decode_args_
 }
 
 // K4, throughput form: one record per LANE (inflate_simt_dev.h); 64 records per workgroup, tables in dynamic LDS.
-// ROUTED: the records come through the length-sorted list built by the k_route_* kernels below (longest first), and only the
-// part of the list behind the n_long longest records is this kernel's.
+// Routing of a big zlib batch: a wave takes as long as its longest record and the batch as long as its longest wave, so with the read
+// lengths of a real run (log-normal, a tail of 100x the median) the lane kernel alone loses to the wave kernel (tools/mixed_lengths.py).
+// So the records are counting-sorted by compressed length (order_dev.h, long_bucket = ROUTE_LONG_BUCKET): a wave then holds records of one
+// bucket, the longest waves start first, and records of 32 KiB and more (a lane would need > 30 ms for one) go to the wave-per-record
+// kernel, which runs beside the lane kernel.
+// ROUTED: the records come through that list (`ord`, longest first), and only the part of the list behind the n_long longest records is
+// this kernel's.
 template <bool ROUTED>
-__global__ __launch_bounds__(64) void k_inflate_simt(s5gpu_decode_args_t a) {
+__global__ __launch_bounds__(64) void k_inflate_simt(s5gpu_decode_args_t a, const uint32_t *ord) {
     uint32_t r = blockIdx.x * 64 + threadIdx.x;
-    if (ROUTED && !a.fields[128].aux_len) {           // aux_len != 0: one length class, the list was not built (file order)
-        const uint32_t n_long = a.fields[128].read_group;
+    if (ROUTED && !ord[ORD_FLAG]) {                   // flag != 0: one length class, none of it long; the list was not built (file order)
+        const uint32_t n_long = ord[ORD_NLONG];
         if (r >= a.n_recs - n_long) return;
-        r = a.fields[n_long + r].reserved;
+        r = ord[ORD_LIST + n_long + r];
     } else if (r >= a.n_recs) return;
     LaneTables &T = reinterpret_cast<LaneTables *>(smem)[threadIdx.x];
     const s5gpu_rec_desc_t d = a.desc[r];
@@ -1266,12 +1178,12 @@ __global__ __launch_bounds__(64) void k_inflate_simt(s5gpu_decode_args_t a) {
     a.fields[r].status = status;
     a.fields[r].payload_len = olen;
 }
-// ... and the wave-per-record kernel over the n_long longest records of the same list (persistent blocks)
-__global__ __launch_bounds__(64) void k_inflate_long(s5gpu_decode_args_t a) {
+// ... and the wave-per-record kernel over the n_long longest records of the same list (persistent blocks; without a list n_long is 0)
+__global__ __launch_bounds__(64) void k_inflate_long(s5gpu_decode_args_t a, const uint32_t *ord) {
     __shared__ InflShared T;
-    const uint32_t n_long = a.fields[128].read_group;
+    const uint32_t n_long = ord[ORD_NLONG];
     for (uint32_t i = blockIdx.x; i < n_long; i += gridDim.x) {
-        const uint32_t r = a.fields[i].reserved;
+        const uint32_t r = ord[ORD_LIST + i];
         const s5gpu_rec_desc_t d = a.desc[r];
         uint32_t olen = 0;
         const int status = zlib_inflate_wave(T, a.in + d.in_off, d.in_len, a.payload + d.pay_off, d.pay_cap, &olen);
@@ -1281,71 +1193,6 @@ __global__ __launch_bounds__(64) void k_inflate_long(s5gpu_decode_args_t a) {
         }
         wave_sync();
     }
-}
-
-// Routing of a big zlib batch.  One lane decodes one record, so a wave takes as long as its longest record and the batch as
-// long as its longest wave: with the read lengths of a real run (log-normal, a tail of 100x the median) the lane kernel alone
-// loses to the wave kernel (tools/mixed_lengths.py).  So the records are counting-sorted by compressed length (128 buckets, four
-// per octave, longest first): a wave then holds records of one bucket, the longest waves start first, and records of 32 KiB
-// and more (a lane would need > 30 ms for one) go to the wave-per-record kernel, which runs beside the lane kernel.
-// Scratch: fields[b].read_group (b < 128) bucket counts then cursors, fields[128].read_group = n_long, fields[i].reserved = the
-// sorted list.  All of it is overwritten or reset by the kernels that follow.
-__device__ __forceinline__ uint32_t route_bucket(uint32_t len) {
-    if (len < 4) return len;
-    const uint32_t hb = 31u - (uint32_t)__clz((int)len);
-    return hb * 4 + ((len >> (hb - 2)) & 3u);
-}
-constexpr uint32_t ROUTE_LONG_BUCKET = 15 * 4;   // compressed records of >= 32 KiB
-__global__ __launch_bounds__(NT) void k_route_zero(s5gpu_decode_args_t a) {
-    if (threadIdx.x < 129) a.fields[threadIdx.x].read_group = 0;
-}
-__global__ __launch_bounds__(NT) void k_route_count(s5gpu_decode_args_t a) {   // workgroup histogram in LDS, one global add per bucket in use
-    __shared__ uint32_t h[128];
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    if (i < a.n_recs) atomicAdd(&h[route_bucket(a.desc[i].in_len)], 1u);
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(&a.fields[threadIdx.x].read_group, h[threadIdx.x]);
-}
-__global__ __launch_bounds__(128) void k_route_scan(s5gpu_decode_args_t a) {   // one workgroup of 128: thread t owns bucket 127 - t
-    __shared__ uint32_t ws[2];
-    const uint32_t b = 127u - threadIdx.x;
-    const uint32_t c = a.fields[b].read_group;
-    const uint32_t incl = wave_incl_add(c);
-    if (lane_id() == 63) ws[wave_id()] = incl;
-    __syncthreads();
-    const uint32_t start = incl - c + (wave_id() ? ws[0] : 0u);
-    a.fields[b].read_group = start;                                           // cursor of the bucket in the descending list
-    if (b == ROUTE_LONG_BUCKET) a.fields[128].read_group = start + c;         // everything in front of the shorter buckets
-    // a batch of one length class (<= 3 neighbouring buckets in use, none of them long) needs no list: file order is as good
-    const uint64_t used = __ballot(c != 0);
-    __shared__ uint64_t su[2];
-    if (lane_id() == 0) su[wave_id()] = used;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // thread t owns bucket 127 - t: su[0] bit i = bucket 127 - i, su[1] bit i = bucket 63 - i
-        const uint64_t hi = su[0], lo = su[1];
-        bool uniform = false;
-        if (hi == 0 && lo != 0) {
-            const int first = __ffsll((long long)lo) - 1, last = 63 - __clzll((long long)lo);
-            uniform = last - first <= 2 && 63 - first < (int)ROUTE_LONG_BUCKET;
-        }
-        a.fields[128].aux_len = uniform ? 1u : 0u;
-    }
-}
-__global__ __launch_bounds__(NT) void k_route_scatter(s5gpu_decode_args_t a) {   // a workgroup reserves one range per bucket
-    __shared__ uint32_t h[128], base[128];
-    if (a.fields[128].aux_len) return;                                             // one length class: no list
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * NT + threadIdx.x;
-    uint32_t b = 0, rank = 0;
-    if (i < a.n_recs) { b = route_bucket(a.desc[i].in_len); rank = atomicAdd(&h[b], 1u); }
-    __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) base[threadIdx.x] = atomicAdd(&a.fields[threadIdx.x].read_group, h[threadIdx.x]);
-    __syncthreads();
-    if (i < a.n_recs) a.fields[base[b] + rank].reserved = i;
 }
 
 // K2 + field parse: payload -> primary fields + int16 raw_signal (slow5_rec_depress_parse, a7/a8)
@@ -1412,7 +1259,7 @@ __device__ __forceinline__ void unpack_record_wg(const s5gpu_decode_args_t &a, u
         f.sampling_rate = __longlong_as_double((long long)v[3]);
         f.aux_off = hl + 8 + sig_bytes;
         f.aux_len = plen - (hl + 8 + sig_bytes);
-        f.reserved = 0;   // scratch of the routing kernels
+        f.reserved = 0;   // the contract of unpack_fused: whatever the caller's array held, 0 at the end
     }
 }
 
@@ -1812,31 +1659,38 @@ static int order_scratch(hipStream_t st, size_t need, uint32_t **out, std::uniqu
     *out = hit->p;
     return S5GPU_OK;
 }
-// builds the list for this batch on `st`; *out = nullptr when the batch is too small for the order to matter.  `hold` keeps the device's pool
-// locked until the caller has enqueued the kernel that reads the list: two threads that share a stream (the default stream, say) must not
-// interleave "build my list" / "build yours" / "read mine".
+// The one builder behind every length-ordered list (order_dev.h): the (device, stream)'s scratch, then the four kernels with `key` on `st`.
+// *out = nullptr when no list is wanted (`list` = false) or none can be had (no scratch: file order is always correct).  `hold` keeps the
+// device's pool locked until the caller has enqueued the kernels that read the list: two threads that share a stream (the default stream,
+// say) must not interleave "build my list" / "build yours" / "read mine".
 // `extra_words` more words of the same scratch (16-byte aligned, behind the list) come back in *extra — the zstd decoders' weights pass; they are
-// handed out whether or not the batch is big enough for a list (want_order = false: no list at all)
-static int launch_order(const s5gpu_decode_args_t *a, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold,
-                        size_t extra_words = 0, uint32_t **extra = nullptr, bool want_order = true) {
+// handed out whether or not a list is built
+template <class Key>
+static int build_order(const Key &key, uint32_t n, bool list, uint32_t long_bucket, hipStream_t st, const uint32_t **out,
+                       std::unique_lock<std::mutex> &hold, size_t extra_words = 0, uint32_t **extra = nullptr) {
     *out = nullptr;
     if (extra) *extra = nullptr;
-    const bool order = want_order && g_order_min && a->n_recs >= g_order_min;
-    if (!order && !(extra && extra_words)) return S5GPU_OK;
-    const size_t list_words = order ? (((size_t)ORD_LIST + a->n_recs + 3) & ~(size_t)3) : 0;
+    if (!list && !(extra && extra_words)) return S5GPU_OK;
+    const size_t list_words = list ? (((size_t)ORD_LIST + n + 3) & ~(size_t)3) : 0;
     uint32_t *p = nullptr;
     { const int rc = order_scratch(st, list_words + (extra ? extra_words : 0), &p, hold); if (rc) return rc; }
     if (!p) return S5GPU_OK;
-    if (order) {
-        const uint32_t nb = (a->n_recs + NT - 1) / NT;
+    if (list) {
+        const uint32_t nb = (n + NT - 1) / NT;
         hipLaunchKernelGGL(k_order_zero, dim3(1), dim3(NT), 0, st, p);
-        hipLaunchKernelGGL(k_order_count, dim3(nb), dim3(NT), 0, st, a->desc, a->n_recs, p);
-        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(128), 0, st, p);
-        hipLaunchKernelGGL(k_order_scatter, dim3(nb), dim3(NT), 0, st, a->desc, a->n_recs, p);
+        hipLaunchKernelGGL(k_order_count<Key>, dim3(nb), dim3(NT), 0, st, key, p);
+        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(128), 0, st, p, long_bucket);
+        hipLaunchKernelGGL(k_order_scatter<Key>, dim3(nb), dim3(NT), 0, st, key, p);
         *out = p;
     }
     if (extra && extra_words) *extra = p + list_words;
     return S5GPU_OK;
+}
+// the decode side's launch order: batches of at least order_min records (want_order = false: no list at all, only the extra words)
+static int launch_order(const s5gpu_decode_args_t *a, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold,
+                        size_t extra_words = 0, uint32_t **extra = nullptr, bool want_order = true) {
+    const bool order = want_order && g_order_min && a->n_recs >= g_order_min;
+    return build_order(OrderByInLen{a->desc, a->n_recs}, a->n_recs, order, 0, st, out, hold, extra_words, extra);
 }
 // zstd batches of at least this many frames get the weights pass (k_zstd_weights: the first tree description of every frame, a frame per lane)
 // in front of the decoder; smaller ones (a `get` of a few reads) are not worth the extra launch.  Option "zstd_pre_min"; 0 = never.
@@ -1846,18 +1700,8 @@ static size_t zstd_pre_words(const s5gpu_decode_args_t *a) {
 }
 // ... the encode side's: the overflow list of a mixed batch (how many reads are on it is only known on the device: the grids cover n_reads)
 static int launch_eorder(const s5gpu_encode_args_t *a, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold) {
-    *out = nullptr;
-    if (!g_order_min || a->n_reads < g_order_min) return S5GPU_OK;
-    uint32_t *p = nullptr;
-    { const int rc = order_scratch(st, (size_t)ORD_LIST + a->n_reads, &p, hold); if (rc) return rc; }
-    if (!p) return S5GPU_OK;
-    const uint32_t nb = (a->n_reads + NT - 1) / NT;
-    hipLaunchKernelGGL(k_order_zero, dim3(1), dim3(NT), 0, st, p);
-    hipLaunchKernelGGL(k_eorder_count, dim3(nb), dim3(NT), 0, st, a->desc, a->ovf, p);
-    hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(128), 0, st, p);
-    hipLaunchKernelGGL(k_eorder_scatter, dim3(nb), dim3(NT), 0, st, a->desc, a->ovf, p);
-    *out = p;
-    return S5GPU_OK;
+    const bool order = g_order_min && a->n_reads >= g_order_min;
+    return build_order(OrderOvfBySamples{a->desc, a->ovf}, a->n_reads, order, 0, st, out, hold);
 }
 
 static void launch_lz(EncParams p, uint32_t n, uint32_t max_payload, hipStream_t st, bool build = false);
@@ -2175,17 +2019,28 @@ void s5kern_release_aux() {   // s5gpu_shutdown (bumps the generation right afte
     g_aux_free.clear();
 }
 
+// Every decode kernel variant is named in one place: a launch (and, for the no-payload forms further down, the occupancy query in front of
+// it) cannot end up with another kernel than the one its caller chose.
+using InflateKernel = void (*)(s5gpu_decode_args_t, const uint32_t *);
+static InflateKernel inflate_par_kernel(int unpack, bool shortrec) {   // inflate only has one shape: SHORT chooses among the unpacking forms' waiting lists
+    if (unpack == 2) return shortrec ? k_inflate_par<2, true> : k_inflate_par<2, false>;
+    if (unpack == 1) return shortrec ? k_inflate_par<1, true> : k_inflate_par<1, false>;
+    return k_inflate_par<0, true>;
+}
+using ZstdInflateKernel = void (*)(s5gpu_decode_args_t, const uint32_t *, const uint8_t *);
+static ZstdInflateKernel zstd_inflate_kernel(int unpack) {
+    return unpack == 2 ? k_zstd_inflate<2> : unpack == 1 ? k_zstd_inflate<1> : k_zstd_inflate<0>;
+}
+
 static int launch_inflate(const s5gpu_decode_args_t *a, hipStream_t st, int unpack = 0) {   // unpack: the inflating wave also parses + decodes (1 svb-zd, 2 ex-zd)
-    std::unique_lock<std::mutex> hold;            // (launch_order's: released when the kernels that read the list are enqueued)
+    std::unique_lock<std::mutex> hold;            // (build_order's: released when the kernels that read the list are enqueued)
     if (a->rec_method == S5GPU_REC_ZSTD) {
         const uint32_t *ord = nullptr;
         uint32_t *ws32 = nullptr;
         { const int rc = launch_order(a, st, &ord, hold, zstd_pre_words(a), &ws32); if (rc) return rc; }
         uint8_t *ws = reinterpret_cast<uint8_t *>(ws32);
         if (ws) hipLaunchKernelGGL(k_zstd_weights, dim3((a->n_recs + 63) / 64), dim3(64), 0, st, *a, ws);
-        if (unpack == 2) hipLaunchKernelGGL(k_zstd_inflate<2>, dim3(a->n_recs), dim3(64), 0, st, *a, ord, ws);
-        else if (unpack == 1) hipLaunchKernelGGL(k_zstd_inflate<1>, dim3(a->n_recs), dim3(64), 0, st, *a, ord, ws);
-        else hipLaunchKernelGGL(k_zstd_inflate<0>, dim3(a->n_recs), dim3(64), 0, st, *a, ord, ws);
+        hipLaunchKernelGGL(zstd_inflate_kernel(unpack), dim3(a->n_recs), dim3(64), 0, st, *a, ord, ws);
     } else if (a->rec_method == S5GPU_REC_ZLIB && g_inflate_par) {
         // the waiting list's size follows what was compressed and how long the records are (inflate_par_dev.h): short svb-zd / ex-zd
         // records take the 256-entry list; long ones (several hundred waiting matches per window in their key bytes: 14.7 ms per 8192
@@ -2195,33 +2050,34 @@ static int launch_inflate(const s5gpu_decode_args_t *a, hipStream_t st, int unpa
         const bool shortrec = a->max_pay_cap != 0 && a->max_pay_cap <= S5_IP_SHORT_PAY * (a->sig_method == S5GPU_SIG_EX_ZD ? 3u : 1u);
         const uint32_t *ord = nullptr;
         { const int rc = launch_order(a, st, &ord, hold); if (rc) return rc; }
-        if (unpack == 2) { if (shortrec) hipLaunchKernelGGL((k_inflate_par<2, true>), dim3(a->n_recs), dim3(64), 0, st, *a, ord); else hipLaunchKernelGGL((k_inflate_par<2, false>), dim3(a->n_recs), dim3(64), 0, st, *a, ord); }
-        else if (unpack == 1) { if (shortrec) hipLaunchKernelGGL((k_inflate_par<1, true>), dim3(a->n_recs), dim3(64), 0, st, *a, ord); else hipLaunchKernelGGL((k_inflate_par<1, false>), dim3(a->n_recs), dim3(64), 0, st, *a, ord); }
-        else hipLaunchKernelGGL((k_inflate_par<0, true>), dim3(a->n_recs), dim3(64), 0, st, *a, ord);
+        hipLaunchKernelGGL(inflate_par_kernel(unpack, shortrec), dim3(a->n_recs), dim3(64), 0, st, *a, ord);
         const uint32_t g = (a->n_recs + 63) / 64 < 4096 ? (a->n_recs + 63) / 64 : 4096;
         if (g_inflate_par == 1) hipLaunchKernelGGL(k_inflate_fallback, dim3(g), dim3(64), 0, st, *a);
     } else if (a->rec_method == S5GPU_REC_ZLIB && a->n_recs >= g_inflate_simt_min) {
         { const int rc = set_lds_attrs(); if (rc) return rc; }
         const uint32_t nb64 = (a->n_recs + 63) / 64;
-        if (a->n_recs < 1024 || !g_inflate_route) {   // tiny batches (tests force the lane kernel on them): no routing
-            hipLaunchKernelGGL(k_inflate_simt<false>, dim3(nb64), dim3(64), 64 * sizeof(LaneTables), st, *a);
+        const uint32_t *ord = nullptr;
+        // routing is the lane kernel's own need (independent of order_min); tiny batches (tests force the lane kernel on them) go without.
+        // `hold` stays locked until BOTH readers of the list are enqueued, the lane kernel on st and k_inflate_long on the helper stream; the
+        // next build on st is ordered behind the helper stream's join event, so the scratch is free again by then, as for the other lists
+        if (a->n_recs >= 1024 && g_inflate_route) {
+            const int rc = build_order(OrderByInLen{a->desc, a->n_recs}, a->n_recs, true, ROUTE_LONG_BUCKET, st, &ord, hold);
+            if (rc) return rc;
+        }
+        if (!ord) {                                   // (no routing, or no scratch for this device: file order is always correct)
+            hipLaunchKernelGGL(k_inflate_simt<false>, dim3(nb64), dim3(64), 64 * sizeof(LaneTables), st, *a, ord);
         } else {
             AuxStream *ax;
             const uint32_t aux_gen = s5host_generation;
             { const int rc = aux_acquire(&ax); if (rc) return rc; }
             struct AuxGuard { AuxStream *a; uint32_t gen; ~AuxGuard() { aux_release(a, gen); } } aux_guard{ax, aux_gen};   // back to the pool on every way out
             AuxStream &t_aux = *ax;
-            const uint32_t nbt = (a->n_recs + NT - 1) / NT;
-            hipLaunchKernelGGL(k_route_zero, dim3(1), dim3(NT), 0, st, *a);
-            hipLaunchKernelGGL(k_route_count, dim3(nbt), dim3(NT), 0, st, *a);
-            hipLaunchKernelGGL(k_route_scan, dim3(1), dim3(128), 0, st, *a);
-            hipLaunchKernelGGL(k_route_scatter, dim3(nbt), dim3(NT), 0, st, *a);
             // the longest records first, on a second stream, beside the lane kernel
             HIP_TRY(hipEventRecord(t_aux.fork, st));
             HIP_TRY(hipStreamWaitEvent(t_aux.st, t_aux.fork, 0));
-            hipLaunchKernelGGL(k_inflate_long, dim3(a->n_recs < 16384 ? a->n_recs : 16384), dim3(64), 0, t_aux.st, *a);
+            hipLaunchKernelGGL(k_inflate_long, dim3(a->n_recs < 16384 ? a->n_recs : 16384), dim3(64), 0, t_aux.st, *a, ord);
             HIP_TRY(hipEventRecord(t_aux.join, t_aux.st));
-            hipLaunchKernelGGL(k_inflate_simt<true>, dim3(nb64), dim3(64), 64 * sizeof(LaneTables), st, *a);
+            hipLaunchKernelGGL(k_inflate_simt<true>, dim3(nb64), dim3(64), 64 * sizeof(LaneTables), st, *a, ord);
             HIP_TRY(hipStreamWaitEvent(st, t_aux.join, 0));
         }
     } else {
@@ -2308,8 +2164,25 @@ extern "C" uint64_t s5gpu_decode_scratch_bytes(uint32_t max_pay_cap) {
     return 64 + slot * (256ull * S5_IP_WAVES * 4 + 256);
 }
 
+// the no-payload kernel variants of s5gpu_decode_dev, by the index it computes: 0 .. 3 = zlib, svb-zd (0, 1) / ex-zd (2, 3) records with the long (even)
+// / short (odd) waiting list; 5 = short svb-zd records kept in LDS; 4 = zstd, which takes one argument more and so has only an address here
+using NpKernel = void (*)(s5gpu_decode_args_t, NpParams);
+static NpKernel np_kernel(int variant) {
+    switch (variant) {
+    case 0: return k_inflate_par_np<false, false>;
+    case 1: return k_inflate_par_np<false, true>;
+    case 2: return k_inflate_par_np<true, false>;
+    case 3: return k_inflate_par_np<true, true>;
+    case 5: return k_inflate_par_np_lp;
+    default: return nullptr;
+    }
+}
+static const void *np_kernel_addr(int variant) {
+    return variant == 4 ? reinterpret_cast<const void *>(k_zstd_inflate_np) : reinterpret_cast<const void *>(np_kernel(variant));
+}
+
 extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
-    if (!a || (a->n_recs && (!a->desc || !a->in || !a->payload || !a->sig_out || !a->fields))) {
+    if (dec_check(a, true, true)) {
         s5gpu_set_error("s5gpu_decode_dev: bad arguments");
         return S5GPU_ERR_ARG;
     }
@@ -2350,14 +2223,7 @@ extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
             int per_cu = 0, cus = 0, dev = 0;
             HIP_TRY(hipGetDevice(&dev));
             HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            switch (variant) {
-            case 0: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_inflate_par_np<false, false>), 64, 0)); break;
-            case 1: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_inflate_par_np<false, true>), 64, 0)); break;
-            case 2: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_inflate_par_np<true, false>), 64, 0)); break;
-            case 3: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_inflate_par_np<true, true>), 64, 0)); break;
-            case 5: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_inflate_par_np_lp, 64, 0)); break;
-            default: HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_zstd_inflate_np, 64, 0)); break;
-            }
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, np_kernel_addr(variant), 64, 0));
             res = (uint32_t)(per_cu > 0 && cus > 0 ? per_cu * cus : 4096);
             s_res[variant].store(res, std::memory_order_relaxed);
         }
@@ -2378,10 +2244,7 @@ extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
             if (zl) { const int rc = launch_order(a, st, &np.ord, hold); if (rc) return rc; }     // tickets in the order of the list: the longest records first
         }
         if (zl) {
-            const bool shortrec = shortrec_np;
-            if (lds_pay) hipLaunchKernelGGL(k_inflate_par_np_lp, dim3((uint32_t)n_main), dim3(64), 0, st, *a, np);
-            else if (np_xz) { if (shortrec) hipLaunchKernelGGL((k_inflate_par_np<true, true>), dim3((uint32_t)n_main), dim3(64), 0, st, *a, np); else hipLaunchKernelGGL((k_inflate_par_np<true, false>), dim3((uint32_t)n_main), dim3(64), 0, st, *a, np); }
-            else { if (shortrec) hipLaunchKernelGGL((k_inflate_par_np<false, true>), dim3((uint32_t)n_main), dim3(64), 0, st, *a, np); else hipLaunchKernelGGL((k_inflate_par_np<false, false>), dim3((uint32_t)n_main), dim3(64), 0, st, *a, np); }
+            hipLaunchKernelGGL(np_kernel(variant), dim3((uint32_t)n_main), dim3(64), 0, st, *a, np);
             hipLaunchKernelGGL(k_inflate_fallback_np, dim3((uint32_t)n_fb), dim3(64), 0, st, *a, np);
         } else {
             uint32_t *ws32 = nullptr;

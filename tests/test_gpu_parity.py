@@ -614,6 +614,136 @@ def test_big_mixed_length_batch_is_routed_by_length(press):
         assert g["status"] == 0 and h["status"] == 0 and q["status"] == 0 and np.array_equal(g["signal"], s) and g["payload"] == h["payload"] == q["payload"]
 
 
+def _length_bucket(n):
+    """the bucket of the library's counting sorts: four per octave"""
+    if n < 4:
+        return n
+    hb = n.bit_length() - 1
+    return hb * 4 + ((n >> (hb - 2)) & 3)
+
+
+_ROUTE_BASE = []
+
+
+def _route_reads(press, lens):
+    """reads cut out of one long synthetic trace (generating a trace costs more than everything else here), encoded as zlib + svb-zd
+    records: (records without their size prefix, their payloads by stock zlib)"""
+    if not _ROUTE_BASE:
+        _ROUTE_BASE.append(ob.synth_read(0x77, 0, 400000))
+    base = _ROUTE_BASE[0]
+    rng = np.random.default_rng(len(lens))
+    sigs = [base[o:o + int(n)] for o, n in zip(rng.integers(0, base.size - int(max(lens)), len(lens)), lens)]
+    recs = [r[8:] for r in press.encode_records(sigs, [_hdr(press, i) for i in range(len(sigs))])]
+    return recs, [zlib.decompress(r) for r in recs]
+
+
+def _inflate_dev(recs, pays, fill):
+    """one s5gpu_inflate_dev call on buffers laid out here, the caller's fields array filled with the byte `fill` beforehand.
+    Returns (the fields as n x 16 words, the payload slots cut to the reported lengths)"""
+    import ctypes as C
+
+    import torch
+    from slow5tools_amd import _lib
+
+    L = _lib.lib()
+    n = len(recs)
+    lens = np.array([len(r) for r in recs], dtype=np.int64)
+    in_off = np.concatenate([[0], np.cumsum((lens + 15) // 16 * 16)]).astype(np.int64)
+    blob = np.zeros(int(in_off[-1]) + 64, dtype=np.uint8)
+    for r, o in zip(recs, in_off[:-1]):
+        blob[o:o + len(r)] = np.frombuffer(r, dtype=np.uint8)
+    caps = (np.array([len(p) for p in pays], dtype=np.int64) + 31) // 16 * 16
+    pay_off = np.concatenate([[0], np.cumsum(caps + 16)]).astype(np.int64)
+    d = np.zeros(n, dtype=_lib.REC_DESC)
+    d["in_off"], d["in_len"], d["pay_off"], d["pay_cap"] = in_off[:-1], lens, pay_off[:-1], caps
+    dev = torch.device("cuda:0")
+    t_in = torch.from_numpy(blob).to(dev)
+    t_desc = torch.from_numpy(d.view(np.uint8).copy()).to(dev)
+    t_pay = torch.zeros(int(pay_off[-1]) + 64, dtype=torch.uint8, device=dev)
+    t_fields = torch.full((n * _lib.REC_FIELDS.itemsize,), fill, dtype=torch.uint8, device=dev)
+    a = _lib.DecodeArgs()
+    a.n_recs, a.rec_method, a.sig_method = n, 1, 1
+    a.desc, a.in_, a.payload, a.fields = t_desc.data_ptr(), t_in.data_ptr(), t_pay.data_ptr(), t_fields.data_ptr()
+    _lib.check(L.s5gpu_inflate_dev(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_inflate_dev")
+    torch.cuda.synchronize(dev)
+    f = t_fields.cpu().numpy().view(np.uint32).reshape(n, 16)
+    pay = t_pay.cpu().numpy()
+    return f, [pay[o:o + min(int(pl), int(c))].tobytes() for o, pl, c in zip(pay_off[:-1], f[:, 1], caps)]
+
+
+def _lane_kernels(L, route):
+    from slow5tools_amd import _lib
+
+    _lib.check(L.s5gpu_set_option(b"inflate_par", 0), "set_option")
+    _lib.check(L.s5gpu_set_option(b"inflate_simt_min", 1), "set_option")
+    _lib.check(L.s5gpu_set_option(b"inflate_route", route), "set_option")
+
+
+def _default_kernels(L):
+    from slow5tools_amd import _lib
+
+    _lib.check(L.s5gpu_set_option(b"inflate_route", 1), "set_option")
+    _lib.check(L.s5gpu_set_option(b"inflate_simt_min", 24576), "set_option")
+    _lib.check(L.s5gpu_set_option(b"inflate_par", 1), "set_option")
+
+
+@pytest.fixture(scope="module")
+def routed_mixed_reads(press):
+    rng = np.random.default_rng(17)
+    ns = np.clip(np.exp(rng.normal(np.log(1500), 1.0, 1025)), 1, 90000).astype(int)
+    ns[:4] = (0, 1, 90000, 60000)
+    return _route_reads(press, ns)
+
+
+@pytest.mark.parametrize("n", [1024, 1025])      # the routing threshold and a whole number of workgroups; one partly filled workgroup more
+def test_inflate_only_routed_call_leaves_the_callers_fields_alone(press, routed_mixed_reads, n):
+    """s5gpu_inflate_dev on a routed batch reports status and payload_len and nothing else: the length-sorted list lives in the library's
+    own scratch, so every other word of the caller's fields array still holds what the caller put there"""
+    from slow5tools_amd import _lib
+
+    L = _lib.lib()
+    recs, pays = routed_mixed_reads[0][:n], routed_mixed_reads[1][:n]
+    assert sum(len(r) >= 32768 for r in recs) >= 2
+    _lane_kernels(L, 1)
+    try:
+        f, got = _inflate_dev(recs, pays, 0xA5)
+    finally:
+        _default_kernels(L)
+    assert (f[:, 0] == 0).all()
+    assert (f[:, 1] == [len(p) for p in pays]).all()
+    for i, (g, p) in enumerate(zip(got, pays)):
+        assert g == p, i
+    bad = np.argwhere(f[:, 2:] != 0xA5A5A5A5)
+    assert bad.size == 0, "fields words overwritten (record, word - 2): %s ..." % bad[:8].tolist()
+
+
+def test_routed_batches_of_one_length_class_and_of_long_records_only(press):
+    """the two ends of the routing: 1100 reads of one length, none of them long (no list is built: the lane kernel takes the batch in file
+    order), and 1100 records of >= 32 KiB each (one length class too, but all of it is the wave kernel's: the list IS built and the lane
+    kernel gets nothing).  Either way the result is what the unrouted lane kernel gives, record for record"""
+    from slow5tools_amd import _lib
+
+    L = _lib.lib()
+    short = _route_reads(press, [2000] * 1100)
+    bs = [_length_bucket(len(r)) for r in short[0]]
+    assert max(bs) - min(bs) <= 2 and max(bs) < 15 * 4                       # one class: at most three neighbouring buckets, below 32 KiB
+    longs = _route_reads(press, np.random.default_rng(5).integers(56000, 64000, 1100))
+    assert min(len(r) for r in longs[0]) >= 32768
+    for recs, pays in (short, longs):
+        try:
+            outs = []
+            for route in (1, 0):
+                _lane_kernels(L, route)
+                outs.append(_inflate_dev(recs, pays, 0))
+        finally:
+            _default_kernels(L)
+        (f1, p1), (f0, p0) = outs
+        assert (f1[:, 0] == 0).all() and (f0[:, 0] == 0).all()
+        assert (f1[:, 1] == f0[:, 1]).all()
+        for i, (g, h, p) in enumerate(zip(p1, p0, pays)):
+            assert g == h == p, i
+
+
 def test_host_batch_with_one_very_long_read_keeps_the_short_reads_fused(press):
     """a batch the device entry point would stage as a whole (longest read >> the LDS budget): the host call names an 8 KiB fused
     budget from the lengths it sees — short reads fused, the long ones through the overflow list; same records either way"""
