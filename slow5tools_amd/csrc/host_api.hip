@@ -20,6 +20,7 @@
 #include "../../include/slow5gpu.h"
 #include <deque>
 #include "host_ctx.h"
+#include "enc_plan.h"
 
 static thread_local char g_err[512] = "";
 namespace s5host { std::mutex g_mu; }
@@ -329,11 +330,10 @@ int s5host::encode_stream_resident(Ctx *c, uint32_t n, const std::vector<s5gpu_r
         // would send such a batch through the staged kernels as a whole; the lengths are known here: when a tenth of the
         // reads or more fit an 8 KiB payload, those take the fused kernel and the rest its overflow list (measured on
         // log-normal lengths, median 6000 samples: 233 -> 285 GB/s; a batch of long reads only loses 3 % to the attempt)
-        const double per = a.sig_method == S5GPU_SIG_SVB_ZD ? 1.55 : a.sig_method == S5GPU_SIG_EX_ZD ? 1.30 : 2.0;
+        const double per = s5plan::fit_per_sample(a.sig_method), budget = s5plan::MIXED_BUDGET;
         uint32_t fit = 0;
-        for (uint32_t i = 0; i < n; i++) fit += desc[i].hdr_len + 8.0 + desc[i].aux_len + per * desc[i].n_samples + 64 <= 8192.0;
-        const uint32_t div = a.sig_method == S5GPU_SIG_SVB_ZD ? 325 : a.sig_method == S5GPU_SIG_EX_ZD ? 950 : 100;
-        if ((uint64_t)a.max_payload * 100 / div > 4ull * 16384 && fit >= n / 10 && fit > 0) a.lds_payload_cap = 8192;
+        for (uint32_t i = 0; i < n; i++) fit += desc[i].hdr_len + 8.0 + desc[i].aux_len + per * desc[i].n_samples + 64 <= budget;
+        if (s5plan::batch_is_long(a.sig_method, a.max_payload, s5plan::BLK) && fit >= n / 10 && fit > 0) a.lds_payload_cap = s5plan::MIXED_BUDGET;
     }
     if ((rc = s5gpu_encode_dev(&a, c->st))) return rc;
     uint8_t *ho_len = (uint8_t *)c->h_out.p;

@@ -2,6 +2,7 @@
 // One read per workgroup (4 x wave64); all intermediates of a read live in LDS; HBM sees the int16
 // samples once (coalesced 16-B loads) and the finished record once (coalesced word stores).
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,12 +24,14 @@
 #include "svb_dev.h"
 #include "exzd_dev.h"
 #include "order_dev.h"
+#include "enc_plan.h"
 
 using namespace s5;
 
 extern "C" void s5gpu_set_error(const char *fmt, ...);
 int s5host_set_option(const char *key, long value);   // host_api.hip: options of the host layer
 extern uint32_t s5host_generation;                    // host_api.hip: bumped by s5gpu_shutdown
+static_assert(s5plan::BLK == (uint32_t)DEFL_BLK && s5plan::SIG_SVB_ZD == S5GPU_SIG_SVB_ZD && s5plan::SIG_EX_ZD == S5GPU_SIG_EX_ZD, "enc_plan.h restates these");
 
 #define HIP_TRY(x)                                                                                   \
     do {                                                                                             \
@@ -1704,46 +1707,102 @@ static int launch_eorder(const s5gpu_encode_args_t *a, hipStream_t st, const uin
     return build_order(OrderOvfBySamples{a->desc, a->ovf}, a->n_reads, order, 0, st, out, hold);
 }
 
-static void launch_lz(EncParams p, uint32_t n, uint32_t max_payload, hipStream_t st, bool build = false);
+static bool rec_method_ok(int m) { return m == S5GPU_REC_NONE || m == S5GPU_REC_ZLIB || m == S5GPU_REC_ZSTD; }
+static bool sig_method_ok(int m) { return m == S5GPU_SIG_NONE || m == S5GPU_SIG_SVB_ZD || m == S5GPU_SIG_EX_ZD; }
 static int enc_check(const s5gpu_encode_args_t *a) {
     if (!a || (a->n_reads && (!a->desc || !a->sig || !a->hdr || !a->slots || !a->out_len))) return S5GPU_ERR_ARG;
-    if (a->rec_method != S5GPU_REC_NONE && a->rec_method != S5GPU_REC_ZLIB && a->rec_method != S5GPU_REC_ZSTD) return S5GPU_ERR_ARG;
-    if (a->sig_method != S5GPU_SIG_NONE && a->sig_method != S5GPU_SIG_SVB_ZD && a->sig_method != S5GPU_SIG_EX_ZD) return S5GPU_ERR_ARG;
+    return rec_method_ok(a->rec_method) && sig_method_ok(a->sig_method) ? S5GPU_OK : S5GPU_ERR_ARG;
+}
+
+// What a launch of an encode kernel carries.  The budget rules are enc_plan.h's; here they become EncParams and bytes of LDS.
+static EncParams enc_params(const s5gpu_encode_args_t *a, bool dbg = false) {   // dbg: S5GPU_DEBUG_STAGE is honoured (s5gpu_encode_dev only)
+    EncParams p;
+    p.a = *a;
+    p.dbg = dbg && getenv("S5GPU_DEBUG_STAGE") ? (uint32_t)atoi(getenv("S5GPU_DEBUG_STAGE")) : 0;
+    p.zseq = g_zstd_sequences;
+    p.obuf_words = 0; p.pay_cap = 0;
+    return p;
+}
+// the staged kernels: one block of payload staged behind the bit buffer (which the build scratch overlays); returns the LDS bytes
+static size_t staged_shape(EncParams &p) {
+    p.obuf_words = (DEFL_BLK + 64) / 4; p.pay_cap = DEFL_BLK;
+    return S_BYTES + 4ull * p.obuf_words + DEFL_BLK;
+}
+// the fused kernels: `cap` bytes of payload; the bit buffer holds a payload's worth and at least the kernel's build scratch (`floor`)
+static size_t fused_shape(EncParams &p, uint32_t cap, uint32_t floor) {
+    p.obuf_words = (cap + 64 > floor ? cap + 64 : floor) / 4; p.pay_cap = cap;
+    return S_BYTES + 4ull * p.obuf_words + cap;
+}
+// the single-pass kernels' outputs and look-back state, the state cleared on `st`
+static int stream_params(StreamParams *sp, uint32_t n_reads, uint8_t *stream_out, uint64_t *rec_off, uint64_t *state, uint32_t *ctl, hipStream_t st) {
+    *sp = StreamParams{reinterpret_cast<unsigned long long *>(state), ctl, stream_out, rec_off};
+    HIP_TRY(hipMemsetAsync(state, 0, 8ull * n_reads, st));
+    HIP_TRY(hipMemsetAsync(ctl, 0, 16, st));
     return S5GPU_OK;
 }
 
-// Function attributes are per device: done once for each device a launch is made on (the batch API runs host threads on
-// several devices at once, so the bookkeeping is a mutex-guarded bit per device ordinal).
-static std::mutex g_attr_mu;
-static std::atomic<uint64_t> g_attr_devs{0};
-static int set_lds_attrs() {
+// Every encode kernel variant is named in one place, as the decode ones further down: a launch takes its kernel from these tables, and
+// set_lds_attrs walks the same tables, so a variant that can be launched cannot be missing the attribute.
+using EncodeKernel = void (*)(EncParams);
+using StreamKernel = void (*)(EncParams, StreamParams);
+static const EncodeKernel ENCODE_FUSED[] = {k_encode_fused<uint32_t, false>, k_encode_fused<uint32_t, true>, k_encode_fused<uint64_t, false>, k_encode_fused<uint64_t, true>,
+                                            k_encode_fused<uint64_t, false, 4>};   // the last: registers for the four workgroups per CU a second launch's LDS allows
+static const StreamKernel ENCODE_STREAM[] = {k_encode_stream<uint32_t, false>, k_encode_stream<uint32_t, true>, k_encode_stream<uint64_t, false>, k_encode_stream<uint64_t, true>};
+static const EncodeKernel ZSTD_FUSED[] = {k_zstd_fused<false>, k_zstd_fused<true>};
+static EncodeKernel encode_fused_kernel(bool wide, bool exzd, bool four_per_cu = false) { return ENCODE_FUSED[four_per_cu ? 4 : 2 * wide + exzd]; }   // (four_per_cu: wide svb-zd only)
+static StreamKernel encode_stream_kernel(bool wide, bool exzd) { return ENCODE_STREAM[2 * wide + exzd]; }
+static EncodeKernel zstd_fused_kernel(bool exzd) { return ZSTD_FUSED[exzd]; }
+// the other kernels that may be launched with more than 64 KiB of dynamic LDS
+static const void *const LDS_KERNELS[] = {(const void *)k_deflate_staged, (const void *)k_deflate_lz<LzLong>, (const void *)k_deflate_lz<LzShort>, (const void *)k_zstd_staged,
+                                          (const void *)k_svbzd_encode, (const void *)k_svbzd_stream, (const void *)k_inflate_simt<false>, (const void *)k_inflate_simt<true>};
+
+// What is known about a device, per ordinal; found out by the first call that needs it there (the batch API runs host threads on several
+// devices at once: atomics, and two threads that find out the same thing at the same time do no harm).  An ordinal past the table has no
+// record and is served uncached: asked every time, never taken for another device.
+constexpr int DEV_MAX = 64;
+struct DeviceFacts {
+    std::atomic<bool> attrs{false};        // hipFuncAttributeMaxDynamicSharedMemorySize is set on every kernel of the tables above
+    std::atomic<int> cus{0};               // compute units
+    std::atomic<uint32_t> np_resident[6];  // workgroups the device holds at once, per no-payload decode variant (np_kernel); 0 = not asked yet
+} static g_dev[DEV_MAX];
+static DeviceFacts *device_facts() {       // the current device's
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < DEV_MAX ? &g_dev[dev] : nullptr;
+}
+static int device_cus(int *cus) {          // (<= 0 where the runtime does not say: not kept)
+    DeviceFacts *f = device_facts();
+    *cus = f ? f->cus.load(std::memory_order_relaxed) : 0;
+    if (*cus > 0) return S5GPU_OK;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    const uint64_t bit = 1ull << (dev & 63);
-    if (g_attr_devs.load(std::memory_order_acquire) & bit) return S5GPU_OK;
-    std::lock_guard<std::mutex> lk(g_attr_mu);
-    if (g_attr_devs.load(std::memory_order_relaxed) & bit) return S5GPU_OK;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_fused<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_fused<uint64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_fused<uint64_t, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_stream<uint32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_stream<uint64_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_fused<uint32_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_fused<uint64_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_stream<uint32_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_encode_stream<uint64_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_deflate_staged), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_deflate_lz<LzLong>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_deflate_lz<LzShort>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_zstd_staged), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_zstd_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_zstd_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_svbzd_encode), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_svbzd_stream), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_inflate_simt<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_inflate_simt<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    g_attr_devs.fetch_or(bit, std::memory_order_release);
+    HIP_TRY(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (f && *cus > 0) f->cus.store(*cus, std::memory_order_relaxed);
     return S5GPU_OK;
+}
+static int set_lds_attrs() {
+    DeviceFacts *f = device_facts();
+    if (f && f->attrs.load(std::memory_order_acquire)) return S5GPU_OK;
+    constexpr int LDS_MAX = 160 * 1024 - 256;
+    for (EncodeKernel k : ENCODE_FUSED) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    for (StreamKernel k : ENCODE_STREAM) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    for (EncodeKernel k : ZSTD_FUSED) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    for (const void *k : LDS_KERNELS) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    if (f) f->attrs.store(true, std::memory_order_release);
+    return S5GPU_OK;
+}
+
+// The LZ77 kernels over parked payloads (out_len[r] = payload length): payloads of at most 8 KiB on LzShort (4 workgroups per CU), the rest on
+// LzLong (1 per CU).  max_payload == 0: unknown (the solo press does not say): both run, each takes its share.
+static void launch_lz(EncParams p, uint32_t n, uint32_t max_payload, hipStream_t st, bool build = false) {
+    staged_shape(p);
+    const bool any_long = max_payload == 0 || max_payload > (uint32_t)LzShort::BLK;
+    const uint32_t gs = n < 8192 ? n : 8192;
+    hipLaunchKernelGGL(k_deflate_lz<LzShort>, dim3(gs), dim3(NT), S_BYTES + LZS_BYTES, st, p, 0, any_long ? 1 : 0 /* which = 0: every record is short */,
+                       build && !any_long ? 1 : 0);
+    if (any_long) {
+        const uint32_t gl = n < 2048 ? n : 2048;
+        hipLaunchKernelGGL(k_deflate_lz<LzLong>, dim3(gl), dim3(LzLong::TN), S_BYTES + 4ull * p.obuf_words + LZ_BYTES, st, p, 0, 1, 0);
+    }
 }
 
 extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
@@ -1752,41 +1811,19 @@ extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
     if (a->n_reads == 0) return S5GPU_OK;
     if ((rc = set_lds_attrs())) return rc;
     hipStream_t st = (hipStream_t)stream_;
-    EncParams p;
-    p.a = *a;
-    p.dbg = getenv("S5GPU_DEBUG_STAGE") ? (uint32_t)atoi(getenv("S5GPU_DEBUG_STAGE")) : 0;
-    p.zseq = g_zstd_sequences;
+    EncParams p = enc_params(a, true);
     if (a->rec_method == S5GPU_REC_NONE) {
-        p.obuf_words = 0; p.pay_cap = 0;
         hipLaunchKernelGGL(k_pack, dim3(a->n_reads), dim3(NT), 0, st, p, 1, nullptr);
         HIP_TRY(hipGetLastError());
         return S5GPU_OK;
     }
     if (!a->ovf) { s5gpu_set_error("s5gpu_encode_dev: args.ovf (n_reads + 1 words of device scratch) is required"); return S5GPU_ERR_ARG; }
-    // LDS budget of the fused kernel.  The payload bound assumes 3 bytes per sample; real signals take
-    // ~1.27 (P(2-byte code) ~1.5 %), so by default keep room for 1.55 bytes per sample: with
-    // ~4 KiB of tables that is ~17 KiB per 4000-sample read -> 8 workgroups per CU.  Anything that does
-    // not fit is redone by the staged kernels (correct for any input, slower).
-    uint32_t cap = a->lds_payload_cap;
-    if (cap == 0) {
-        // the bounds assume the worst case (3 B/sample for svb-zd, 9.5 for ex-zd); real signals take ~1.27 / ~1.06
-        cap = a->sig_method == S5GPU_SIG_SVB_ZD ? (uint32_t)((uint64_t)a->max_payload * 155 / 325) + 128
-            : a->sig_method == S5GPU_SIG_EX_ZD ? (uint32_t)((uint64_t)a->max_payload * 130 / 950) + 256 : a->max_payload;
-    }
-    if (cap > a->max_payload) cap = a->max_payload;
-    if (cap > (uint32_t)DEFL_BLK) cap = DEFL_BLK;
-    cap = (cap + 15u) & ~15u;
-    // every read certainly longer than the fused budget?  (min payload ~ 1.25 B/sample of a 3.25 B/sample bound)
-    // (a caller that names an LDS budget knows its batch is mixed: short reads fused, the rest through the overflow list)
-    const bool all_staged = a->lds_payload_cap ? false
-                          : a->sig_method == S5GPU_SIG_EX_ZD ? (uint64_t)a->max_payload * 100 / 950 > 4ull * DEFL_BLK
-                          : a->sig_method == S5GPU_SIG_SVB_ZD ? (uint64_t)a->max_payload * 100 / 325 > 4ull * DEFL_BLK
-                                                              : a->max_payload > 4u * DEFL_BLK;
-    const uint32_t st_obuf = (DEFL_BLK + 64) / 4;
-    const size_t st_lds = S_BYTES + 4ull * st_obuf + DEFL_BLK;   // the build scratch overlays the bit buffer
+    // LDS budget of the fused kernel (enc_plan.h): 1.55 bytes per sample by default; with ~4 KiB of tables that is ~17 KiB per 4000-sample
+    // read -> 8 workgroups per CU.  Anything that does not fit is redone by the staged kernels (correct for any input, slower).
+    const uint32_t cap = s5plan::fused_cap(a->sig_method, a->max_payload, a->lds_payload_cap, DEFL_BLK);
     if (a->rec_method == S5GPU_REC_ZLIB && a->sig_method == S5GPU_SIG_NONE) {
         // raw int16 samples: the redundancy is repeated sample pairs at any distance, not runs — the LZ77 matcher (lz_dev.h)
-        p.obuf_words = st_obuf; p.pay_cap = DEFL_BLK;
+        staged_shape(p);
         // raw-signal records: a batch of short ones (payloads of one 8 KiB block) builds its payloads inside the matcher's kernel
         const bool all_short = a->max_payload != 0 && a->max_payload <= (uint32_t)LzShort::BLK;
         if (!all_short) hipLaunchKernelGGL(k_pack, dim3(a->n_reads), dim3(NT), 0, st, p, 0, nullptr);
@@ -1800,15 +1837,13 @@ extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
         HIP_TRY(hipGetLastError());
         return S5GPU_OK;
     }
-    if (!all_staged) {
+    if (!s5plan::all_staged(a->sig_method, a->max_payload, a->lds_payload_cap, DEFL_BLK)) {
         HIP_TRY(hipMemsetAsync(a->ovf, 0, 4, st));
-        p.pay_cap = cap;
         const bool xz = a->sig_method == S5GPU_SIG_EX_ZD, zs = a->rec_method == S5GPU_REC_ZSTD;
-        const uint32_t floor_b = zs ? BZ_BYTES : B_BYTES;
-        p.obuf_words = (cap + 64 > floor_b ? cap + 64 : floor_b) / 4;
-        const size_t lds = S_BYTES + 4ull * p.obuf_words + p.pay_cap;
-        if (zs) { if (xz) hipLaunchKernelGGL(k_zstd_fused<true>, dim3(a->n_reads), dim3(NT), lds, st, p); else hipLaunchKernelGGL(k_zstd_fused<false>, dim3(a->n_reads), dim3(NT), lds, st, p); }
-        else {
+        if (zs) {
+            const size_t lds = fused_shape(p, cap, BZ_BYTES);
+            hipLaunchKernelGGL(zstd_fused_kernel(xz), dim3(a->n_reads), dim3(NT), lds, st, p);
+        } else {
             // A caller that names an LDS budget has a batch of mixed lengths.  Option "fused_tier2" (round 4, off by default) gives it TWO fused
             // launches — the named budget at eight workgroups per CU for the short reads, then up to one 16 KiB DEFLATE block for the reads in
             // between, which the staged kernels take through HBM twice; only what fits neither goes on the overflow list.  The first launch leaves
@@ -1819,23 +1854,18 @@ extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
             if (cap2 > (uint32_t)DEFL_BLK) cap2 = DEFL_BLK;
             if (cap2 <= cap) cap2 = 0;
             if (cap2) { HIP_TRY(hipMemsetAsync(a->out_len, 0, 4ull * a->n_reads, st)); p.tier = 1; }
-            auto fused = [&](uint32_t c, size_t l) {
-                if (c <= 8192) { if (xz) hipLaunchKernelGGL((k_encode_fused<uint32_t, true>), dim3(a->n_reads), dim3(NT), l, st, p); else hipLaunchKernelGGL(k_encode_fused<uint32_t>, dim3(a->n_reads), dim3(NT), l, st, p); }
-                else { if (xz) hipLaunchKernelGGL((k_encode_fused<uint64_t, true>), dim3(a->n_reads), dim3(NT), l, st, p); else hipLaunchKernelGGL(k_encode_fused<uint64_t>, dim3(a->n_reads), dim3(NT), l, st, p); }
-            };
-            fused(cap, lds);
+            const size_t lds = fused_shape(p, cap, B_BYTES);
+            hipLaunchKernelGGL(encode_fused_kernel(s5plan::wide(cap), xz), dim3(a->n_reads), dim3(NT), lds, st, p);
             if (cap2) {
                 p.tier = 2;
-                p.pay_cap = cap2;
-                p.obuf_words = (cap2 + 64 > B_BYTES ? cap2 + 64 : B_BYTES) / 4;
-                const size_t l2 = S_BYTES + 4ull * p.obuf_words + p.pay_cap;
-                if (cap2 > 8192 && !xz) hipLaunchKernelGGL((k_encode_fused<uint64_t, false, 4>), dim3(a->n_reads), dim3(NT), l2, st, p);   // registers for the four workgroups per CU its LDS allows
-                else fused(cap2, l2);
+                const size_t lds2 = fused_shape(p, cap2, B_BYTES);
+                const bool wide2 = s5plan::wide(cap2);   // (wide svb-zd: the variant with registers for the four workgroups per CU its LDS allows)
+                hipLaunchKernelGGL(encode_fused_kernel(wide2, xz, wide2 && !xz), dim3(a->n_reads), dim3(NT), lds2, st, p);
                 p.tier = 0;
             }
         }
         // overflow reads (usually none: the two launches below then exit at once)
-        p.obuf_words = st_obuf; p.pay_cap = DEFL_BLK;
+        const size_t st_lds = staged_shape(p);
         const uint32_t g = a->n_reads < 8192 ? a->n_reads : 8192;   // persistent loops over the list; enough workgroups for the CUs to balance
         // the reads on the list, longest first (a caller that names an LDS budget has a mixed batch; otherwise the list is usually empty)
         const uint32_t *eord = nullptr;
@@ -1845,7 +1875,7 @@ extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
         if (zs) hipLaunchKernelGGL(k_zstd_staged, dim3(g), dim3(NT), st_lds, st, p, 1);
         else hipLaunchKernelGGL(k_deflate_staged, dim3(g), dim3(S5_STAGED_TN), st_lds, st, p, 1, eord);
     } else {
-        p.obuf_words = st_obuf; p.pay_cap = DEFL_BLK;
+        const size_t st_lds = staged_shape(p);
         hipLaunchKernelGGL(k_pack, dim3(a->n_reads), dim3(NT), 0, st, p, 0, nullptr);
         if (a->rec_method == S5GPU_REC_ZSTD) hipLaunchKernelGGL(k_zstd_staged, dim3(a->n_reads), dim3(NT), st_lds, st, p, 0);
         else hipLaunchKernelGGL(k_deflate_staged, dim3(a->n_reads), dim3(S5_STAGED_TN), st_lds, st, p, 0, nullptr);
@@ -1854,36 +1884,10 @@ extern "C" int s5gpu_encode_dev(const s5gpu_encode_args_t *a, void *stream_) {
     return S5GPU_OK;
 }
 
-// The LZ77 kernels over parked payloads (out_len[r] = payload length): payloads of at most 8 KiB on LzShort (4 workgroups per CU), the rest on
-// LzLong (1 per CU).  max_payload == 0: unknown (the solo press does not say): both run, each takes its share.
-static void launch_lz(EncParams p, uint32_t n, uint32_t max_payload, hipStream_t st, bool build) {
-    p.obuf_words = (DEFL_BLK + 64) / 4;
-    const bool any_long = max_payload == 0 || max_payload > (uint32_t)LzShort::BLK;
-    const uint32_t gs = n < 8192 ? n : 8192;
-    hipLaunchKernelGGL(k_deflate_lz<LzShort>, dim3(gs), dim3(NT), S_BYTES + LZS_BYTES, st, p, 0, any_long ? 1 : 0 /* which = 0: every record is short */,
-                       build && !any_long ? 1 : 0);
-    if (any_long) {
-        const uint32_t gl = n < 2048 ? n : 2048;
-        hipLaunchKernelGGL(k_deflate_lz<LzLong>, dim3(gl), dim3(LzLong::TN), S_BYTES + 4ull * p.obuf_words + LZ_BYTES, st, p, 0, 1, 0);
-    }
-}
-
-static uint32_t fused_cap(const s5gpu_encode_args_t *a) {
-    uint32_t cap = a->lds_payload_cap;
-    if (cap == 0) {
-        // the bounds assume the worst case (3 B/sample for svb-zd, 9.5 for ex-zd); real signals take ~1.27 / ~1.06
-        cap = a->sig_method == S5GPU_SIG_SVB_ZD ? (uint32_t)((uint64_t)a->max_payload * 155 / 325) + 128
-            : a->sig_method == S5GPU_SIG_EX_ZD ? (uint32_t)((uint64_t)a->max_payload * 130 / 950) + 256 : a->max_payload;
-    }
-    if (cap > a->max_payload) cap = a->max_payload;
-    if (cap > (uint32_t)DEFL_BLK) cap = DEFL_BLK;
-    return (cap + 15u) & ~15u;
-}
-
 extern "C" int s5gpu_encode_stream_dev(const s5gpu_encode_args_t *a, uint8_t *stream_out, uint64_t *rec_off, uint64_t *state,
                                        uint32_t *ctl, void *stream_) {
     if (!a || !a->desc || !a->sig || !a->hdr || !a->out_len || !stream_out || !rec_off || !state || !ctl ||
-        a->rec_method != S5GPU_REC_ZLIB || a->sig_method < S5GPU_SIG_NONE || a->sig_method > S5GPU_SIG_EX_ZD) {
+        a->rec_method != S5GPU_REC_ZLIB || !sig_method_ok(a->sig_method)) {
         s5gpu_set_error("s5gpu_encode_stream_dev: bad arguments (zlib record press only)");
         return S5GPU_ERR_ARG;
     }
@@ -1891,23 +1895,12 @@ extern "C" int s5gpu_encode_stream_dev(const s5gpu_encode_args_t *a, uint8_t *st
     int rc;
     if ((rc = set_lds_attrs())) return rc;
     hipStream_t st = (hipStream_t)stream_;
-    EncParams p;
-    p.a = *a;
-    p.dbg = 0; p.zseq = g_zstd_sequences;
+    EncParams p = enc_params(a);
     StreamParams sp;
-    sp.state = reinterpret_cast<unsigned long long *>(state);
-    sp.ctl = ctl;
-    sp.stream = stream_out;
-    sp.rec_off = rec_off;
-    HIP_TRY(hipMemsetAsync(state, 0, 8ull * a->n_reads, st));
-    HIP_TRY(hipMemsetAsync(ctl, 0, 16, st));
-    const uint32_t cap = fused_cap(a);
-    p.pay_cap = cap;
-    p.obuf_words = (cap + 64 > B_BYTES ? cap + 64 : B_BYTES) / 4;
-    const size_t lds = S_BYTES + 4ull * p.obuf_words + p.pay_cap;
-    const bool xz = a->sig_method == S5GPU_SIG_EX_ZD;
-    if (cap <= 8192) { if (xz) hipLaunchKernelGGL((k_encode_stream<uint32_t, true>), dim3(a->n_reads), dim3(NT), lds, st, p, sp); else hipLaunchKernelGGL(k_encode_stream<uint32_t>, dim3(a->n_reads), dim3(NT), lds, st, p, sp); }
-    else { if (xz) hipLaunchKernelGGL((k_encode_stream<uint64_t, true>), dim3(a->n_reads), dim3(NT), lds, st, p, sp); else hipLaunchKernelGGL(k_encode_stream<uint64_t>, dim3(a->n_reads), dim3(NT), lds, st, p, sp); }
+    if ((rc = stream_params(&sp, a->n_reads, stream_out, rec_off, state, ctl, st))) return rc;
+    const uint32_t cap = s5plan::fused_cap(a->sig_method, a->max_payload, a->lds_payload_cap, DEFL_BLK);
+    const size_t lds = fused_shape(p, cap, B_BYTES);
+    hipLaunchKernelGGL(encode_stream_kernel(s5plan::wide(cap), a->sig_method == S5GPU_SIG_EX_ZD), dim3(a->n_reads), dim3(NT), lds, st, p, sp);
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
 }
@@ -1919,11 +1912,8 @@ extern "C" int s5gpu_pack_parked_dev(const s5gpu_encode_args_t *a, void *stream_
     int rc = enc_check(a);
     if (rc) { s5gpu_set_error("s5gpu_pack_parked_dev: bad arguments"); return rc; }
     if (a->n_reads == 0) return S5GPU_OK;
-    EncParams p;
-    p.a = *a;
-    p.dbg = 0; p.zseq = g_zstd_sequences;
-    p.obuf_words = (DEFL_BLK + 64) / 4;
-    p.pay_cap = DEFL_BLK;
+    EncParams p = enc_params(a);
+    staged_shape(p);
     hipLaunchKernelGGL(k_pack, dim3(a->n_reads), dim3(NT), 0, (hipStream_t)stream_, p, 0, nullptr);
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
@@ -1934,12 +1924,8 @@ extern "C" int s5gpu_deflate_parked_dev(const s5gpu_encode_args_t *a, void *stre
     if (rc) { s5gpu_set_error("s5gpu_deflate_parked_dev: bad arguments"); return rc; }
     if (a->n_reads == 0) return S5GPU_OK;
     if ((rc = set_lds_attrs())) return rc;
-    EncParams p;
-    p.a = *a;
-    p.dbg = 0; p.zseq = g_zstd_sequences;
-    p.obuf_words = (DEFL_BLK + 64) / 4;
-    p.pay_cap = DEFL_BLK;
-    const size_t lds = S_BYTES + 4ull * p.obuf_words + DEFL_BLK;
+    EncParams p = enc_params(a);
+    const size_t lds = staged_shape(p);
     if (a->rec_method == S5GPU_REC_ZSTD) hipLaunchKernelGGL(k_zstd_staged, dim3(a->n_reads), dim3(NT), lds, (hipStream_t)stream_, p, 0);
     else if (a->sig_method == S5GPU_SIG_NONE)   // byte ranges of unknown kind (the solo zlib press): the LZ77 matcher
         launch_lz(p, a->n_reads, a->max_payload, (hipStream_t)stream_);
@@ -1955,16 +1941,21 @@ static uint32_t g_inflate_par = 1;             // zlib records: the decoder that
 static uint32_t g_inflate_route = 1;           // big zlib batches: sort by length, long records to the wave kernel (below)
 static uint32_t g_np_lds_payload = 1;          // no-payload decode of short svb-zd records: the uncompressed record stays in LDS (option "np_lds_payload")
 static uint32_t g_inflate_simt_min = 24576;   // measured crossover on 4000-sample reads: 16384 wave 3.0 ms vs lane 4.2 ms, 32768 wave 5.8 vs lane 4.5
+// the options of this file: values lo .. hi are taken, and the bits of `keep` kept
+static const struct Option { const char *name; uint32_t *var; long lo, hi; uint32_t keep; } OPTIONS[] = {
+    {"inflate_simt_min", &g_inflate_simt_min, 0, LONG_MAX, ~0u},
+    {"inflate_route", &g_inflate_route, 0, 1, ~0u},
+    {"np_lds_payload", &g_np_lds_payload, 0, 1, ~0u},
+    {"fused_tier2", &g_fused_tier2, 0, DEFL_BLK, ~15u},
+    {"zstd_sequences", &g_zstd_sequences, 0, 1, ~0u},
+    {"unpack_fused", &g_unpack_fused, 0, 1, ~0u},
+    {"inflate_par", &g_inflate_par, 0, 2, ~0u},            // 2 (tools): no fallback pass, declined records keep status 8
+    {"zstd_pre_min", &g_zstd_pre_min, 0, LONG_MAX, ~0u},   // zstd batches: weights pass from this many frames on (0: never)
+    {"order_min", &g_order_min, 0, LONG_MAX, ~0u},         // big zlib batches: longest records first from this many records on (0: never)
+};
 extern "C" int s5gpu_set_option(const char *key, long value) {
-    if (key && strcmp(key, "inflate_simt_min") == 0 && value >= 0) { g_inflate_simt_min = (uint32_t)value; return S5GPU_OK; }
-    if (key && strcmp(key, "inflate_route") == 0 && (value == 0 || value == 1)) { g_inflate_route = (uint32_t)value; return S5GPU_OK; }
-    if (key && strcmp(key, "np_lds_payload") == 0 && (value == 0 || value == 1)) { g_np_lds_payload = (uint32_t)value; return S5GPU_OK; }
-    if (key && strcmp(key, "fused_tier2") == 0 && value >= 0 && value <= DEFL_BLK) { g_fused_tier2 = (uint32_t)value & ~15u; return S5GPU_OK; }
-    if (key && strcmp(key, "zstd_sequences") == 0 && (value == 0 || value == 1)) { g_zstd_sequences = (uint32_t)value; return S5GPU_OK; }
-    if (key && strcmp(key, "unpack_fused") == 0 && (value == 0 || value == 1)) { g_unpack_fused = (uint32_t)value; return S5GPU_OK; }
-    if (key && strcmp(key, "inflate_par") == 0 && value >= 0 && value <= 2) { g_inflate_par = (uint32_t)value; return S5GPU_OK; }   // 2 (tools): no fallback pass, declined records keep status 8
-    if (key && strcmp(key, "zstd_pre_min") == 0 && value >= 0) { g_zstd_pre_min = (uint32_t)value; return S5GPU_OK; }   // zstd batches: weights pass from this many frames on (0: never)
-    if (key && strcmp(key, "order_min") == 0 && value >= 0) { g_order_min = (uint32_t)value; return S5GPU_OK; }   // big zlib batches: longest records first from this many records on (0: never)
+    for (const Option &o : OPTIONS)
+        if (key && strcmp(key, o.name) == 0 && value >= o.lo && value <= o.hi) { *o.var = (uint32_t)value & o.keep; return S5GPU_OK; }
     if (s5host_set_option(key, value) == S5GPU_OK) return S5GPU_OK;
     s5gpu_set_error("s5gpu_set_option: unknown option");
     return S5GPU_ERR_ARG;
@@ -2115,15 +2106,9 @@ extern "C" int s5gpu_svbzd_encode_dev(const s5gpu_encode_args_t *a, void *stream
     int rc = enc_check(a);
     if (rc) { s5gpu_set_error("s5gpu_svbzd_encode_dev: bad arguments"); return rc; }
     if (a->n_reads == 0) return S5GPU_OK;
-    EncParams p;
-    p.a = *a;
-    p.dbg = 0; p.zseq = g_zstd_sequences;
-    p.obuf_words = 0;
-    // LDS for one blob at ~1.55 bytes/sample (max_payload is the 3.25 bytes/sample bound), at most 64 KiB
-    uint64_t cap = a->lds_payload_cap ? a->lds_payload_cap : (uint64_t)a->max_payload * 155 / 325 + 128;
-    if (cap > 64 * 1024) cap = 64 * 1024;
-    p.pay_cap = (uint32_t)((cap + 15) & ~15ull);
     if ((rc = set_lds_attrs())) return rc;
+    EncParams p = enc_params(a);
+    p.pay_cap = s5plan::svb_blob_cap(a->max_payload, a->lds_payload_cap, 1);   // LDS for one blob
     hipLaunchKernelGGL(k_svbzd_encode, dim3(a->n_reads), dim3(NT), p.pay_cap, (hipStream_t)stream_, p);
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
@@ -2139,21 +2124,10 @@ extern "C" int s5gpu_svbzd_encode_stream_dev(const s5gpu_encode_args_t *a, uint8
     int rc;
     if ((rc = set_lds_attrs())) return rc;
     hipStream_t st = (hipStream_t)stream_;
-    EncParams p;
-    p.a = *a;
-    p.dbg = 0; p.zseq = g_zstd_sequences;
-    p.obuf_words = 0;
-    uint64_t cap = a->lds_payload_cap ? a->lds_payload_cap : (uint64_t)a->max_payload * 155 / 325 + 128;   // per blob, as s5gpu_svbzd_encode_dev
-    cap *= S5_SVS_G;                                                                                      // ... and a group's blobs back to back
-    if (cap > 64 * 1024) cap = 64 * 1024;
-    p.pay_cap = (uint32_t)((cap + 15) & ~15ull);
+    EncParams p = enc_params(a);
+    p.pay_cap = s5plan::svb_blob_cap(a->max_payload, a->lds_payload_cap, S5_SVS_G);   // a group's blobs back to back
     StreamParams sp;
-    sp.state = reinterpret_cast<unsigned long long *>(state);
-    sp.ctl = ctl;
-    sp.stream = stream_out;
-    sp.rec_off = rec_off;
-    HIP_TRY(hipMemsetAsync(state, 0, 8ull * a->n_reads, st));
-    HIP_TRY(hipMemsetAsync(ctl, 0, 16, st));
+    if ((rc = stream_params(&sp, a->n_reads, stream_out, rec_off, state, ctl, st))) return rc;
     hipLaunchKernelGGL(k_svbzd_stream, dim3((a->n_reads + S5_SVS_G - 1) / S5_SVS_G), dim3(NT), p.pay_cap + 16, st, p, sp);   // + the copy's look-ahead word
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
@@ -2186,11 +2160,7 @@ extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
         s5gpu_set_error("s5gpu_decode_dev: bad arguments");
         return S5GPU_ERR_ARG;
     }
-    if ((a->rec_method != S5GPU_REC_NONE && a->rec_method != S5GPU_REC_ZLIB && a->rec_method != S5GPU_REC_ZSTD) ||
-        (a->sig_method != S5GPU_SIG_NONE && a->sig_method != S5GPU_SIG_SVB_ZD && a->sig_method != S5GPU_SIG_EX_ZD)) {
-        s5gpu_set_error("s5gpu_decode_dev: unsupported method");
-        return S5GPU_ERR_ARG;
-    }
+    if (!rec_method_ok(a->rec_method) || !sig_method_ok(a->sig_method)) { s5gpu_set_error("s5gpu_decode_dev: unsupported method"); return S5GPU_ERR_ARG; }
     if (a->n_recs == 0) return S5GPU_OK;
     hipStream_t st = (hipStream_t)stream_;
     if (a->flags & S5GPU_DEC_NO_PAYLOAD) {
@@ -2217,15 +2187,14 @@ extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
         // declines what turns out not to fit)
         const bool lds_pay = zl && !np_xz && g_np_lds_payload && a->max_in_len != 0 && a->max_in_len <= (uint32_t)IP_SPAN - 96u;
         const int variant = !zl ? 4 : lds_pay ? 5 : (np_xz ? 2 : 0) + (shortrec_np ? 1 : 0);
-        static std::atomic<uint32_t> s_res[6] = {{0}, {0}, {0}, {0}, {0}, {0}};
-        uint32_t res = s_res[variant].load(std::memory_order_relaxed);
+        DeviceFacts *facts = device_facts();
+        uint32_t res = facts ? facts->np_resident[variant].load(std::memory_order_relaxed) : 0;
         if (!res) {
-            int per_cu = 0, cus = 0, dev = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            int per_cu = 0, cus = 0;
+            { const int rc = device_cus(&cus); if (rc) return rc; }
             HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, np_kernel_addr(variant), 64, 0));
             res = (uint32_t)(per_cu > 0 && cus > 0 ? per_cu * cus : 4096);
-            s_res[variant].store(res, std::memory_order_relaxed);
+            if (facts) facts->np_resident[variant].store(res, std::memory_order_relaxed);
         }
         const uint64_t resident = res;
         if (n_main > resident) n_main = resident;
@@ -2272,27 +2241,24 @@ extern "C" int s5gpu_decode_dev(const s5gpu_decode_args_t *a, void *stream_) {
     return S5GPU_OK;
 }
 
-extern "C" int s5gpu_compact_dev(uint32_t n, const s5gpu_read_desc_t *desc, const uint8_t *slots, const uint32_t *out_len,
-                                 uint64_t *rec_off, uint8_t *stream, uint64_t *tmp, void *stream_) {
-    if (n == 0) return S5GPU_OK;
-    if (!desc || !slots || !out_len || !rec_off || !stream || !tmp) return S5GPU_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream_;
-    const uint32_t nb = (n + SCAN_CH - 1) / SCAN_CH;
-    hipLaunchKernelGGL(k_scan_partial, dim3(nb), dim3(NT), 0, st, out_len, n, tmp);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(NT), 0, st, tmp, nb);
-    hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(NT), 0, st, out_len, n, tmp, rec_off);
-    hipLaunchKernelGGL(k_compact, dim3(n), dim3(NT), 0, st, desc, slots, out_len, rec_off, stream);
-    HIP_TRY(hipGetLastError());
-    return S5GPU_OK;
-}
-
-// the scan of s5gpu_compact_dev alone: off[i] = len[0] + ... + len[i-1], off[n] = total (the line offsets of skim_api.hip)
+// the scan of s5gpu_compact_dev, also on its own: off[i] = len[0] + ... + len[i-1], off[n] = total (the line offsets of skim_api.hip)
 int s5_scan_lengths(const uint32_t *len, uint32_t n, uint64_t *off, uint64_t *tmp, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     const uint32_t nb = (n + SCAN_CH - 1) / SCAN_CH;
     hipLaunchKernelGGL(k_scan_partial, dim3(nb), dim3(NT), 0, st, len, n, tmp);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(NT), 0, st, tmp, nb);
     hipLaunchKernelGGL(k_scan_final, dim3(nb), dim3(NT), 0, st, len, n, tmp, off);
+    HIP_TRY(hipGetLastError());
+    return S5GPU_OK;
+}
+
+extern "C" int s5gpu_compact_dev(uint32_t n, const s5gpu_read_desc_t *desc, const uint8_t *slots, const uint32_t *out_len,
+                                 uint64_t *rec_off, uint8_t *stream, uint64_t *tmp, void *stream_) {
+    if (n == 0) return S5GPU_OK;
+    if (!desc || !slots || !out_len || !rec_off || !stream || !tmp) return S5GPU_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream_;
+    { const int rc = s5_scan_lengths(out_len, n, rec_off, tmp, st); if (rc) return rc; }
+    hipLaunchKernelGGL(k_compact, dim3(n), dim3(NT), 0, st, desc, slots, out_len, rec_off, stream);
     HIP_TRY(hipGetLastError());
     return S5GPU_OK;
 }
@@ -2332,15 +2298,9 @@ int s5_qts_round_strided(int16_t *sig, uint32_t n, const void *sig_off, uint32_t
     if (bits < 1 || bits > 16) { s5gpu_set_error("qts rounding: bits %u outside 1..16", bits); return S5GPU_ERR_ARG; }
     if (n == 0) return S5GPU_OK;
     if (!sig || !sig_off || !n_samples) { s5gpu_set_error("qts rounding: NULL argument"); return S5GPU_ERR_ARG; }
-    static std::atomic<int> cus[64];
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    int cu = dev >= 0 && dev < 64 ? cus[dev].load() : 0;
-    if (cu <= 0) {
-        HIP_TRY(hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev));
-        if (cu <= 0) cu = 256;
-        if (dev >= 0 && dev < 64) cus[dev].store(cu);
-    }
+    int cu = 0;
+    { const int rc = device_cus(&cu); if (rc) return rc; }
+    if (cu <= 0) cu = 256;
     QtsRecs R = {(const uint8_t *)sig_off, (const uint8_t *)n_samples, off_stride, len_stride, n};
     hipLaunchKernelGGL(k_qts_round, dim3(4 * cu), dim3(NT), 0, st, sig, R, bits);
     HIP_TRY(hipGetLastError());
@@ -2403,27 +2363,20 @@ extern "C" int s5gpu_synth_hdr_dev(uint8_t *hdr, uint64_t n_reads, uint64_t firs
     return S5GPU_OK;
 }
 
-#ifdef S5_LZPROBE   // tools/lz_phases.py only (variant build): the phase clocks of lz_dev.h, read and cleared
-extern "C" int s5gpu_lzprobe_read(unsigned long long *out16) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(s5::g_lzprobe), sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(s5::g_lzprobe), z, sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
+// variant builds of tools/ only: the phase clocks of a decoder or the matcher, read and cleared
+template <size_t N>
+static int probe_read(unsigned long long (&clocks)[N], unsigned long long *out) {
+    unsigned long long z[N] = {0};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(clocks), sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(clocks), z, sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
     return S5GPU_OK;
 }
+#ifdef S5_LZPROBE   // tools/lz_phases.py (lz_dev.h)
+extern "C" int s5gpu_lzprobe_read(unsigned long long *out16) { return probe_read(s5::g_lzprobe, out16); }
 #endif
-#ifdef S5_IPROBE   // tools/inflate_phases.py only (variant build): the phase clocks of inflate_par_dev.h, read and cleared
-extern "C" int s5gpu_iprobe_read(unsigned long long *out20) {
-    unsigned long long z[20] = {0};
-    if (hipMemcpyFromSymbol(out20, HIP_SYMBOL(s5::g_iprobe), sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(s5::g_iprobe), z, sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
-    return S5GPU_OK;
-}
+#ifdef S5_IPROBE   // tools/inflate_phases.py (inflate_par_dev.h)
+extern "C" int s5gpu_iprobe_read(unsigned long long *out20) { return probe_read(s5::g_iprobe, out20); }
 #endif
-#ifdef S5_ZPROBE   // tools/zstd_phases.py only (variant build): the phase clocks of zstd_dev.h, read and cleared
-extern "C" int s5gpu_zprobe_read(unsigned long long *out16) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(s5::g_zprobe), sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(s5::g_zprobe), z, sizeof z) != hipSuccess) return S5GPU_ERR_HIP;
-    return S5GPU_OK;
-}
+#ifdef S5_ZPROBE   // tools/zstd_phases.py (zstd_dev.h)
+extern "C" int s5gpu_zprobe_read(unsigned long long *out16) { return probe_read(s5::g_zprobe, out16); }
 #endif

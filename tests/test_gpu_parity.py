@@ -196,6 +196,34 @@ def test_single_pass_stream_equals_slots_plus_compaction(press, n_reads):
     assert (b.out_len[:n_reads].cpu().numpy() == want_len).all()
 
 
+@pytest.mark.parametrize("n", [4000, 6400])
+@pytest.mark.parametrize("sig_method", [1, 2])
+def test_every_encode_stream_variant_equals_slots_plus_compaction(press, sig_method, n):
+    """svb-zd / ex-zd x an LDS budget below / above 8 KiB (4000 samples: 6384 / 5472 bytes; 6400: 10096 / 8592): the four k_encode_stream
+    variants and the four eight-per-CU k_encode_fused ones, stream against slots + compaction.  Reads 31 .. 37 of the seed give payloads
+    of 5135-5158 / 4178-4214 / 8169-8191 / 6633-6665 bytes (CPU oracle): all fit their budget, nothing may overflow."""
+    n_reads = 7
+    b = press.DeviceBatch([n] * n_reads, rec_method=press.REC_ZLIB, sig_method=sig_method)
+    b.synth(seed=0x5105, first=31)
+    b.encode()
+    b.compact()
+    want, off_want = b.stream_bytes()
+    assert int(b.ovf[0].item()) == 0                        # every read took the fused kernel
+    want_len = b.out_len[:n_reads].cpu().numpy().copy()
+    recs = b.records()
+    b.stream_out.zero_()
+    b.rec_off.zero_()
+    for _ in range(2):
+        b.encode_stream()
+    got, off_got = b.stream_bytes()
+    assert b.stream_ok()
+    assert list(off_got[: n_reads + 1]) == list(off_want[: n_reads + 1])
+    assert got == want
+    assert (b.out_len[:n_reads].cpu().numpy() == want_len).all()
+    assert b"".join(recs) == want
+    _check_records(press, ob.synth_reads(0x5105, 31, n_reads, n), [_hdr(press, 31 + i) for i in range(n_reads)], None, recs, press.REC_ZLIB, sig_method)
+
+
 def test_single_pass_stream_reports_lds_overflow(press):
     rng = np.random.default_rng(3)
     sig = ob.synth_reads(0x5105, 0, 64, 4000)
