@@ -286,7 +286,10 @@ size_t s5o_zstd_restated_decompress(const uint8_t *in, size_t len, uint8_t *out,
     const int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, checksum = (fhd >> 2) & 1, did = fhd & 3;
     if (fhd & 8) return ERR;
     if (did) return ERR;                            /* no dictionaries */
-    if (!single) { if (p >= len) return ERR; p++; } /* window descriptor: the whole output is addressable here */
+    if (!single) {                                  /* window descriptor: the whole output is addressable here, but a window log above 31 is refused as libzstd does */
+        if (p >= len || (in[p] >> 3) + 10 > 31) return ERR;
+        p++;
+    }
     const int fcs_bytes = fcs_flag == 0 ? single : fcs_flag == 1 ? 2 : fcs_flag == 2 ? 4 : 8;
     if (p + (size_t)fcs_bytes > len) return ERR;
     uint64_t fcs = 0;
@@ -318,7 +321,7 @@ size_t s5o_zstd_restated_decompress(const uint8_t *in, size_t len, uint8_t *out,
             memset(out + o, in[p], bsize); o += bsize; p += 1;
             continue;
         }
-        if (p + bsize > len || bsize < 2) { bad = 1; break; }
+        if (p + bsize > len || bsize < 3) { bad = 1; break; }   /* libzstd: a compressed block has at least 3 bytes */
         const uint8_t *b = in + p, *bend = b + bsize;
         p += bsize;
         /* ---- literals ---- */
@@ -364,9 +367,11 @@ size_t s5o_zstd_restated_decompress(const uint8_t *in, size_t len, uint8_t *out,
         /* ---- sequences ---- */
         if (q >= bend) { bad = 1; break; }
         uint32_t nseq = *q++;
+        if (nseq == 0 && q != bend) { bad = 1; break; }   /* no sequences: the section is that one byte */
         if (nseq >= 128) {
             if (nseq == 255) { if (q + 2 > bend) { bad = 1; break; } nseq = q[0] + (q[1] << 8) + 0x7F00; q += 2; }
             else { if (q + 1 > bend) { bad = 1; break; } nseq = ((nseq - 128) << 8) + q[0]; q += 1; }
+            if (nseq == 0) { bad = 1; break; }      /* a count of zero in the long form */
         }
         size_t li = 0;
         if (nseq) {

@@ -746,7 +746,7 @@ __device__ __forceinline__ int zstd_decode_wave(ZstdShared &T, const uint8_t *in
     const uint32_t fhd = in[4];
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, checksum = (fhd >> 2) & 1;
     if ((fhd & 8) || (fhd & 3)) return INF_ERR_HEADER;            // reserved bit / dictionary
-    if (!single) p++;
+    if (!single) { if ((in[p] >> 3) + 10u > 31u) return INF_ERR_HEADER; p++; }   // window log above 31: refused as libzstd does (len >= 6: the byte is there)
     const uint32_t fcs_bytes = fcs_flag == 0 ? single : fcs_flag == 1 ? 2u : fcs_flag == 2 ? 4u : 8u;
     if (p + fcs_bytes > len) return INF_ERR_TRUNC;
     uint64_t fcs = 0;
@@ -780,7 +780,7 @@ __device__ __forceinline__ int zstd_decode_wave(ZstdShared &T, const uint8_t *in
             continue;
         }
         if (p + bsize > len) { status = INF_ERR_TRUNC; break; }
-        if (bsize < 2) { status = INF_ERR_DATA; break; }
+        if (bsize < 3) { status = INF_ERR_DATA; break; }          // libzstd: a compressed block has at least 3 bytes
         const uint8_t *b = in + p;
         const uint32_t bend = bsize;                              // offsets below are relative to b
         p += bsize;
@@ -878,9 +878,11 @@ __device__ __forceinline__ int zstd_decode_wave(ZstdShared &T, const uint8_t *in
         // ---- sequences section ----
         if (q >= bend) { status = INF_ERR_DATA; break; }
         uint32_t nseq = b[q++];
+        if (nseq == 0 && q != bend) { status = INF_ERR_DATA; break; }   // no sequences: the section is that one byte
         if (nseq >= 128) {
             if (nseq == 255) { if (q + 2 > bend) { status = INF_ERR_DATA; break; } nseq = b[q] + (b[q + 1] << 8) + 0x7F00; q += 2; }
             else { if (q + 1 > bend) { status = INF_ERR_DATA; break; } nseq = ((nseq - 128) << 8) + b[q]; q += 1; }
+            if (nseq == 0) { status = INF_ERR_DATA; break; }      // a count of zero in the long form
         }
         uint32_t li = 0;
         if (nseq) {
