@@ -506,6 +506,29 @@ int s5gpu_signal_windows_dev(uint32_t n, const int16_t *sig, const uint64_t *sig
 int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
                               int sig_method, uint32_t n_q, const double *q, s5gpu_sig_stats_t *stats_out, s5gpu_rec_fields_t *fields_out);
 
+/* ---- sum: a content digest per read, independent of the presses the record was stored with, hashed on the device (docs/codecs.md §4.12) ----
+ * The CANONICAL record C(r) of a read is its record as a BLOW5 file with record press none and signal press none stores it, without the u64
+ * size prefix:  u16 read_id_len | read_id | u32 read_group | 4 x f64 | u64 N | N x int16 LE | the aux bytes unchanged.  Its digest is
+ * XXH64(C(r), seed 0).  C(r) is never built: the kernel hashes payload[0, 2 + id_len + 36), the 8 bytes of N, 2N bytes of the record's
+ * signal slot and payload[aux_off, aux_off + aux_len) as one stream.  The digest resists accidents, not adversaries.
+ *
+ * s5gpu_digest_dev: the input is what the full form of s5gpu_decode_dev (flags = 0) left behind: the descriptors it was given, its payload
+ * slots, its sig_out and its fields (all device; payload and sig 16-byte aligned, desc / fields / digest 8).  digest[i] = the digest of
+ * record i, or 0 for a record with fields[i].status != 0 or whose fields point outside its own slots: nothing of such a record is read.
+ * The kernel loads aligned 8-byte words: it touches [pay_off, pay_off + pay_cap) and the record's signal slot rounded out to 16 bytes and
+ * nothing else, so 16 readable bytes must follow the last slot of `payload` and of `sig`.  sig_method: the signal press the records were
+ * decoded from (S5GPU_SIG_*; checked, the decoded form does not depend on it).  Asynchronous on hip_stream. */
+int s5gpu_digest_dev(uint32_t n, const s5gpu_rec_desc_t *desc, const uint8_t *payload, const int16_t *sig, const s5gpu_rec_fields_t *fields,
+                     int sig_method, uint64_t *digest, void *hip_stream);
+/* The digests of the n records of a file chunk (framed as for s5gpu_decode_stream) and of n records anywhere in host memory (bytes without the
+ * u64 prefix): one upload, the full decode, the digest kernel, and a download of 8 bytes per record; every record press x signal press.  Both
+ * run on the FIRST device in use.  A corrupt record fails the call with S5GPU_ERR_DATA: its status_out[i] (may be NULL) is the decoder's
+ * (s5gpu_rec_fields_t.status) and its digest 0; the other records' digests are valid. */
+int s5gpu_digest_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+                        int sig_method, uint64_t *digest_out, int32_t *status_out);
+int s5gpu_digest_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, uint64_t *digest_out,
+                       int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

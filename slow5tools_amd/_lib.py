@@ -139,6 +139,10 @@ def lib():
     L.s5gpu_signal_stats_dev.argtypes = [u32, vp, vp, vp, vp, u32, vp, vp, vp]
     L.s5gpu_signal_windows_dev.argtypes = [u32, vp, vp, vp, vp, vp, u32, vp, vp, u32, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     L.s5gpu_signal_stats_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, u32, vp, vp, vp]
+    # sum: per-record content digests of decoded records on the device, of a file chunk and of records anywhere in host memory
+    L.s5gpu_digest_dev.argtypes = [u32, vp, vp, vp, vp, i32, vp, vp]
+    L.s5gpu_digest_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, vp, vp]
+    L.s5gpu_digest_batch.argtypes = [u32, vp, vp, i32, i32, vp, vp]
     _LIB = L
     return L
 
@@ -157,4 +161,5 @@ EXPORTS = [
     "s5gpu_svbzd_decode_dev", "s5gpu_set_option", "s5gpu_recompress_batch", "s5gpu_patch_u32_dev", "s5gpu_encode_stream_dev",
     "s5gpu_svbzd_encode_stream_dev", "s5gpu_pack_parked_dev", "s5gpu_warmup",
     "s5gpu_signal_stats_dev", "s5gpu_signal_windows_dev", "s5gpu_signal_stats_stream",
+    "s5gpu_digest_dev", "s5gpu_digest_stream", "s5gpu_digest_batch",
 ]

@@ -1706,6 +1706,10 @@ static int launch_eorder(const s5gpu_encode_args_t *a, hipStream_t st, const uin
     const bool order = g_order_min && a->n_reads >= g_order_min;
     return build_order(OrderOvfBySamples{a->desc, a->ovf}, a->n_reads, order, 0, st, out, hold);
 }
+// ... the digest's: decoded records by canonical length (digest_kernels.hip); a batch of one wave's worth of records needs no order
+int s5kern_digest_order(const digk::DigRecs &R, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold) {
+    return build_order(OrderByCanonLen{R.desc, R.fields, R.n}, R.n, R.n > 16, 0, st, out, hold);
+}
 
 static bool rec_method_ok(int m) { return m == S5GPU_REC_NONE || m == S5GPU_REC_ZLIB || m == S5GPU_REC_ZSTD; }
 static bool sig_method_ok(int m) { return m == S5GPU_SIG_NONE || m == S5GPU_SIG_SVB_ZD || m == S5GPU_SIG_EX_ZD; }

@@ -2,17 +2,19 @@
 //
 // One wave (or lane) decodes one record, so a batch ends when its longest record does — and a record of 300 k samples takes a wave ~15 ms however
 // idle the rest of the device is.  In file order it starts wherever it happens to stand: 262 144 records with the read lengths of a real
-// run decode in 23.7 ms, 16.6 ms with the longest first (tools/mixed_lengths.py: the rate per sample of a batch of equal reads).  Three lists
+// run decode in 23.7 ms, 16.6 ms with the longest first (tools/mixed_lengths.py: the rate per sample of a batch of equal reads).  Four lists
 // are built this way, all in the library's per-(device, stream) scratch (kernels.hip: order_scratch):
 //   * the launch order of the wave-per-record decoders (round 3): records by compressed length;
 //   * the overflow list of a mixed ENCODE batch (round 4: the reads the staged kernels redo) by number of samples — a 300 k-sample read keeps
 //     one workgroup busy for most of a millisecond, and in list order (the order in which the fused kernel's workgroups happened to give
 //     up) it starts wherever it stands.  The list holds read indices;
-//   * the routing of big zlib batches to the lane and wave kernels (round 1): records by compressed length, the ones of >= 32 KiB in front.
+//   * the routing of big zlib batches to the lane and wave kernels (round 1): records by compressed length, the ones of >= 32 KiB in front;
+//   * the order in which k_rec_digest takes decoded records: by the length of their canonical form, so that the sixteen records of a wave end together.
 // Scratch layout: ord[0..127] bucket counts, then cursors; ord[ORD_NLONG]: how many items stand in front of the buckets below `long_bucket`
 // (0 when the build names none); ord[ORD_FLAG] != 0: one length class, no list (file order is as good); the list from ord[ORD_LIST] on.
 #pragma once
 #include "dev_common.h"
+#include "digest_dev.h"
 #include "../../include/slow5gpu.h"
 
 constexpr uint32_t ORD_NLONG = 128, ORD_FLAG = 129, ORD_LIST = 132;
@@ -32,6 +34,8 @@ __device__ __forceinline__ uint32_t ovf_at(const uint32_t *ovf, const uint32_t *
     return ord && !ord[ORD_FLAG] ? ord[ORD_LIST + it] : ovf[1 + it];
 }
 
+// (a translation unit that only READS a list defines S5_ORDER_LIST_ONLY: the sort's kernels below live in kernels.hip alone)
+#ifndef S5_ORDER_LIST_ONLY
 // What is sorted: for grid index i, is there an item, which id goes on the list, and how long is it.
 struct OrderByInLen {            // the records of a decode batch by compressed length
     const s5gpu_rec_desc_t *desc;
@@ -39,6 +43,17 @@ struct OrderByInLen {            // the records of a decode batch by compressed 
     __device__ __forceinline__ bool item(uint32_t i, uint32_t &id, uint32_t &len) const {
         if (i >= n) return false;
         id = i; len = desc[i].in_len;
+        return true;
+    }
+};
+struct OrderByCanonLen {         // the decoded records of a digest batch by the length of their canonical form (a failed record: 0)
+    const s5gpu_rec_desc_t *desc;
+    const s5gpu_rec_fields_t *fields;
+    uint32_t n;
+    __device__ __forceinline__ bool item(uint32_t i, uint32_t &id, uint32_t &len) const {
+        if (i >= n) return false;
+        const digk::Pieces P = digk::pieces_of(desc[i], fields[i]);
+        id = i; len = P.total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)P.total;
         return true;
     }
 };
@@ -107,3 +122,4 @@ __global__ __launch_bounds__(s5::NT) void k_order_scatter(Key key, uint32_t *ord
     __syncthreads();
     if (have) ord[ORD_LIST + base[b] + rank] = id;
 }
+#endif  // S5_ORDER_LIST_ONLY
