@@ -529,6 +529,58 @@ int s5gpu_digest_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const
 int s5gpu_digest_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, uint64_t *digest_out,
                        int32_t *status_out);
 
+/* ---- stats: what is in a whole file's signal, accumulated on the device while the batches stream through (docs/codecs.md §4.13) ----
+ * One accumulator per file stays in device memory; its 528 720 bytes come back once.  Every member is an integer sum, minimum, maximum, OR or
+ * AND over the records with status 0 and their n_eff samples (the rule of "signals" above): the result does not depend on the batches the file
+ * was cut into, on their order or on the launch shape.  A record with status != 0 adds 1 to n_failed and nothing else; none of its samples is
+ * loaded.  The layout is fixed (little-endian, no padding). */
+typedef struct s5gpu_file_stats {
+    uint64_t n_reads;          /* records with status 0                                                                     */
+    uint64_t n_failed;         /* records with any other status                                                             */
+    uint64_t n_samples;
+    int64_t sum;
+    uint64_t sumsq;            /* the sum of x^2 modulo 2^64: it WRAPS (x^2 <= 2^30, so not before 2^34 samples)             */
+    int32_t min, max;          /* 32767 / -32768 while there is no sample                                                   */
+    uint32_t or_bits;          /* OR of (uint16_t)x; 0 while there is no sample                                             */
+    uint32_t and_bits;         /* AND of (uint16_t)x; 0xFFFF while there is no sample                                       */
+    uint32_t len_min, len_max; /* samples of the shortest / longest read; 0xFFFFFFFF / 0 while there is no read             */
+    uint64_t len_hist[33];     /* reads by length class: [0] reads of 0 samples, else [1 + floor(log2 n)]                   */
+    uint64_t rg_reads[256];    /* reads of read group g < 256                                                               */
+    uint64_t rg_samples[256];  /* their samples                                                                             */
+    uint64_t rg_other;         /* reads of read groups >= 256 (their samples are in n_samples only)                         */
+    uint64_t hist[65536];      /* samples of value x at [x + 32768]                                                         */
+} s5gpu_file_stats_t;
+/* acc: device memory, 8-byte aligned, sizeof(s5gpu_file_stats_t).  reset: the empty accumulator.  accum: adds n records; the input is what
+ * s5gpu_decode_dev left behind, exactly as for s5gpu_signal_stats_dev (sig 16-byte aligned; sig_off / sig_cap / fields device arrays).  Both are
+ * asynchronous on hip_stream; accum calls on one acc may run on several streams at once (it only adds with atomics).
+ * A workgroup counts the samples inside a window of values in LDS and sends the others straight to acc->hist with 64-bit atomics; it empties
+ * its LDS counters into acc->hist before one of them could wrap, and at its end.  Where the window lies changes the time, never the result.
+ * s5gpu_set_option (tests, tools):
+ *   "fstats_window_lo"     -1 (default): each workgroup centres the window on the mean of the first samples it meets; 0 .. 65535: the bin
+ *                          (value + 32768) of the window's low edge, moved down where the window would pass bin 65535.
+ *   "fstats_lds_bins"      bins of the window: 0 (no LDS histogram: every sample is a global atomic) or a power of two from 64 to 2048 (default).
+ *   "fstats_flush_samples" 1 .. 4294967295 (default): a workgroup empties its LDS counters before a read would take the samples it has counted
+ *                          since the last time past this number.
+ *   "fstats_grid"          1 .. 1024 (default): the most workgroups of one launch; below the record count a workgroup walks several records. */
+size_t s5gpu_file_stats_bytes(void);   /* sizeof(s5gpu_file_stats_t) as the library was built */
+int s5gpu_file_stats_reset_dev(s5gpu_file_stats_t *acc, void *hip_stream);
+int s5gpu_file_stats_accum_dev(uint32_t n, const int16_t *sig, const uint64_t *sig_off, const uint32_t *sig_cap, const s5gpu_rec_fields_t *fields,
+                               s5gpu_file_stats_t *acc, void *hip_stream);
+/* The chunk calls: an opaque per-file handle that owns one accumulator on the FIRST device in use (NULL + s5gpu_last_error() on failure).
+ * add_stream: n records framed as for s5gpu_decode_stream: one upload, one decode (fields + signals only where the methods allow
+ * S5GPU_DEC_NO_PAYLOAD, the full form otherwise; every record press x signal press), the accumulate kernel; nothing comes back but
+ * status_out[i] (may be NULL).  A corrupt record fails the call with S5GPU_ERR_DATA: it is counted in n_failed, the other records of the batch
+ * are accumulated, and the handle stays usable.  Only then may the batch be decoded more than once: the decoder's own retry of records that
+ * outgrew their guessed slots stops at a corrupt record, so the batch is decoded again without the corrupt ones (at most three more times; in
+ * the full form each of these uploads the chunk again); a record that still has status 5 or 6 after the last is counted in n_failed.
+ * close: the single download into *out (may be NULL: the accumulator is abandoned) and the end of the handle, whatever it returns.
+ * Not built: several devices per file (a file's batches all go to the first device), a choice of qts bits from or_bits (`degrade -b auto`),
+ * and N50, which needs the sorted read lengths and not their classes. */
+void *s5gpu_file_stats_open(void);
+int s5gpu_file_stats_add_stream(void *h, uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len,
+                                int rec_method, int sig_method, int32_t *status_out);
+int s5gpu_file_stats_close(void *h, s5gpu_file_stats_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ REC_FIELDS = np.dtype([("status", "<i4"), ("payload_len", "<u4"), ("n_samples", 
                        ("read_group", "<u4"), ("aux_off", "<u4"), ("aux_len", "<u4"), ("reserved", "<u4"),
                        ("digitisation", "<f8"), ("offset", "<f8"), ("range", "<f8"), ("sampling_rate", "<f8")])
 assert READ_DESC.itemsize == 48 and REC_DESC.itemsize == 40 and REC_FIELDS.itemsize == 64
+# s5gpu_file_stats_t: the file-wide accumulator of "stats" (slow5tools_amd/fstats.py)
+FILE_STATS = np.dtype([("n_reads", "<u8"), ("n_failed", "<u8"), ("n_samples", "<u8"), ("sum", "<i8"), ("sumsq", "<u8"),
+                       ("min", "<i4"), ("max", "<i4"), ("or_bits", "<u4"), ("and_bits", "<u4"), ("len_min", "<u4"), ("len_max", "<u4"),
+                       ("len_hist", "<u8", (33,)), ("rg_reads", "<u8", (256,)), ("rg_samples", "<u8", (256,)), ("rg_other", "<u8"),
+                       ("hist", "<u8", (65536,))])
+assert FILE_STATS.itemsize == 528720
 
 
 class EncodeArgs(C.Structure):
@@ -143,6 +149,15 @@ def lib():
     L.s5gpu_digest_dev.argtypes = [u32, vp, vp, vp, vp, i32, vp, vp]
     L.s5gpu_digest_stream.argtypes = [u32, vp, C.c_size_t, vp, vp, i32, i32, vp, vp]
     L.s5gpu_digest_batch.argtypes = [u32, vp, vp, i32, i32, vp, vp]
+    # stats: the file-wide accumulator on the device, and the per-file handle of the chunk calls
+    L.s5gpu_file_stats_bytes.restype = C.c_size_t
+    L.s5gpu_file_stats_bytes.argtypes = []
+    L.s5gpu_file_stats_reset_dev.argtypes = [vp, vp]
+    L.s5gpu_file_stats_accum_dev.argtypes = [u32, vp, vp, vp, vp, vp, vp]
+    L.s5gpu_file_stats_open.restype = vp
+    L.s5gpu_file_stats_open.argtypes = []
+    L.s5gpu_file_stats_add_stream.argtypes = [vp, u32, vp, C.c_size_t, vp, vp, i32, i32, vp]
+    L.s5gpu_file_stats_close.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -162,4 +177,6 @@ EXPORTS = [
     "s5gpu_svbzd_encode_stream_dev", "s5gpu_pack_parked_dev", "s5gpu_warmup",
     "s5gpu_signal_stats_dev", "s5gpu_signal_windows_dev", "s5gpu_signal_stats_stream",
     "s5gpu_digest_dev", "s5gpu_digest_stream", "s5gpu_digest_batch",
+    "s5gpu_file_stats_bytes", "s5gpu_file_stats_reset_dev", "s5gpu_file_stats_accum_dev", "s5gpu_file_stats_open", "s5gpu_file_stats_add_stream",
+    "s5gpu_file_stats_close",
 ]

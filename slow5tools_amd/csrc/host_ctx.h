@@ -116,6 +116,10 @@ int qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits);
 // ... the records sitting framed in one host buffer (a file chunk): [base, base + bytes) is uploaded as it is, rec[i] point into it
 int decode_resident_framed(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig,
                            std::vector<s5gpu_rec_desc_t> &rd, std::vector<s5gpu_rec_fields_t> &ff, int32_t *status, const uint8_t *base, size_t bytes);
+// fields + signals only (S5GPU_DEC_NO_PAYLOAD) of framed records the caller has uploaded to c->d_in (chunk + b0 onwards): descriptors in
+// c->d_desc2, signals in c->d_sig2, fields in c->d_fields and ff; S5GPU_ERR_DATA when a record is corrupt (signal_api.hip)
+int decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+                     int sig_method, std::vector<s5gpu_rec_fields_t> &ff);
 // encode descriptors already on the device -> the contiguous BLOW5 record stream in c->d_stream (what the ordered fwrite loop
 // emits); off[i] / off[n] = record offsets / total, on the host (host_api.hip)
 int encode_stream_resident(Ctx *c, uint32_t n, const std::vector<s5gpu_read_desc_t> &desc, s5gpu_encode_args_t a, uint64_t slots_bytes,

@@ -65,8 +65,8 @@ extern "C" int s5gpu_signal_windows_dev(uint32_t n, const int16_t *sig, const ui
 // fields + signals only (S5GPU_DEC_NO_PAYLOAD) of the framed records already uploaded to c->d_in: descriptors in c->d_desc2, signals in c->d_sig2,
 // fields in c->d_fields and ff.  A record that outgrew its guessed scratch or signal slot (status 5 / 6) has the batch decoded again with the sizes
 // it reported.  Corrupt records: S5GPU_ERR_DATA, everything else of the batch is in place.
-static int decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
-                            int sig_method, std::vector<s5gpu_rec_fields_t> &ff) {
+int s5host::decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+                             int sig_method, std::vector<s5gpu_rec_fields_t> &ff) {
     int rc;
     std::vector<uint32_t> pcap(n), scap(n);
     std::vector<s5gpu_rec_desc_t> rd(n);
@@ -161,7 +161,7 @@ extern "C" int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t c
     if (np) {
         if ((rc = c->d_in.reserve(e1 - b0 + 64))) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t *)chunk + b0, e1 - b0, hipMemcpyHostToDevice, c->st));
-        drc = decode_np_framed(c, n, (const uint8_t *)chunk, b0, rec_pos, rec_len, rec_method, sig_method, ff);
+        drc = s5host::decode_np_framed(c, n, (const uint8_t *)chunk, b0, rec_pos, rec_len, rec_method, sig_method, ff);
     } else {
         std::vector<const void *> rec(n);
         std::vector<size_t> len(n);
