@@ -581,6 +581,100 @@ int s5gpu_file_stats_add_stream(void *h, uint32_t n, const void *chunk, size_t c
                                 int rec_method, int sig_method, int32_t *status_out);
 int s5gpu_file_stats_close(void *h, s5gpu_file_stats_t *out);
 
+/* ---- diff: where and by how much the reads of two files differ, compared on the device (docs/codecs.md §4.14) ----
+ * A PAIR is read ia of decoded batch A and read ib of decoded batch B; each batch is what s5gpu_decode_dev left behind, and the two may come
+ * from different record and signal presses.  The sample count of each side is n_eff (the rule of "signals" above) and nothing else;
+ * n_cmp = min(n_a, n_b); d[i] = b[i] - a[i] as int32 for i < n_cmp.  Samples past n_cmp are never loaded.  Every member is an integer. */
+enum { S5GPU_DIFF_SIGNAL = 1,          /* n_diff > 0                                                                             */
+       S5GPU_DIFF_LEN = 2,             /* n_a != n_b                                                                             */
+       S5GPU_DIFF_READ_GROUP = 4,
+       S5GPU_DIFF_DIGITISATION = 8,    /* the four doubles are compared bit for bit: 0.0 and -0.0 differ, equal-bit NaNs are equal */
+       S5GPU_DIFF_OFFSET = 16,
+       S5GPU_DIFF_RANGE = 32,
+       S5GPU_DIFF_SAMPLING_RATE = 64,
+       S5GPU_DIFF_ID = 128,            /* id length or bytes differ; only compared when both sides bring their payloads            */
+       S5GPU_DIFF_AUX = 256,           /* aux_len or an aux byte differs; only compared when both sides bring their payloads       */
+       S5GPU_DIFF_FAILED = 0x4000,     /* either status is not 0, or (payloads given) a side's fields point outside its own payload slot: nothing
+                                        * of the pair is loaded, every other member is 0, first_diff and max_at are 0xFFFFFFFF     */
+       S5GPU_DIFF_BAD_PAIR = 0x8000 }; /* ia >= A.n or ib >= B.n: checked before anything is loaded through the index; every other member as
+                                        * for FAILED                                                                               */
+#define S5GPU_DIFF_NONE 0xFFFFFFFFu    /* first_diff / max_at: no such sample */
+typedef struct s5gpu_sig_diff {        /* 80 bytes, little-endian, no padding */
+    int32_t status_a, status_b;        /* the decoder's statuses                                      */
+    uint32_t n_a, n_b;                 /* n_eff of each side                                          */
+    uint32_t flags;                    /* S5GPU_DIFF_*                                                */
+    uint32_t n_diff;                   /* count of d[i] != 0                                          */
+    uint32_t first_diff;               /* smallest such i; S5GPU_DIFF_NONE when none                  */
+    uint32_t max_abs;                  /* max of abs(d[i]): 0 .. 65535                                */
+    uint32_t max_at;                   /* SMALLEST i reaching max_abs; S5GPU_DIFF_NONE when n_diff == 0 */
+    uint32_t reserved;                 /* 0                                                           */
+    int64_t sum_d;
+    uint64_t sum_abs;
+    uint64_t sum_sq;                   /* exact: d^2 < 2^32 and n < 2^32                              */
+    int64_t sum_a;                     /* the sum of a[i] over i < n_cmp, for the SNR                 */
+    uint64_t sumsq_a;                  /* the sum of a[i]^2 over i < n_cmp                            */
+} s5gpu_sig_diff_t;
+#define S5GPU_DIFF_BINS 131071
+/* The file-wide accumulator: 1 048 696 bytes that stay in device memory and come back once.  The 64-bit sums WRAP; sum_sq cannot before 2^32
+ * samples.  Every member is an integer sum, maximum or count: the result does not depend on the batches, their order or the launch shape. */
+typedef struct s5gpu_diff_acc {
+    uint64_t n_pairs;
+    uint64_t n_failed;                 /* FAILED or BAD_PAIR                                                     */
+    uint64_t n_differ;                 /* pairs that are not failed and whose flags are not 0                    */
+    uint64_t n_signal, n_len;
+    uint64_t n_fields;                 /* any of READ_GROUP .. SAMPLING_RATE                                     */
+    uint64_t n_aux, n_id;
+    uint64_t n_samples;                /* the sum of n_cmp                                                       */
+    uint64_t n_diff;
+    int64_t sum_d;
+    uint64_t sum_abs, sum_sq;
+    int64_t sum_a;
+    uint64_t sumsq_a;
+    uint32_t max_abs, reserved;
+    uint64_t hist[S5GPU_DIFF_BINS];    /* samples with difference d at [d + 65535]                               */
+} s5gpu_diff_acc_t;
+/* One decoded batch as the kernel takes it: device arrays of n entries, as for s5gpu_signal_stats_dev (sig 16-byte aligned, every sig_off a
+ * multiple of 8 samples).  payload (16-byte aligned) / pay_off / pay_cap: the payload slots of the full form of s5gpu_decode_dev; payload == NULL
+ * on either side means that ID and AUX are not compared (and pay_off / pay_cap of that side are not read). */
+typedef struct s5gpu_diff_side {
+    uint32_t n;
+    const int16_t *sig;
+    const uint64_t *sig_off;
+    const uint32_t *sig_cap;
+    const s5gpu_rec_fields_t *fields;
+    const uint8_t *payload;
+    const uint64_t *pay_off;
+    const uint32_t *pay_cap;
+} s5gpu_diff_side_t;
+/* Pair p = (pair_a[p], pair_b[p]) (device arrays of n_pairs u32) -> out[p] and, added with atomics, *acc; either of out (8-byte aligned) and acc
+ * (8-byte aligned, reset by s5gpu_diff_acc_reset_dev) may be NULL.  Asynchronous on hip_stream.  The ID and AUX bytes are loaded only after
+ * both ranges are shown to lie inside their own payload slots.  A workgroup counts the differences d != 0 inside a window of values around 0
+ * in LDS and sends the others straight to acc->hist with 64-bit atomics; d == 0 is never counted sample by sample: bin 65535 receives
+ * n_samples - n_diff.  s5gpu_set_option (tests, tools):
+ *   "diff_lds_bins"      bins of the window [-bins/2, bins/2): 0 (every differing sample is a global atomic) or a power of two from 8 to 256
+ *                        (default 64).  Changes the time, never the result.
+ *   "diff_flush_samples" 1 .. 4294967295 (default): a workgroup empties its LDS counters before a pair would take the samples it has counted
+ *                        since the last time past this number (no u32 counter can wrap).
+ *   "diff_grid"          1 .. 1024 (default): the most workgroups of one launch; below the pair count a workgroup walks several pairs. */
+size_t s5gpu_diff_acc_bytes(void);     /* sizeof(s5gpu_diff_acc_t) as the library was built */
+int s5gpu_diff_acc_reset_dev(s5gpu_diff_acc_t *acc, void *hip_stream);
+int s5gpu_signal_diff_dev(uint32_t n_pairs, const uint32_t *pair_a, const uint32_t *pair_b, const s5gpu_diff_side_t *A, const s5gpu_diff_side_t *B,
+                          s5gpu_sig_diff_t *out, s5gpu_diff_acc_t *acc, void *hip_stream);
+/* The per-file handle: it owns one accumulator and buffers for side A on the FIRST device in use (NULL + s5gpu_last_error() on failure).
+ * add_batch: pair i is record i of each list (bytes without the u64 prefix, anywhere in host memory, as for s5gpu_digest_batch).  A is decoded
+ * in full (payloads kept, so that aux and id can be compared) and its signal slab, payload slab, descriptors and fields are copied device to
+ * device into the handle's buffers; then B is decoded in the same context, k_sig_diff runs and n x 80 bytes come back into out[] (may be NULL).
+ * This costs one extra pass over A's decoded bytes; holding two contexts instead was not built.  status_a / status_b (may be NULL): the
+ * decoder's statuses.  A corrupt record on either side fails the call with S5GPU_ERR_DATA: its pair is FAILED and counted in n_failed, the
+ * other pairs are valid and the handle stays usable (the batch is decoded again without the corrupt records, at most three more times, as
+ * s5gpu_file_stats_add_stream does).  close: the single download into *acc_out (may be NULL) and the end of the handle, whatever it returns.
+ * Not built: SLOW5 text input, several devices per file. */
+void *s5gpu_diff_open(void);
+int s5gpu_diff_add_batch(void *h, uint32_t n, const void *const *rec_a, const size_t *len_a, int rec_a_method, int sig_a_method,
+                         const void *const *rec_b, const size_t *len_b, int rec_b_method, int sig_b_method, s5gpu_sig_diff_t *out,
+                         int32_t *status_a, int32_t *status_b);
+int s5gpu_diff_close(void *h, s5gpu_diff_acc_t *acc_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,17 @@ FILE_STATS = np.dtype([("n_reads", "<u8"), ("n_failed", "<u8"), ("n_samples", "<
                        ("len_hist", "<u8", (33,)), ("rg_reads", "<u8", (256,)), ("rg_samples", "<u8", (256,)), ("rg_other", "<u8"),
                        ("hist", "<u8", (65536,))])
 assert FILE_STATS.itemsize == 528720
+# s5gpu_sig_diff_t / s5gpu_diff_acc_t: a pair's row and the file-wide accumulator of "diff" (slow5tools_amd/diff.py)
+SIG_DIFF = np.dtype([("status_a", "<i4"), ("status_b", "<i4"), ("n_a", "<u4"), ("n_b", "<u4"), ("flags", "<u4"), ("n_diff", "<u4"),
+                     ("first_diff", "<u4"), ("max_abs", "<u4"), ("max_at", "<u4"), ("reserved", "<u4"), ("sum_d", "<i8"), ("sum_abs", "<u8"),
+                     ("sum_sq", "<u8"), ("sum_a", "<i8"), ("sumsq_a", "<u8")])
+DIFF_BINS = 131071
+DIFF_ACC = np.dtype([("n_pairs", "<u8"), ("n_failed", "<u8"), ("n_differ", "<u8"), ("n_signal", "<u8"), ("n_len", "<u8"), ("n_fields", "<u8"),
+                     ("n_aux", "<u8"), ("n_id", "<u8"), ("n_samples", "<u8"), ("n_diff", "<u8"), ("sum_d", "<i8"), ("sum_abs", "<u8"),
+                     ("sum_sq", "<u8"), ("sum_a", "<i8"), ("sumsq_a", "<u8"), ("max_abs", "<u4"), ("reserved", "<u4"), ("hist", "<u8", (DIFF_BINS,))])
+assert SIG_DIFF.itemsize == 80 and DIFF_ACC.itemsize == 1048696
+DIFF_SIGNAL, DIFF_LEN, DIFF_READ_GROUP, DIFF_DIGITISATION, DIFF_OFFSET, DIFF_RANGE, DIFF_SAMPLING_RATE, DIFF_ID, DIFF_AUX = (1 << k for k in range(9))
+DIFF_FAILED, DIFF_BAD_PAIR, DIFF_NONE = 0x4000, 0x8000, 0xFFFFFFFF
 
 
 class EncodeArgs(C.Structure):
@@ -65,6 +76,15 @@ class SkimLayout(C.Structure):
                 ("type", C.c_uint8 * SKIM_MAX_AUX), ("role", C.c_uint8 * SKIM_MAX_AUX), ("n_labels", C.c_uint16 * SKIM_MAX_AUX),
                 ("label_first", C.c_uint16 * SKIM_MAX_AUX), ("name_off", C.c_uint32 * SKIM_MAX_AUX), ("name_len", C.c_uint32 * SKIM_MAX_AUX),
                 ("label_off", C.c_uint32 * SKIM_MAX_LABELS), ("label_len", C.c_uint16 * SKIM_MAX_LABELS), ("text", C.c_char * SKIM_TEXT)]
+
+
+class DiffSide(C.Structure):
+    """s5gpu_diff_side_t"""
+    _fields_ = [("n", C.c_uint32), ("sig", C.c_void_p), ("sig_off", C.c_void_p), ("sig_cap", C.c_void_p), ("fields", C.c_void_p),
+                ("payload", C.c_void_p), ("pay_off", C.c_void_p), ("pay_cap", C.c_void_p)]
+
+
+assert C.sizeof(DiffSide) == 64
 
 
 class S5GpuError(RuntimeError):
@@ -158,6 +178,15 @@ def lib():
     L.s5gpu_file_stats_open.argtypes = []
     L.s5gpu_file_stats_add_stream.argtypes = [vp, u32, vp, C.c_size_t, vp, vp, i32, i32, vp]
     L.s5gpu_file_stats_close.argtypes = [vp, vp]
+    # diff: two decoded batches compared pair by pair on the device, the accumulator, and the per-file handle
+    L.s5gpu_diff_acc_bytes.restype = C.c_size_t
+    L.s5gpu_diff_acc_bytes.argtypes = []
+    L.s5gpu_diff_acc_reset_dev.argtypes = [vp, vp]
+    L.s5gpu_signal_diff_dev.argtypes = [u32, vp, vp, C.POINTER(DiffSide), C.POINTER(DiffSide), vp, vp, vp]
+    L.s5gpu_diff_open.restype = vp
+    L.s5gpu_diff_open.argtypes = []
+    L.s5gpu_diff_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
+    L.s5gpu_diff_close.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -179,4 +208,5 @@ EXPORTS = [
     "s5gpu_digest_dev", "s5gpu_digest_stream", "s5gpu_digest_batch",
     "s5gpu_file_stats_bytes", "s5gpu_file_stats_reset_dev", "s5gpu_file_stats_accum_dev", "s5gpu_file_stats_open", "s5gpu_file_stats_add_stream",
     "s5gpu_file_stats_close",
+    "s5gpu_diff_acc_bytes", "s5gpu_diff_acc_reset_dev", "s5gpu_signal_diff_dev", "s5gpu_diff_open", "s5gpu_diff_add_batch", "s5gpu_diff_close",
 ]

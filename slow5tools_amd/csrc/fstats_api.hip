@@ -93,46 +93,28 @@ extern "C" int s5gpu_file_stats_add_stream(void *handle, uint32_t n, const void 
         HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t *)chunk + b0, e1 - b0, hipMemcpyHostToDevice, c->st));
     }
     std::vector<s5gpu_rec_fields_t> ff;
-    auto decode = [&](uint32_t m, const uint64_t *pos, const uint32_t *len) {
-        if (np) return s5host::decode_np_framed(c, m, (const uint8_t *)chunk, b0, pos, len, rec_method, sig_method, ff);
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> len;
+    auto decode = [&](uint32_t m, const uint32_t *idx) {
+        pos.resize(m); len.resize(m);
+        for (uint32_t k = 0; k < m; k++) { pos[k] = rec_pos[idx[k]]; len[k] = rec_len[idx[k]]; }
+        if (np) return s5host::decode_np_framed(c, m, (const uint8_t *)chunk, b0, pos.data(), len.data(), rec_method, sig_method, ff);
         std::vector<const void *> rec(m);
         std::vector<size_t> l(m);
         std::vector<s5gpu_rec_desc_t> rd;
         for (uint32_t i = 0; i < m; i++) { rec[i] = (const uint8_t *)chunk + pos[i]; l[i] = len[i]; }
         return s5host::decode_resident_framed(c, m, rec.data(), l.data(), rec_method, sig_method, rd, ff, nullptr, (const uint8_t *)chunk + b0, (size_t)(e1 - b0));
     };
-    // The decoder redoes the records that outgrew their guessed slots (status 5 / 6) itself, but its retry stops at the first attempt that meets
-    // a corrupt record.  Those records must be counted all the same: while some are left the batch is decoded again without the corrupt ones,
-    // which are counted here.  What still has status 5 / 6 after the last round is counted as failed by the kernel (n_eff = 0).
-    enum { ROUNDS = 4 };
-    std::vector<uint32_t> cur(n);
-    std::vector<uint64_t> pos(rec_pos, rec_pos + n);
-    std::vector<uint32_t> len(rec_len, rec_len + n);
-    for (uint32_t i = 0; i < n; i++) cur[i] = i;
-    uint32_t dropped = 0;
+    // Corrupt records must be counted all the same: s5host::decode_dropping_corrupt decodes the batch again without them while records that
+    // outgrew their slots are left; the dropped ones are counted here.  What still has status 5 / 6 after the last round is counted as failed by
+    // the kernel (n_eff = 0: it counts the record and reads nothing of it).
+    std::vector<uint32_t> cur;
+    std::vector<int32_t> status(n);
     bool corrupt = false;
-    for (int round = 0;; round++) {
-        const uint32_t m = (uint32_t)cur.size();
-        const int drc = m ? decode(m, pos.data(), len.data()) : S5GPU_OK;
-        if (drc && drc != S5GPU_ERR_DATA) return drc;
-        corrupt |= drc != 0;
-        bool unfinished = false, droppable = false;
-        for (uint32_t k = 0; k < m; k++) {
-            if (status_out) status_out[cur[k]] = ff[k].status;
-            unfinished |= ff[k].status == 5 || ff[k].status == 6;
-            droppable |= ff[k].status != 0 && ff[k].status != 5 && ff[k].status != 6;
-        }
-        if (!drc || !unfinished || !droppable || round + 1 == ROUNDS) {
-            // a failed record has n_eff = 0: the kernel counts it and reads nothing of it
-            if ((rc = fsk::launch_accum(resident(c, m), h->d_acc, c->st)) || (rc = fsk::launch_add_failed(h->d_acc, dropped, c->st))) return rc;
-            break;
-        }
-        uint32_t w = 0;
-        for (uint32_t k = 0; k < m; k++)
-            if (ff[k].status == 0 || ff[k].status == 5 || ff[k].status == 6) { cur[w] = cur[k]; pos[w] = pos[k]; len[w] = len[k]; w++; }
-        dropped += m - w;
-        cur.resize(w); pos.resize(w); len.resize(w);
-    }
+    if ((rc = s5host::decode_dropping_corrupt(n, decode, ff, cur, status.data(), &corrupt))) return rc;
+    if (status_out) memcpy(status_out, status.data(), sizeof(int32_t) * n);
+    const uint32_t m = (uint32_t)cur.size();
+    if ((rc = fsk::launch_accum(resident(c, m), h->d_acc, c->st)) || (rc = fsk::launch_add_failed(h->d_acc, n - m, c->st))) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));                      // the next holder of this context overwrites the signals
     if (corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0; it is counted in n_failed)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;

@@ -120,6 +120,36 @@ int decode_resident_framed(Ctx *c, uint32_t n, const void *const *rec, const siz
 // c->d_desc2, signals in c->d_sig2, fields in c->d_fields and ff; S5GPU_ERR_DATA when a record is corrupt (signal_api.hip)
 int decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
                      int sig_method, std::vector<s5gpu_rec_fields_t> &ff);
+// The rule the per-file handles share for a batch with corrupt records.  The decoder redoes the records that outgrew their guessed slots
+// (status 5 / 6) itself, but its retry stops at the first attempt that meets a corrupt record.  The other records' results must be valid all
+// the same: while such records are left, the batch is decoded again without the corrupt ones, at most three more times.
+// decode(m, idx) decodes the records idx[0, m) of the caller's batch and leaves their fields in ff[0, m); S5GPU_ERR_DATA from it is not an error
+// here but sets *corrupt.  On return cur lists the records of the LAST decode, in order (what is resident in the context), ff holds their
+// fields, and status[i] (n entries) the last status seen of every record of the batch, the dropped ones included.
+template <class Decode>
+int decode_dropping_corrupt(uint32_t n, Decode decode, std::vector<s5gpu_rec_fields_t> &ff, std::vector<uint32_t> &cur, int32_t *status, bool *corrupt) {
+    enum { ROUNDS = 4 };
+    cur.resize(n);
+    for (uint32_t i = 0; i < n; i++) cur[i] = i;
+    for (int round = 0;; round++) {
+        const uint32_t m = (uint32_t)cur.size();
+        if (m == 0) ff.clear();
+        const int drc = m ? decode(m, cur.data()) : S5GPU_OK;
+        if (drc && drc != S5GPU_ERR_DATA) return drc;
+        *corrupt |= drc != 0;
+        bool unfinished = false, droppable = false;
+        for (uint32_t k = 0; k < m; k++) {
+            status[cur[k]] = ff[k].status;
+            unfinished |= ff[k].status == 5 || ff[k].status == 6;
+            droppable |= ff[k].status != 0 && ff[k].status != 5 && ff[k].status != 6;
+        }
+        if (!drc || !unfinished || !droppable || round + 1 == ROUNDS) return S5GPU_OK;
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < m; k++)
+            if (ff[k].status == 0 || ff[k].status == 5 || ff[k].status == 6) cur[w++] = cur[k];
+        cur.resize(w);
+    }
+}
 // encode descriptors already on the device -> the contiguous BLOW5 record stream in c->d_stream (what the ordered fwrite loop
 // emits); off[i] / off[n] = record offsets / total, on the host (host_api.hip)
 int encode_stream_resident(Ctx *c, uint32_t n, const std::vector<s5gpu_read_desc_t> &desc, s5gpu_encode_args_t a, uint64_t slots_bytes,
