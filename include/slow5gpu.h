@@ -675,6 +675,39 @@ int s5gpu_diff_add_batch(void *h, uint32_t n, const void *const *rec_a, const si
                          int32_t *status_a, int32_t *status_b);
 int s5gpu_diff_close(void *h, s5gpu_diff_acc_t *acc_out);
 
+/* ---- events: scrappie-style event segmentation of DECODED reads, on the device (docs/codecs.md §4.15) ----
+ * A read of n = n_eff samples (the rule of "signals" above) is cut at the peaks of two sliding t-tests: windows w1 < w2 (1 .. 64), thresholds
+ * thr1 / thr2 and a peak height, all finite.  The t-statistic is computed on the raw integers, sqrt(num / den) with integer num and den, so the
+ * cut points are reproducible bit for bit; no equality with a float32 implementation is promised at ties.  DNA: 3, 6, 1.4, 9.0, 0.2;
+ * RNA: 7, 14, 2.5, 9.0, 1.0.  A read with n > 0 has peaks + 1 events that tile [0, n); n = 0 has none. */
+typedef struct s5gpu_event_params {
+    uint32_t w1, w2;
+    double thr1, thr2, peak_height;
+} s5gpu_event_params_t;
+typedef struct s5gpu_event {   /* 16 bytes, little-endian */
+    uint32_t start;            /* first sample                                                                             */
+    uint32_t length;           /* samples (>= 1)                                                                           */
+    float mean;                /* S5GPU_NORM_RAW: float32(S / L) in double; S5GPU_NORM_PA: float32((S / L + offset) * (range / digitisation)) */
+    float stdv;                /* float32(sqrt(max(Q / L - (S / L)^2, 0))), every operation rounded on its own; PA: times |range / digitisation| */
+} s5gpu_event_t;
+#define S5GPU_STATUS_EVENTS_OVERFLOW 17   /* ev_status[i]: the read has more events than its slot holds */
+/* n records -> n_events[i] = the events of read i (always the number found), ev_status[i] = 0, the decoder's status of a failed record (no
+ * events), or S5GPU_STATUS_EVENTS_OVERFLOW; rows [ev_off[i], ev_off[i] + min(n_events[i], ev_cap[i])) of `rows` (16-byte aligned) are written
+ * and nothing else.  rows == NULL: the count pass, ev_off / ev_cap are not read.  mode: S5GPU_NORM_RAW or S5GPU_NORM_PA.  p: a HOST struct;
+ * everything else device arrays of n entries.  S5GPU_ERR_ARG (nothing launched): w1 = 0, w1 >= w2, w2 > 64, a non-finite parameter, another
+ * mode.  Asynchronous on hip_stream. */
+int s5gpu_signal_events_dev(uint32_t n, const int16_t *sig, const uint64_t *sig_off, const uint32_t *sig_cap, const s5gpu_rec_fields_t *fields,
+                            const s5gpu_event_params_t *p, int mode, const uint64_t *ev_off, const uint32_t *ev_cap, s5gpu_event_t *rows,
+                            uint32_t *n_events, int32_t *ev_status, void *hip_stream);
+/* The events of n records anywhere in host memory (bytes without the u64 prefix, as for s5gpu_digest_batch), on the FIRST device in use: one
+ * upload, the decode, the count pass, an exclusive scan on the device, the fill pass, and the rows come back in one download (the n + 1 row
+ * offsets, 8 bytes each, come back before it: the host has to know the room).  ev_first[i] .. ev_first[i + 1]: the rows of read i in
+ * rows_out; rows_cap in rows.  Too little room: S5GPU_ERR_NOMEM and ev_first[0] = the rows needed.  A corrupt record fails the call with
+ * S5GPU_ERR_DATA: its status_out[i] (may be NULL) is the decoder's and it has no rows; the other reads' events are valid. */
+int s5gpu_signal_events_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                              const s5gpu_event_params_t *p, int mode, s5gpu_event_t *rows_out, size_t rows_cap, uint64_t *ev_first,
+                              int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

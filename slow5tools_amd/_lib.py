@@ -87,6 +87,15 @@ class DiffSide(C.Structure):
 assert C.sizeof(DiffSide) == 64
 
 
+class EventParams(C.Structure):
+    """s5gpu_event_params_t"""
+    _fields_ = [("w1", C.c_uint32), ("w2", C.c_uint32), ("thr1", C.c_double), ("thr2", C.c_double), ("peak_height", C.c_double)]
+
+
+assert C.sizeof(EventParams) == 32
+STATUS_EVENTS_OVERFLOW = 17
+
+
 class S5GpuError(RuntimeError):
     pass
 
@@ -187,6 +196,9 @@ def lib():
     L.s5gpu_diff_open.argtypes = []
     L.s5gpu_diff_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.s5gpu_diff_close.argtypes = [vp, vp]
+    # events: event segmentation of decoded reads on the device, and of records anywhere in host memory
+    L.s5gpu_signal_events_dev.argtypes = [u32, vp, vp, vp, vp, C.POINTER(EventParams), i32, vp, vp, vp, vp, vp, vp]
+    L.s5gpu_signal_events_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), i32, vp, C.c_size_t, vp, vp]
     _LIB = L
     return L
 
@@ -209,4 +221,5 @@ EXPORTS = [
     "s5gpu_file_stats_bytes", "s5gpu_file_stats_reset_dev", "s5gpu_file_stats_accum_dev", "s5gpu_file_stats_open", "s5gpu_file_stats_add_stream",
     "s5gpu_file_stats_close",
     "s5gpu_diff_acc_bytes", "s5gpu_diff_acc_reset_dev", "s5gpu_signal_diff_dev", "s5gpu_diff_open", "s5gpu_diff_add_batch", "s5gpu_diff_close",
+    "s5gpu_signal_events_dev", "s5gpu_signal_events_batch",
 ]

@@ -24,6 +24,7 @@
 #include "svb_dev.h"
 #include "exzd_dev.h"
 #include "order_dev.h"
+#include "event_dev.h"
 #include "enc_plan.h"
 
 using namespace s5;
@@ -1711,6 +1712,10 @@ static int launch_eorder(const s5gpu_encode_args_t *a, hipStream_t st, const uin
 // ... the digest's: decoded records by canonical length (digest_kernels.hip); a batch of one wave's worth of records needs no order
 int s5kern_digest_order(const digk::DigRecs &R, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold) {
     return build_order(OrderByCanonLen{R.desc, R.fields, R.n}, R.n, R.n > 16, 0, st, out, hold);
+}
+// ... the event detector's: decoded reads by n_eff (event_kernels.hip); a batch of one wave's worth of reads needs no order
+int s5kern_event_order(const sigk::SigRecs &R, hipStream_t st, const uint32_t **out, std::unique_lock<std::mutex> &hold) {
+    return build_order(OrderBySigLen{R}, R.n, R.n > 64, 0, st, out, hold);
 }
 
 static bool rec_method_ok(int m) { return m == S5GPU_REC_NONE || m == S5GPU_REC_ZLIB || m == S5GPU_REC_ZSTD; }

@@ -9,12 +9,14 @@
 //     one workgroup busy for most of a millisecond, and in list order (the order in which the fused kernel's workgroups happened to give
 //     up) it starts wherever it stands.  The list holds read indices;
 //   * the routing of big zlib batches to the lane and wave kernels (round 1): records by compressed length, the ones of >= 32 KiB in front;
-//   * the order in which k_rec_digest takes decoded records: by the length of their canonical form, so that the sixteen records of a wave end together.
+//   * the order in which k_rec_digest takes decoded records: by the length of their canonical form, so that the sixteen records of a wave end together;
+//   * the order in which k_sig_events takes decoded reads: by n_eff, a read per lane, so that the 64 reads of a wave end together.
 // Scratch layout: ord[0..127] bucket counts, then cursors; ord[ORD_NLONG]: how many items stand in front of the buckets below `long_bucket`
 // (0 when the build names none); ord[ORD_FLAG] != 0: one length class, no list (file order is as good); the list from ord[ORD_LIST] on.
 #pragma once
 #include "dev_common.h"
 #include "digest_dev.h"
+#include "signal_dev.h"
 #include "../../include/slow5gpu.h"
 
 constexpr uint32_t ORD_NLONG = 128, ORD_FLAG = 129, ORD_LIST = 132;
@@ -54,6 +56,15 @@ struct OrderByCanonLen {         // the decoded records of a digest batch by the
         if (i >= n) return false;
         const digk::Pieces P = digk::pieces_of(desc[i], fields[i]);
         id = i; len = P.total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)P.total;
+        return true;
+    }
+};
+struct OrderBySigLen {           // the decoded reads of an event batch by the samples a kernel may touch (a failed record: 0)
+    sigk::SigRecs R;
+    __device__ __forceinline__ bool item(uint32_t i, uint32_t &id, uint32_t &len) const {
+        if (i >= R.n) return false;
+        int32_t st;
+        id = i; len = R.n_eff(i, &st);
         return true;
     }
 };
