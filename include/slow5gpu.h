@@ -708,6 +708,55 @@ int s5gpu_signal_events_batch(uint32_t n, const void *const *rec, const size_t *
                               const s5gpu_event_params_t *p, int mode, s5gpu_event_t *rows_out, size_t rows_cap, uint64_t *ev_first,
                               int32_t *status_out);
 
+/* ---- map: subsequence DTW of each read's events against a reference squiggle, on the device (docs/codecs.md §4.16) ----
+ * quant: float32 values m[0 .. L) -> int16.  In double, strictly left to right, every operation rounded on its own: mu = (sum m) / L,
+ * sd = sqrt((sum (m - mu)^2) / L); L = 0, sd = 0 or sd not finite: every q = 0; else q[j] = clamp(rint(((m[j] - mu) / sd) * scale), -clip, clip),
+ * round-half-even.  A read's QUERY is quant of the means (S5GPU_NORM_RAW: quant is invariant under a positive affine map up to rounding) of
+ * its event rows [skip, skip + qlen), qlen = min(qmax, max(E - skip, 0)); qlen < qmin: no query, qlen = 0, S5GPU_STATUS_QUERY_SHORT.
+ * sDTW, exact in integers: c(i,j) = |q[i] - r[j]|, D[0][j] = c(0,j) (the start is free), D[i][0] = D[i-1][0] + c(i,0), else
+ * D[i][j] = c(i,j) + min(D[i-1][j-1], D[i-1][j], D[i][j-1]); D[i][j] <= 65535 (i + 1) < 2^26 for qlen <= 1024, so uint32 holds it for any R.
+ * cost = min_j D[qlen-1][j], end = the smallest such j; start (want_start) = the column in row 0 of the path to (qlen-1, end) that takes at
+ * every cell the predecessor of least D, ties to the diagonal, then (i-1, j), then (i, j-1). */
+typedef struct s5gpu_map_params {
+    uint32_t skip;             /* event rows left out in front (adaptor, stall)                 */
+    uint32_t qmax;             /* 1 .. 1024: rows of the query at most, and the query matrix's pitch */
+    uint32_t qmin;             /* 1 .. qmax: a read with fewer rows after skip has no query     */
+    double scale;              /* finite, > 0; 32.0                                             */
+    int32_t clip;              /* 1 .. 32767; 127                                               */
+    int32_t want_start;        /* != 0: the row's start is computed                             */
+} s5gpu_map_params_t;
+typedef struct s5gpu_map_row {  /* 16 bytes, little-endian */
+    uint32_t cost;             /* 0xFFFFFFFF: the read has no query                             */
+    uint32_t qlen;             /* event rows used                                               */
+    int32_t start;             /* first reference index of the path; -1: not asked for, or no query */
+    int32_t end;               /* last reference index of the path (inclusive); -1: no query    */
+} s5gpu_map_row_t;
+#define S5GPU_STATUS_QUERY_SHORT 18   /* status[i]: fewer than qmin event rows behind skip */
+/* quant on the host (the same header function the kernel runs, compiled without contraction): for the reference.  S5GPU_ERR_ARG: scale
+ * not finite or <= 0, clip outside 1 .. 32767, a NULL pointer with L > 0. */
+int s5gpu_quantise_host(const float *m, size_t L, double scale, int32_t clip, int16_t *q);
+/* The queries of n reads from their event rows as s5gpu_signal_events_dev / the scan left them: rows, first (n + 1 entries: the rows of read i
+ * are rows[first[i] .. first[i + 1])) and ev_status (may be NULL: all 0).  queries: [n, p->qmax] int16, row i = the query of read i and zeros
+ * behind qlen[i]; status[i] = ev_status[i] when that is not 0 (no query: a failed record, an overflowed slot), else 0 or
+ * S5GPU_STATUS_QUERY_SHORT.  p: a HOST struct (want_start is not read); everything else device arrays.  S5GPU_ERR_ARG (nothing launched):
+ * qmax = 0 or > 1024, qmin = 0 or > qmax, scale not finite or <= 0, clip outside 1 .. 32767, a NULL or misaligned pointer.  Asynchronous. */
+int s5gpu_event_queries_dev(uint32_t n, const s5gpu_event_t *rows, const uint64_t *first, const int32_t *ev_status, const s5gpu_map_params_t *p,
+                            int16_t *queries, uint32_t *qlen, int32_t *status, void *hip_stream);
+/* sDTW of n queries (row i of `queries`, pitch qpitch <= 1024 values, its first min(qlen[i], qpitch) values) against ref[0 .. R), a device
+ * int16 array, 1 <= R <= 2^31 - 1: out_rows[i] (16-byte aligned) is written for every i and nothing else; qlen[i] = 0: the empty row
+ * 0xFFFFFFFF, 0, -1, -1.  One wave per read; the reference is not split, so few reads against a very long reference is not this call's case.
+ * S5GPU_ERR_ARG (nothing launched): qpitch = 0 or > 1024, R = 0 or > 2^31 - 1, a NULL or misaligned pointer.  Asynchronous on hip_stream. */
+int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, int want_start,
+                   s5gpu_map_row_t *out_rows, void *hip_stream);
+/* n records anywhere in host memory (bytes without the u64 prefix) against the quantised reference ref_host[0 .. R) (HOST memory), on the FIRST
+ * device in use: the decode, the event passes (event_params, S5GPU_NORM_RAW), the queries, sDTW, and one download of 16 n bytes into
+ * rows_out[0 .. n).  status_out[i] (may be NULL): 0, S5GPU_STATUS_QUERY_SHORT or the decoder's.  A corrupt record fails the call with
+ * S5GPU_ERR_DATA: its status_out[i] is the decoder's and its row is the empty row; the other reads' rows are valid.  S5GPU_ERR_ARG before
+ * anything is launched: the cases of the two calls above and of s5gpu_signal_events_dev, an unsupported method. */
+int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                    const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const int16_t *ref_host, uint32_t R,
+                    s5gpu_map_row_t *rows_out, int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

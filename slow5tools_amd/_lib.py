@@ -96,6 +96,15 @@ assert C.sizeof(EventParams) == 32
 STATUS_EVENTS_OVERFLOW = 17
 
 
+class MapParams(C.Structure):
+    """s5gpu_map_params_t"""
+    _fields_ = [("skip", C.c_uint32), ("qmax", C.c_uint32), ("qmin", C.c_uint32), ("scale", C.c_double), ("clip", C.c_int32), ("want_start", C.c_int32)]
+
+
+assert C.sizeof(MapParams) == 32
+STATUS_QUERY_SHORT = 18
+
+
 class S5GpuError(RuntimeError):
     pass
 
@@ -199,6 +208,11 @@ def lib():
     # events: event segmentation of decoded reads on the device, and of records anywhere in host memory
     L.s5gpu_signal_events_dev.argtypes = [u32, vp, vp, vp, vp, C.POINTER(EventParams), i32, vp, vp, vp, vp, vp, vp]
     L.s5gpu_signal_events_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), i32, vp, C.c_size_t, vp, vp]
+    # map: the quantiser on the host, the queries of event rows and sDTW on the device, and records anywhere in host memory
+    L.s5gpu_quantise_host.argtypes = [vp, C.c_size_t, C.c_double, C.c_int32, vp]
+    L.s5gpu_event_queries_dev.argtypes = [u32, vp, vp, vp, C.POINTER(MapParams), vp, vp, vp, vp]
+    L.s5gpu_sdtw_dev.argtypes = [u32, vp, u32, vp, vp, u32, i32, vp, vp]
+    L.s5gpu_map_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), vp, u32, vp, vp]
     _LIB = L
     return L
 
@@ -222,4 +236,5 @@ EXPORTS = [
     "s5gpu_file_stats_close",
     "s5gpu_diff_acc_bytes", "s5gpu_diff_acc_reset_dev", "s5gpu_signal_diff_dev", "s5gpu_diff_open", "s5gpu_diff_add_batch", "s5gpu_diff_close",
     "s5gpu_signal_events_dev", "s5gpu_signal_events_batch",
+    "s5gpu_quantise_host", "s5gpu_event_queries_dev", "s5gpu_sdtw_dev", "s5gpu_map_batch",
 ]

@@ -1,0 +1,171 @@
+// dtw_api.hip — host side of the map calls (include/slow5gpu.h, "map"): the quantiser on the host, argument checks and the launches of
+// the device entry points, and s5gpu_map_batch: upload -> decode -> event passes -> queries -> sDTW -> 16 bytes per read come back
+// (and, before the fill pass, the 8 bytes of the event total: the host has to know the room the rows need).
+// Neither the decoded signals nor the events leave the device.
+#include <math.h>
+
+#include "dtw_dev.h"
+#include "event_dev.h"
+#include "host_ctx.h"
+
+namespace {
+
+int check_quant(const char *who, double scale, int32_t clip) {
+    if (!isfinite(scale) || !(scale > 0.0)) { s5gpu_set_error("%s: scale %g (finite, > 0)", who, scale); return S5GPU_ERR_ARG; }
+    if (clip < 1 || clip > 32767) { s5gpu_set_error("%s: clip %d (1 .. 32767)", who, clip); return S5GPU_ERR_ARG; }
+    return S5GPU_OK;
+}
+
+int check_params(const char *who, const s5gpu_map_params_t *p) {
+    if (!p) { s5gpu_set_error("%s: NULL parameters", who); return S5GPU_ERR_ARG; }
+    if (p->qmax == 0 || p->qmax > dtwk::QMAX) { s5gpu_set_error("%s: qmax %u (1 .. %u)", who, p->qmax, dtwk::QMAX); return S5GPU_ERR_ARG; }
+    if (p->qmin == 0 || p->qmin > p->qmax) { s5gpu_set_error("%s: qmin %u (1 .. qmax = %u)", who, p->qmin, p->qmax); return S5GPU_ERR_ARG; }
+    return check_quant(who, p->scale, p->clip);
+}
+
+int check_ref(const char *who, uint32_t R) {
+    if (R == 0 || R > 0x7FFFFFFFu) { s5gpu_set_error("%s: a reference of %u values (1 .. 2^31 - 1)", who, R); return S5GPU_ERR_ARG; }
+    return S5GPU_OK;
+}
+
+dtwk::QueryArgs args_of(const s5gpu_event_t *rows, const uint64_t *first, const int32_t *ev_status, const s5gpu_map_params_t *p, int16_t *queries,
+                        uint32_t *qlen, int32_t *status) {
+    dtwk::QueryArgs A;
+    A.rows = rows; A.first = first; A.ev_status = ev_status;
+    A.skip = p->skip; A.qmax = p->qmax; A.qmin = p->qmin; A.scale = p->scale; A.clip = p->clip;
+    A.queries = queries; A.qlen = qlen; A.status = status;
+    return A;
+}
+
+}  // namespace
+
+extern "C" int s5gpu_quantise_host(const float *m, size_t L, double scale, int32_t clip, int16_t *q) {
+    DTW_NO_CONTRACT
+    const char *who = "s5gpu_quantise_host";
+    int rc;
+    if ((rc = check_quant(who, scale, clip))) return rc;
+    if (L == 0) return S5GPU_OK;
+    if (!m || !q) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    double mu, sd;
+    dtwk::quant_stats(m, 1, L, &mu, &sd);
+    const bool ok = dtwk::quant_ok(sd);
+    for (size_t j = 0; j < L; j++) q[j] = ok ? dtwk::quant_one(m[j], mu, sd, scale, clip) : (int16_t)0;
+    return S5GPU_OK;
+}
+
+extern "C" int s5gpu_event_queries_dev(uint32_t n, const s5gpu_event_t *rows, const uint64_t *first, const int32_t *ev_status,
+                                       const s5gpu_map_params_t *p, int16_t *queries, uint32_t *qlen, int32_t *status, void *stream) {
+    const char *who = "s5gpu_event_queries_dev";
+    int rc;
+    if ((rc = check_params(who, p))) return rc;
+    if (n == 0) return S5GPU_OK;
+    if (!first || !queries || !qlen || !status) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }   // (rows: NULL when no read has one)
+    if (((uintptr_t)rows & 15u) || ((uintptr_t)first & 7u) || ((uintptr_t)ev_status & 3u) || ((uintptr_t)queries & 1u) || ((uintptr_t)qlen & 3u) ||
+        ((uintptr_t)status & 3u)) {
+        s5gpu_set_error("%s: misaligned argument (rows: 16 bytes)", who);
+        return S5GPU_ERR_ARG;
+    }
+    return dtwk::launch_queries(n, args_of(rows, first, ev_status, p, queries, qlen, status), (hipStream_t)stream);
+}
+
+extern "C" int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, int want_start,
+                              s5gpu_map_row_t *out_rows, void *stream) {
+    const char *who = "s5gpu_sdtw_dev";
+    int rc;
+    if (qpitch == 0 || qpitch > dtwk::QMAX) { s5gpu_set_error("%s: a pitch of %u values (1 .. %u)", who, qpitch, dtwk::QMAX); return S5GPU_ERR_ARG; }
+    if ((rc = check_ref(who, R))) return rc;
+    if (!ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
+    if (n == 0) return S5GPU_OK;
+    if (!queries || !qlen || !out_rows) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    if (((uintptr_t)queries & 1u) || ((uintptr_t)qlen & 3u) || ((uintptr_t)ref & 1u) || ((uintptr_t)out_rows & 15u)) {
+        s5gpu_set_error("%s: misaligned argument (out_rows: 16 bytes)", who);
+        return S5GPU_ERR_ARG;
+    }
+    return dtwk::launch_sdtw(n, queries, qpitch, qlen, ref, R, want_start != 0, out_rows, (hipStream_t)stream);
+}
+
+extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                               const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R,
+                               s5gpu_map_row_t *rows_out, int32_t *status_out) {
+    const char *who = "s5gpu_map_batch";
+    int rc;
+    // (n = 0: the event call checks its parameters and launches nothing)
+    if ((rc = s5gpu_signal_events_dev(0, nullptr, nullptr, nullptr, nullptr, ep, S5GPU_NORM_RAW, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+    if ((rc = check_params(who, mp)) || (rc = check_ref(who, R))) return rc;
+    if ((rec_method != S5GPU_REC_NONE && rec_method != S5GPU_REC_ZLIB && rec_method != S5GPU_REC_ZSTD) ||
+        (sig_method != S5GPU_SIG_NONE && sig_method != S5GPU_SIG_SVB_ZD && sig_method != S5GPU_SIG_EX_ZD)) {
+        s5gpu_set_error("%s: unsupported method", who);
+        return S5GPU_ERR_ARG;
+    }
+    if (!ref_host || (n && (!rec || !rec_len || !rows_out))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    for (uint32_t i = 0; i < n; i++)
+        if (!rec[i] && rec_len[i]) { s5gpu_set_error("%s: record %u is NULL", who, i); return S5GPU_ERR_ARG; }
+    if (n == 0) return S5GPU_OK;
+    if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
+    s5host::CtxHold hold;
+    if ((rc = hold.acquire(0))) return rc;
+    Ctx *c = hold.c;
+    // the decode; a batch with corrupt records is decoded again without them while others still wait for a larger slot (host_ctx.h)
+    std::vector<s5gpu_rec_desc_t> rd;
+    std::vector<s5gpu_rec_fields_t> ff;
+    std::vector<uint32_t> cur;
+    std::vector<int32_t> status(n, 0);
+    std::vector<const void *> r2;
+    std::vector<size_t> l2;
+    bool corrupt = false;
+    auto decode = [&](uint32_t m, const uint32_t *idx) {
+        r2.resize(m); l2.resize(m);
+        for (uint32_t k = 0; k < m; k++) { r2[k] = rec[idx[k]]; l2[k] = rec_len[idx[k]]; }
+        return s5host::decode_resident(c, m, r2.data(), l2.data(), rec_method, sig_method, rd, ff, nullptr);
+    };
+    if ((rc = s5host::decode_dropping_corrupt(n, decode, ff, cur, status.data(), &corrupt))) return rc;
+    const uint32_t m = (uint32_t)cur.size();
+    const s5gpu_map_row_t empty = {dtwk::NO_COST, 0, -1, -1};
+    for (uint32_t i = 0; i < n; i++) rows_out[i] = empty;                 // what a record that was dropped keeps
+    if (m) {
+        // on the device: first[m + 1] (u64), the events' counts and statuses [m], qlen[m], the queries' statuses [m], the result rows [m] ...
+        const size_t o_cnt = up(8ull * (m + 1), 16), o_est = o_cnt + up(4ull * m, 16), o_ql = o_est + up(4ull * m, 16), o_qst = o_ql + up(4ull * m, 16),
+                     o_out = o_qst + up(4ull * m, 16);
+        if ((rc = c->d_patch.reserve(o_out + 16ull * m + 64)) || (rc = c->h_out.reserve(16ull * m + 64))) return rc;
+        uint8_t *dp = (uint8_t *)c->d_patch.p;
+        uint64_t *d_first = (uint64_t *)dp;
+        uint32_t *d_cnt = (uint32_t *)(dp + o_cnt), *d_ql = (uint32_t *)(dp + o_ql);
+        int32_t *d_est = (int32_t *)(dp + o_est), *d_qst = (int32_t *)(dp + o_qst);
+        s5gpu_map_row_t *d_out = (s5gpu_map_row_t *)(dp + o_out);
+        const sigk::SigRecs S = {(const int16_t *)c->d_sig2.p, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off),
+                                 (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)c->d_fields.p,
+                                 sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), m};
+        evk::EvArgs E;
+        E.w1 = ep->w1; E.w2 = ep->w2; E.thr1 = ep->thr1; E.thr2 = ep->thr2; E.peak_height = ep->peak_height; E.mode = S5GPU_NORM_RAW;
+        E.ev_off = nullptr; E.ev_cap = nullptr; E.rows = nullptr; E.n_events = d_cnt; E.ev_status = d_est;
+        if ((rc = evk::launch_events(S, E, c->st)) || (rc = evk::launch_scan(m, d_cnt, d_first, c->st))) return rc;
+        uint64_t total = 0;                                               // the host has to know the room the rows need
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, d_first + m, 8, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        memcpy(&total, c->h_out.p, 8);
+        // ... and the event rows, the query matrix and the reference
+        const size_t o_q = up(16ull * total, 16), o_ref = o_q + up(2ull * m * mp->qmax, 16);
+        if ((rc = c->d_stream.reserve(o_ref + 2ull * R + 64))) return rc;
+        uint8_t *ds = (uint8_t *)c->d_stream.p;
+        s5gpu_event_t *d_rows = (s5gpu_event_t *)ds;
+        int16_t *d_q = (int16_t *)(ds + o_q), *d_ref = (int16_t *)(ds + o_ref);
+        HIP_TRY(hipMemcpyAsync(d_ref, ref_host, 2ull * R, hipMemcpyHostToDevice, c->st));
+        if (total) {
+            E.ev_off = d_first; E.ev_cap = d_cnt; E.rows = d_rows;
+            if ((rc = evk::launch_events(S, E, c->st))) return rc;
+        }
+        if ((rc = dtwk::launch_queries(m, args_of(d_rows, d_first, d_est, mp, d_q, d_ql, d_qst), c->st)) ||
+            (rc = dtwk::launch_sdtw(m, d_q, mp->qmax, d_ql, d_ref, R, mp->want_start != 0, d_out, c->st)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, d_out, 16ull * m, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        const s5gpu_map_row_t *hr = (const s5gpu_map_row_t *)c->h_out.p;
+        for (uint32_t k = 0; k < m; k++) {                                // (a decoded read without a query: too few events, its row says so)
+            rows_out[cur[k]] = hr[k];
+            if (hr[k].qlen == 0 && status[cur[k]] == 0) status[cur[k]] = S5GPU_STATUS_QUERY_SHORT;
+        }
+    }
+    if (status_out) memcpy(status_out, status.data(), sizeof(int32_t) * n);
+    if (corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its row is empty)", who); return S5GPU_ERR_DATA; }
+    return S5GPU_OK;
+}

@@ -1,0 +1,161 @@
+// dtw_kernels.hip — subsequence DTW of each read's events against a reference squiggle on the device (docs/codecs.md §4.16):
+//   k_ev_query : per read, the quantised means of its event rows [skip, skip + qlen) as a row of the [n, qmax] int16 query matrix
+//   k_sdtw     : per read, (cost, qlen, start, end) of the best alignment of its query to a piece of the reference
+// k_sdtw is the project's one O(query x reference) kernel: a wave per read, systolic.  Lane l owns rows [l G, (l + 1) G) of the DTW matrix
+// (G = 1, 2, 4, 8, 16: the smallest with 64 G >= qlen, a kernel each), its query values and its cells of the column it did last in
+// registers.  At step t lane l does column t - l: from lane l - 1 it takes that lane's bottom cell of the same column (what it took one
+// step earlier is the diagonal) and the reference value, one DPP wave shift each; lane 0 gets the reference value by v_readlane from a
+// 64-value block that the wave loads together every 64 steps.  A cell is min3, absolute difference, add on uint32: D < 2^26 (§4.16).
+// Every lane steps at every step, before its column 0 and behind column R - 1 too (dtw_dev.h, FAR): no step has a predicate.
+// Nothing can index outside what it owns by construction (the rules of signal_kernels.hip):
+//   1. trip counts come from R and qlen only (qlen clamped to the pitch and to 64 G);
+//   2. no sample, cost or position forms an address: `end` and `start` are written as values;
+//   3. a wave shares nothing but the shifts, which every lane executes: there is no barrier and no LDS;
+//   4. a wave writes the one 16-byte row of its read; k_ev_query writes row i of the matrix, qlen[i] and status[i] of its read.
+#include "dev_common.h"
+#include "dtw_dev.h"
+
+extern "C" void s5gpu_set_error(const char *fmt, ...);
+
+using namespace dtwk;
+
+// a read per lane: at most qmax <= 1024 means each, a negligible share of the work
+__global__ __launch_bounds__(256) void k_ev_query(uint32_t n, QueryArgs A) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t f0 = A.first[i], f1 = A.first[i + 1];
+    const uint64_t E = f1 > f0 ? f1 - f0 : 0;
+    const uint64_t avail = E > A.skip ? E - A.skip : 0;
+    uint32_t ql = avail < A.qmax ? (uint32_t)avail : A.qmax;
+    int32_t st = A.ev_status ? A.ev_status[i] : 0;
+    if (st != 0) ql = 0;                                                  // the rows of a failed record or an overflowed slot are no query
+    else if (ql < A.qmin) { ql = 0; st = S5GPU_STATUS_QUERY_SHORT; }
+    int16_t *q = A.queries + i * A.qmax;
+    if (ql) {
+        const float *m = &A.rows[f0 + A.skip].mean;
+        const size_t stride = sizeof(s5gpu_event_t) / sizeof(float);
+        double mu, sd;
+        quant_stats(m, stride, ql, &mu, &sd);
+        const bool ok = quant_ok(sd);
+        for (uint32_t j = 0; j < ql; j++) q[j] = ok ? quant_one(m[j * stride], mu, sd, A.scale, A.clip) : (int16_t)0;
+    }
+    for (uint32_t j = ql; j < A.qmax; j++) q[j] = 0;
+    A.qlen[i] = ql;
+    A.status[i] = st;
+}
+
+// lane l <- lane l - 1; lane 0 <- fill.  DPP wave_shr:1 without bound_ctrl: a lane with no source keeps `old`.  One v_mov_b32_dpp, where
+// __shfl_up is a ds_bpermute_b32 with its address arithmetic and a select for lane 0.
+__device__ __forceinline__ uint32_t shift_up1(uint32_t v, uint32_t fill) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
+}
+// ... lane 0 <- 0: with bound_ctrl a lane with no source reads 0, and no register has to be filled first
+__device__ __forceinline__ uint32_t shift_up1_zero(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
+}
+
+// The steps of one read: lane `last` holds row Q - 1 as its row KB and does column R - 1 at step R - 1 + last (R < 2^31).  Every lane
+// steps at every step (dtw_dev.h, FAR): the shifts need every lane, and no step has a branch.
+template <int G, bool WS, int KB>
+__device__ __forceinline__ void sdtw_walk(Lane<G, WS> &L, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane) {
+    const uint32_t steps = R + last;
+    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
+    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
+    auto step = [&](uint32_t rblk, uint32_t k, uint32_t t) {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)k);
+        rcur = shift_up1(rcur, r0);
+        const uint32_t up = shift_up1_zero(L.d[G - 1]);
+        const int32_t sup = WS ? (int32_t)shift_up1((uint32_t)L.s[G - 1], t + 1) : -1;
+        lane_step(L, rcur, up, sup);
+        lane_best<G, WS, KB>(L, j, R);
+        j++;
+    };
+    constexpr int UNROLL = G >= 8 ? 2 : 8;                                 // (a step of 16 rows is long enough in itself)
+    uint32_t tb = 0;
+    for (; tb + 64 <= steps; tb += 64) {
+        const uint32_t at = tb + lane;                                     // the wave's block of reference values, zeros behind R
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+#pragma unroll UNROLL
+        for (uint32_t k = 0; k < 64; k++) step(rblk, k, tb + k);
+    }
+    if (tb < steps) {
+        const uint32_t at = tb + lane;
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+        for (uint32_t k = 0; k < steps - tb; k++) step(rblk, k, tb + k);
+    }
+}
+// kb -> the walk compiled for it (kb is the same in every lane: scalar branches, once per read)
+template <int G, bool WS, int KB = 0>
+struct Walk {
+    static __device__ __forceinline__ void run(int kb, Lane<G, WS> &L, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane) {
+        if (kb == KB) sdtw_walk<G, WS, KB>(L, ref, R, last, lane);
+        else if constexpr (KB + 1 < G) Walk<G, WS, KB + 1>::run(kb, L, ref, R, last, lane);
+    }
+};
+
+template <int G, bool WS>
+__global__ __launch_bounds__(256) void k_sdtw(uint32_t n, const int16_t *__restrict__ queries, uint32_t qpitch, const uint32_t *__restrict__ qlen,
+                                              const int16_t *__restrict__ ref, uint32_t R, U4 *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t read = (uint64_t)blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (read >= n) return;                                                // (the wave's branch: `read` is the same in its 64 lanes)
+    uint32_t Q = qlen[read];
+    Q = Q < qpitch ? Q : qpitch;
+    Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Q < QMAX ? Q : QMAX));
+    if (Q > 64u * G || (G > 1 && Q <= 32u * G)) return;                    // another launch's read
+    if (Q == 0) {
+        if (lane == 0) out[read] = result_row(NO_COST, 0, -1, -1);
+        return;
+    }
+    Lane<G, WS> L;
+    lane_init(L, lane == 0);
+    const int16_t *q = queries + read * qpitch;
+#pragma unroll
+    for (int k = 0; k < G; k++) {
+        const uint32_t row = lane * G + k;
+        L.q[k] = biased(row < Q ? q[row] : (int16_t)0);                    // rows at or beyond Q: cells nobody reads
+    }
+    const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1 ...
+    const int kb = (int)(Q - 1 - last * G);                                // ... and which of its rows it is
+    Walk<G, WS>::run(kb, L, ref, R, last, lane);
+    if (lane == last) out[read] = result_row(L.best, Q, WS ? L.best_start : -1, L.best_end);
+}
+
+#define DTW_LAUNCH_CHECK(what)                                                            \
+    do {                                                                                  \
+        hipError_t e_ = hipGetLastError();                                                \
+        if (e_ != hipSuccess) {                                                           \
+            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
+            return S5GPU_ERR_HIP;                                                         \
+        }                                                                                 \
+    } while (0)
+
+int dtwk::launch_queries(uint32_t n, const QueryArgs &A, hipStream_t st) {
+    if (n == 0) return S5GPU_OK;
+    hipLaunchKernelGGL(k_ev_query, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, st, n, A);
+    DTW_LAUNCH_CHECK("k_ev_query");
+    return S5GPU_OK;
+}
+
+template <int G>
+static int launch_class(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                        U4 *out, hipStream_t st) {
+    const dim3 grid((uint32_t)(((uint64_t)n + 3u) / 4u)), block(256);
+    if (want_start) hipLaunchKernelGGL((k_sdtw<G, true>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, out);
+    else hipLaunchKernelGGL((k_sdtw<G, false>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, out);
+    DTW_LAUNCH_CHECK("k_sdtw");
+    return S5GPU_OK;
+}
+
+// A launch per lane height that a query of at most qpitch rows can need; a wave whose read belongs to another launch returns at once.
+int dtwk::launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                      s5gpu_map_row_t *out, hipStream_t st) {
+    if (n == 0) return S5GPU_OK;
+    U4 *o = reinterpret_cast<U4 *>(out);
+    int rc = launch_class<1>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
+    if (!rc && qpitch > 64) rc = launch_class<2>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
+    if (!rc && qpitch > 128) rc = launch_class<4>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
+    if (!rc && qpitch > 256) rc = launch_class<8>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
+    if (!rc && qpitch > 512) rc = launch_class<16>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
+    return rc;
+}
