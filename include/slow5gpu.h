@@ -757,6 +757,39 @@ int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, i
                     const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const int16_t *ref_host, uint32_t R,
                     s5gpu_map_row_t *rows_out, int32_t *status_out);
 
+/* ---- align: the whole path of a read's sDTW alignment, event to reference (docs/codecs.md §4.17) ----
+ * The path of a read starts at (qlen - 1, end) and follows the chosen predecessor (the rule of map) to row 0, where it arrives at (0, start).
+ * It is monotone, so two values per query row i describe it: lo[i] <= hi[i], the first and last reference column that event i is aligned
+ * to.  lo[0] = start, hi[qlen - 1] = end, lo[i] - hi[i - 1] is 0 or 1, and the c(i,j) of all its cells add up to cost.  lo and hi are
+ * [n, qpitch] int32 matrices, -1 behind qlen and in every row of a read without a path. */
+#define S5GPU_STATUS_PATH_WIDE 19     /* status[i]: the span end - start + 1 is above wmax: no path */
+#define S5GPU_STATUS_PATH_ROW 20      /* status[i]: the read has a query but its row is unusable: start < 0 (made without want_start),
+                                         start > end, end >= R, a qlen that is not the query's, or decisions that do not lead to (0, start) */
+/* The scratch bytes one read needs in s5gpu_sdtw_path_dev: 2 bits per cell of its 64 lanes over wmax + 63 steps; 0 for a qpitch or wmax that
+ * call refuses.  Monotone in both arguments. */
+size_t s5gpu_sdtw_path_slot_bytes(uint32_t qpitch, uint32_t wmax);
+/* The paths of n reads: queries, qpitch, qlen, ref, R as for s5gpu_sdtw_dev, and rows = what that call wrote with want_start, all DEVICE
+ * arrays.  The recurrence is run again over the columns [start, end] of each read only, its decisions are kept in `scratch` and walked
+ * back.  wmax (1 .. 2^20): the widest span that gets a path; it bounds the scratch, not the quality.  lo, hi ([n, qpitch]) and status ([n]:
+ * 0, S5GPU_STATUS_PATH_WIDE or S5GPU_STATUS_PATH_ROW; a read with qlen = 0 has 0 and no path) are written, and nothing else outside the
+ * scratch.  Reads are handled in groups of scratch_bytes / slot reads, one after the other on the stream.  S5GPU_ERR_NOMEM: the scratch is
+ * smaller than one slot.  S5GPU_ERR_ARG (nothing launched): the cases of s5gpu_sdtw_dev, wmax = 0 or > 2^20, a NULL or misaligned pointer
+ * (scratch: 16 bytes; rows: 16; lo, hi, status: 4).  Asynchronous on hip_stream.
+ * s5gpu_set_option (tests, tools): "sdtw_path_passes" (1 .. 3, default 3): 1 launches the pass that writes the decisions only, 2 the walk
+ * only (over what an earlier call left in the scratch and the outputs); tools/sdtw_path_time.py times the passes apart with it. */
+int s5gpu_sdtw_path_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R,
+                        const s5gpu_map_row_t *rows, uint32_t wmax, void *scratch, size_t scratch_bytes, int32_t *lo, int32_t *hi,
+                        int32_t *status, void *hip_stream);
+/* s5gpu_map_batch with want_start forced on, then the paths, on the FIRST device in use; one download brings back rows_out[0 .. n),
+ * lo_out and hi_out ([n, qmax] int32) and events_out (may be NULL; [n, qmax]: the event rows [skip, skip + qlen) of the read's query, zeros
+ * behind qlen).  The scratch is at most 256 MiB (one slot above that: S5GPU_ERR_NOMEM).  status_out[i] (may be NULL): the decoder's,
+ * S5GPU_STATUS_QUERY_SHORT, S5GPU_STATUS_PATH_WIDE, S5GPU_STATUS_PATH_ROW or 0.  A corrupt record fails the call with S5GPU_ERR_DATA: its
+ * status is the decoder's, its row the empty row, its lo and hi -1 and its events zero; the other reads are valid.  S5GPU_ERR_ARG before
+ * anything is launched: the cases of s5gpu_map_batch, wmax = 0 or > 2^20. */
+int s5gpu_align_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                      const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, uint32_t wmax, const int16_t *ref_host,
+                      uint32_t R, s5gpu_map_row_t *rows_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out, int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

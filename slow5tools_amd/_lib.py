@@ -103,6 +103,7 @@ class MapParams(C.Structure):
 
 assert C.sizeof(MapParams) == 32
 STATUS_QUERY_SHORT = 18
+STATUS_PATH_WIDE, STATUS_PATH_ROW = 19, 20
 
 
 class S5GpuError(RuntimeError):
@@ -213,6 +214,11 @@ def lib():
     L.s5gpu_event_queries_dev.argtypes = [u32, vp, vp, vp, C.POINTER(MapParams), vp, vp, vp, vp]
     L.s5gpu_sdtw_dev.argtypes = [u32, vp, u32, vp, vp, u32, i32, vp, vp]
     L.s5gpu_map_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), vp, u32, vp, vp]
+    # align: the scratch a read's path needs, the paths of mapped queries on the device, and records anywhere in host memory
+    L.s5gpu_sdtw_path_slot_bytes.argtypes = [u32, u32]
+    L.s5gpu_sdtw_path_slot_bytes.restype = C.c_size_t
+    L.s5gpu_sdtw_path_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, u32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.s5gpu_align_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), u32, vp, u32, vp, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -237,4 +243,5 @@ EXPORTS = [
     "s5gpu_diff_acc_bytes", "s5gpu_diff_acc_reset_dev", "s5gpu_signal_diff_dev", "s5gpu_diff_open", "s5gpu_diff_add_batch", "s5gpu_diff_close",
     "s5gpu_signal_events_dev", "s5gpu_signal_events_batch",
     "s5gpu_quantise_host", "s5gpu_event_queries_dev", "s5gpu_sdtw_dev", "s5gpu_map_batch",
+    "s5gpu_sdtw_path_slot_bytes", "s5gpu_sdtw_path_dev", "s5gpu_align_batch",
 ]

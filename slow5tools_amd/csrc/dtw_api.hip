@@ -1,12 +1,12 @@
 // dtw_api.hip — host side of the map calls (include/slow5gpu.h, "map"): the quantiser on the host, argument checks and the launches of
 // the device entry points, and s5gpu_map_batch: upload -> decode -> event passes -> queries -> sDTW -> 16 bytes per read come back
 // (and, before the fill pass, the 8 bytes of the event total: the host has to know the room the rows need).
-// Neither the decoded signals nor the events leave the device.
+// Neither the decoded signals nor the events leave the device.  The chain up to the queries is map_front (dtw_host.h), which
+// s5gpu_align_batch (dtw_path_api.hip) runs too.
 #include <math.h>
 
-#include "dtw_dev.h"
+#include "dtw_host.h"
 #include "event_dev.h"
-#include "host_ctx.h"
 
 namespace {
 
@@ -84,10 +84,8 @@ extern "C" int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitc
     return dtwk::launch_sdtw(n, queries, qpitch, qlen, ref, R, want_start != 0, out_rows, (hipStream_t)stream);
 }
 
-extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
-                               const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R,
-                               s5gpu_map_row_t *rows_out, int32_t *status_out) {
-    const char *who = "s5gpu_map_batch";
+int dtwk::map_front_check(const char *who, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                          const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R, bool outputs) {
     int rc;
     // (n = 0: the event call checks its parameters and launches nothing)
     if ((rc = s5gpu_signal_events_dev(0, nullptr, nullptr, nullptr, nullptr, ep, S5GPU_NORM_RAW, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
@@ -97,75 +95,93 @@ extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t 
         s5gpu_set_error("%s: unsupported method", who);
         return S5GPU_ERR_ARG;
     }
-    if (!ref_host || (n && (!rec || !rec_len || !rows_out))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    if (!ref_host || (n && (!rec || !rec_len || !outputs))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
     for (uint32_t i = 0; i < n; i++)
         if (!rec[i] && rec_len[i]) { s5gpu_set_error("%s: record %u is NULL", who, i); return S5GPU_ERR_ARG; }
-    if (n == 0) return S5GPU_OK;
-    if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
-    s5host::CtxHold hold;
-    if ((rc = hold.acquire(0))) return rc;
-    Ctx *c = hold.c;
+    return S5GPU_OK;
+}
+
+int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, const s5gpu_event_params_t *ep,
+                    const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R, MapFront &F) {
+    int rc;
+    if ((rc = F.hold.acquire(0))) return rc;
+    Ctx *c = F.hold.c;
     // the decode; a batch with corrupt records is decoded again without them while others still wait for a larger slot (host_ctx.h)
     std::vector<s5gpu_rec_desc_t> rd;
     std::vector<s5gpu_rec_fields_t> ff;
-    std::vector<uint32_t> cur;
-    std::vector<int32_t> status(n, 0);
     std::vector<const void *> r2;
     std::vector<size_t> l2;
-    bool corrupt = false;
+    F.status.assign(n, 0);
+    F.corrupt = false;
     auto decode = [&](uint32_t m, const uint32_t *idx) {
         r2.resize(m); l2.resize(m);
         for (uint32_t k = 0; k < m; k++) { r2[k] = rec[idx[k]]; l2[k] = rec_len[idx[k]]; }
         return s5host::decode_resident(c, m, r2.data(), l2.data(), rec_method, sig_method, rd, ff, nullptr);
     };
-    if ((rc = s5host::decode_dropping_corrupt(n, decode, ff, cur, status.data(), &corrupt))) return rc;
-    const uint32_t m = (uint32_t)cur.size();
+    if ((rc = s5host::decode_dropping_corrupt(n, decode, ff, F.cur, F.status.data(), &F.corrupt))) return rc;
+    const uint32_t m = F.m = (uint32_t)F.cur.size();
+    if (m == 0) return S5GPU_OK;
+    // on the device: first[m + 1] (u64), the events' counts and statuses [m], qlen[m], the queries' statuses [m], the result rows [m] ...
+    const size_t o_cnt = up(8ull * (m + 1), 16), o_est = o_cnt + up(4ull * m, 16), o_ql = o_est + up(4ull * m, 16), o_qst = o_ql + up(4ull * m, 16),
+                 o_out = o_qst + up(4ull * m, 16);
+    if ((rc = c->d_patch.reserve(o_out + 16ull * m + 64)) || (rc = c->h_out.reserve(16ull * m + 64))) return rc;
+    uint8_t *dp = (uint8_t *)c->d_patch.p;
+    uint64_t *d_first = (uint64_t *)dp;
+    uint32_t *d_cnt = (uint32_t *)(dp + o_cnt), *d_ql = (uint32_t *)(dp + o_ql);
+    int32_t *d_est = (int32_t *)(dp + o_est), *d_qst = (int32_t *)(dp + o_qst);
+    const sigk::SigRecs S = {(const int16_t *)c->d_sig2.p, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off),
+                             (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)c->d_fields.p,
+                             sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), m};
+    evk::EvArgs E;
+    E.w1 = ep->w1; E.w2 = ep->w2; E.thr1 = ep->thr1; E.thr2 = ep->thr2; E.peak_height = ep->peak_height; E.mode = S5GPU_NORM_RAW;
+    E.ev_off = nullptr; E.ev_cap = nullptr; E.rows = nullptr; E.n_events = d_cnt; E.ev_status = d_est;
+    if ((rc = evk::launch_events(S, E, c->st)) || (rc = evk::launch_scan(m, d_cnt, d_first, c->st))) return rc;
+    uint64_t total = 0;                                                   // the host has to know the room the rows need
+    HIP_TRY(hipMemcpyAsync(c->h_out.p, d_first + m, 8, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    memcpy(&total, c->h_out.p, 8);
+    // ... and the event rows, the query matrix and the reference
+    const size_t o_q = up(16ull * total, 16), o_ref = o_q + up(2ull * m * mp->qmax, 16);
+    if ((rc = c->d_stream.reserve(o_ref + 2ull * R + 64))) return rc;
+    uint8_t *ds = (uint8_t *)c->d_stream.p;
+    s5gpu_event_t *d_rows = (s5gpu_event_t *)ds;
+    int16_t *d_q = (int16_t *)(ds + o_q), *d_ref = (int16_t *)(ds + o_ref);
+    HIP_TRY(hipMemcpyAsync(d_ref, ref_host, 2ull * R, hipMemcpyHostToDevice, c->st));
+    if (total) {
+        E.ev_off = d_first; E.ev_cap = d_cnt; E.rows = d_rows;
+        if ((rc = evk::launch_events(S, E, c->st))) return rc;
+    }
+    if ((rc = dtwk::launch_queries(m, args_of(d_rows, d_first, d_est, mp, d_q, d_ql, d_qst), c->st))) return rc;
+    F.d_rows = d_rows; F.d_first = d_first; F.d_q = d_q; F.d_ql = d_ql; F.d_ref = d_ref;
+    F.d_out = (s5gpu_map_row_t *)(dp + o_out);
+    return S5GPU_OK;
+}
+
+extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                               const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R,
+                               s5gpu_map_row_t *rows_out, int32_t *status_out) {
+    const char *who = "s5gpu_map_batch";
+    int rc;
+    if ((rc = dtwk::map_front_check(who, n, rec, rec_len, rec_method, sig_method, ep, mp, ref_host, R, rows_out != nullptr))) return rc;
+    if (n == 0) return S5GPU_OK;
+    if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
+    dtwk::MapFront F;
+    if ((rc = dtwk::map_front(n, rec, rec_len, rec_method, sig_method, ep, mp, ref_host, R, F))) return rc;
+    Ctx *c = F.hold.c;
+    const uint32_t m = F.m;
     const s5gpu_map_row_t empty = {dtwk::NO_COST, 0, -1, -1};
     for (uint32_t i = 0; i < n; i++) rows_out[i] = empty;                 // what a record that was dropped keeps
     if (m) {
-        // on the device: first[m + 1] (u64), the events' counts and statuses [m], qlen[m], the queries' statuses [m], the result rows [m] ...
-        const size_t o_cnt = up(8ull * (m + 1), 16), o_est = o_cnt + up(4ull * m, 16), o_ql = o_est + up(4ull * m, 16), o_qst = o_ql + up(4ull * m, 16),
-                     o_out = o_qst + up(4ull * m, 16);
-        if ((rc = c->d_patch.reserve(o_out + 16ull * m + 64)) || (rc = c->h_out.reserve(16ull * m + 64))) return rc;
-        uint8_t *dp = (uint8_t *)c->d_patch.p;
-        uint64_t *d_first = (uint64_t *)dp;
-        uint32_t *d_cnt = (uint32_t *)(dp + o_cnt), *d_ql = (uint32_t *)(dp + o_ql);
-        int32_t *d_est = (int32_t *)(dp + o_est), *d_qst = (int32_t *)(dp + o_qst);
-        s5gpu_map_row_t *d_out = (s5gpu_map_row_t *)(dp + o_out);
-        const sigk::SigRecs S = {(const int16_t *)c->d_sig2.p, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off),
-                                 (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)c->d_fields.p,
-                                 sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), m};
-        evk::EvArgs E;
-        E.w1 = ep->w1; E.w2 = ep->w2; E.thr1 = ep->thr1; E.thr2 = ep->thr2; E.peak_height = ep->peak_height; E.mode = S5GPU_NORM_RAW;
-        E.ev_off = nullptr; E.ev_cap = nullptr; E.rows = nullptr; E.n_events = d_cnt; E.ev_status = d_est;
-        if ((rc = evk::launch_events(S, E, c->st)) || (rc = evk::launch_scan(m, d_cnt, d_first, c->st))) return rc;
-        uint64_t total = 0;                                               // the host has to know the room the rows need
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, d_first + m, 8, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-        memcpy(&total, c->h_out.p, 8);
-        // ... and the event rows, the query matrix and the reference
-        const size_t o_q = up(16ull * total, 16), o_ref = o_q + up(2ull * m * mp->qmax, 16);
-        if ((rc = c->d_stream.reserve(o_ref + 2ull * R + 64))) return rc;
-        uint8_t *ds = (uint8_t *)c->d_stream.p;
-        s5gpu_event_t *d_rows = (s5gpu_event_t *)ds;
-        int16_t *d_q = (int16_t *)(ds + o_q), *d_ref = (int16_t *)(ds + o_ref);
-        HIP_TRY(hipMemcpyAsync(d_ref, ref_host, 2ull * R, hipMemcpyHostToDevice, c->st));
-        if (total) {
-            E.ev_off = d_first; E.ev_cap = d_cnt; E.rows = d_rows;
-            if ((rc = evk::launch_events(S, E, c->st))) return rc;
-        }
-        if ((rc = dtwk::launch_queries(m, args_of(d_rows, d_first, d_est, mp, d_q, d_ql, d_qst), c->st)) ||
-            (rc = dtwk::launch_sdtw(m, d_q, mp->qmax, d_ql, d_ref, R, mp->want_start != 0, d_out, c->st)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, d_out, 16ull * m, hipMemcpyDeviceToHost, c->st));
+        if ((rc = dtwk::launch_sdtw(m, F.d_q, mp->qmax, F.d_ql, F.d_ref, R, mp->want_start != 0, F.d_out, c->st))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, F.d_out, 16ull * m, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
         const s5gpu_map_row_t *hr = (const s5gpu_map_row_t *)c->h_out.p;
         for (uint32_t k = 0; k < m; k++) {                                // (a decoded read without a query: too few events, its row says so)
-            rows_out[cur[k]] = hr[k];
-            if (hr[k].qlen == 0 && status[cur[k]] == 0) status[cur[k]] = S5GPU_STATUS_QUERY_SHORT;
+            rows_out[F.cur[k]] = hr[k];
+            if (hr[k].qlen == 0 && F.status[F.cur[k]] == 0) F.status[F.cur[k]] = S5GPU_STATUS_QUERY_SHORT;
         }
     }
-    if (status_out) memcpy(status_out, status.data(), sizeof(int32_t) * n);
-    if (corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its row is empty)", who); return S5GPU_ERR_DATA; }
+    if (status_out) memcpy(status_out, F.status.data(), sizeof(int32_t) * n);
+    if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its row is empty)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;
 }

@@ -1,7 +1,8 @@
-// dtw_dev.h — what dtw_kernels.hip and dtw_api.hip share: the quantiser, the sDTW cell, a lane's step of the systolic scheme and the
-// launchers (docs/codecs.md §4.16).
-// With S5_DTW_HOST defined only the quantiser and the lane code are declared, as plain C++: tests/test_map.py compiles them for the CPU
-// and runs the very code a lane runs, 64 lanes in a loop with the lane exchange passed in, against the restatement, without a device.
+// dtw_dev.h — what dtw_kernels.hip, dtw_path_kernels.hip and their host sides share: the quantiser, the sDTW cell, a lane's step of the
+// systolic scheme, the packing of a path's decisions and the walk back through them, and the launchers (docs/codecs.md §4.16, §4.17).
+// With S5_DTW_HOST defined only the quantiser, the lane code and the path code are declared, as plain C++: tests/test_map.py and
+// tests/test_align.py compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
+// against the restatement, without a device.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -141,7 +142,100 @@ DTW_HD U4 result_row(uint32_t cost, uint32_t qlen, int32_t start, int32_t end) {
     return o;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the path (§4.17)
+// The alignment path of a read, walked back through the decisions of the window [start, end] of its row.  A decision is a 2-bit code:
+// 0 the diagonal, 1 (i - 1, j), 2 (i, j - 1); 3 does not occur.  A lane's step makes 2 G bits, row k of the lane at bits [2 k, 2 k + 2);
+// 16 / G steps fill a 32-bit word, step s of the word at bits [2 G s, 2 G (s + 1)).  A read's words lie [word][lane]: lane l's word w, which
+// holds its steps [w 16 / G, (w + 1) 16 / G), is words[w * 64 + l].  At step t lane l does window column t - l.
+constexpr uint32_t WMAX = 1u << 20;          // columns of the widest window
+
+// the lane height of a query of Q rows: the smallest G with 64 G >= Q (Q <= QMAX)
+DTW_HD uint32_t lane_height(uint32_t Q) { return Q <= 64 ? 1u : Q <= 128 ? 2u : Q <= 256 ? 4u : Q <= 512 ? 8u : 16u; }
+// words of a lane that hold `steps` steps, and of the slot of a read of at most qpitch rows and wmax columns (its last lane is 63 at most)
+DTW_HD uint32_t path_words(uint32_t G, uint32_t steps) { const uint32_t spw = 16u / G; return (steps + spw - 1) / spw; }
+DTW_HD uint32_t path_slot_words(uint32_t qpitch, uint32_t wmax) { return path_words(lane_height(qpitch), wmax + 63u); }
+
+// lane_step without S, yielding the decisions: the same min3 and the same two compares that choose S there
+template <int G>
+DTW_HD uint32_t lane_step_dirs(Lane<G, false> &L, uint32_t r, uint32_t up) {
+    uint32_t dg = L.dg, codes = 0;
+    L.dg = up;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int k = 0; k < G; k++) {
+        const uint32_t left = L.d[k];
+        const uint32_t m = min3u(dg, up, left);
+        const uint32_t nd = absdiff(L.q[k], r) + m;
+        codes |= (dg == m ? 0u : up == m ? 1u : 2u) << (2 * k);
+        dg = left; up = nd;
+        L.d[k] = nd;
+    }
+    return codes;
+}
+// the codes of step s of a word (s < 16 / G) put into it
+DTW_HD uint32_t path_pack(uint32_t word, uint32_t codes, uint32_t s, uint32_t G) { return word | codes << (2u * G * s); }
+// cell (i, j) of the window -> the index of the word that holds its code, and the code's shift in it
+DTW_HD uint32_t path_cell(uint32_t G, uint32_t i, uint32_t j, uint32_t *shift) {
+    const uint32_t l = i / G, k = i - l * G, t = j + l, spw = 16u / G, w = t / spw;
+    *shift = 2u * G * (t - w * spw) + 2u * k;
+    return w * 64u + l;
+}
+
+// Is the row of a read with a query of Q >= 1 rows usable, and its window at most wmax wide?  -> 0 and *W, or the status (*W = 0)
+DTW_HD int32_t path_row_check(const U4 &row, uint32_t Q, uint32_t R, uint32_t wmax, uint32_t *W) {
+    const int32_t start = (int32_t)row.z, end = (int32_t)row.w;
+    *W = 0;
+    if (row.y != Q || start < 0 || start > end || (uint32_t)end >= R) return S5GPU_STATUS_PATH_ROW;
+    const uint32_t w = (uint32_t)(end - start) + 1u;
+    if (w > wmax) return S5GPU_STATUS_PATH_WIDE;
+    *W = w;
+    return 0;
+}
+
+// The walk: from (Q - 1, W - 1) along the decisions to row 0, which it has to reach in window column 0.  lo[i], hi[i] (i < Q) get the first
+// and last column of row i, as absolute columns.  A decision read from memory chooses the next word, so everything is bounded here: at
+// most Q + W trips; i < Q and j < W checked before each use; a word index is clamped to the slot; a code of 3, a step out of the window or
+// an arrival in row 0 right of column 0 ends the walk.  -> 0, or S5GPU_STATUS_PATH_ROW (lo and hi then hold a partial path: the caller
+// overwrites them)
+DTW_HD int32_t path_walk(const uint32_t *words, uint32_t slot_words, uint32_t G, uint32_t Q, uint32_t W, int32_t start, int32_t *lo, int32_t *hi) {
+    if (Q == 0 || W == 0 || slot_words == 0) return S5GPU_STATUS_PATH_ROW;
+    const uint32_t top = slot_words * 64u - 1u;
+    uint32_t i = Q - 1, j = W - 1, at = 0xFFFFFFFFu, word = 0;
+    hi[i] = start + (int32_t)j;
+    for (uint32_t trip = 0; trip < Q + W; trip++) {
+        if (i >= Q || j >= W) break;
+        if (i == 0) {
+            if (j != 0) break;
+            lo[0] = start;
+            return 0;
+        }
+        uint32_t shift;
+        uint32_t x = path_cell(G, i, j, &shift);
+        x = x < top ? x : top;
+        if (x != at) { word = words[x]; at = x; }                          // (a word holds 16 / G steps of G rows: most moves stay in it)
+        const uint32_t code = (word >> shift) & 3u;
+        if (code == 3u || (code != 1u && j == 0)) break;
+        if (code == 2u) { j--; continue; }
+        lo[i] = start + (int32_t)j;
+        i--;
+        if (code == 0u) j--;
+        hi[i] = start + (int32_t)j;
+    }
+    return S5GPU_STATUS_PATH_ROW;
+}
+
 #ifndef S5_DTW_HOST
+// lane l <- lane l - 1; lane 0 <- fill.  DPP wave_shr:1 without bound_ctrl: a lane with no source keeps `old`.  One v_mov_b32_dpp, where
+// __shfl_up is a ds_bpermute_b32 with its address arithmetic and a select for lane 0.
+__device__ __forceinline__ uint32_t shift_up1(uint32_t v, uint32_t fill) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
+}
+// ... lane 0 <- 0: with bound_ctrl a lane with no source reads 0, and no register has to be filled first
+__device__ __forceinline__ uint32_t shift_up1_zero(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
+}
+
 struct QueryArgs {
     const s5gpu_event_t *rows;
     const uint64_t *first;           // n + 1
@@ -158,6 +252,26 @@ int launch_queries(uint32_t n, const QueryArgs &A, hipStream_t st);
 // k_sdtw over n reads, on st: a launch per class of lane height that qpitch allows
 int launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
                 s5gpu_map_row_t *out, hipStream_t st);
+struct PathArgs {
+    const int16_t *queries;          // [n, qpitch]
+    uint32_t qpitch;
+    const uint32_t *qlen;
+    const int16_t *ref;
+    uint32_t R;
+    const U4 *rows;                  // what k_sdtw<G, true> wrote
+    uint32_t wmax;
+    uint32_t *scratch;               // n slots of slot_words * 64 words
+    uint32_t slot_words;
+    int32_t *lo, *hi;                // [n, qpitch]
+    int32_t *status;
+};
+// k_sdtw_dirs (a launch per class of lane height) and k_sdtw_trace over n reads, on st; which = 1: the first only, 2: the second only
+int launch_path(uint32_t n, const PathArgs &A, hipStream_t st, int which = 3);
+// s5gpu_set_option's keys of the path call (dtw_path_api.hip)
+int path_set_option(const char *key, long value);
+// k_ev_gather: rows [first[i] + skip, ... + qlen[i]) of every read into row i of out [n, qmax], zeros behind
+int launch_event_gather(uint32_t n, const s5gpu_event_t *rows, const uint64_t *first, const uint32_t *qlen, uint32_t skip, uint32_t qmax,
+                        s5gpu_event_t *out, hipStream_t st);
 #endif
 
 }  // namespace dtwk

@@ -44,16 +44,7 @@ __global__ __launch_bounds__(256) void k_ev_query(uint32_t n, QueryArgs A) {
     A.status[i] = st;
 }
 
-// lane l <- lane l - 1; lane 0 <- fill.  DPP wave_shr:1 without bound_ctrl: a lane with no source keeps `old`.  One v_mov_b32_dpp, where
-// __shfl_up is a ds_bpermute_b32 with its address arithmetic and a select for lane 0.
-__device__ __forceinline__ uint32_t shift_up1(uint32_t v, uint32_t fill) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
-}
-// ... lane 0 <- 0: with bound_ctrl a lane with no source reads 0, and no register has to be filled first
-__device__ __forceinline__ uint32_t shift_up1_zero(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
-}
-
+// (the wave shifts shift_up1 and shift_up1_zero: dtw_dev.h)
 // The steps of one read: lane `last` holds row Q - 1 as its row KB and does column R - 1 at step R - 1 + last (R < 2^31).  Every lane
 // steps at every step (dtw_dev.h, FAR): the shifts need every lane, and no step has a branch.
 template <int G, bool WS, int KB>
