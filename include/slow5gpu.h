@@ -790,6 +790,56 @@ int s5gpu_align_batch(uint32_t n, const void *const *rec, const size_t *rec_len,
                       const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, uint32_t wmax, const int16_t *ref_host,
                       uint32_t R, s5gpu_map_row_t *rows_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out, int32_t *status_out);
 
+/* ---- pileup: per-reference-position statistics of aligned events, accumulated on the device (docs/codecs.md §4.18) ----
+ * The transpose of align: what the reads say about reference column j.  Inputs are those of s5gpu_sdtw_path_dev and what it wrote: queries,
+ * qlen (Q = min(qlen[i], qpitch)), ref, lo, hi, status, and optionally the query's event rows as an [n, qpitch] matrix.  A read is USED iff
+ * status = 0, Q >= 1, every row i < Q has 0 <= lo[i] <= hi[i] < R and every row 1 <= i < Q has lo[i] - hi[i-1] in {0, 1}; status != 0 or
+ * Q = 0: SKIPPED; a failed row check: BAD, and nothing of the read is accumulated.  The cells of a used read are (i, j), i < Q,
+ * lo[i] <= j <= hi[i]; a cell is first in its column iff i = 0 or j > hi[i-1].  Every member is an integer sum, minimum or maximum over
+ * all used reads, so the result does not depend on the order of reads, batches, streams or atomics. */
+typedef struct s5gpu_pile_col {  /* 48 bytes, little-endian: column j of the table */
+    uint32_t depth;            /* cells that are first in their column: the reads with start <= j <= end */
+    uint32_t n_events;         /* cells in the column (fewer than 2^32)                         */
+    uint64_t n_samples;        /* sum of events[i].length; 0 when no events are given; an event that spans several columns counts in each */
+    int64_t sum_q;             /* sum of q[i]                                                   */
+    uint64_t sumsq_q;          /* sum of q[i]^2                                                 */
+    uint64_t sum_cost;         /* sum of |q[i] - r[j]|                                          */
+    int32_t min_q, max_q;      /* 32767 / -32768 while the column is empty                      */
+} s5gpu_pile_col_t;
+typedef struct s5gpu_pile_total {  /* 64 bytes in front of the columns */
+    uint64_t reads_used, reads_skipped, reads_bad;
+    uint64_t cells;            /* = sum of n_events over the columns                            */
+    uint64_t cost;             /* = sum of sum_cost over the columns; for paths of s5gpu_sdtw_path_dev the sum of the rows' cost */
+    uint32_t R;
+    uint32_t reserved[5];
+} s5gpu_pile_total_t;
+/* 64 + 48 R: the bytes of an accumulator of R columns; 0 for R = 0 or R > 2^26 */
+size_t s5gpu_pileup_bytes(uint32_t R);
+/* Writes the empty accumulator (zeros, the 32767 / -32768 pairs, R) to acc (DEVICE memory, 16-byte aligned, s5gpu_pileup_bytes(R)).
+ * S5GPU_ERR_ARG (nothing launched): R = 0 or > 2^26, a NULL or misaligned acc.  Asynchronous on hip_stream. */
+int s5gpu_pileup_reset_dev(void *acc, uint32_t R, void *hip_stream);
+/* Adds n reads to acc, which s5gpu_pileup_reset_dev wrote for the same R, and writes nothing else; all pointers DEVICE memory.  Calls on
+ * one acc may run on several streams at once.  n = 0: S5GPU_OK, nothing launched.  S5GPU_ERR_ARG (nothing launched): qpitch = 0 or
+ * > 1024, R = 0 or > 2^26, a NULL pointer (events may be NULL) or a misaligned one (acc, events: 16 bytes; qlen, lo, hi, status: 4).
+ * Asynchronous on hip_stream.
+ * s5gpu_set_option (tests, tools): "pileup_lds_cols" (0, or a power of two 64 .. 1024; default 1024): the columns a workgroup keeps in LDS
+ * (0: every cell is a global atomic); "pileup_grid" (1 .. 1024, default 1024): the most workgroups of one launch.  Neither changes the result. */
+int s5gpu_pileup_accum_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R,
+                           const int32_t *lo, const int32_t *hi, const int32_t *status, const s5gpu_event_t *events, void *acc, void *hip_stream);
+/* The per-file handle: an accumulator of R columns on the FIRST device in use and the parameters of the chain.  ref_host[0 .. R) (HOST
+ * memory) is copied.  NULL (s5gpu_last_error says why): the S5GPU_ERR_ARG cases of s5gpu_align_batch, R > 2^26, a read's scratch above
+ * 256 MiB, no device, no memory. */
+void *s5gpu_pileup_open(const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, uint32_t wmax, const int16_t *ref_host,
+                        uint32_t R);
+/* The chain of s5gpu_align_batch on n records, then their cells added to the handle's accumulator; lo and hi never leave the device:
+ * rows_out[0 .. n) (may be NULL) and status_out[0 .. n) (may be NULL) are all that comes back.  A record that is not used counts in
+ * reads_skipped or reads_bad.  A corrupt record makes the call return S5GPU_ERR_DATA: its status is the decoder's, the other reads are
+ * accumulated and the handle stays usable. */
+int s5gpu_pileup_add_batch(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                           s5gpu_map_row_t *rows_out, int32_t *status_out);
+/* Downloads the accumulator to acc_out (HOST memory, s5gpu_pileup_bytes(R); may be NULL) and ends the handle, whatever it returns. */
+int s5gpu_pileup_close(void *handle, void *acc_out);
+
 #ifdef __cplusplus
 }
 #endif

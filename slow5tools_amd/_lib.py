@@ -104,6 +104,12 @@ class MapParams(C.Structure):
 assert C.sizeof(MapParams) == 32
 STATUS_QUERY_SHORT = 18
 STATUS_PATH_WIDE, STATUS_PATH_ROW = 19, 20
+# s5gpu_pile_col_t / s5gpu_pile_total_t: a column and the totals row of "pileup" (slow5tools_amd/pileup.py)
+PileCol = np.dtype([("depth", "<u4"), ("n_events", "<u4"), ("n_samples", "<u8"), ("sum_q", "<i8"), ("sumsq_q", "<u8"), ("sum_cost", "<u8"),
+                    ("min_q", "<i4"), ("max_q", "<i4")])
+PileTotal = np.dtype([("reads_used", "<u8"), ("reads_skipped", "<u8"), ("reads_bad", "<u8"), ("cells", "<u8"), ("cost", "<u8"), ("R", "<u4"),
+                      ("reserved", "<u4", (5,))])
+assert PileCol.itemsize == 48 and PileTotal.itemsize == 64
 
 
 class S5GpuError(RuntimeError):
@@ -219,6 +225,15 @@ def lib():
     L.s5gpu_sdtw_path_slot_bytes.restype = C.c_size_t
     L.s5gpu_sdtw_path_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, u32, vp, C.c_size_t, vp, vp, vp, vp]
     L.s5gpu_align_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), u32, vp, u32, vp, vp, vp, vp, vp]
+    # pileup: the per-reference-position table on the device, and the per-file handle
+    L.s5gpu_pileup_bytes.argtypes = [u32]
+    L.s5gpu_pileup_bytes.restype = C.c_size_t
+    L.s5gpu_pileup_reset_dev.argtypes = [vp, u32, vp]
+    L.s5gpu_pileup_accum_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+    L.s5gpu_pileup_open.restype = vp
+    L.s5gpu_pileup_open.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), u32, vp, u32]
+    L.s5gpu_pileup_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp]
+    L.s5gpu_pileup_close.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -244,4 +259,5 @@ EXPORTS = [
     "s5gpu_signal_events_dev", "s5gpu_signal_events_batch",
     "s5gpu_quantise_host", "s5gpu_event_queries_dev", "s5gpu_sdtw_dev", "s5gpu_map_batch",
     "s5gpu_sdtw_path_slot_bytes", "s5gpu_sdtw_path_dev", "s5gpu_align_batch",
+    "s5gpu_pileup_bytes", "s5gpu_pileup_reset_dev", "s5gpu_pileup_accum_dev", "s5gpu_pileup_open", "s5gpu_pileup_add_batch", "s5gpu_pileup_close",
 ]
