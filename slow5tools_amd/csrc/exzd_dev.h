@@ -228,6 +228,22 @@ __device__ __forceinline__ uint32_t svb32_decode_chunk(const uint8_t *keys, uint
     return total;
 }
 
+// What both decoders below refuse (status 7), as oracle/exzd.c (s5o_exzd_decode) refuses it:
+//  * a count the blob cannot hold.  A blob of L >= 16 bytes has 16 bytes of head and at least one byte per position (a byte of
+//    `rest`, or a data byte of each of the two lists), so N - 1 <= L - 16 — the other end of s5o_exzd_bound(n) = 24 + 2 * (ceil(n / 4)
+//    + 4 n) + n, the most a blob of n samples takes.  Checked BEFORE the capacity test: a status 6 makes the caller retry with a
+//    slot of the count reported, and a damaged count would be up to 4.29 G samples;
+//  * exception positions that do not strictly increase or reach N - 1.  Positions are sums of gap + 1 in 32 bits; every entry is
+//    compared with the one before it (exzd_gaps_increase), which catches every wrap: a sum that wraps lands below its predecessor
+//    unless one gap + 1 is 0 itself, and that one repeats its predecessor.  With that, the chunk's last position < N - 1 bounds all;
+//  * a section that is not consumed exactly: keys + data bytes read must equal its u32 length, for both lists.
+// run = position of the previous entry + 1 (0 in front of the first), g = gap + 1: the next run, and whether it moved forward
+__device__ __forceinline__ uint32_t exzd_gaps_increase(uint32_t run, uint32_t g, int &err) {
+    const uint32_t next = run + g;
+    if (next <= run) err = 1;
+    return next;
+}
+
 // blob (HBM) -> int16 samples.  Returns 0 ok, 6 output too small (*n_out = samples needed), 7 malformed.
 __device__ __forceinline__ int exzd_decode_wg(const uint8_t *blob, uint64_t L, int16_t *__restrict__ out, uint32_t cap, uint32_t *n_out,
                                               ExzdScratch &X, uint32_t *ws) {
@@ -240,6 +256,7 @@ __device__ __forceinline__ int exzd_decode_wg(const uint8_t *blob, uint64_t L, i
     if (n64 == 0) return L == 10 ? 0 : 7;
     if (n64 > 0xFFFFFFF0ull || q > 15 || L < 16) return 7;
     const uint32_t n = (uint32_t)n64, np = n - 1;
+    if ((uint64_t)np > L - 16) return 7;        // a count the blob cannot hold is malformed, never "slot too small"
     *n_out = n;
     if (n > cap) return 6;
     const uint32_t z0 = (uint32_t)blob[10] | ((uint32_t)blob[11] << 8);
@@ -249,20 +266,21 @@ __device__ __forceinline__ int exzd_decode_wg(const uint8_t *blob, uint64_t L, i
     const uint32_t nk = (nex + 3) >> 2;
     const uint8_t *pkeys = nullptr, *pdata = nullptr, *pend = nullptr, *vkeys = nullptr, *vdata = nullptr, *vend = nullptr;
     uint64_t at = 16;
+    uint32_t pdlen = 0, vdlen = 0;              // data bytes of the two lists: section length minus keys
     if (nex) {
         uint32_t sl = 0;
         if (at + 4 > L) return 7;
         for (int b = 0; b < 4; b++) sl |= (uint32_t)blob[at + b] << (8 * b);
         at += 4;
         if (sl < nk || at + sl > L) return 7;
-        pkeys = blob + at; pdata = pkeys + nk; pend = pkeys + sl;
+        pkeys = blob + at; pdata = pkeys + nk; pend = pkeys + sl; pdlen = sl - nk;
         at += sl;
         if (at + 4 > L) return 7;
         sl = 0;
         for (int b = 0; b < 4; b++) sl |= (uint32_t)blob[at + b] << (8 * b);
         at += 4;
         if (sl < nk || at + sl > L) return 7;
-        vkeys = blob + at; vdata = vkeys + nk; vend = vkeys + sl;
+        vkeys = blob + at; vdata = vkeys + nk; vend = vkeys + sl; vdlen = sl - nk;
         at += sl;
     }
     if (L - at != (uint64_t)np - nex) return 7;
@@ -289,8 +307,7 @@ __device__ __forceinline__ int exzd_decode_wg(const uint8_t *blob, uint64_t L, i
             uint32_t run = acarry + block_excl_add(s, ws, tot);
 #pragma unroll
             for (int k = 0; k < 16; k++) {
-                run += g[k];
-                if (16u * tid + k < cc) X.epos[16 * tid + k] = run - 1u;
+                if (16u * tid + k < cc) { run = exzd_gaps_increase(run, g[k], err); X.epos[16 * tid + k] = run - 1u; }
             }
             acarry += tot;
             __syncthreads();
@@ -351,7 +368,7 @@ __device__ __forceinline__ int exzd_decode_wg(const uint8_t *blob, uint64_t L, i
     __syncthreads();
     if (err) atomicOr(&X.red[0], 1u);
     __syncthreads();
-    if (X.red[0] || e0 != nex || rb != np - nex) return 7;
+    if (X.red[0] || e0 != nex || rb != np - nex || pd != pdlen || vd != vdlen) return 7;   // (e0 == nex: every chunk was read)
     return 0;
 }
 
@@ -413,6 +430,7 @@ __device__ __forceinline__ int exzd_decode_wave(const uint8_t *blob, uint64_t L,
     if (n64 == 0) return L == 10 ? 0 : 7;
     if (n64 > 0xFFFFFFF0ull || q > 15 || L < 16) return 7;
     const uint32_t n = (uint32_t)n64, np = n - 1;
+    if ((uint64_t)np > L - 16) return 7;        // a count the blob cannot hold is malformed, never "slot too small"
     n_out = n;
     if (n > cap) return 6;
     const uint32_t z0 = (uint32_t)blob[10] | ((uint32_t)blob[11] << 8);
@@ -422,20 +440,21 @@ __device__ __forceinline__ int exzd_decode_wave(const uint8_t *blob, uint64_t L,
     const uint32_t nk = (nex + 3) >> 2;
     const uint8_t *pkeys = nullptr, *pdata = nullptr, *pend = nullptr, *vkeys = nullptr, *vdata = nullptr, *vend = nullptr;
     uint64_t at = 16;
+    uint32_t pdlen = 0, vdlen = 0;              // data bytes of the two lists: section length minus keys
     if (nex) {
         uint32_t sl = 0;
         if (at + 4 > L) return 7;
         for (int b = 0; b < 4; b++) sl |= (uint32_t)blob[at + b] << (8 * b);
         at += 4;
         if (sl < nk || at + sl > L) return 7;
-        pkeys = blob + at; pdata = pkeys + nk; pend = pkeys + sl;
+        pkeys = blob + at; pdata = pkeys + nk; pend = pkeys + sl; pdlen = sl - nk;
         at += sl;
         if (at + 4 > L) return 7;
         sl = 0;
         for (int b = 0; b < 4; b++) sl |= (uint32_t)blob[at + b] << (8 * b);
         at += 4;
         if (sl < nk || at + sl > L) return 7;
-        vkeys = blob + at; vdata = vkeys + nk; vend = vkeys + sl;
+        vkeys = blob + at; vdata = vkeys + nk; vend = vkeys + sl; vdlen = sl - nk;
         at += sl;
     }
     if (L - at != (uint64_t)np - nex) return 7;
@@ -462,8 +481,7 @@ __device__ __forceinline__ int exzd_decode_wave(const uint8_t *blob, uint64_t L,
             uint32_t run = acarry + incl - sum;
 #pragma unroll
             for (int k = 0; k < 8; k++) {
-                run += g[k];
-                if (8u * lane + k < cc) X.epos[8 * lane + k] = run - 1u;
+                if (8u * lane + k < cc) { run = exzd_gaps_increase(run, g[k], err); X.epos[8 * lane + k] = run - 1u; }
             }
             acarry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             wave_sync();
@@ -547,7 +565,7 @@ __device__ __forceinline__ int exzd_decode_wave(const uint8_t *blob, uint64_t L,
         wave_sync();
     }
     if (lane == 0 && !broke) out[np] = (int16_t)((uint32_t)ycarry << q);   // the last sample (sample 0 when there is no other)
-    if (broke || __ballot(err != 0) || e0 != nex || rb != np - nex) return 7;
+    if (broke || __ballot(err != 0) || e0 != nex || rb != np - nex || pd != pdlen || vd != vdlen) return 7;   // (e0 == nex: every chunk was read)
     return 0;
 }
 

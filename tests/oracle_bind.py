@@ -333,6 +333,20 @@ def exzd_decode(blob):
     return out
 
 
+def exzd_decode_bounded(blob):
+    """s5o_exzd_decode called directly with an output buffer of len(blob) + 8 samples, whatever count the blob names: a well-formed
+    blob of L >= 16 bytes holds at most L - 15 samples, and the oracle rejects every other one before its first store (exzd_decode
+    above sizes its array from the count, gigabytes for a damaged one).  None when the oracle rejects."""
+    blob = bytes(blob)
+    b = np.frombuffer(blob + b"\x00", dtype=np.uint8)
+    out = np.empty(len(blob) + 8, dtype=np.int16)
+    n = C.c_uint64(0)
+    if lib().s5o_exzd_decode(_ptr(b), len(blob), _ptr(out), C.byref(n)) != 0:
+        return None
+    assert n.value <= len(out)
+    return out[:n.value].copy()
+
+
 # ---- §8f row 4: zstd record press ----
 # The reference calls libzstd (a dependency, not vendored).  The real library is the oracle where the image has it
 # (libzstd.so.1, no headers needed); oracle/zstd_dec.c is a restatement of the frame decoder that is pinned against it.

@@ -62,6 +62,25 @@ def test_reencode_reference_exzd_records_payload_identical(press, name):
         assert o[8:] == zlib.decompress(r)
 
 
+def _oracle_says(pay, hdr_len):
+    """the ex-zd blob cut out of a payload (head | u64 L | blob | aux) and the oracle's samples for it, None where the oracle rejects
+    (called directly with a small buffer: a damaged count would size ob.exzd_decode's array)"""
+    L = struct.unpack_from("<Q", pay, hdr_len)[0]
+    at = hdr_len + 8
+    if L > len(pay) - at:
+        return None
+    return ob.exzd_decode_bounded(pay[at:at + L])
+
+
+def _check_against_oracle(g, want, what):
+    """status 0 exactly when the oracle accepts, the samples are then the oracle's; otherwise 7"""
+    if want is None:
+        assert g["status"] == 7, (what, g["status"])
+    else:
+        assert g["status"] == 0, (what, g["status"])
+        assert np.array_equal(g["signal"], want), what
+
+
 def _signals(rng):
     out = [np.zeros(0, np.int16), np.array([7], np.int16), np.array([-32768, 32767], np.int16), np.zeros(300, np.int16)]
     for n in (2, 3, 15, 16, 17, 18, 4095, 4096, 4097, 4098, 8193, 12289, 70000):
@@ -121,10 +140,15 @@ def test_decode_rejects_malformed_exzd_blobs(press):
         else:
             b[p:p + 4] = rng.integers(0, 256, 4, dtype=np.uint8).tobytes()
         variants.append(bytes(b[:len(good)]))
-    for g in press.decode_records(variants, press.REC_NONE, press.SIG_EX_ZD, raise_on_error=False):
+    accepted = 0
+    for v, g in zip(variants, press.decode_records(variants, press.REC_NONE, press.SIG_EX_ZD, raise_on_error=False)):
         assert g["status"] in (0, 6, 7)
+        want = _oracle_says(v, len(hdr))
+        _check_against_oracle(g, want, v[at:at + 24].hex())
         if g["status"] == 0:
             assert len(g["signal"]) == len(sig)
+            accepted += 1
+    assert 0 < accepted < len(variants)                   # (a hit on a plain delta byte leaves a valid blob: both sides occur)
 
 
 def test_wave_decoder_behind_the_inflate_equals_the_workgroup_decoder(press):
@@ -172,6 +196,8 @@ def test_wave_decoder_behind_the_inflate_equals_the_workgroup_decoder(press):
             assert a["aux"] == b["aux"] and a["read_id"] == b["read_id"]
             if i < len(sigs):
                 assert np.array_equal(a["signal"], sigs[i]), i
+        if i >= len(sigs):                                # the damaged ones: the oracle referees status and samples
+            _check_against_oracle(a, _oracle_says(pays[i], len(hdr)), i)
     assert sum(1 for g in fused[len(sigs):] if g["status"] == 7) >= 8
 
 

@@ -252,7 +252,7 @@ def _batch():
 SENT = 0x5A5A
 
 
-def _dev_decode(recs, form, sig_caps, rec_method=0, pay_caps=None, np_cap=None, n_slots=3, max_in_len=0):
+def _dev_decode(recs, form, sig_caps, rec_method=0, pay_caps=None, np_cap=None, n_slots=3, max_in_len=0, sig_method=1):
     """One device call on buffers laid out here.  form "blob": s5gpu_svbzd_decode_dev (recs are blobs); "full": s5gpu_decode_dev;
     "np": s5gpu_decode_dev with S5GPU_DEC_NO_PAYLOAD, n_slots scratch slots of np_cap, filled with 0xA5 beforehand.  Every signal slot
     is followed by at least 8 sentinel samples, which must survive.  Returns (fields, signals, payload or scratch buffer)."""
@@ -270,7 +270,7 @@ def _dev_decode(recs, form, sig_caps, rec_method=0, pay_caps=None, np_cap=None, 
     d = np.zeros(n, dtype=_lib.REC_DESC)
     d["in_off"], d["in_len"], d["sig_off"], d["sig_cap"] = in_off[:-1], lens, sig_off[:-1], caps
     a = _lib.DecodeArgs()
-    a.n_recs, a.rec_method, a.sig_method = n, rec_method, 1
+    a.n_recs, a.rec_method, a.sig_method = n, rec_method, sig_method
     dev = torch.device("cuda:0")
     if form == "full":
         pc = np.asarray(pay_caps, dtype=np.int64)
