@@ -367,10 +367,8 @@ static int ascii_to_blow5_stream_any(uint32_t n, const void *chunk, size_t chunk
                                            void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !line_pos || !line_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_ascii_to_blow5_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++) {
-        if (status) status[i] = 0;
-        if (line_pos[i] > chunk_bytes || line_len[i] > chunk_bytes - line_pos[i]) { s5gpu_set_error("line %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-    }
+    if (status) memset(status, 0, sizeof(int32_t) * n);
+    if (s5rules::chunk_span("s5gpu_ascii_to_blow5_stream", "line", n, chunk_bytes, line_pos, line_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     s5host::ShareGather sg(G);
@@ -384,13 +382,9 @@ static int ascii_to_blow5_stream_any(uint32_t n, const void *chunk, size_t chunk
         s5_trace("ascii_to_blow5_stream: context acquired");
         // scalar and aux columns on the host; the raw_signal column stays where it is
         std::vector<Line> L(m);
-        uint64_t text_bytes = 0, b0 = UINT64_MAX, e1 = 0;
-        for (uint32_t i = lo; i < hi; i++) {
-            text_bytes += line_len[i];
-            b0 = b0 < line_pos[i] ? b0 : line_pos[i];
-            e1 = e1 > line_pos[i] + line_len[i] ? e1 : line_pos[i] + line_len[i];
-        }
-        b0 &= ~15ull;
+        uint64_t text_bytes = 0, b0, e1;               // (this share's part of the span: the bounds held for the whole batch)
+        (void)s5rules::chunk_span("s5gpu_ascii_to_blow5_stream", "line", m, chunk_bytes, line_pos + lo, line_len + lo, &b0, &e1);
+        for (uint32_t i = lo; i < hi; i++) text_bytes += line_len[i];
         parallel_for(m, text_bytes, [&](uint32_t a, uint32_t b) {
             for (uint32_t i = a; i < b; i++)
                 parse_line(base_p + line_pos[lo + i], line_len[lo + i], n_aux, aux_type, new_read_group ? new_read_group + lo + i : nullptr, drop_aux, L[i]);
@@ -611,10 +605,8 @@ static int blow5_to_ascii_stream_any(uint32_t n, const void *chunk, size_t chunk
                                            void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_blow5_to_ascii_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++) {
-        if (status) status[i] = 0;
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-    }
+    if (status) memset(status, 0, sizeof(int32_t) * n);
+    if (s5rules::chunk_span("s5gpu_blow5_to_ascii_stream", "record", n, chunk_bytes, rec_pos, rec_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     s5host::ShareGather sg(G);
@@ -624,12 +616,8 @@ static int blow5_to_ascii_stream_any(uint32_t n, const void *chunk, size_t chunk
         if (r) return sg.fail(r, slot);
         Ctx *c = hold.c;
         const uint32_t m = hi - lo;
-        uint64_t b0 = UINT64_MAX, e1 = 0;
-        for (uint32_t i = lo; i < hi; i++) {
-            b0 = b0 < rec_pos[i] ? b0 : rec_pos[i];
-            e1 = e1 > rec_pos[i] + rec_len[i] ? e1 : rec_pos[i] + rec_len[i];
-        }
-        b0 &= ~15ull;
+        uint64_t b0, e1;                               // (this share's part of the span: the bounds held for the whole batch)
+        (void)s5rules::chunk_span("s5gpu_blow5_to_ascii_stream", "record", m, chunk_bytes, rec_pos + lo, rec_len + lo, &b0, &e1);
         std::vector<const void *> rec(m);
         std::vector<size_t> len(m);
         for (uint32_t i = 0; i < m; i++) { rec[i] = (const uint8_t *)chunk + rec_pos[lo + i]; len[i] = rec_len[lo + i]; }
@@ -773,10 +761,8 @@ extern "C" int s5gpu_ascii_to_ascii_stream(uint32_t n, const void *chunk, size_t
                                            void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !line_pos || !line_len || !out_buf || !out_off || (n_aux && !aux_type)) { s5gpu_set_error("s5gpu_ascii_to_ascii_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++) {
-        if (status) status[i] = 0;
-        if (line_pos[i] > chunk_bytes || line_len[i] > chunk_bytes - line_pos[i]) { s5gpu_set_error("line %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-    }
+    if (status) memset(status, 0, sizeof(int32_t) * n);
+    if (s5rules::chunk_span("s5gpu_ascii_to_ascii_stream", "line", n, chunk_bytes, line_pos, line_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     s5host::ShareGather sg(G);
@@ -790,13 +776,9 @@ extern "C" int s5gpu_ascii_to_ascii_stream(uint32_t n, const void *chunk, size_t
         // 1. the scalar and aux columns on the host: parsed, then printed back into the prefix and suffix of the line
         std::vector<Line> L(m);
         std::vector<std::string> pre(m), suf(m);
-        uint64_t text_bytes = 0, b0 = UINT64_MAX, e1 = 0;
-        for (uint32_t i = lo; i < hi; i++) {
-            text_bytes += line_len[i];
-            b0 = b0 < line_pos[i] ? b0 : line_pos[i];
-            e1 = e1 > line_pos[i] + line_len[i] ? e1 : line_pos[i] + line_len[i];
-        }
-        b0 &= ~15ull;
+        uint64_t text_bytes = 0, b0, e1;               // (this share's part of the span: the bounds held for the whole batch)
+        (void)s5rules::chunk_span("s5gpu_ascii_to_ascii_stream", "line", m, chunk_bytes, line_pos + lo, line_len + lo, &b0, &e1);
+        for (uint32_t i = lo; i < hi; i++) text_bytes += line_len[i];
         const uint32_t out_aux = drop_aux ? 0 : n_aux;
         parallel_for(m, text_bytes, [&](uint32_t a, uint32_t b) {
             for (uint32_t i = a; i < b; i++) {

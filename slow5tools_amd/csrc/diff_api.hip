@@ -13,17 +13,12 @@ struct Handle {
     Buf pairs, rows;
 };
 
-bool methods_ok(int rec_method, int sig_method) {
-    return (rec_method == S5GPU_REC_NONE || rec_method == S5GPU_REC_ZLIB || rec_method == S5GPU_REC_ZSTD) &&
-           (sig_method == S5GPU_SIG_NONE || sig_method == S5GPU_SIG_SVB_ZD || sig_method == S5GPU_SIG_EX_ZD);
-}
-
 // a decoded batch whose descriptors are the decoder's own table
 dfk::Side side_of(const void *sig, const void *desc, const void *fields, const void *pay, uint32_t n) {
     const uint8_t *d = (const uint8_t *)desc;
     const uint32_t s = sizeof(s5gpu_rec_desc_t);
-    return {(const int16_t *)sig, d + offsetof(s5gpu_rec_desc_t, sig_off), d + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)fields,
-            (const uint8_t *)pay, d + offsetof(s5gpu_rec_desc_t, pay_off), d + offsetof(s5gpu_rec_desc_t, pay_cap), s, s, s, s, n};
+    const sigk::SigRecs S = s5host::sig_recs_of(sig, desc, fields, n);
+    return {S.sig, S.off, S.cap, S.fields, (const uint8_t *)pay, d + offsetof(s5gpu_rec_desc_t, pay_off), d + offsetof(s5gpu_rec_desc_t, pay_cap), s, s, s, s, n};
 }
 
 int check_side(const char *who, const char *name, const s5gpu_diff_side_t *S) {
@@ -76,22 +71,10 @@ extern "C" int s5gpu_signal_diff_dev(uint32_t n_pairs, const uint32_t *pair_a, c
 }
 
 extern "C" void *s5gpu_diff_open(void) {
-    if (s5host::n_devices() == 0) return nullptr;
-    s5host::CtxHold hold;
-    if (hold.acquire(0)) return nullptr;
-    Ctx *c = hold.c;
     Handle *h = new Handle;
-    hipError_t e = hipMalloc((void **)&h->d_acc, sizeof(s5gpu_diff_acc_t));
-    if (e != hipSuccess) {
-        s5gpu_set_error("s5gpu_diff_open: allocation of the accumulator failed: %s", hipGetErrorString(e));
-        delete h;
-        return nullptr;
-    }
-    if (dfk::launch_reset(h->d_acc, c->st) != S5GPU_OK || hipStreamSynchronize(c->st) != hipSuccess) {
-        (void)hipFree(h->d_acc);
-        delete h;
-        return nullptr;
-    }
+    h->d_acc = (s5gpu_diff_acc_t *)s5host::acc_open("s5gpu_diff_open", sizeof(s5gpu_diff_acc_t),
+                                                     [](void *acc, hipStream_t st) { return dfk::launch_reset((s5gpu_diff_acc_t *)acc, st); });
+    if (!h->d_acc) { delete h; return nullptr; }
     return h;
 }
 
@@ -101,36 +84,24 @@ extern "C" int s5gpu_diff_add_batch(void *handle, uint32_t n, const void *const 
     const char *who = "s5gpu_diff_add_batch";
     Handle *h = (Handle *)handle;
     if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
-    if (!methods_ok(rec_a_method, sig_a_method) || !methods_ok(rec_b_method, sig_b_method)) { s5gpu_set_error("%s: unsupported method", who); return S5GPU_ERR_ARG; }
+    if (!s5rules::methods_ok(rec_a_method, sig_a_method) || !s5rules::methods_ok(rec_b_method, sig_b_method)) { s5gpu_set_error("%s: unsupported method", who); return S5GPU_ERR_ARG; }
     if (n == 0) return S5GPU_OK;
     if (!rec_a || !len_a || !rec_b || !len_b) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++)
-        if ((!rec_a[i] && len_a[i]) || (!rec_b[i] && len_b[i])) { s5gpu_set_error("%s: record %u is NULL", who, i); return S5GPU_ERR_ARG; }
+    int rc;
+    if ((rc = s5rules::host_records_ok(who, n, rec_a, len_a)) || (rc = s5rules::host_records_ok(who, n, rec_b, len_b))) return rc;
     if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
     s5host::CtxHold hold;
-    int rc;
     if ((rc = hold.acquire(0))) return rc;
     Ctx *c = hold.c;
 
-    std::vector<s5gpu_rec_desc_t> rd;
-    std::vector<s5gpu_rec_fields_t> ff;
-    std::vector<const void *> r;
-    std::vector<size_t> l;
-    auto decoder = [&](const void *const *rec, const size_t *len, int rec_method, int sig_method) {
-        return [&, rec, len, rec_method, sig_method](uint32_t m, const uint32_t *idx) {
-            r.resize(m); l.resize(m);
-            for (uint32_t k = 0; k < m; k++) { r[k] = rec[idx[k]]; l[k] = len[idx[k]]; }
-            return s5host::decode_resident(c, m, r.data(), l.data(), rec_method, sig_method, rd, ff, nullptr);
-        };
-    };
-    bool corrupt = false;
-    std::vector<uint32_t> cur_a, cur_b;
-    std::vector<int32_t> st_a(n), st_b(n);
     // A: decoded in full, then moved out of the context's way
-    if ((rc = s5host::decode_dropping_corrupt(n, decoder(rec_a, len_a, rec_a_method, sig_a_method), ff, cur_a, st_a.data(), &corrupt))) return rc;
-    const uint32_t m_a = (uint32_t)cur_a.size();
+    s5host::Resident RA, RB;                                               // (one at a time: RA's arrays are copied before B is decoded)
+    if ((rc = s5host::resident_records(c, n, rec_a, len_a, rec_a_method, sig_a_method, RA))) return rc;
+    const uint32_t m_a = RA.m;
+    const std::vector<uint32_t> cur_a(RA.cur, RA.cur + m_a);               // (B's decode takes the context's host arrays over)
+    const std::vector<int32_t> st_a(RA.status, RA.status + n);
     if (m_a) {
-        const s5gpu_rec_desc_t &last = rd[m_a - 1];                        // the slots lie in record order (decode_resident)
+        const s5gpu_rec_desc_t &last = RA.rd[m_a - 1];                        // the slots lie in record order (decode_resident)
         const uint64_t so = last.sig_off + up((uint64_t)last.sig_cap + 8, 8), po = last.pay_off + up((uint64_t)last.pay_cap + 16, 16);
         if ((rc = h->sig.reserve(so * 2 + 64)) || (rc = h->pay.reserve(po + 64)) || (rc = h->desc.reserve(sizeof(s5gpu_rec_desc_t) * m_a)) ||
             (rc = h->fields.reserve(sizeof(s5gpu_rec_fields_t) * m_a)))
@@ -141,15 +112,15 @@ extern "C" int s5gpu_diff_add_batch(void *handle, uint32_t n, const void *const 
         HIP_TRY(hipMemcpyAsync(h->fields.p, c->d_fields.p, sizeof(s5gpu_rec_fields_t) * m_a, hipMemcpyDeviceToDevice, c->st));
     }
     // B: stays where the decoder left it
-    if ((rc = s5host::decode_dropping_corrupt(n, decoder(rec_b, len_b, rec_b_method, sig_b_method), ff, cur_b, st_b.data(), &corrupt))) return rc;
-    const uint32_t m_b = (uint32_t)cur_b.size();
+    if ((rc = s5host::resident_records(c, n, rec_b, len_b, rec_b_method, sig_b_method, RB))) return rc;
+    const uint32_t m_b = RB.m;
     if (status_a) memcpy(status_a, st_a.data(), sizeof(int32_t) * n);
-    if (status_b) memcpy(status_b, st_b.data(), sizeof(int32_t) * n);
+    if (status_b) memcpy(status_b, RB.status, sizeof(int32_t) * n);
 
-    // the pairs whose two records are resident; a pair with a record the loop above dropped is FAILED here, with the decoder's statuses
+    // the pairs whose two records are resident; a pair with a record the front dropped is FAILED here, with the decoder's statuses
     std::vector<uint32_t> at_a(n, 0xFFFFFFFFu), at_b(n, 0xFFFFFFFFu), sent;
     for (uint32_t k = 0; k < m_a; k++) at_a[cur_a[k]] = k;
-    for (uint32_t k = 0; k < m_b; k++) at_b[cur_b[k]] = k;
+    for (uint32_t k = 0; k < m_b; k++) at_b[RB.cur[k]] = k;
     for (uint32_t i = 0; i < n; i++)
         if (at_a[i] != 0xFFFFFFFFu && at_b[i] != 0xFFFFFFFFu) sent.push_back(i);
     const uint32_t ns = (uint32_t)sent.size();
@@ -168,30 +139,18 @@ extern "C" int s5gpu_diff_add_batch(void *handle, uint32_t n, const void *const 
     if ((rc = dfk::launch_add_failed(h->d_acc, n - ns, c->st))) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));                                  // the next holder of this context overwrites B
     if (out) {
-        for (uint32_t i = 0; i < n; i++) out[i] = failed_row(st_a[i], st_b[i]);
+        for (uint32_t i = 0; i < n; i++) out[i] = failed_row(st_a[i], RB.status[i]);
         const s5gpu_sig_diff_t *rows = (const s5gpu_sig_diff_t *)c->h_out.p;
         for (uint32_t k = 0; k < ns; k++) out[sent[k]] = rows[k];
     }
-    if (corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0; its pair is FAILED and counted in n_failed)", who); return S5GPU_ERR_DATA; }
+    if (RA.corrupt || RB.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0; its pair is FAILED and counted in n_failed)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;
 }
 
 extern "C" int s5gpu_diff_close(void *handle, s5gpu_diff_acc_t *acc_out) {
     Handle *h = (Handle *)handle;
     if (!h) return S5GPU_OK;
-    auto fetch = [&]() -> int {
-        s5host::CtxHold hold;
-        int r;
-        if ((r = hold.acquire(0))) return r;
-        Ctx *c = hold.c;
-        if ((r = c->h_out.reserve(sizeof(s5gpu_diff_acc_t) + 64))) return r;
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, h->d_acc, sizeof(s5gpu_diff_acc_t), hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-        memcpy(acc_out, c->h_out.p, sizeof(s5gpu_diff_acc_t));
-        return S5GPU_OK;
-    };
-    const int rc = h->d_acc && acc_out ? fetch() : S5GPU_OK;
-    if (h->d_acc) (void)hipFree(h->d_acc);                                 // whatever the download did: the handle ends here
+    const int rc = s5host::acc_close(h->d_acc, sizeof(s5gpu_diff_acc_t), acc_out);
     h->sig.release(); h->pay.release(); h->desc.release(); h->fields.release(); h->pairs.release(); h->rows.release();
     delete h;
     return rc;

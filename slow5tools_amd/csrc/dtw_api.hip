@@ -2,11 +2,11 @@
 // the device entry points, and s5gpu_map_batch: upload -> decode -> event passes -> queries -> sDTW -> 16 bytes per read come back
 // (and, before the fill pass, the 8 bytes of the event total: the host has to know the room the rows need).
 // Neither the decoded signals nor the events leave the device.  The chain up to the queries is map_front (dtw_host.h), which
-// s5gpu_align_batch (dtw_path_api.hip) runs too.
+// s5gpu_align_batch (dtw_path_api.hip) and s5gpu_pileup_add_batch (pileup_api.hip) run too.
 #include <math.h>
 
 #include "dtw_host.h"
-#include "event_dev.h"
+#include "event_host.h"
 
 namespace {
 
@@ -23,11 +23,6 @@ int check_params(const char *who, const s5gpu_map_params_t *p) {
     return check_quant(who, p->scale, p->clip);
 }
 
-int check_ref(const char *who, uint32_t R) {
-    if (R == 0 || R > 0x7FFFFFFFu) { s5gpu_set_error("%s: a reference of %u values (1 .. 2^31 - 1)", who, R); return S5GPU_ERR_ARG; }
-    return S5GPU_OK;
-}
-
 dtwk::QueryArgs args_of(const s5gpu_event_t *rows, const uint64_t *first, const int32_t *ev_status, const s5gpu_map_params_t *p, int16_t *queries,
                         uint32_t *qlen, int32_t *status) {
     dtwk::QueryArgs A;
@@ -38,6 +33,11 @@ dtwk::QueryArgs args_of(const s5gpu_event_t *rows, const uint64_t *first, const 
 }
 
 }  // namespace
+
+int dtwk::check_ref(const char *who, uint32_t R) {
+    if (R == 0 || R > 0x7FFFFFFFu) { s5gpu_set_error("%s: a reference of %u values (1 .. 2^31 - 1)", who, R); return S5GPU_ERR_ARG; }
+    return S5GPU_OK;
+}
 
 extern "C" int s5gpu_quantise_host(const float *m, size_t L, double scale, int32_t clip, int16_t *q) {
     DTW_NO_CONTRACT
@@ -73,7 +73,7 @@ extern "C" int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitc
     const char *who = "s5gpu_sdtw_dev";
     int rc;
     if (qpitch == 0 || qpitch > dtwk::QMAX) { s5gpu_set_error("%s: a pitch of %u values (1 .. %u)", who, qpitch, dtwk::QMAX); return S5GPU_ERR_ARG; }
-    if ((rc = check_ref(who, R))) return rc;
+    if ((rc = dtwk::check_ref(who, R))) return rc;
     if (!ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
     if (n == 0) return S5GPU_OK;
     if (!queries || !qlen || !out_rows) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
@@ -87,18 +87,10 @@ extern "C" int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitc
 int dtwk::map_front_check(const char *who, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
                           const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R, bool outputs) {
     int rc;
-    // (n = 0: the event call checks its parameters and launches nothing)
-    if ((rc = s5gpu_signal_events_dev(0, nullptr, nullptr, nullptr, nullptr, ep, S5GPU_NORM_RAW, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
-    if ((rc = check_params(who, mp)) || (rc = check_ref(who, R))) return rc;
-    if ((rec_method != S5GPU_REC_NONE && rec_method != S5GPU_REC_ZLIB && rec_method != S5GPU_REC_ZSTD) ||
-        (sig_method != S5GPU_SIG_NONE && sig_method != S5GPU_SIG_SVB_ZD && sig_method != S5GPU_SIG_EX_ZD)) {
-        s5gpu_set_error("%s: unsupported method", who);
-        return S5GPU_ERR_ARG;
-    }
+    if ((rc = evk::check_params(who, ep, S5GPU_NORM_RAW)) || (rc = check_params(who, mp)) || (rc = check_ref(who, R))) return rc;
+    if (!s5rules::methods_ok(rec_method, sig_method)) { s5gpu_set_error("%s: unsupported method", who); return S5GPU_ERR_ARG; }
     if (!ref_host || (n && (!rec || !rec_len || !outputs))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++)
-        if (!rec[i] && rec_len[i]) { s5gpu_set_error("%s: record %u is NULL", who, i); return S5GPU_ERR_ARG; }
-    return S5GPU_OK;
+    return s5rules::host_records_ok(who, n, rec, rec_len);
 }
 
 int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, const s5gpu_event_params_t *ep,
@@ -106,20 +98,8 @@ int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, i
     int rc;
     if ((rc = F.hold.acquire(0))) return rc;
     Ctx *c = F.hold.c;
-    // the decode; a batch with corrupt records is decoded again without them while others still wait for a larger slot (host_ctx.h)
-    std::vector<s5gpu_rec_desc_t> rd;
-    std::vector<s5gpu_rec_fields_t> ff;
-    std::vector<const void *> r2;
-    std::vector<size_t> l2;
-    F.status.assign(n, 0);
-    F.corrupt = false;
-    auto decode = [&](uint32_t m, const uint32_t *idx) {
-        r2.resize(m); l2.resize(m);
-        for (uint32_t k = 0; k < m; k++) { r2[k] = rec[idx[k]]; l2[k] = rec_len[idx[k]]; }
-        return s5host::decode_resident(c, m, r2.data(), l2.data(), rec_method, sig_method, rd, ff, nullptr);
-    };
-    if ((rc = s5host::decode_dropping_corrupt(n, decode, ff, F.cur, F.status.data(), &F.corrupt))) return rc;
-    const uint32_t m = F.m = (uint32_t)F.cur.size();
+    if ((rc = s5host::resident_records(c, n, rec, rec_len, rec_method, sig_method, F))) return rc;
+    const uint32_t m = F.m;
     if (m == 0) return S5GPU_OK;
     // on the device: first[m + 1] (u64), the events' counts and statuses [m], qlen[m], the queries' statuses [m], the result rows [m] ...
     const size_t o_cnt = up(8ull * (m + 1), 16), o_est = o_cnt + up(4ull * m, 16), o_ql = o_est + up(4ull * m, 16), o_qst = o_ql + up(4ull * m, 16),
@@ -129,17 +109,9 @@ int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, i
     uint64_t *d_first = (uint64_t *)dp;
     uint32_t *d_cnt = (uint32_t *)(dp + o_cnt), *d_ql = (uint32_t *)(dp + o_ql);
     int32_t *d_est = (int32_t *)(dp + o_est), *d_qst = (int32_t *)(dp + o_qst);
-    const sigk::SigRecs S = {(const int16_t *)c->d_sig2.p, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off),
-                             (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)c->d_fields.p,
-                             sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), m};
-    evk::EvArgs E;
-    E.w1 = ep->w1; E.w2 = ep->w2; E.thr1 = ep->thr1; E.thr2 = ep->thr2; E.peak_height = ep->peak_height; E.mode = S5GPU_NORM_RAW;
-    E.ev_off = nullptr; E.ev_cap = nullptr; E.rows = nullptr; E.n_events = d_cnt; E.ev_status = d_est;
-    if ((rc = evk::launch_events(S, E, c->st)) || (rc = evk::launch_scan(m, d_cnt, d_first, c->st))) return rc;
+    const sigk::SigRecs S = s5host::resident_sig_recs(c, m);
     uint64_t total = 0;                                                   // the host has to know the room the rows need
-    HIP_TRY(hipMemcpyAsync(c->h_out.p, d_first + m, 8, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(hipStreamSynchronize(c->st));
-    memcpy(&total, c->h_out.p, 8);
+    if ((rc = evk::events_count(c, S, ep, S5GPU_NORM_RAW, d_first, d_cnt, d_est, 1, &total))) return rc;
     // ... and the event rows, the query matrix and the reference
     const size_t o_q = up(16ull * total, 16), o_ref = o_q + up(2ull * m * mp->qmax, 16);
     if ((rc = c->d_stream.reserve(o_ref + 2ull * R + 64))) return rc;
@@ -147,10 +119,7 @@ int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, i
     s5gpu_event_t *d_rows = (s5gpu_event_t *)ds;
     int16_t *d_q = (int16_t *)(ds + o_q), *d_ref = (int16_t *)(ds + o_ref);
     HIP_TRY(hipMemcpyAsync(d_ref, ref_host, 2ull * R, hipMemcpyHostToDevice, c->st));
-    if (total) {
-        E.ev_off = d_first; E.ev_cap = d_cnt; E.rows = d_rows;
-        if ((rc = evk::launch_events(S, E, c->st))) return rc;
-    }
+    if (total && (rc = evk::launch_events(S, evk::args_of(ep, S5GPU_NORM_RAW, d_first, d_cnt, d_rows, d_cnt, d_est), c->st))) return rc;
     if ((rc = dtwk::launch_queries(m, args_of(d_rows, d_first, d_est, mp, d_q, d_ql, d_qst), c->st))) return rc;
     F.d_rows = d_rows; F.d_first = d_first; F.d_q = d_q; F.d_ql = d_ql; F.d_ref = d_ref;
     F.d_out = (s5gpu_map_row_t *)(dp + o_out);
@@ -168,20 +137,13 @@ extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t 
     dtwk::MapFront F;
     if ((rc = dtwk::map_front(n, rec, rec_len, rec_method, sig_method, ep, mp, ref_host, R, F))) return rc;
     Ctx *c = F.hold.c;
-    const uint32_t m = F.m;
-    const s5gpu_map_row_t empty = {dtwk::NO_COST, 0, -1, -1};
-    for (uint32_t i = 0; i < n; i++) rows_out[i] = empty;                 // what a record that was dropped keeps
-    if (m) {
-        if ((rc = dtwk::launch_sdtw(m, F.d_q, mp->qmax, F.d_ql, F.d_ref, R, mp->want_start != 0, F.d_out, c->st))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, F.d_out, 16ull * m, hipMemcpyDeviceToHost, c->st));
+    if (F.m) {
+        if ((rc = dtwk::launch_sdtw(F.m, F.d_q, mp->qmax, F.d_ql, F.d_ref, R, mp->want_start != 0, F.d_out, c->st))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, F.d_out, 16ull * F.m, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
-        const s5gpu_map_row_t *hr = (const s5gpu_map_row_t *)c->h_out.p;
-        for (uint32_t k = 0; k < m; k++) {                                // (a decoded read without a query: too few events, its row says so)
-            rows_out[F.cur[k]] = hr[k];
-            if (hr[k].qlen == 0 && F.status[F.cur[k]] == 0) F.status[F.cur[k]] = S5GPU_STATUS_QUERY_SHORT;
-        }
     }
-    if (status_out) memcpy(status_out, F.status.data(), sizeof(int32_t) * n);
+    dtwk::scatter_rows(F, n, (const s5gpu_map_row_t *)c->h_out.p, nullptr, rows_out);
+    if (status_out) memcpy(status_out, F.status, sizeof(int32_t) * n);
     if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its row is empty)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;
 }

@@ -674,9 +674,7 @@ static int decode_batch_dev(int slot, uint32_t n, const void *const *rec, const 
     std::vector<uint32_t> pcap(n), scap(n);
     for (uint32_t i = 0; i < n; i++) {
         if (rec_len[i] > 0xFFFFFF00ull) { s5gpu_set_error("record %u larger than 4 GiB", i); return S5GPU_ERR_ARG; }
-        const uint64_t g = payload_guess(rec_method, rec[i], rec_len[i]);
-        pcap[i] = (uint32_t)(g > 0xFFFFFF00ull ? 0xFFFFFF00ull : g);
-        scap[i] = pcap[i];   // >= 1 byte per sample in either signal format... refined below
+        scap[i] = pcap[i] = s5rules::first_cap(payload_guess(rec_method, rec[i], rec_len[i]));   // >= 1 byte per sample in either signal format... refined below
     }
     int overall = S5GPU_OK;
     for (int attempt = 0; attempt < 3; attempt++) {
@@ -720,7 +718,7 @@ static int decode_batch_dev(int slot, uint32_t n, const void *const *rec, const 
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = idx[k];
             const s5gpu_rec_fields_t &f = ff[k];
-            if (f.status == 5 && attempt < 2) { pcap[i] = f.payload_len ? f.payload_len : (pcap[i] < 0x10000000u ? 8 * pcap[i] + 65536 : 0xFFFFFF00u); if (scap[i] < f.payload_len) scap[i] = f.payload_len; continue; }
+            if (f.status == 5 && attempt < 2) { pcap[i] = s5rules::grown_cap(pcap[i], f.payload_len); if (scap[i] < f.payload_len) scap[i] = f.payload_len; continue; }
             if (f.status == 6 && attempt < 2) { scap[i] = f.n_samples; continue; }
             fields[i] = f;
             done[i] = 1;
@@ -827,7 +825,7 @@ extern "C" int s5gpu_solo_batch(int stage, uint32_t n, const void *const *in, co
     std::vector<uint32_t> pcap(n), scap(n);
     std::vector<uint8_t> done(n, 0);
     for (uint32_t i = 0; i < n; i++) {
-        if (infl) { const uint64_t g = payload_guess(stage == 4 ? S5GPU_REC_ZSTD : S5GPU_REC_ZLIB, in[i], in_len[i]); pcap[i] = (uint32_t)(g > 0xFFFFFF00ull ? 0xFFFFFF00ull : g); scap[i] = 0; }
+        if (infl) { pcap[i] = s5rules::first_cap(payload_guess(stage == 4 ? S5GPU_REC_ZSTD : S5GPU_REC_ZLIB, in[i], in_len[i])); scap[i] = 0; }
         else if (exzd_dec) {
             // the blob goes in as the signal of a record without id and aux (EXZD_HEAD zero bytes of head + u64 L); N sits at blob + 1
             uint64_t ns = 0;
@@ -892,7 +890,7 @@ extern "C" int s5gpu_solo_batch(int stage, uint32_t n, const void *const *in, co
         for (uint32_t k = 0; k < m; k++) {
             const uint32_t i = idx[k];
             const s5gpu_rec_fields_t &f = ff[k];
-            if (f.status == 5 && attempt < 2) { pcap[i] = f.payload_len ? f.payload_len : (pcap[i] < 0x10000000u ? 8 * pcap[i] + 65536 : 0xFFFFFF00u); continue; }
+            if (f.status == 5 && attempt < 2) { pcap[i] = s5rules::grown_cap(pcap[i], f.payload_len); continue; }
             if (f.status == 6 && attempt < 2) { scap[i] = f.n_samples; continue; }
             done[i] = 1;
             if (status) status[i] = f.status;
@@ -930,8 +928,7 @@ static int decode_resident_impl(Ctx *c, uint32_t n, const void *const *rec, cons
     std::vector<uint32_t> pcap(n), scap(n);
     for (uint32_t i = 0; i < n; i++) {
         if (rec_len[i] > 0xFFFFFF00ull / 8) { s5gpu_set_error("record %u too large", i); return S5GPU_ERR_ARG; }
-        { const uint64_t g = payload_guess(from_rec, rec[i], rec_len[i]); pcap[i] = (uint32_t)(g > 0xFFFFFF00ull ? 0xFFFFFF00ull : g); }
-        scap[i] = pcap[i];   // a sample takes at least one payload byte in either signal format
+        scap[i] = pcap[i] = s5rules::first_cap(payload_guess(from_rec, rec[i], rec_len[i]));   // a sample takes at least one payload byte in either signal format
     }
     rd.resize(n);
     ff.resize(n);
@@ -980,12 +977,8 @@ static int decode_resident_impl(Ctx *c, uint32_t n, const void *const *rec, cons
         HIP_TRY(hipMemcpyAsync(ff.data(), c->d_fields.p, sizeof(s5gpu_rec_fields_t) * n, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
         s5_trace("decode_resident: fields back");
-        bool retry = false, bad = false;
-        for (uint32_t i = 0; i < n; i++) {
-            if (ff[i].status == 5 && attempt < 2) { pcap[i] = ff[i].payload_len ? ff[i].payload_len : (pcap[i] < 0x10000000u ? 8 * pcap[i] + 65536 : 0xFFFFFF00u); if (scap[i] < pcap[i]) scap[i] = pcap[i]; retry = true; }
-            else if (ff[i].status == 6 && attempt < 2) { scap[i] = ff[i].n_samples; retry = true; }
-            else if (ff[i].status != 0) { bad = true; if (status) status[i] = ff[i].status; }
-        }
+        bool bad = false;
+        const bool retry = s5rules::grow_batch(n, ff.data(), attempt, pcap.data(), scap.data(), status, &bad);
         if (bad) { s5gpu_set_error("at least one input record is corrupt (see status[i])"); return S5GPU_ERR_DATA; }
         if (!retry) break;   // rare: a record inflated to more than 4x its size; the whole batch is decoded again with exact slots
     }
@@ -995,8 +988,141 @@ static int decode_resident_impl(Ctx *c, uint32_t n, const void *const *rec, cons
 // qts rounding of what decode_resident left in c->d_sig2: record i's samples start at d_desc2[i].sig_off, d_fields[i].n_samples of them (both
 // tables already on the device, in record order, the slots apart)
 int s5host::qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits) {
-    return s5_qts_round_strided((int16_t *)c->d_sig2.p, n, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off), sizeof(s5gpu_rec_desc_t),
-                                (const uint8_t *)c->d_fields.p + offsetof(s5gpu_rec_fields_t, n_samples), sizeof(s5gpu_rec_fields_t), bits, c->st);
+    const sigk::SigRecs S = resident_sig_recs(c, n);
+    return s5_qts_round_strided((int16_t *)c->d_sig2.p, n, S.off, S.off_stride, (const uint8_t *)S.fields + offsetof(s5gpu_rec_fields_t, n_samples),
+                                sizeof(s5gpu_rec_fields_t), bits, c->st);
+}
+
+// fields + signals only (S5GPU_DEC_NO_PAYLOAD) of the framed records already uploaded to c->d_in.  A record that outgrew its guessed scratch or
+// signal slot (status 5 / 6) has the batch decoded again with the sizes it reported, as in decode_resident_impl.
+int s5host::decode_np_framed(Ctx *c, const char *who, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len,
+                             int rec_method, int sig_method, std::vector<s5gpu_rec_fields_t> &ff) {
+    int rc;
+    std::vector<uint32_t> pcap(n), scap(n);
+    std::vector<s5gpu_rec_desc_t> rd(n);
+    uint32_t max_in = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (rec_len[i] > 0xFFFFFF00u / 8) { s5gpu_set_error("%s: record %u too large", who, i); return S5GPU_ERR_ARG; }
+        scap[i] = pcap[i] = s5rules::first_cap(payload_guess(rec_method, chunk + rec_pos[i], rec_len[i]));
+        max_in = max_in > rec_len[i] ? max_in : rec_len[i];
+    }
+    ff.resize(n);
+    if ((rc = c->d_desc2.reserve(sizeof(s5gpu_rec_desc_t) * n)) || (rc = c->d_fields.reserve(sizeof(s5gpu_rec_fields_t) * n)) ||
+        (rc = c->h_in.reserve(sizeof(s5gpu_rec_desc_t) * n + 64)) || (rc = c->h_out.reserve(sizeof(s5gpu_rec_fields_t) * n + 64)))
+        return rc;
+    for (int attempt = 0;; attempt++) {
+        uint64_t so = 0;
+        uint32_t max_cap = 64;
+        for (uint32_t i = 0; i < n; i++) {
+            s5gpu_rec_desc_t &d = rd[i];
+            memset(&d, 0, sizeof d);
+            d.in_off = rec_pos[i] - b0; d.in_len = rec_len[i];
+            d.sig_off = so; d.sig_cap = scap[i];
+            so += up((uint64_t)scap[i] + 8, 8);
+            max_cap = max_cap > pcap[i] ? max_cap : pcap[i];
+        }
+        // scratch: a slot per workgroup the decoder can use; more slots than records (and its fallback's) buy nothing
+        const uint64_t slot = ((uint64_t)max_cap + 16 + 15) & ~15ull;
+        uint64_t scratch = s5gpu_decode_scratch_bytes(max_cap);
+        const uint64_t enough = 64 + slot * ((uint64_t)n + 257), floor_ = 64 + 2 * slot, ceil_ = 1ull << 30;
+        if (scratch > enough) scratch = enough;
+        if (scratch > ceil_) scratch = ceil_;
+        if (scratch < floor_) scratch = floor_;
+        if ((rc = c->d_pay.reserve(scratch)) || (rc = c->d_sig2.reserve(so * 2 + 64))) return rc;
+        memcpy(c->h_in.p, rd.data(), sizeof(s5gpu_rec_desc_t) * n);
+        HIP_TRY(hipMemcpyAsync(c->d_desc2.p, c->h_in.p, sizeof(s5gpu_rec_desc_t) * n, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipMemsetAsync(c->d_fields.p, 0, sizeof(s5gpu_rec_fields_t) * n, c->st));
+        s5gpu_decode_args_t da;
+        memset(&da, 0, sizeof da);
+        da.n_recs = n; da.rec_method = rec_method; da.sig_method = sig_method; da.flags = S5GPU_DEC_NO_PAYLOAD;
+        da.desc = (const s5gpu_rec_desc_t *)c->d_desc2.p; da.in = (const uint8_t *)c->d_in.p;
+        da.payload = (uint8_t *)c->d_pay.p; da.payload_bytes = scratch; da.max_pay_cap = max_cap; da.max_in_len = max_in;
+        da.sig_out = (int16_t *)c->d_sig2.p; da.fields = (s5gpu_rec_fields_t *)c->d_fields.p;
+        if ((rc = s5gpu_decode_dev(&da, c->st))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_fields.p, sizeof(s5gpu_rec_fields_t) * n, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        memcpy(ff.data(), c->h_out.p, sizeof(s5gpu_rec_fields_t) * n);
+        bool bad = false;
+        const bool retry = s5rules::grow_batch(n, ff.data(), attempt, pcap.data(), scap.data(), nullptr, &bad);
+        if (bad) { s5gpu_set_error("%s: at least one record is corrupt (see its status)", who); return S5GPU_ERR_DATA; }
+        if (!retry) break;
+    }
+    return S5GPU_OK;
+}
+
+// the dropping rule around one way of decoding: what it leaves in R
+template <class Decode>
+static int resident_of(Ctx *c, uint32_t n, Decode decode, s5host::Resident &R) {
+    c->r_status.assign(n, 0);
+    R.corrupt = false;
+    const int rc = s5rules::decode_dropping_corrupt(n, decode, c->r_ff, c->r_cur, c->r_status.data(), &R.corrupt);
+    R.m = (uint32_t)c->r_cur.size();
+    R.cur = c->r_cur.data(); R.status = c->r_status.data(); R.ff = c->r_ff.data(); R.rd = c->r_rd.data();
+    return rc;
+}
+
+int s5host::resident_records(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, Resident &R) {
+    std::vector<const void *> r;
+    std::vector<size_t> l;
+    return resident_of(c, n, [&](uint32_t m, const uint32_t *idx) {
+        r.resize(m); l.resize(m);
+        for (uint32_t k = 0; k < m; k++) { r[k] = rec[idx[k]]; l[k] = rec_len[idx[k]]; }
+        return decode_resident_impl(c, m, r.data(), l.data(), rec_method, sig_method, c->r_rd, c->r_ff, nullptr, nullptr);
+    }, R);
+}
+
+int s5host::resident_chunk(Ctx *c, const char *who, uint32_t n, const void *chunk, uint64_t b0, uint64_t e1, const uint64_t *rec_pos, const uint32_t *rec_len,
+                           int rec_method, int sig_method, bool want_payload, Resident &R) {
+    const uint8_t *base = (const uint8_t *)chunk;
+    const bool np = !want_payload && s5rules::decodes_without_payload(rec_method, sig_method);
+    if (np) {                                                  // the one upload: a second decode of a part of the batch reads the same bytes
+        int rc;
+        if ((rc = c->d_in.reserve(e1 - b0 + 64))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->d_in.p, base + b0, e1 - b0, hipMemcpyHostToDevice, c->st));
+    }
+    std::vector<uint64_t> pos;
+    std::vector<uint32_t> len;
+    std::vector<const void *> r;
+    std::vector<size_t> l;
+    return resident_of(c, n, [&](uint32_t m, const uint32_t *idx) {
+        if (np) {
+            pos.resize(m); len.resize(m);
+            for (uint32_t k = 0; k < m; k++) { pos[k] = rec_pos[idx[k]]; len[k] = rec_len[idx[k]]; }
+            return decode_np_framed(c, who, m, base, b0, pos.data(), len.data(), rec_method, sig_method, c->r_ff);
+        }
+        r.resize(m); l.resize(m);
+        for (uint32_t k = 0; k < m; k++) { r[k] = base + rec_pos[idx[k]]; l[k] = rec_len[idx[k]]; }
+        const FramedSrc fs = {base + b0, (size_t)(e1 - b0)};
+        return decode_resident_impl(c, m, r.data(), l.data(), rec_method, sig_method, c->r_rd, c->r_ff, nullptr, &fs);
+    }, R);
+}
+
+void *s5host::acc_open(const char *who, size_t bytes, const std::function<int(void *, hipStream_t)> &reset) {
+    if (n_devices() == 0) return nullptr;
+    CtxHold hold;
+    if (hold.acquire(0)) return nullptr;
+    void *d_acc = nullptr;
+    const hipError_t e = hipMalloc(&d_acc, bytes);
+    if (e != hipSuccess) { s5gpu_set_error("%s: allocation of the accumulator failed: %s", who, hipGetErrorString(e)); return nullptr; }
+    if (reset(d_acc, hold.c->st) != S5GPU_OK || hipStreamSynchronize(hold.c->st) != hipSuccess) { (void)hipFree(d_acc); return nullptr; }
+    return d_acc;
+}
+
+int s5host::acc_close(void *d_acc, size_t bytes, void *out, bool direct) {
+    auto fetch = [&]() -> int {
+        CtxHold hold;
+        int r;
+        if ((r = hold.acquire(0))) return r;
+        Ctx *c = hold.c;
+        if (!direct && (r = c->h_out.reserve(bytes + 64))) return r;
+        HIP_TRY(hipMemcpyAsync(direct ? out : c->h_out.p, d_acc, bytes, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        if (!direct) memcpy(out, c->h_out.p, bytes);
+        return S5GPU_OK;
+    };
+    const int rc = d_acc && out ? fetch() : S5GPU_OK;
+    if (d_acc) (void)hipFree(d_acc);                            // whatever the download did: the handle ends here
+    return rc;
 }
 
 // ---- view / merge worker for a whole batch, device-resident between decode and encode ----
@@ -1237,8 +1363,7 @@ extern "C" int s5gpu_decode_stream(uint32_t n, const void *chunk, size_t chunk_b
                                    int sig_method, int16_t *sig_out, size_t sig_cap, uint64_t *sig_off, s5gpu_rec_fields_t *fields) {
     if (n == 0) { if (sig_off) sig_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !sig_out || !sig_off || !fields) { s5gpu_set_error("s5gpu_decode_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++)
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
+    if (s5rules::chunk_span("s5gpu_decode_stream", "record", n, chunk_bytes, rec_pos, rec_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     // a share that waits behind a failing one gives up before it has looked at its records: their statuses must not read as "ok"
@@ -1252,12 +1377,8 @@ extern "C" int s5gpu_decode_stream(uint32_t n, const void *chunk, size_t chunk_b
         s5_trace("decode_stream: context held");
         Ctx *c = hold.c;
         const uint32_t m = hi - lo;
-        uint64_t b0 = UINT64_MAX, e1 = 0;
-        for (uint32_t i = lo; i < hi; i++) {
-            b0 = b0 < rec_pos[i] ? b0 : rec_pos[i];
-            e1 = e1 > rec_pos[i] + rec_len[i] ? e1 : rec_pos[i] + rec_len[i];
-        }
-        b0 &= ~15ull;
+        uint64_t b0, e1;                               // (this share's part of the span: the bounds held for the whole batch)
+        (void)s5rules::chunk_span("s5gpu_decode_stream", "record", m, chunk_bytes, rec_pos + lo, rec_len + lo, &b0, &e1);
         std::vector<const void *> rec(m);
         std::vector<size_t> len(m);
         for (uint32_t i = 0; i < m; i++) { rec[i] = (const uint8_t *)chunk + rec_pos[lo + i]; len[i] = rec_len[lo + i]; }
@@ -1320,8 +1441,8 @@ extern "C" int s5gpu_record_ids_stream(uint32_t n, const void *chunk, size_t chu
                                        uint32_t id_pitch, char *ids, uint16_t *id_len, int32_t *status) {
     if (n == 0) return S5GPU_OK;
     if (!chunk || !rec_pos || !rec_len || !ids || !id_len || !status || id_pitch == 0 || id_pitch > 65535) { s5gpu_set_error("s5gpu_record_ids_stream: bad argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++)
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
+    int rc;
+    if ((rc = s5rules::chunk_span("s5gpu_record_ids_stream", "record", n, chunk_bytes, rec_pos, rec_len, nullptr, nullptr))) return rc;
     const uint8_t *base = (const uint8_t *)chunk;
     auto take = [&](uint32_t i, const uint8_t *head, uint32_t have) {        // head = the record's first uncompressed bytes
         status[i] = 7; id_len[i] = 0;
@@ -1339,8 +1460,7 @@ extern "C" int s5gpu_record_ids_stream(uint32_t n, const void *chunk, size_t chu
     }
     if (rec_method != S5GPU_REC_ZLIB) { s5gpu_set_error("s5gpu_record_ids_stream: zlib or uncompressed records (zstd frames take the general decode)"); return S5GPU_ERR_ARG; }
     s5host::CtxHold hold;
-    int rc = hold.acquire();
-    if (rc) return rc;
+    if ((rc = hold.acquire())) return rc;
     Ctx *c = hold.c;
     const uint32_t FRONT = 1024, hp = (uint32_t)up(2ull + id_pitch, 16);
     std::vector<uint32_t> todo(n);
@@ -1410,10 +1530,8 @@ static int recompress_stream_any(uint32_t n, const void *chunk, size_t chunk_byt
                                  size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t qts_bits) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !out_buf || !out_off) { s5gpu_set_error("s5gpu_recompress_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    for (uint32_t i = 0; i < n; i++) {
-        if (status) status[i] = 0;
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-    }
+    if (status) memset(status, 0, sizeof(int32_t) * n);
+    if (s5rules::chunk_span("s5gpu_recompress_stream", "record", n, chunk_bytes, rec_pos, rec_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     s5host::ShareGather sg(G);
@@ -1423,12 +1541,8 @@ static int recompress_stream_any(uint32_t n, const void *chunk, size_t chunk_byt
         if (r) return sg.fail(r, slot);
         Ctx *c = hold.c;
         const uint32_t m = hi - lo;
-        // the extent of this share of the chunk (the records of a share are contiguous in a file chunk)
-        const uint64_t e0 = rec_pos[lo] & ~15ull;
-        uint64_t e1 = 0;
-        for (uint32_t i = lo; i < hi; i++) e1 = e1 > rec_pos[i] + rec_len[i] ? e1 : rec_pos[i] + rec_len[i];
-        uint64_t b0 = e0;
-        for (uint32_t i = lo; i < hi; i++) b0 = b0 < rec_pos[i] ? b0 : rec_pos[i] & ~15ull;
+        uint64_t b0, e1;                               // (this share's part of the span: the bounds held for the whole batch)
+        (void)s5rules::chunk_span("s5gpu_recompress_stream", "record", m, chunk_bytes, rec_pos + lo, rec_len + lo, &b0, &e1);
         std::vector<const void *> rec(m);
         std::vector<size_t> len(m);
         for (uint32_t i = 0; i < m; i++) { rec[i] = (const uint8_t *)chunk + rec_pos[lo + i]; len[i] = rec_len[lo + i]; }

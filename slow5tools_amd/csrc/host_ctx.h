@@ -1,5 +1,5 @@
-// host_ctx.h — shared by the host-side translation units of libslow5gpu.so (host_api.hip, ascii_api.hip):
-// error macro, grow-only workspaces, the per-process context and the threaded host loop.
+// host_ctx.h — shared by every host-side translation unit of libslow5gpu.so (the *_api.hip files): error macro, grow-only workspaces, the
+// per-process context, the threaded host loop, and the resident-decode front of the analysis calls (defined in host_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "../../include/slow5gpu.h"
+#include "resident_rules.h"
+#include "signal_dev.h"
 
 extern "C" void s5gpu_set_error(const char *fmt, ...);
 extern "C" const char *s5gpu_last_error(void);
@@ -61,6 +63,11 @@ struct Ctx {
     Buf d_sig, d_hdr, d_aux, d_desc, d_slots, d_len, d_ovf, d_in, d_pay, d_fields, d_stream, d_scan, d_sig2, d_desc2, d_patch;
     Buf d_txt, d_tdesc, d_gather;   // SLOW5 ASCII path (ascii_api.hip)
     Buf h_in, h_out;   // pinned staging
+    // host side of the resident-decode front, grow-only like the rest: a call's s5host::Resident borrows them (no allocation per call)
+    std::vector<s5gpu_rec_desc_t> r_rd;
+    std::vector<s5gpu_rec_fields_t> r_ff;
+    std::vector<uint32_t> r_cur;
+    std::vector<int32_t> r_status;
     hipStream_t st = nullptr;
     hipEvent_t ev_up = nullptr;   // "this context's uploads have landed" (upload_landed, host_api.hip); made on first use
     int slot = 0;                 // the device slot this context belongs to
@@ -117,39 +124,42 @@ int qts_round_decoded(Ctx *c, uint32_t n, uint32_t bits);
 int decode_resident_framed(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int from_rec, int from_sig,
                            std::vector<s5gpu_rec_desc_t> &rd, std::vector<s5gpu_rec_fields_t> &ff, int32_t *status, const uint8_t *base, size_t bytes);
 // fields + signals only (S5GPU_DEC_NO_PAYLOAD) of framed records the caller has uploaded to c->d_in (chunk + b0 onwards): descriptors in
-// c->d_desc2, signals in c->d_sig2, fields in c->d_fields and ff; S5GPU_ERR_DATA when a record is corrupt (signal_api.hip)
-int decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
-                     int sig_method, std::vector<s5gpu_rec_fields_t> &ff);
-// The rule the per-file handles share for a batch with corrupt records.  The decoder redoes the records that outgrew their guessed slots
-// (status 5 / 6) itself, but its retry stops at the first attempt that meets a corrupt record.  The other records' results must be valid all
-// the same: while such records are left, the batch is decoded again without the corrupt ones, at most three more times.
-// decode(m, idx) decodes the records idx[0, m) of the caller's batch and leaves their fields in ff[0, m); S5GPU_ERR_DATA from it is not an error
-// here but sets *corrupt.  On return cur lists the records of the LAST decode, in order (what is resident in the context), ff holds their
-// fields, and status[i] (n entries) the last status seen of every record of the batch, the dropped ones included.
-template <class Decode>
-int decode_dropping_corrupt(uint32_t n, Decode decode, std::vector<s5gpu_rec_fields_t> &ff, std::vector<uint32_t> &cur, int32_t *status, bool *corrupt) {
-    enum { ROUNDS = 4 };
-    cur.resize(n);
-    for (uint32_t i = 0; i < n; i++) cur[i] = i;
-    for (int round = 0;; round++) {
-        const uint32_t m = (uint32_t)cur.size();
-        if (m == 0) ff.clear();
-        const int drc = m ? decode(m, cur.data()) : S5GPU_OK;
-        if (drc && drc != S5GPU_ERR_DATA) return drc;
-        *corrupt |= drc != 0;
-        bool unfinished = false, droppable = false;
-        for (uint32_t k = 0; k < m; k++) {
-            status[cur[k]] = ff[k].status;
-            unfinished |= ff[k].status == 5 || ff[k].status == 6;
-            droppable |= ff[k].status != 0 && ff[k].status != 5 && ff[k].status != 6;
-        }
-        if (!drc || !unfinished || !droppable || round + 1 == ROUNDS) return S5GPU_OK;
-        uint32_t w = 0;
-        for (uint32_t k = 0; k < m; k++)
-            if (ff[k].status == 0 || ff[k].status == 5 || ff[k].status == 6) cur[w++] = cur[k];
-        cur.resize(w);
-    }
+// c->d_desc2, signals in c->d_sig2, fields in c->d_fields and ff; S5GPU_ERR_DATA ("<who>: ...") when a record is corrupt, everything else
+// of the batch is in place
+int decode_np_framed(Ctx *c, const char *who, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len,
+                     int rec_method, int sig_method, std::vector<s5gpu_rec_fields_t> &ff);
+// The resident-decode front: what every analysis call runs between its checks and its launches.  One rule: a batch with corrupt records is
+// decoded again without them while others still wait for a larger slot (s5rules::decode_dropping_corrupt).  What is resident afterwards:
+// the m records cur[0, m) of the batch, in that order, in c->d_desc2 / c->d_sig2 / c->d_fields (and c->d_pay after a full decode); ff[k] and
+// rd[k] (full decodes only) are theirs on the host; status[i] (n entries) is the last status of every record of the batch, the dropped ones
+// included.  The arrays are the context's own (Ctx::r_*): they hold until its next decode, and no longer than the caller holds the context.
+struct Resident {
+    uint32_t m = 0;
+    const uint32_t *cur = nullptr;
+    int32_t *status = nullptr;
+    bool corrupt = false;
+    const s5gpu_rec_fields_t *ff = nullptr;
+    const s5gpu_rec_desc_t *rd = nullptr;
+};
+// ... of records anywhere in host memory, decoded in full
+int resident_records(Ctx *c, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, Resident &R);
+// ... of the records of a file chunk whose span [b0, e1) s5rules::chunk_span gave.  Without want_payload the pairs of methods that allow it
+// are decoded with S5GPU_DEC_NO_PAYLOAD: the span is uploaded once, every round reads the same bytes.
+int resident_chunk(Ctx *c, const char *who, uint32_t n, const void *chunk, uint64_t b0, uint64_t e1, const uint64_t *rec_pos, const uint32_t *rec_len,
+                   int rec_method, int sig_method, bool want_payload, Resident &R);
+// a decoder's own descriptor table (and its signals and fields) as the signal kernels take it, and that of the context's last decode
+inline sigk::SigRecs sig_recs_of(const void *sig, const void *desc, const void *fields, uint32_t n) {
+    const uint8_t *d = (const uint8_t *)desc;
+    return {(const int16_t *)sig, d + offsetof(s5gpu_rec_desc_t, sig_off), d + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)fields,
+            sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), n};
 }
+inline sigk::SigRecs resident_sig_recs(Ctx *c, uint32_t m) { return sig_recs_of(c->d_sig2.p, c->d_desc2.p, c->d_fields.p, m); }
+// A per-file accumulator on the first device in use (the handles of stats, diff and pileup).  acc_open: `bytes` allocated, reset(acc, stream)
+// queued on a context's stream and waited for; NULL (and a message) when anything fails.  acc_close: the accumulator brought to out (NULL:
+// not wanted) through the pinned staging buffer — or, direct, straight into out: a pileup table may be gigabytes — then freed, whatever
+// the download did.
+void *acc_open(const char *who, size_t bytes, const std::function<int(void *, hipStream_t)> &reset);
+int acc_close(void *d_acc, size_t bytes, void *out, bool direct = false);
 // encode descriptors already on the device -> the contiguous BLOW5 record stream in c->d_stream (what the ordered fwrite loop
 // emits); off[i] / off[n] = record offsets / total, on the host (host_api.hip)
 int encode_stream_resident(Ctx *c, uint32_t n, const std::vector<s5gpu_read_desc_t> &desc, s5gpu_encode_args_t a, uint64_t slots_bytes,

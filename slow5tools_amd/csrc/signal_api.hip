@@ -62,73 +62,6 @@ extern "C" int s5gpu_signal_windows_dev(uint32_t n, const int16_t *sig, const ui
     return sigk::launch_windows(R, A, dtype, (hipStream_t)stream);
 }
 
-// fields + signals only (S5GPU_DEC_NO_PAYLOAD) of the framed records already uploaded to c->d_in: descriptors in c->d_desc2, signals in c->d_sig2,
-// fields in c->d_fields and ff.  A record that outgrew its guessed scratch or signal slot (status 5 / 6) has the batch decoded again with the sizes
-// it reported.  Corrupt records: S5GPU_ERR_DATA, everything else of the batch is in place.
-int s5host::decode_np_framed(Ctx *c, uint32_t n, const uint8_t *chunk, uint64_t b0, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
-                             int sig_method, std::vector<s5gpu_rec_fields_t> &ff) {
-    int rc;
-    std::vector<uint32_t> pcap(n), scap(n);
-    std::vector<s5gpu_rec_desc_t> rd(n);
-    uint32_t max_in = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (rec_len[i] > 0xFFFFFF00u / 8) { s5gpu_set_error("record %u too large", i); return S5GPU_ERR_ARG; }
-        const uint64_t g = s5host::payload_guess_of(rec_method, chunk + rec_pos[i], rec_len[i]);
-        pcap[i] = (uint32_t)(g > 0xFFFFFF00ull ? 0xFFFFFF00ull : g);
-        scap[i] = pcap[i];                       // a sample takes at least one payload byte in either signal format
-        max_in = max_in > rec_len[i] ? max_in : rec_len[i];
-    }
-    ff.resize(n);
-    if ((rc = c->d_desc2.reserve(sizeof(s5gpu_rec_desc_t) * n)) || (rc = c->d_fields.reserve(sizeof(s5gpu_rec_fields_t) * n)) ||
-        (rc = c->h_in.reserve(sizeof(s5gpu_rec_desc_t) * n + 64)) || (rc = c->h_out.reserve(sizeof(s5gpu_rec_fields_t) * n + 64)))
-        return rc;
-    for (int attempt = 0;; attempt++) {
-        uint64_t so = 0;
-        uint32_t max_cap = 64;
-        for (uint32_t i = 0; i < n; i++) {
-            s5gpu_rec_desc_t &d = rd[i];
-            memset(&d, 0, sizeof d);
-            d.in_off = rec_pos[i] - b0; d.in_len = rec_len[i];
-            d.sig_off = so; d.sig_cap = scap[i];
-            so += up((uint64_t)scap[i] + 8, 8);
-            max_cap = max_cap > pcap[i] ? max_cap : pcap[i];
-        }
-        // scratch: a slot per workgroup the decoder can use; more slots than records (and its fallback's) buy nothing
-        const uint64_t slot = ((uint64_t)max_cap + 16 + 15) & ~15ull;
-        uint64_t scratch = s5gpu_decode_scratch_bytes(max_cap);
-        const uint64_t enough = 64 + slot * ((uint64_t)n + 257), floor_ = 64 + 2 * slot, ceil_ = 1ull << 30;
-        if (scratch > enough) scratch = enough;
-        if (scratch > ceil_) scratch = ceil_;
-        if (scratch < floor_) scratch = floor_;
-        if ((rc = c->d_pay.reserve(scratch)) || (rc = c->d_sig2.reserve(so * 2 + 64))) return rc;
-        memcpy(c->h_in.p, rd.data(), sizeof(s5gpu_rec_desc_t) * n);
-        HIP_TRY(hipMemcpyAsync(c->d_desc2.p, c->h_in.p, sizeof(s5gpu_rec_desc_t) * n, hipMemcpyHostToDevice, c->st));
-        HIP_TRY(hipMemsetAsync(c->d_fields.p, 0, sizeof(s5gpu_rec_fields_t) * n, c->st));
-        s5gpu_decode_args_t da;
-        memset(&da, 0, sizeof da);
-        da.n_recs = n; da.rec_method = rec_method; da.sig_method = sig_method; da.flags = S5GPU_DEC_NO_PAYLOAD;
-        da.desc = (const s5gpu_rec_desc_t *)c->d_desc2.p; da.in = (const uint8_t *)c->d_in.p;
-        da.payload = (uint8_t *)c->d_pay.p; da.payload_bytes = scratch; da.max_pay_cap = max_cap; da.max_in_len = max_in;
-        da.sig_out = (int16_t *)c->d_sig2.p; da.fields = (s5gpu_rec_fields_t *)c->d_fields.p;
-        if ((rc = s5gpu_decode_dev(&da, c->st))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_fields.p, sizeof(s5gpu_rec_fields_t) * n, hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-        memcpy(ff.data(), c->h_out.p, sizeof(s5gpu_rec_fields_t) * n);
-        bool retry = false, bad = false;
-        for (uint32_t i = 0; i < n; i++) {
-            if (ff[i].status == 5 && attempt < 2) {
-                pcap[i] = ff[i].payload_len > pcap[i] ? ff[i].payload_len : (pcap[i] < 0x10000000u ? 8 * pcap[i] + 65536 : 0xFFFFFF00u);
-                if (scap[i] < pcap[i]) scap[i] = pcap[i];
-                retry = true;
-            } else if (ff[i].status == 6 && attempt < 2) { scap[i] = ff[i].n_samples; retry = true; }
-            else if (ff[i].status != 0) bad = true;
-        }
-        if (bad) { s5gpu_set_error("s5gpu_signal_stats_stream: at least one record is corrupt (see stats_out[i].status)"); return S5GPU_ERR_DATA; }
-        if (!retry) break;
-    }
-    return S5GPU_OK;
-}
-
 extern "C" int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
                                          int sig_method, uint32_t n_q, const double *q, s5gpu_sig_stats_t *stats_out, s5gpu_rec_fields_t *fields_out) {
     const char *who = "s5gpu_signal_stats_stream";
@@ -137,31 +70,19 @@ extern "C" int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t c
     if ((rc = check_quantiles(who, n_q, q, &Q))) return rc;
     if (n == 0) return S5GPU_OK;
     if (!chunk || !rec_pos || !rec_len || !stats_out) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
-    if ((rec_method != S5GPU_REC_NONE && rec_method != S5GPU_REC_ZLIB && rec_method != S5GPU_REC_ZSTD) ||
-        (sig_method != S5GPU_SIG_NONE && sig_method != S5GPU_SIG_SVB_ZD && sig_method != S5GPU_SIG_EX_ZD)) {
-        s5gpu_set_error("%s: unsupported method", who);
-        return S5GPU_ERR_ARG;
-    }
-    uint64_t b0 = UINT64_MAX, e1 = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-        b0 = b0 < rec_pos[i] ? b0 : rec_pos[i];
-        e1 = e1 > rec_pos[i] + rec_len[i] ? e1 : rec_pos[i] + rec_len[i];
-    }
-    b0 &= ~15ull;
+    if (!s5rules::methods_ok(rec_method, sig_method)) { s5gpu_set_error("%s: unsupported method", who); return S5GPU_ERR_ARG; }
+    uint64_t b0, e1;
+    if ((rc = s5rules::chunk_span(who, "record", n, chunk_bytes, rec_pos, rec_len, &b0, &e1))) return rc;
     if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
     s5host::CtxHold hold;
     if ((rc = hold.acquire(0))) return rc;
     Ctx *c = hold.c;
     std::vector<s5gpu_rec_fields_t> ff;
-    // the decoders that keep no payload: zlib / zstd + svb-zd and zlib + ex-zd; every other pair of methods is decoded in full
-    const bool np = (sig_method == S5GPU_SIG_SVB_ZD && (rec_method == S5GPU_REC_ZLIB || rec_method == S5GPU_REC_ZSTD)) ||
-                    (sig_method == S5GPU_SIG_EX_ZD && rec_method == S5GPU_REC_ZLIB);
     int drc;
-    if (np) {
+    if (s5rules::decodes_without_payload(rec_method, sig_method)) {
         if ((rc = c->d_in.reserve(e1 - b0 + 64))) return rc;
         HIP_TRY(hipMemcpyAsync(c->d_in.p, (const uint8_t *)chunk + b0, e1 - b0, hipMemcpyHostToDevice, c->st));
-        drc = s5host::decode_np_framed(c, n, (const uint8_t *)chunk, b0, rec_pos, rec_len, rec_method, sig_method, ff);
+        drc = s5host::decode_np_framed(c, who, n, (const uint8_t *)chunk, b0, rec_pos, rec_len, rec_method, sig_method, ff);
     } else {
         std::vector<const void *> rec(n);
         std::vector<size_t> len(n);
@@ -170,17 +91,13 @@ extern "C" int s5gpu_signal_stats_stream(uint32_t n, const void *chunk, size_t c
         drc = s5host::decode_resident_framed(c, n, rec.data(), len.data(), rec_method, sig_method, rd, ff, nullptr, (const uint8_t *)chunk + b0, (size_t)(e1 - b0));
     }
     if (drc && drc != S5GPU_ERR_DATA) return drc;
-    const std::string data_msg = drc ? s5gpu_last_error() : "";
     // the statistics of what the decode left on the device: a failed record has n_eff = 0, so the kernel reads nothing of it
     if ((rc = c->d_patch.reserve(sizeof(s5gpu_sig_stats_t) * n)) || (rc = c->h_out.reserve(sizeof(s5gpu_sig_stats_t) * (size_t)n + 64))) return rc;
-    const sigk::SigRecs R = {(const int16_t *)c->d_sig2.p, (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_off),
-                             (const uint8_t *)c->d_desc2.p + offsetof(s5gpu_rec_desc_t, sig_cap), (const s5gpu_rec_fields_t *)c->d_fields.p,
-                             sizeof(s5gpu_rec_desc_t), sizeof(s5gpu_rec_desc_t), n};
-    if ((rc = sigk::launch_stats(R, Q, (s5gpu_sig_stats_t *)c->d_patch.p, c->st))) return rc;
+    if ((rc = sigk::launch_stats(s5host::resident_sig_recs(c, n), Q, (s5gpu_sig_stats_t *)c->d_patch.p, c->st))) return rc;
     HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_patch.p, sizeof(s5gpu_sig_stats_t) * n, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(hipStreamSynchronize(c->st));
     memcpy(stats_out, c->h_out.p, sizeof(s5gpu_sig_stats_t) * n);
     if (fields_out) memcpy(fields_out, ff.data(), sizeof(s5gpu_rec_fields_t) * n);
-    if (drc) { s5gpu_set_error("%s", data_msg.c_str()); return drc; }
-    return S5GPU_OK;
+    if (drc) s5gpu_set_error("%s: at least one record is corrupt (see stats_out[i].status)", who);
+    return drc;
 }

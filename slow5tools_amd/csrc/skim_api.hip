@@ -128,7 +128,7 @@ extern "C" int s5gpu_skim_layout_parse(const char *header, size_t len, s5gpu_ski
 }
 
 // One device's share of a chunk: records [lo, hi).  Returns the share's lines through sg (ShareGather) into out_buf.
-static int skim_share(int slot, uint32_t lo, uint32_t hi, const void *chunk, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
+static int skim_share(int slot, uint32_t lo, uint32_t hi, const void *chunk, size_t chunk_bytes, const uint64_t *rec_pos, const uint32_t *rec_len, int rec_method,
                       int sig_method, const s5gpu_skim_layout_t *layout, void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status, uint32_t n,
                       s5host::ShareGather &sg) {
     s5host::CtxHold hold;
@@ -141,12 +141,8 @@ static int skim_share(int slot, uint32_t lo, uint32_t hi, const void *chunk, con
         s5gpu_set_error("%s failed: %s", what, hipGetErrorString(e));
         return sg.fail(S5GPU_ERR_HIP, slot);
     };
-    uint64_t b0 = UINT64_MAX, e1 = 0;
-    for (uint32_t i = lo; i < hi; i++) {
-        b0 = b0 < rec_pos[i] ? b0 : rec_pos[i];
-        e1 = e1 > rec_pos[i] + rec_len[i] ? e1 : rec_pos[i] + rec_len[i];
-    }
-    b0 &= ~15ull;
+    uint64_t b0, e1;                                   // (this share's part of the span: the bounds held for the whole batch)
+    (void)s5rules::chunk_span("s5gpu_skim_stream", "record", m, chunk_bytes, rec_pos + lo, rec_len + lo, &b0, &e1);
     const uint8_t *base = (const uint8_t *)chunk + b0;
     const bool packed = rec_method != S5GPU_REC_NONE;
     // device table: layout | len (u32 m) | status (i32 m) | off (u64 m + 1) | scan scratch
@@ -166,7 +162,7 @@ static int skim_share(int slot, uint32_t lo, uint32_t hi, const void *chunk, con
     std::vector<uint32_t> pcap(m);
     for (uint32_t i = 0; i < m; i++) {
         const uint64_t g = packed ? s5host::payload_guess_of(rec_method, (const uint8_t *)chunk + rec_pos[lo + i], rec_len[lo + i]) : 0;
-        pcap[i] = (uint32_t)(g > 0xFFFFFF00ull ? 0xFFFFFF00ull : g);
+        pcap[i] = s5rules::first_cap(g);
     }
     skim::SkimArgs sa;
     memset(&sa, 0, sizeof sa);
@@ -213,7 +209,7 @@ static int skim_share(int slot, uint32_t lo, uint32_t hi, const void *chunk, con
             if (hs[i] == 5 && packed && attempt < 2) {   // a record inflated to more than its guessed slot: redo with the size it needs
                 s5gpu_rec_fields_t f;
                 if ((r = hip(hipMemcpy(&f, (const s5gpu_rec_fields_t *)c->d_fields.p + i, sizeof f, hipMemcpyDeviceToHost), "download"))) return r;
-                pcap[i] = f.payload_len > pcap[i] ? f.payload_len : (pcap[i] < 0x10000000u ? 8 * pcap[i] + 65536 : 0xFFFFFF00u);
+                pcap[i] = s5rules::grown_cap(pcap[i], f.payload_len);
                 retry = true;
             } else if (hs[i] > 0) {
                 bad = true;
@@ -286,11 +282,7 @@ extern "C" int s5gpu_skim_stream(uint32_t n, const void *chunk, size_t chunk_byt
                                  int sig_method, const s5gpu_skim_layout_t *layout, void *out_buf, size_t out_cap, uint64_t *out_off, int32_t *status) {
     if (n == 0) { if (out_off) out_off[0] = 0; return S5GPU_OK; }
     if (!chunk || !rec_pos || !rec_len || !layout || !out_buf || !out_off) { s5gpu_set_error("s5gpu_skim_stream: NULL argument"); return S5GPU_ERR_ARG; }
-    if ((rec_method != S5GPU_REC_NONE && rec_method != S5GPU_REC_ZLIB && rec_method != S5GPU_REC_ZSTD) ||
-        (sig_method != S5GPU_SIG_NONE && sig_method != S5GPU_SIG_SVB_ZD && sig_method != S5GPU_SIG_EX_ZD)) {
-        s5gpu_set_error("s5gpu_skim_stream: unsupported method");
-        return S5GPU_ERR_ARG;
-    }
+    if (!s5rules::methods_ok(rec_method, sig_method)) { s5gpu_set_error("s5gpu_skim_stream: unsupported method"); return S5GPU_ERR_ARG; }
     if (layout->n_aux > S5GPU_SKIM_MAX_AUX) { s5gpu_set_error("s5gpu_skim_stream: layout with %u aux fields", layout->n_aux); return S5GPU_ERR_ARG; }
     for (uint32_t a = 0; a < layout->n_aux; a++)
         if (layout->role[a] == S5GPU_SKIM_ENUM && (uint32_t)layout->label_first[a] + layout->n_labels[a] > S5GPU_SKIM_MAX_LABELS) {
@@ -306,15 +298,13 @@ extern "C" int s5gpu_skim_stream(uint32_t n, const void *chunk, size_t chunk_byt
                 return S5GPU_ERR_ARG;
             }
     }
-    for (uint32_t i = 0; i < n; i++) {
-        if (status) status[i] = 0;
-        if (rec_pos[i] > chunk_bytes || rec_len[i] > chunk_bytes - rec_pos[i]) { s5gpu_set_error("record %u lies outside the chunk", i); return S5GPU_ERR_ARG; }
-    }
+    if (status) memset(status, 0, sizeof(int32_t) * n);
+    if (s5rules::chunk_span("s5gpu_skim_stream", "record", n, chunk_bytes, rec_pos, rec_len, nullptr, nullptr)) return S5GPU_ERR_ARG;
     const int G = s5host::n_devices();
     if (G == 0) return S5GPU_ERR_NODEV;
     s5host::ShareGather sg(G);
     const int rc = s5host::for_each_device_range(n, [&](int slot, uint32_t lo, uint32_t hi) -> int {
-        const int r = skim_share(slot, lo, hi, chunk, rec_pos, rec_len, rec_method, sig_method, layout, out_buf, out_cap, out_off, status, n, sg);
+        const int r = skim_share(slot, lo, hi, chunk, chunk_bytes, rec_pos, rec_len, rec_method, sig_method, layout, out_buf, out_cap, out_off, status, n, sg);
         if (r) sg.fail(r, slot);
         return r;
     });
