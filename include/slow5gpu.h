@@ -757,6 +757,78 @@ int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t *rec_len, i
                     const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const int16_t *ref_host, uint32_t R,
                     s5gpu_map_row_t *rows_out, int32_t *status_out);
 
+/* ---- map, the second-best hit and a mapping quality (docs/codecs.md §4.19) ----
+ * L[j] = D[qlen-1][j], (cost, end) as above.  Column j lies in block j >> bshift, bshift in 6 .. 30.  cost2 = the minimum of L[j] over the columns
+ * whose block differs from end's block by at least 2 (the best hit's block and both neighbours are excluded: the same hit shifted by a few
+ * columns is no runner-up), end2 the smallest such j; no such column: 0xFFFFFFFF and -1.  mapq = 0 when cost2 is 0xFFFFFFFF or 0, else
+ * (60 (cost2 - cost)) / cost2 in integer division, 0 .. 60: a separation ratio, not a calibrated probability. */
+typedef struct s5gpu_map_second {  /* 16 bytes, little-endian */
+    uint32_t cost2;            /* 0xFFFFFFFF: no runner-up (or no query)                        */
+    int32_t end2;              /* last reference index of the runner-up (inclusive); -1: none   */
+    uint32_t mapq;             /* 0 .. 60                                                       */
+    uint32_t zero;
+} s5gpu_map_second_t;
+/* s5gpu_sdtw_dev, and out_second[i] (16-byte aligned) beside out_rows[i], which is bit for bit what s5gpu_sdtw_dev writes; qlen[i] = 0:
+ * 0xFFFFFFFF, -1, 0, 0.  One pass over the reference.  S5GPU_ERR_ARG (nothing launched): the cases of s5gpu_sdtw_dev, bshift outside 6 .. 30,
+ * a NULL or misaligned out_second. */
+int s5gpu_sdtw2_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, int want_start,
+                    uint32_t bshift, s5gpu_map_row_t *out_rows, s5gpu_map_second_t *out_second, void *hip_stream);
+/* s5gpu_map_batch with the second-best hit: one download of 32 n bytes; second_out[i] of a read without a query or of a dropped record is
+ * 0xFFFFFFFF, -1, 0, 0.  S5GPU_ERR_ARG before anything is launched: the cases of s5gpu_map_batch, bshift outside 6 .. 30, a NULL second_out. */
+int s5gpu_map2_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                     const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const int16_t *ref_host, uint32_t R,
+                     uint32_t bshift, s5gpu_map_row_t *rows_out, s5gpu_map_second_t *second_out, int32_t *status_out);
+
+/* ---- a reference squiggle from sequences and a k-mer model, on the host (docs/codecs.md §4.19; no device is needed) ----
+ * Model: 4^k float levels, k in 1 .. 10, indexed by the k-mer's rank in base 4 (A, C, G, T = 0 .. 3, the first base most significant).  A contig
+ * of L >= k bases has Lk = L - k + 1 levels, lev[p] = the level of seq[p .. p + k); a k-mer that holds any other letter takes the table's mean
+ * (the double sum in rank order, divided, rounded to float).  Bases are read without case, U as T.  Segments, in this order per contig:
+ * the forward levels, then (strands = 2) the levels of the reverse complement, whose column p' is forward k-mer start Lk - 1 - p'; rna != 0: one
+ * segment, the forward levels in reversed order (strands is not read).  A contig shorter than k has no segment.  All segments' levels are
+ * quantised together (s5gpu_quantise_host(scale, clip)); between consecutive segments stand W = (2048 clip) / (32768 - clip) + 1 columns of
+ * -32768, which no best path of a query within +-clip of at most 1024 rows touches, so a hit's start and end lie in one segment. */
+typedef struct s5gpu_refseq_segment {
+    uint32_t contig;           /* index of the contig                                           */
+    int32_t strand;            /* '+' or '-'                                                    */
+    uint32_t offset;           /* the segment's first column in the reference                   */
+    uint32_t Lk;               /* its columns                                                   */
+    int32_t reversed;          /* != 0: column p' is forward k-mer start Lk - 1 - p'            */
+    uint32_t zero;
+    const char *name;          /* the contig's name (the handle's: valid until it is closed)    */
+} s5gpu_refseq_segment_t;
+typedef struct s5gpu_refseq_loc {  /* 16 bytes */
+    uint32_t contig;           /* 0xFFFFFFFF: a wall column                                     */
+    int32_t strand;            /* '+' or '-'; 0: a wall column                                  */
+    uint32_t pos;              /* 0-based start of the column's k-mer on the forward strand     */
+    uint32_t segment;          /* the segment; for a wall column the one in front of it         */
+} s5gpu_refseq_loc_t;
+#define S5GPU_REFSEQ_WALL 1      /* s5gpu_refseq_locate: the column is a wall column */
+/* The levels of a model file -> *levels_out (4^k floats, to be freed with s5gpu_kmer_model_free) and *k_out.  One line per k-mer: the k-mer
+ * (ACGT), a tab or spaces, level_mean in strtod syntax; further columns are ignored; empty lines and lines that start with '#' or "kmer" are
+ * skipped.  S5GPU_ERR_ARG: the file cannot be read; S5GPU_ERR_DATA: a line that is neither, k-mers of different lengths or of k outside
+ * 1 .. 10, a k-mer twice, or not every one of the 4^k there. */
+int s5gpu_kmer_model_load(const char *path, float **levels_out, uint32_t *k_out);
+void s5gpu_kmer_model_free(float *levels);
+/* A reference from n_contigs sequences in memory (seqs[i]: lens[i] bytes, no terminator needed; names[i]: a C string).  NULL
+ * (s5gpu_last_error says why): a NULL argument, k outside 1 .. 10, strands not 1 or 2, the cases of s5gpu_quantise_host, W > 64, no contig
+ * of k or more bases, more than 2^31 - 1 columns. */
+void *s5gpu_refseq_build(uint32_t n_contigs, const char *const *names, const char *const *seqs, const size_t *lens, const float *model_levels,
+                         uint32_t k, int strands, int rna, double scale, int32_t clip);
+/* ... from a FASTA file (>name up to the first white space; the sequence may span lines) and a model file.  NULL also for an unreadable
+ * file, a FASTA without a '>' line or with sequence in front of the first, and the cases of s5gpu_kmer_model_load. */
+void *s5gpu_refseq_open(const char *fasta_path, const char *model_path, int strands, int rna, double scale, int32_t clip);
+const int16_t *s5gpu_refseq_ref(const void *h, uint32_t *R_out);            /* the quantised reference with its walls; the handle's */
+uint32_t s5gpu_refseq_n_segments(const void *h);
+int s5gpu_refseq_segment(const void *h, uint32_t i, s5gpu_refseq_segment_t *info);     /* S5GPU_ERR_ARG: i is no segment */
+uint32_t s5gpu_refseq_n_contigs(const void *h);
+/* contig i as it was given: its name, its bases and its levels (0: shorter than k, no segment); any output may be NULL */
+int s5gpu_refseq_contig(const void *h, uint32_t i, const char **name_out, uint64_t *len_out, uint32_t *Lk_out);
+/* k, the wall width W and the clip the reference was built with (a map call has to use the same clip: the wall argument needs it) */
+int s5gpu_refseq_params(const void *h, uint32_t *k_out, uint32_t *W_out, int32_t *clip_out);
+/* reference column -> contig, strand, forward k-mer start: S5GPU_OK; S5GPU_REFSEQ_WALL for a wall column; S5GPU_ERR_ARG: col >= R */
+int s5gpu_refseq_locate(const void *h, uint32_t col, s5gpu_refseq_loc_t *loc);
+void s5gpu_refseq_close(void *h);
+
 /* ---- align: the whole path of a read's sDTW alignment, event to reference (docs/codecs.md §4.17) ----
  * The path of a read starts at (qlen - 1, end) and follows the chosen predecessor (the rule of map) to row 0, where it arrives at (0, start).
  * It is monotone, so two values per query row i describe it: lo[i] <= hi[i], the first and last reference column that event i is aligned

@@ -104,6 +104,21 @@ class MapParams(C.Structure):
 assert C.sizeof(MapParams) == 32
 STATUS_QUERY_SHORT = 18
 STATUS_PATH_WIDE, STATUS_PATH_ROW = 19, 20
+
+
+class RefSeqSegment(C.Structure):
+    """s5gpu_refseq_segment_t"""
+    _fields_ = [("contig", C.c_uint32), ("strand", C.c_int32), ("offset", C.c_uint32), ("Lk", C.c_uint32), ("reversed", C.c_int32), ("zero", C.c_uint32),
+                ("name", C.c_char_p)]
+
+
+class RefSeqLoc(C.Structure):
+    """s5gpu_refseq_loc_t"""
+    _fields_ = [("contig", C.c_uint32), ("strand", C.c_int32), ("pos", C.c_uint32), ("segment", C.c_uint32)]
+
+
+assert C.sizeof(RefSeqSegment) == 32 and C.sizeof(RefSeqLoc) == 16
+REFSEQ_WALL = 1
 # s5gpu_pile_col_t / s5gpu_pile_total_t: a column and the totals row of "pileup" (slow5tools_amd/pileup.py)
 PileCol = np.dtype([("depth", "<u4"), ("n_events", "<u4"), ("n_samples", "<u8"), ("sum_q", "<i8"), ("sumsq_q", "<u8"), ("sum_cost", "<u8"),
                     ("min_q", "<i4"), ("max_q", "<i4")])
@@ -220,6 +235,28 @@ def lib():
     L.s5gpu_event_queries_dev.argtypes = [u32, vp, vp, vp, C.POINTER(MapParams), vp, vp, vp, vp]
     L.s5gpu_sdtw_dev.argtypes = [u32, vp, u32, vp, vp, u32, i32, vp, vp]
     L.s5gpu_map_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), vp, u32, vp, vp]
+    # map with the second-best hit, and a reference from sequences and a k-mer model (host only)
+    L.s5gpu_sdtw2_dev.argtypes = [u32, vp, u32, vp, vp, u32, i32, u32, vp, vp, vp]
+    L.s5gpu_map2_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), vp, u32, u32, vp, vp, vp]
+    L.s5gpu_kmer_model_load.argtypes = [C.c_char_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(u32)]
+    L.s5gpu_kmer_model_free.argtypes = [C.POINTER(C.c_float)]
+    L.s5gpu_kmer_model_free.restype = None
+    L.s5gpu_refseq_build.restype = vp
+    L.s5gpu_refseq_build.argtypes = [u32, vp, vp, vp, vp, u32, i32, i32, C.c_double, i32]
+    L.s5gpu_refseq_open.restype = vp
+    L.s5gpu_refseq_open.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.c_double, i32]
+    L.s5gpu_refseq_ref.restype = vp
+    L.s5gpu_refseq_ref.argtypes = [vp, C.POINTER(u32)]
+    L.s5gpu_refseq_n_segments.restype = u32
+    L.s5gpu_refseq_n_segments.argtypes = [vp]
+    L.s5gpu_refseq_n_contigs.restype = u32
+    L.s5gpu_refseq_n_contigs.argtypes = [vp]
+    L.s5gpu_refseq_segment.argtypes = [vp, u32, C.POINTER(RefSeqSegment)]
+    L.s5gpu_refseq_contig.argtypes = [vp, u32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(u32)]
+    L.s5gpu_refseq_params.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]
+    L.s5gpu_refseq_locate.argtypes = [vp, u32, C.POINTER(RefSeqLoc)]
+    L.s5gpu_refseq_close.argtypes = [vp]
+    L.s5gpu_refseq_close.restype = None
     # align: the scratch a read's path needs, the paths of mapped queries on the device, and records anywhere in host memory
     L.s5gpu_sdtw_path_slot_bytes.argtypes = [u32, u32]
     L.s5gpu_sdtw_path_slot_bytes.restype = C.c_size_t
@@ -258,6 +295,9 @@ EXPORTS = [
     "s5gpu_diff_acc_bytes", "s5gpu_diff_acc_reset_dev", "s5gpu_signal_diff_dev", "s5gpu_diff_open", "s5gpu_diff_add_batch", "s5gpu_diff_close",
     "s5gpu_signal_events_dev", "s5gpu_signal_events_batch",
     "s5gpu_quantise_host", "s5gpu_event_queries_dev", "s5gpu_sdtw_dev", "s5gpu_map_batch",
+    "s5gpu_sdtw2_dev", "s5gpu_map2_batch", "s5gpu_kmer_model_load", "s5gpu_kmer_model_free", "s5gpu_refseq_build", "s5gpu_refseq_open", "s5gpu_refseq_ref",
+    "s5gpu_refseq_n_segments", "s5gpu_refseq_segment", "s5gpu_refseq_n_contigs", "s5gpu_refseq_contig", "s5gpu_refseq_params", "s5gpu_refseq_locate",
+    "s5gpu_refseq_close",
     "s5gpu_sdtw_path_slot_bytes", "s5gpu_sdtw_path_dev", "s5gpu_align_batch",
     "s5gpu_pileup_bytes", "s5gpu_pileup_reset_dev", "s5gpu_pileup_accum_dev", "s5gpu_pileup_open", "s5gpu_pileup_add_batch", "s5gpu_pileup_close",
 ]

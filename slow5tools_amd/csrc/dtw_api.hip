@@ -1,6 +1,7 @@
 // dtw_api.hip — host side of the map calls (include/slow5gpu.h, "map"): the quantiser on the host, argument checks and the launches of
 // the device entry points, and s5gpu_map_batch: upload -> decode -> event passes -> queries -> sDTW -> 16 bytes per read come back
 // (and, before the fill pass, the 8 bytes of the event total: the host has to know the room the rows need).
+// s5gpu_sdtw2_dev and s5gpu_map2_batch are the same with the second-best hit beside each row (k_sdtw2, docs/codecs.md §4.19).
 // Neither the decoded signals nor the events leave the device.  The chain up to the queries is map_front (dtw_host.h), which
 // s5gpu_align_batch (dtw_path_api.hip) and s5gpu_pileup_add_batch (pileup_api.hip) run too.
 #include <math.h>
@@ -84,6 +85,28 @@ extern "C" int s5gpu_sdtw_dev(uint32_t n, const int16_t *queries, uint32_t qpitc
     return dtwk::launch_sdtw(n, queries, qpitch, qlen, ref, R, want_start != 0, out_rows, (hipStream_t)stream);
 }
 
+static int check_bshift(const char *who, uint32_t bshift) {
+    if (bshift < 6 || bshift > 30) { s5gpu_set_error("%s: a block shift of %u (6 .. 30)", who, bshift); return S5GPU_ERR_ARG; }
+    return S5GPU_OK;
+}
+
+extern "C" int s5gpu_sdtw2_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, int want_start,
+                               uint32_t bshift, s5gpu_map_row_t *out_rows, s5gpu_map_second_t *out_second, void *stream) {
+    const char *who = "s5gpu_sdtw2_dev";
+    int rc;
+    if (qpitch == 0 || qpitch > dtwk::QMAX) { s5gpu_set_error("%s: a pitch of %u values (1 .. %u)", who, qpitch, dtwk::QMAX); return S5GPU_ERR_ARG; }
+    if ((rc = dtwk::check_ref(who, R)) || (rc = check_bshift(who, bshift))) return rc;
+    if (!ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
+    if (!out_second || ((uintptr_t)out_second & 15u)) { s5gpu_set_error("%s: out_second is NULL or not 16-byte aligned", who); return S5GPU_ERR_ARG; }
+    if (n == 0) return S5GPU_OK;
+    if (!queries || !qlen || !out_rows) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    if (((uintptr_t)queries & 1u) || ((uintptr_t)qlen & 3u) || ((uintptr_t)ref & 1u) || ((uintptr_t)out_rows & 15u)) {
+        s5gpu_set_error("%s: misaligned argument (out_rows: 16 bytes)", who);
+        return S5GPU_ERR_ARG;
+    }
+    return dtwk::launch_sdtw2(n, queries, qpitch, qlen, ref, R, want_start != 0, bshift, out_rows, out_second, (hipStream_t)stream);
+}
+
 int dtwk::map_front_check(const char *who, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
                           const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R, bool outputs) {
     int rc;
@@ -145,5 +168,41 @@ extern "C" int s5gpu_map_batch(uint32_t n, const void *const *rec, const size_t 
     dtwk::scatter_rows(F, n, (const s5gpu_map_row_t *)c->h_out.p, nullptr, rows_out);
     if (status_out) memcpy(status_out, F.status, sizeof(int32_t) * n);
     if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its row is empty)", who); return S5GPU_ERR_DATA; }
+    return S5GPU_OK;
+}
+
+// s5gpu_map_batch through k_sdtw2: the second rows of the m decoded reads are made in c->d_gather (the front leaves it alone) and come back
+// behind the rows, in one download
+extern "C" int s5gpu_map2_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                                const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const int16_t *ref_host, uint32_t R, uint32_t bshift,
+                                s5gpu_map_row_t *rows_out, s5gpu_map_second_t *second_out, int32_t *status_out) {
+    const char *who = "s5gpu_map2_batch";
+    const s5gpu_map_second_t none = {dtwk::NO_COST, -1, 0, 0};
+    int rc;
+    if ((rc = dtwk::map_front_check(who, n, rec, rec_len, rec_method, sig_method, ep, mp, ref_host, R, rows_out != nullptr && second_out != nullptr)) ||
+        (rc = check_bshift(who, bshift)))
+        return rc;
+    if (n == 0) return S5GPU_OK;
+    if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
+    dtwk::MapFront F;
+    if ((rc = dtwk::map_front(n, rec, rec_len, rec_method, sig_method, ep, mp, ref_host, R, F))) return rc;
+    Ctx *c = F.hold.c;
+    const uint32_t m = F.m;
+    const s5gpu_map_second_t *h2 = nullptr;
+    if (m) {
+        const size_t o2 = up(16ull * m, 16);
+        if ((rc = c->d_gather.reserve(32ull * m + 64)) || (rc = c->h_out.reserve(o2 + 16ull * m + 64))) return rc;
+        s5gpu_map_row_t *d_rows = (s5gpu_map_row_t *)c->d_gather.p;
+        s5gpu_map_second_t *d_second = (s5gpu_map_second_t *)((uint8_t *)c->d_gather.p + o2);
+        if ((rc = dtwk::launch_sdtw2(m, F.d_q, mp->qmax, F.d_ql, F.d_ref, R, mp->want_start != 0, bshift, d_rows, d_second, c->st))) return rc;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, c->d_gather.p, o2 + 16ull * m, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        h2 = (const s5gpu_map_second_t *)((const uint8_t *)c->h_out.p + o2);
+    }
+    dtwk::scatter_rows(F, n, (const s5gpu_map_row_t *)c->h_out.p, nullptr, rows_out);
+    for (uint32_t i = 0; i < n; i++) second_out[i] = none;
+    for (uint32_t k = 0; k < m; k++) second_out[F.cur[k]] = h2[k];
+    if (status_out) memcpy(status_out, F.status, sizeof(int32_t) * n);
+    if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0 and its rows are empty)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;
 }

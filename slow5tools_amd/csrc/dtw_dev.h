@@ -1,7 +1,7 @@
 // dtw_dev.h — what dtw_kernels.hip, dtw_path_kernels.hip and their host sides share: the quantiser, the sDTW cell, a lane's step of the
 // systolic scheme, the packing of a path's decisions and the walk back through them, and the launchers (docs/codecs.md §4.16, §4.17).
-// With S5_DTW_HOST defined only the quantiser, the lane code and the path code are declared, as plain C++: tests/test_map.py and
-// tests/test_align.py compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
+// With S5_DTW_HOST defined only the quantiser, the lane code and the path code are declared, as plain C++: tests/test_map.py,
+// tests/test_map_second.py and tests/test_align.py compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
 // against the restatement, without a device.
 #pragma once
 #include <math.h>
@@ -142,6 +142,73 @@ DTW_HD U4 result_row(uint32_t cost, uint32_t qlen, int32_t start, int32_t end) {
     return o;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- a lane of k_sdtw2 (§4.19)
+// The second-best hit in the same pass.  Column j lies in block j >> bshift.  A lane keeps the least of its row KB in the block it is in, with
+// the smallest column that has it, and the four least block minima seen so far, sorted by value, the earlier block first among equals
+// (a column tells its block).  Four are enough: the runner-up is the first of them whose block is not within 1 of the first one's, and at
+// most three blocks are that near.  Only the lane that holds row Q - 1 is read in the end; an empty entry is (NO_COST, -1).
+struct Second {
+    uint32_t cur;
+    int32_t cur_col;
+    uint32_t v[4];
+    int32_t c[4];
+};
+DTW_HD void second_init(Second &S) {
+    S.cur = NO_COST; S.cur_col = -1;
+    for (int i = 0; i < 4; i++) { S.v[i] = NO_COST; S.c[i] = -1; }
+}
+// After lane_step at column j, beside lane_best and with its guard (j < R) and its strict <
+template <int G, bool WS, int KB>
+DTW_HD void lane_second(const Lane<G, WS> &L, Second &S, uint32_t j, uint32_t R) {
+    static_assert(KB >= 0 && KB < G, "a row of the lane");
+    const uint32_t cand = L.d[KB];
+    if (cand < S.cur && j < R) { S.cur = cand; S.cur_col = (int32_t)j; }
+}
+// When the lane of row Q - 1 has done the last column of a block, or column R - 1: the block's minimum goes into the list (strict <: behind its
+// equals; once it is in, the rest moves down one place) and the next block starts empty.  An empty block changes nothing.  Which step that
+// is depends on the step and the lane of row Q - 1 alone, so a wave takes it as one scalar branch, every lane with it.
+DTW_HD void second_flush(Second &S) {
+    uint32_t v = S.cur;
+    int32_t c = S.cur_col;
+    bool in = false;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 4; i++) {
+        in = in || v < S.v[i];
+        const uint32_t tv = S.v[i];
+        const int32_t tc = S.c[i];
+        S.v[i] = in ? v : tv; S.c[i] = in ? c : tc;
+        v = in ? tv : v; c = in ? tc : c;
+    }
+    S.cur = NO_COST; S.cur_col = -1;
+}
+// the step at which second_flush is due in a lane that does column j of R: the last column of a block (and, after the walk, once more)
+DTW_HD bool second_block_ends(uint32_t j, uint32_t bshift) { const uint32_t mask = (1u << bshift) - 1u; return (j & mask) == mask; }
+// mapq: 60 (cost2 - cost) / cost2 in integers, 0 .. 60; 0 without a runner-up or with one of cost 0.  A separation ratio, no probability.
+DTW_HD uint32_t second_mapq(uint32_t cost, uint32_t cost2) {
+    return cost2 == NO_COST || cost2 == 0u ? 0u : (60u * (cost2 - cost)) / cost2;                      // (cost <= cost2 < 2^26: the product fits)
+}
+// after the last flush: (cost2, end2, mapq, 0)
+DTW_HD U4 second_row(const Second &S, uint32_t bshift) {
+    U4 o;
+    o.x = NO_COST; o.y = (uint32_t)-1; o.z = 0; o.w = 0;
+    if (S.c[0] < 0) return o;
+    const int32_t b0 = S.c[0] >> bshift;
+    bool found = false;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int i = 1; i < 4; i++) {
+        const int32_t b = S.c[i] >> bshift;
+        const bool ok = !found && S.c[i] >= 0 && (b >= b0 + 2 || b + 2 <= b0);
+        if (ok) { o.x = S.v[i]; o.y = (uint32_t)S.c[i]; }
+        found = found || ok;
+    }
+    o.z = second_mapq(S.v[0], o.x);
+    return o;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the path (§4.17)
 // The alignment path of a read, walked back through the decisions of the window [start, end] of its row.  A decision is a 2-bit code:
 // 0 the diagonal, 1 (i - 1, j), 2 (i, j - 1); 3 does not occur.  A lane's step makes 2 G bits, row k of the lane at bits [2 k, 2 k + 2);
@@ -252,6 +319,9 @@ int launch_queries(uint32_t n, const QueryArgs &A, hipStream_t st);
 // k_sdtw over n reads, on st: a launch per class of lane height that qpitch allows
 int launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
                 s5gpu_map_row_t *out, hipStream_t st);
+// k_sdtw2 likewise: the same rows, and the second-best hit of every read with blocks of 2^bshift columns (6 .. 30)
+int launch_sdtw2(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                 uint32_t bshift, s5gpu_map_row_t *out, s5gpu_map_second_t *out2, hipStream_t st);
 struct PathArgs {
     const int16_t *queries;          // [n, qpitch]
     uint32_t qpitch;

@@ -1,6 +1,7 @@
 // dtw_kernels.hip — subsequence DTW of each read's events against a reference squiggle on the device (docs/codecs.md §4.16):
 //   k_ev_query : per read, the quantised means of its event rows [skip, skip + qlen) as a row of the [n, qmax] int16 query matrix
 //   k_sdtw     : per read, (cost, qlen, start, end) of the best alignment of its query to a piece of the reference
+//   k_sdtw2    : k_sdtw, and (cost2, end2, mapq) of the best hit at least two blocks of columns away (§4.19), in the same pass
 // k_sdtw is the project's one O(query x reference) kernel: a wave per read, systolic.  Lane l owns rows [l G, (l + 1) G) of the DTW matrix
 // (G = 1, 2, 4, 8, 16: the smallest with 64 G >= qlen, a kernel each), its query values and its cells of the column it did last in
 // registers.  At step t lane l does column t - l: from lane l - 1 it takes that lane's bottom cell of the same column (what it took one
@@ -112,7 +113,85 @@ __global__ __launch_bounds__(256) void k_sdtw(uint32_t n, const int16_t *__restr
     if (lane == last) out[read] = result_row(L.best, Q, WS ? L.best_start : -1, L.best_end);
 }
 
-#define DTW_LAUNCH_CHECK(what)                                                            \
+// ---- k_sdtw2: k_sdtw with the second-best hit (§4.19).  The walk of sdtw_walk with lane_second beside lane_best, and second_flush where the
+// lane of row Q - 1 has done the last column of a block: it does column t - last at step t, both the same in the whole wave, and a block is at
+// least the 64 steps of a reference block long, so in every 64 steps there is at most one such step, kf, found once: a scalar compare and
+// branch per step, taken once per block, every lane with it (the other lanes' lists are never read).
+template <int G, bool WS, int KB>
+__device__ __forceinline__ void sdtw_walk2(Lane<G, WS> &L, Second &S, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane,
+                                           uint32_t bshift) {
+    const uint32_t steps = R + last, mask = (1u << bshift) - 1u;
+    uint32_t rcur = 0;
+    uint32_t j = 0u - lane;
+    auto step = [&](uint32_t rblk, uint32_t k, uint32_t t, uint32_t kf) {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)k);
+        rcur = shift_up1(rcur, r0);
+        const uint32_t up = shift_up1_zero(L.d[G - 1]);
+        const int32_t sup = WS ? (int32_t)shift_up1((uint32_t)L.s[G - 1], t + 1) : -1;
+        lane_step(L, rcur, up, sup);
+        lane_best<G, WS, KB>(L, j, R);
+        lane_second<G, WS, KB>(L, S, j, R);
+        if (k == kf) second_flush(S);
+        j++;
+    };
+    constexpr int UNROLL = G >= 8 ? 2 : 8;
+    uint32_t tb = 0;
+    for (; tb + 64 <= steps; tb += 64) {
+        const uint32_t at = tb + lane;
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+        const uint32_t kf = (last + mask - tb) & mask;                     // (tb + kf - last) & mask == mask; 64 or more: not in these steps
+#pragma unroll UNROLL
+        for (uint32_t k = 0; k < 64; k++) step(rblk, k, tb + k, kf);
+    }
+    if (tb < steps) {
+        const uint32_t at = tb + lane;
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+        const uint32_t kf = (last + mask - tb) & mask;
+        for (uint32_t k = 0; k < steps - tb; k++) step(rblk, k, tb + k, kf);
+    }
+    second_flush(S);                                                       // column R - 1 (nothing, where it ended a block)
+}
+template <int G, bool WS, int KB = 0>
+struct Walk2 {
+    static __device__ __forceinline__ void run(int kb, Lane<G, WS> &L, Second &S, const int16_t *__restrict__ ref, uint32_t R, uint32_t last,
+                                               uint32_t lane, uint32_t bshift) {
+        if (kb == KB) sdtw_walk2<G, WS, KB>(L, S, ref, R, last, lane, bshift);
+        else if constexpr (KB + 1 < G) Walk2<G, WS, KB + 1>::run(kb, L, S, ref, R, last, lane, bshift);
+    }
+};
+
+template <int G, bool WS>
+__global__ __launch_bounds__(256) void k_sdtw2(uint32_t n, const int16_t *__restrict__ queries, uint32_t qpitch, const uint32_t *__restrict__ qlen,
+                                               const int16_t *__restrict__ ref, uint32_t R, uint32_t bshift, U4 *__restrict__ out,
+                                               U4 *__restrict__ out2) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t read = (uint64_t)blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (read >= n) return;
+    uint32_t Q = qlen[read];
+    Q = Q < qpitch ? Q : qpitch;
+    Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Q < QMAX ? Q : QMAX));
+    if (Q > 64u * G || (G > 1 && Q <= 32u * G)) return;                    // another launch's read
+    Second S;
+    second_init(S);
+    if (Q == 0) {
+        if (lane == 0) { out[read] = result_row(NO_COST, 0, -1, -1); out2[read] = second_row(S, bshift); }
+        return;
+    }
+    Lane<G, WS> L;
+    lane_init(L, lane == 0);
+    const int16_t *q = queries + read * qpitch;
+#pragma unroll
+    for (int k = 0; k < G; k++) {
+        const uint32_t row = lane * G + k;
+        L.q[k] = biased(row < Q ? q[row] : (int16_t)0);
+    }
+    const uint32_t last = (Q - 1) / G;
+    const int kb = (int)(Q - 1 - last * G);
+    Walk2<G, WS>::run(kb, L, S, ref, R, last, lane, bshift);
+    if (lane == last) { out[read] = result_row(L.best, Q, WS ? L.best_start : -1, L.best_end); out2[read] = second_row(S, bshift); }
+}
+
+#define DTW_LAUNCH_CHECK(what)                                                           \
     do {                                                                                  \
         hipError_t e_ = hipGetLastError();                                                \
         if (e_ != hipSuccess) {                                                           \
@@ -136,6 +215,28 @@ static int launch_class(uint32_t n, const int16_t *queries, uint32_t qpitch, con
     else hipLaunchKernelGGL((k_sdtw<G, false>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, out);
     DTW_LAUNCH_CHECK("k_sdtw");
     return S5GPU_OK;
+}
+
+template <int G>
+static int launch_class2(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                         uint32_t bshift, U4 *out, U4 *out2, hipStream_t st) {
+    const dim3 grid((uint32_t)(((uint64_t)n + 3u) / 4u)), block(256);
+    if (want_start) hipLaunchKernelGGL((k_sdtw2<G, true>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, bshift, out, out2);
+    else hipLaunchKernelGGL((k_sdtw2<G, false>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, bshift, out, out2);
+    DTW_LAUNCH_CHECK("k_sdtw2");
+    return S5GPU_OK;
+}
+
+int dtwk::launch_sdtw2(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                       uint32_t bshift, s5gpu_map_row_t *out, s5gpu_map_second_t *out2, hipStream_t st) {
+    if (n == 0) return S5GPU_OK;
+    U4 *o = reinterpret_cast<U4 *>(out), *o2 = reinterpret_cast<U4 *>(out2);
+    int rc = launch_class2<1>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
+    if (!rc && qpitch > 64) rc = launch_class2<2>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
+    if (!rc && qpitch > 128) rc = launch_class2<4>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
+    if (!rc && qpitch > 256) rc = launch_class2<8>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
+    if (!rc && qpitch > 512) rc = launch_class2<16>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
+    return rc;
 }
 
 // A launch per lane height that a query of at most qpitch rows can need; a wave whose read belongs to another launch returns at once.

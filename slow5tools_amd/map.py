@@ -11,6 +11,8 @@ start are reproducible bit for bit.
   map_dev     : a DecodedDev -> (MAP_ROW array, status): events, queries, sDTW; only the 16 n result bytes (and the statuses) leave the device
   read_map    : records -> (MAP_ROW array, status) through s5gpu_map_batch: compressed bytes go up, 16 bytes per read come back
   file_map    : a .blow5 file and a reference file -> (ids, MAP_ROW array) through the s5map tool
+  sdtw2_dev, map2_dev, read_map2 : the same with the second-best hit and a mapping quality beside each row (MAP_SECOND; §4.19)
+  RefSeq      : a reference made from sequences and a k-mer model on the host, both strands, and the way back from columns to positions
 
 There is no host implementation of the alignment here: the library has no CPU path.
 """
@@ -29,6 +31,9 @@ from .events import DNA, RNA  # noqa: F401  (RNA: for callers)
 # numpy mirror of s5gpu_map_row_t (include/slow5gpu.h)
 MAP_ROW = np.dtype([("cost", "<u4"), ("qlen", "<u4"), ("start", "<i4"), ("end", "<i4")])
 assert MAP_ROW.itemsize == 16
+# ... and of s5gpu_map_second_t: the runner-up of a read (cost2 = NO_COST and end2 = -1: none) and the mapping quality 0 .. 60
+MAP_SECOND = np.dtype([("cost2", "<u4"), ("end2", "<i4"), ("mapq", "<u4"), ("zero", "<u4")])
+assert MAP_SECOND.itemsize == 16
 NO_COST = 0xFFFFFFFF
 SCALE, CLIP = 32.0, 127
 # the tool's defaults: event rows left out in front, rows of the query at most, rows a read needs
@@ -121,6 +126,166 @@ def read_map(records, ref, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, event_par
     if rc != 0 and (raise_on_error or rc != -5):
         check(rc, "s5gpu_map_batch")
     return rows, status
+
+
+# ---------------------------------------------------------------------------------------------------------------- the second-best hit (§4.19)
+
+def default_bshift(qmax=QMAX):
+    """the smallest block shift in 6 .. 30 whose block of 2^shift columns holds qmax columns"""
+    return max(6, (int(qmax) - 1).bit_length())
+
+
+def sdtw2_dev(queries, qlen, ref_tensor, want_start=False, bshift=None):
+    """k_sdtw2: sdtw_dev and the second-best hit in the same pass -> (rows, second): rows what sdtw_dev returns, second an [n, 4] int32 tensor,
+    columns cost2 (as uint32 bits), end2, mapq, 0.  bshift: blocks of 2^bshift columns (6 .. 30; default: the pitch fits a block).  Asynchronous,
+    on the current stream."""
+    import torch
+
+    if queries.dtype != torch.int16 or ref_tensor.dtype != torch.int16 or queries.dim() != 2 or ref_tensor.dim() != 1:
+        raise ValueError("sdtw2_dev: queries [n, qpitch] and ref_tensor [R] are int16 tensors")
+    queries, ref_tensor, qlen = queries.contiguous(), ref_tensor.contiguous(), qlen.to(torch.int32).contiguous()
+    n, dev = int(queries.shape[0]), queries.device
+    bshift = default_bshift(queries.shape[1]) if bshift is None else int(bshift)
+    out = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+    out2 = torch.zeros((max(n, 1), 4), dtype=torch.int32, device=dev)
+    check(_lib.lib().s5gpu_sdtw2_dev(n, queries.data_ptr(), int(queries.shape[1]), qlen.data_ptr(), ref_tensor.data_ptr() if ref_tensor.numel() else None,
+                                     int(ref_tensor.numel()), 1 if want_start else 0, bshift, out.data_ptr(), out2.data_ptr(),
+                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_sdtw2_dev")
+    return out[:n], out2[:n]
+
+
+def _ref_of(ref, clip, who):
+    """the int16 reference of a call: an array, or a RefSeq, whose walls hold only for the clip it was built with"""
+    if isinstance(ref, RefSeq):
+        if int(clip) != ref.clip:
+            raise ValueError("%s: clip %d, but the reference was built with clip %d (its walls are sized for that)" % (who, int(clip), ref.clip))
+        return ref.ref
+    return ref
+
+
+def map2_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, want_start=False, bshift=None):
+    """map_dev with the second-best hit -> (MAP_ROW array, MAP_SECOND array, status) on the host.  ref: an int16 numpy array, a device tensor
+    or a RefSeq."""
+    import torch
+
+    ref = _ref_of(ref, clip, "map2_dev")
+    rows, first = _events.events_dev(dec, event_params, "raw")
+    fst = dec.t_fields.view(torch.int32).view(-1, 16)[:dec.n, 0].contiguous()
+    q, ql, st = queries_dev(rows, first, fst, skip, qmax, qmin, scale, clip)
+    r = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int16))
+    out, out2 = sdtw2_dev(q, ql, r.to(dec.dev), want_start, bshift)
+    return (out.cpu().numpy().view(MAP_ROW).reshape(-1).copy(), out2.cpu().numpy().view(MAP_SECOND).reshape(-1).copy(), st.cpu().numpy().copy())
+
+
+def read_map2(records, ref, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP,
+              want_start=False, bshift=None, raise_on_error=True):
+    """read_map with the second-best hit, through s5gpu_map2_batch -> (MAP_ROW array, MAP_SECOND array, status).  ref: an int16 array or a
+    RefSeq.  A corrupt record raises; with raise_on_error=False it has its status and empty rows, the others are valid."""
+    L = _lib.lib()
+    n = len(records)
+    ep, mp = _events._params(event_params), _params(skip, qmax, qmin, scale, clip, want_start)
+    r = np.ascontiguousarray(_ref_of(ref, clip, "read_map2"), dtype=np.int16)
+    bshift = default_bshift(qmax) if bshift is None else int(bshift)
+    vp = C.c_void_p
+    rb = [bytes(x) for x in records]
+    rbuf = [C.create_string_buffer(x, max(len(x), 1)) for x in rb]
+    rec_p = (vp * max(n, 1))(*[C.addressof(b) for b in rbuf])
+    rl = (C.c_size_t * max(n, 1))(*[len(x) for x in rb])
+    rows = np.zeros(n, dtype=MAP_ROW)
+    second = np.zeros(n, dtype=MAP_SECOND)
+    status = np.zeros(n, dtype=np.int32)
+    rc = L.s5gpu_map2_batch(n, rec_p, rl, rec_method, sig_method, C.byref(ep), C.byref(mp), r.ctypes.data_as(vp), len(r), bshift, rows.ctypes.data_as(vp),
+                            second.ctypes.data_as(vp), status.ctypes.data_as(vp))
+    if rc != 0 and (raise_on_error or rc != -5):
+        check(rc, "s5gpu_map2_batch")
+    return rows, second, status
+
+
+class RefSeq:
+    """A reference squiggle made from sequences and a k-mer model on the host (s5gpu_refseq_*, §4.19): per contig the forward levels, then
+    (DNA, strands=2) those of the reverse complement, or (rna) the forward levels reversed; all quantised together, walls of -32768 between
+    the segments.
+
+      RefSeq(fasta=path, model=path)                          from files
+      RefSeq(contigs=[(name, sequence), ...], levels=array)   from memory: levels the 4^k model levels in k-mer rank order
+
+      .ref        the int16 reference (a numpy array): what read_map2, read_align and Pileup take
+      .segments   a list of (contig, name, strand, offset, Lk), strand '+' or '-'
+      .contigs    a list of (name, bases, Lk); Lk = 0: shorter than k, no segment
+      .k, .wall, .clip
+    """
+
+    def __init__(self, fasta=None, model=None, contigs=None, levels=None, strands=2, rna=False, scale=SCALE, clip=CLIP):
+        L = _lib.lib()
+        self._h = None
+        if (fasta is None) == (contigs is None) or (fasta is None) != (model is None) or (contigs is None) != (levels is None):
+            raise ValueError("RefSeq: fasta and model, or contigs and levels")
+        if fasta is not None:
+            h = L.s5gpu_refseq_open(os.fsencode(fasta), os.fsencode(model), int(strands), 1 if rna else 0, float(scale), int(clip))
+        else:
+            lv = np.ascontiguousarray(levels, dtype=np.float32)
+            k = (max(len(lv), 1).bit_length() - 1) // 2
+            if lv.ndim != 1 or k < 1 or len(lv) != 4 ** k:
+                raise ValueError("RefSeq: levels holds 4^k values, k in 1 .. 10")
+            names = [n if isinstance(n, bytes) else str(n).encode() for n, s in contigs]
+            seqs = [s if isinstance(s, bytes) else str(s).encode() for n, s in contigs]
+            m = max(len(names), 1)
+            name_p, seq_p = (C.c_char_p * m)(*names), (C.c_char_p * m)(*seqs)
+            lens = (C.c_size_t * m)(*[len(s) for s in seqs])
+            h = L.s5gpu_refseq_build(len(names), name_p, seq_p, lens, lv.ctypes.data_as(C.c_void_p), k, int(strands), 1 if rna else 0, float(scale), int(clip))
+        if not h:
+            raise _lib.S5GpuError("RefSeq: " + L.s5gpu_last_error().decode(errors="replace"))
+        self._h = C.c_void_p(h)
+        R, k, W, cl = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        p = L.s5gpu_refseq_ref(self._h, C.byref(R))
+        check(L.s5gpu_refseq_params(self._h, C.byref(k), C.byref(W), C.byref(cl)), "s5gpu_refseq_params")
+        self.ref = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int16)), (R.value,)).copy()
+        self.k, self.wall, self.clip = k.value, W.value, cl.value
+        self.segments, self.contigs = [], []
+        for i in range(L.s5gpu_refseq_n_segments(self._h)):
+            s = _lib.RefSeqSegment()
+            check(L.s5gpu_refseq_segment(self._h, i, C.byref(s)), "s5gpu_refseq_segment")
+            self.segments.append((s.contig, s.name.decode(errors="replace"), chr(s.strand), s.offset, s.Lk))
+        for i in range(L.s5gpu_refseq_n_contigs(self._h)):
+            nm, ln, lk = C.c_char_p(), C.c_uint64(), C.c_uint32()
+            check(L.s5gpu_refseq_contig(self._h, i, C.byref(nm), C.byref(ln), C.byref(lk)), "s5gpu_refseq_contig")
+            self.contigs.append((nm.value.decode(errors="replace"), ln.value, lk.value))
+
+    def locate(self, cols):
+        """reference columns -> a list of (contig, strand, pos): the contig's index, '+' or '-', the 0-based start of the column's k-mer on the
+        forward strand; a wall column: (-1, 'wall', -1)"""
+        L, out, loc = _lib.lib(), [], _lib.RefSeqLoc()
+        for c in np.asarray(cols, dtype=np.int64).reshape(-1):
+            rc = L.s5gpu_refseq_locate(self._h, int(c) if 0 <= c < 2 ** 32 else 0xFFFFFFFF, C.byref(loc))
+            if rc == _lib.REFSEQ_WALL:
+                out.append((-1, "wall", -1))
+            else:
+                check(rc, "s5gpu_refseq_locate")
+                out.append((loc.contig, chr(loc.strand), loc.pos))
+        return out
+
+    def spans(self, rows):
+        """the (start, end) of MAP_ROW rows -> a list of (contig, strand, pos_lo, pos_hi), pos_lo <= pos_hi the first and last k-mer start on
+        the forward strand; None for a row without a query or without a start, and for a span that is not inside one segment"""
+        out = []
+        for r in np.asarray(rows).reshape(-1):
+            if r["qlen"] == 0 or r["start"] < 0 or r["end"] < 0:
+                out.append(None)
+                continue
+            (c0, s0, p0), (c1, s1, p1) = self.locate([r["start"], r["end"]])
+            out.append((c0, s0, min(p0, p1), max(p0, p1)) if (c0, s0) == (c1, s1) and c0 >= 0 else None)
+        return out
+
+    def close(self):
+        if self._h is not None:
+            _lib.lib().s5gpu_refseq_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def file_map(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, want_start=False):
