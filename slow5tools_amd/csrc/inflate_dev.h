@@ -130,11 +130,19 @@ __device__ __forceinline__ void infl_reload(uint32_t *win, const uint8_t *src, u
     b.wpos = back;
 }
 
+// A code that leaves code space unused, by zlib's rule (inflate_table): the code-length code never may; the lit/len and the distance code
+// of a dynamic block only as ONE code of one bit (an empty block; a stream of runs) or, the distance code, as no code at all (a block of
+// literals).  The fixed block's 30 distance symbols are what they are.  ncodes: codes in use, n1: those of one bit.
+enum { INF_CODE_FIXED = 0, INF_CODE_DATA = 1, INF_CODE_CL = 2 };
+__device__ __forceinline__ bool infl_incomplete_ok(int rule, uint32_t ncodes, uint32_t n1) {
+    return rule == INF_CODE_FIXED || (rule == INF_CODE_DATA && (ncodes == 0u || (ncodes == 1u && n1 == 1u)));
+}
+
 // Build canonical tables + LUT for one alphabet from lens[0..n).  All 64 lanes of the wave.
-// Returns nonzero if over-subscribed (incomplete codes are tolerated like zlib does for single-code
-// distance trees; a code that does not exist simply never matches and reports INF_ERR_DATA).
+// Returns nonzero if over-subscribed, or incomplete where `rule` does not allow it (a code that does not exist in an allowed
+// incomplete set simply never matches and reports INF_ERR_DATA).
 __device__ __forceinline__ int infl_build(const uint8_t *lens, int n, uint16_t *count, uint16_t *syms, uint16_t *lut,
-                                          int lutbits, int lenshift) {
+                                          int lutbits, int lenshift, int rule) {
     const int lane = lane_id();
     if (lane < 16) count[lane] = 0;
     for (int i = lane; i < (1 << lutbits); i += 64) lut[i] = 0;
@@ -164,7 +172,7 @@ __device__ __forceinline__ int infl_build(const uint8_t *lens, int n, uint16_t *
             if (left < 0) bad = 1;
             if (lane == 0) count[b] = (uint16_t)cnt[b];
         }
-        if (bad) return 1;
+        if (bad || (left > 0 && !infl_incomplete_ok(rule, o, cnt[1]))) return 1;
     }
     const uint64_t lt = (1ull << lane) - 1;
     for (int base = 0; base < n; base += 64) {
@@ -224,7 +232,7 @@ __device__ __forceinline__ int infl_slow(BitIn &b, const uint16_t *count, const 
 // Canonical tables WITHOUT a lookup table (the parallel decoder): count[l] and the symbols in canonical order.  Counts by LDS
 // atomics; a symbol's place = first place of its length + the symbols of that length in front of it, and the ballots that count
 // those run over the lengths that OCCUR in a slice of 64 symbols (six or seven), not over all fifteen.
-__device__ __forceinline__ int infl_build_syms(const uint8_t *lens, int n, uint16_t *count, uint16_t *syms, uint32_t *scratch16) {
+__device__ __forceinline__ int infl_build_syms(const uint8_t *lens, int n, uint16_t *count, uint16_t *syms, uint32_t *scratch16, int rule) {
     const int lane = lane_id();
     if (lane < 16) scratch16[lane] = 0;
     wave_sync();
@@ -242,6 +250,7 @@ __device__ __forceinline__ int infl_build_syms(const uint8_t *lens, int n, uint1
         // Kraft: sum c_l * 2^(15 - l) <= 2^15
         const uint32_t k = wave_sum(lane >= 1 && lane < 16 ? c << (15 - lane) : 0u);
         if (k > 32768u) return 1;
+        if (k < 32768u && !infl_incomplete_ok(rule, (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), (uint32_t)__builtin_amdgcn_readlane((int)c, 1))) return 1;
     }
     if (lane < 16) count[lane] = (uint16_t)c;
     for (int base = 0; base < n; base += 64) {
@@ -353,7 +362,7 @@ __device__ __forceinline__ int infl_cl_sequence_wave(TT &T, BitIn &b, int tot, i
 // seven bits that start no code: "symbol 31", a token of 14 bits — the chain of infl_cl_sequence_wave2 walks over it like over any other
 // token (behind the sequence lies the block's data, garbage to this code), and only a lane that meets it INSIDE the sequence reports it.  Built by DECODING, like the lit/len table of inflate_par_dev.h: entry i is the code that starts the seven bits i, found by
 // comparing them (first bit on top) with the left-justified end of every length's codes — uniform values.  sorted: >= 19 entries of scratch,
-// adj: >= 8.  Returns 1 if the lengths are over-subscribed (an incomplete set is tolerated: its unused entries are CL7_NOCODE).
+// adj: >= 8.  Returns 1 if the lengths are over-subscribed or incomplete (zlib refuses an incomplete code-length code when it builds the table).
 constexpr uint32_t CL7_NOCODE = 31u | (7u << 5) | (14u << 8);
 __device__ __forceinline__ int infl_build_cl7(const uint8_t *lens19, uint16_t *lut, uint16_t *sorted, uint16_t *adj) {
     const int lane = lane_id();
@@ -374,7 +383,7 @@ __device__ __forceinline__ int infl_build_cl7(const uint8_t *lens19, uint16_t *l
         left = (left << 1) - (int)c;
         if (left < 0) over = true;
     }
-    if (over) return 1;
+    if (over || left > 0) return 1;
     if (l) sorted[place] = (uint16_t)lane;
     if (lane >= 1 && lane < 8) adj[lane] = (uint16_t)adjv;
     wave_sync();
@@ -401,12 +410,13 @@ __device__ __forceinline__ int infl_build_cl7(const uint8_t *lens19, uint16_t *l
 // Tables of an alphabet of at most 32 symbols and lengths up to 15 — the distance code — in the manner of infl_build_cl7 (one lane per symbol,
 // every lookup entry decoded once) instead of the generic builder's two loops over fifteen lengths and its symbol-by-symbol table fill:
 // count[1..15] and the symbols in canonical order (what the canonical walk behind a lookup miss reads), lut[1 << LB] = symbol | length << 5 for
-// codes of up to LB bits, 0 for everything longer or unused.  adj: 16 entries of scratch.  Returns 1 if over-subscribed.
+// codes of up to LB bits, 0 for everything longer or unused.  adj: 16 entries of scratch.  Returns 1 if over-subscribed, or incomplete where
+// `rule` does not allow it.
 template <int LB>
-__device__ __forceinline__ int infl_build_small(const uint8_t *lens, int n, uint16_t *count, uint16_t *syms, uint16_t *lut, uint16_t *adj) {
+__device__ __forceinline__ int infl_build_small(const uint8_t *lens, int n, uint16_t *count, uint16_t *syms, uint16_t *lut, uint16_t *adj, int rule) {
     const int lane = lane_id();
     const uint32_t l = lane < n && lane < 32 ? (uint32_t)lens[lane] : 0u;
-    uint32_t first = 0, offs = 0, place = 0, adjv = 0, cntv = 0;
+    uint32_t first = 0, offs = 0, place = 0, adjv = 0, cntv = 0, n1 = 0;
     uint32_t lim[LB + 1];
     int left = 1;
     bool over = false;
@@ -419,13 +429,14 @@ __device__ __forceinline__ int infl_build_small(const uint8_t *lens, int n, uint
             if (lane == bb) cntv = c;
         }
         if (lane == bb) adjv = offs - first;
+        if (bb == 1) n1 = c;
         if (bb <= LB) lim[bb] = (first + c) << (LB - bb);
         offs += c;
         first = (first + c) << 1;
         left = (left << 1) - (int)c;
         if (left < 0) over = true;
     }
-    if (over) return 1;
+    if (over || (left > 0 && !infl_incomplete_ok(rule, offs, n1))) return 1;
     if (l) syms[place] = (uint16_t)lane;
     if (lane < 16) { count[lane] = (uint16_t)cntv; adj[lane] = (uint16_t)adjv; }
     wave_sync();
@@ -645,9 +656,10 @@ __device__ __forceinline__ int infl_block_tables(TT &T, const uint8_t *src, uint
         wave_sync();
         IPP(1)
         IPC(1)
-        // the code-length code reuses the distance tables' storage (built before the real ones)
-        if (PARCL) { if (infl_build_cl7(T.lens, T.cl_lut(), T.dsym, T.dcount)) return INF_ERR_DATA; }
-        else if (infl_build(T.lens, 19, T.dcount, T.dsym, T.cl_lut(), 7, 5)) return INF_ERR_DATA;
+        // the code-length code reuses the distance tables' storage (built before the real ones).  (Lengths out of the zero padding are no
+        // code: a set that is refused with the reader behind the end is the stream's end, not bad data — asked on the way out only)
+        if (PARCL) { if (infl_build_cl7(T.lens, T.cl_lut(), T.dsym, T.dcount)) return bi_consumed_bits(b) > total_bits ? INF_ERR_TRUNC : INF_ERR_DATA; }
+        else if (infl_build(T.lens, 19, T.dcount, T.dsym, T.cl_lut(), 7, 5, INF_CODE_CL)) return bi_consumed_bits(b) > total_bits ? INF_ERR_TRUNC : INF_ERR_DATA;
         IPP(2)
         IPC(2)
         int bad = 0;
@@ -696,12 +708,13 @@ __device__ __forceinline__ int infl_block_tables(TT &T, const uint8_t *src, uint
     const uint8_t *ll = type == 1 ? T.lens : T.lens + 32;
     const uint8_t *dl = type == 1 ? T.lens + 288 : T.lens + 32 + nl;
     if (type == 2 && ll[256] == 0) return INF_ERR_DATA;
-    if constexpr (LITLUT == 0) { if (infl_build_syms(ll, nl, T.lcount, T.lsym, reinterpret_cast<uint32_t *>(T.llut))) return INF_ERR_DATA; }   // (T.llut: >= 64 bytes of scratch)
-    else { if (infl_build(ll, nl, T.lcount, T.lsym, T.llut, LITLUT, 9)) return INF_ERR_DATA; }
+    const int rule = type == 2 ? INF_CODE_DATA : INF_CODE_FIXED;
+    if constexpr (LITLUT == 0) { if (infl_build_syms(ll, nl, T.lcount, T.lsym, reinterpret_cast<uint32_t *>(T.llut), rule)) return INF_ERR_DATA; }   // (T.llut: >= 64 bytes of scratch)
+    else { if (infl_build(ll, nl, T.lcount, T.lsym, T.llut, LITLUT, 9, rule)) return INF_ERR_DATA; }
     IPP(4)
     IPC(4)
-    if constexpr (PARCL) { if (infl_build_small<DBITS>(dl, nd, T.dcount, T.dsym, T.dlut, T.ladj)) return INF_ERR_DATA; }     // (T.ladj: scratch until the lit/len limits are set up)
-    else { if (infl_build(dl, nd, T.dcount, T.dsym, T.dlut, DBITS, 5)) return INF_ERR_DATA; }
+    if constexpr (PARCL) { if (infl_build_small<DBITS>(dl, nd, T.dcount, T.dsym, T.dlut, T.ladj, rule)) return INF_ERR_DATA; }     // (T.ladj: scratch until the lit/len limits are set up)
+    else { if (infl_build(dl, nd, T.dcount, T.dsym, T.dlut, DBITS, 5, rule)) return INF_ERR_DATA; }
     IPP(5)
     IPC(5)
     return INF_OK;
@@ -744,13 +757,15 @@ __device__ __forceinline__ int zlib_inflate_wave(InflShared &T, const uint8_t *i
     const uint16_t dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
     const uint8_t dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
     *out_len = 0;
-    if (in_len < 6) return INF_ERR_TRUNC;
+    if (in_len < (HEAD ? 2u : 6u)) return INF_ERR_TRUNC;
     {
         const uint32_t cmf = in[0], flg = in[1];
         if ((cmf & 0x0F) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 0x20)) return INF_ERR_HEADER;
     }
     const uint8_t *src = in + 2;
-    const uint32_t total = in_len - 6;            // deflate data bytes (the Adler-32 trailer is not part of them)
+    // deflate data bytes: the Adler-32 trailer is not part of them.  HEAD reads no trailer, and its input may be any front of the stream: every
+    // byte behind the header is data (the token that completes `cap` may end in the front's last byte)
+    const uint32_t total = in_len - (HEAD ? 2u : 6u);
     const uint64_t total_bits = 8ull * total;
     BitIn b;
     b.buf = 0; b.cnt = 0; b.wpos = 0; b.wbase = 0;
@@ -782,7 +797,7 @@ __device__ __forceinline__ int zlib_inflate_wave(InflShared &T, const uint8_t *i
             const uint32_t len = bi_get(b, 16);
             const uint32_t nlen = bi_get(b, 16);
             const uint32_t pos = (uint32_t)(bi_consumed_bits(b) >> 3);   // byte offset of the raw data
-            if ((len ^ 0xFFFFu) != nlen) { status = INF_ERR_DATA; break; }
+            if ((len ^ 0xFFFFu) != nlen) { status = 8ull * pos > total_bits ? INF_ERR_TRUNC : INF_ERR_DATA; break; }   // (LEN / NLEN out of the zero padding: the stream ended)
             if (8ull * pos > total_bits || (uint64_t)pos + len > total) { status = INF_ERR_TRUNC; break; }
             wave_sync();
             infl_flush(T.ring, out, flushed, o, cap, adA, adB);
@@ -851,7 +866,9 @@ __device__ __forceinline__ int zlib_inflate_wave(InflShared &T, const uint8_t *i
                     // cycles per symbol instead of an LDS round trip each), and the lanes at the visited offsets store their
                     // literals side by side.  Stops at the first symbol that is not a LUT-resolved literal (match, end of
                     // block, long code); that symbol takes the one-at-a-time route below.
-                    {
+                    // (HEAD: not within 64 bytes of `cap` — a run takes literals BEHIND the one that completes the head with it, out of the
+                    // zero padding if the input is a front that ends there, and the front would count as too short)
+                    if (!HEAD || o + 64u <= cap) {
                         const uint32_t abit = 32u * b.wpos - (uint32_t)b.cnt + (uint32_t)lane;   // window bit address of my offset
                         const uint32_t w0 = T.win[abit >> 5], w1 = T.win[(abit >> 5) + 1];
                         const uint32_t ev = T.llut[(uint32_t)((((uint64_t)w1 << 32) | w0) >> (abit & 31)) & ((1 << INF_LBITS) - 1)];
@@ -913,7 +930,9 @@ __device__ __forceinline__ int zlib_inflate_wave(InflShared &T, const uint8_t *i
                     if (mdist > o) { st = 2; break; }
                     break;
                 }
-                if (st != 2 && bi_consumed_bits(b) > total_bits) st = 3;   // decoded out of the zero padding past the end
+                // decoded out of the zero padding past the end.  (HEAD: also when those zeros made a wrong token of it — the input may be a front cut
+                // anywhere, and a token that runs over its end is the cut's doing, whatever it looks like)
+                if ((HEAD || st != 2) && bi_consumed_bits(b) > total_bits) st = 3;
             }
             if (st == 2 || st == 3) { status = st == 2 ? INF_ERR_DATA : INF_ERR_TRUNC; break; }
             if (st == 1) break;
@@ -950,7 +969,8 @@ __device__ __forceinline__ int zlib_inflate_wave(InflShared &T, const uint8_t *i
         infl_flush(T.ring, out, flushed, o, cap, adA, adB);
         const uint8_t *t = in + in_len - 4;
         const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-        if (o <= cap && ((adB << 16) | adA) != want) status = INF_ERR_ADLER;
+        // (the trailer stands right behind the last block: with bytes in between, these four are not the stream's Adler-32, whatever they hold)
+        if (o <= cap && (((adB << 16) | adA) != want || (uint32_t)((bi_consumed_bits(b) + 7) >> 3) != total)) status = INF_ERR_ADLER;
     }
     *out_len = o;
     if (status == INF_OK && o > cap) status = INF_ERR_OVERFLOW;

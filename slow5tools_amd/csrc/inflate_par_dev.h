@@ -567,7 +567,7 @@ __device__ __forceinline__ int zlib_inflate_par(SH &T, const uint8_t *in, uint32
             bi_need32_u(b, T.win);
             const uint32_t len = bi_get(b, 16), nlen = bi_get(b, 16);
             const uint32_t at = (uint32_t)(bi_consumed_bits(b) >> 3);
-            if ((len ^ 0xFFFFu) != nlen) return INF_ERR_DATA;
+            if ((len ^ 0xFFFFu) != nlen) return 8ull * at > total_bits ? INF_ERR_TRUNC : INF_ERR_DATA;   // (LEN / NLEN out of the zero padding: as inflate_dev.h)
             if ((uint64_t)at + len > total) return INF_ERR_TRUNC;
             if (o + len > cap) return INF_NEED_FALLBACK;
             for (uint32_t i = lane; i < len; i += 64) out[o + i] = src[at + i];
@@ -842,7 +842,7 @@ __device__ __forceinline__ int zlib_inflate_par(SH &T, const uint8_t *in, uint32
     }
     IPP(12)
     IPP_FLUSH
-    if (((adB << 16) | adA) != want) return INF_ERR_ADLER;
+    if (((adB << 16) | adA) != want || (uint32_t)((pos + 7) >> 3) != total) return INF_ERR_ADLER;   // (bytes between the last block and the trailer: as inflate_dev.h)
     return INF_OK;
 }
 

@@ -103,14 +103,17 @@ __device__ __forceinline__ int lane_slow(LaneBits &b, const uint16_t *count, con
     }
     return -1;
 }
-// count / syms of a small alphabet (n <= 32) from lengths get(s).  Nonzero if over-subscribed.
+// count / syms of a small alphabet (n <= 32) from lengths get(s).  Nonzero if over-subscribed, or incomplete where `rule` (inflate_dev.h:
+// infl_incomplete_ok) does not allow it.
 template <typename F>
-__device__ __forceinline__ int lane_build_small(F get, int n, uint16_t *count, uint8_t *syms) {
+__device__ __forceinline__ int lane_build_small(F get, int n, uint16_t *count, uint8_t *syms, int rule) {
     for (int i = 0; i < 16; i++) count[i] = 0;
     for (int s = 0; s < n; s++) count[get(s)]++;
+    const uint32_t ncodes = (uint32_t)(n - count[0]);
     count[0] = 0;
     int left = 1;
     for (int l = 1; l <= 15; l++) { left = (left << 1) - count[l]; if (left < 0) return 1; }
+    if (left > 0 && !infl_incomplete_ok(rule, ncodes, count[1])) return 1;
     uint16_t offs[16];
     offs[1] = 0;
     for (int l = 1; l < 15; l++) offs[l + 1] = (uint16_t)(offs[l] + count[l]);
@@ -118,10 +121,11 @@ __device__ __forceinline__ int lane_build_small(F get, int n, uint16_t *count, u
     return 0;
 }
 // lit/len tables from the nibbles lens4[0..n): symbols in canonical order (T.lsym / T.lhi), T.ladj, and the limits.
-__device__ __forceinline__ int lane_build_litlen(LaneTables &T, LaneBuild &B, int n, LaneLimits &lim) {
+__device__ __forceinline__ int lane_build_litlen(LaneTables &T, LaneBuild &B, int n, LaneLimits &lim, int rule) {
     for (int i = 0; i < 16; i++) B.tmp[i] = 0;
     for (int i = 0; i < 9; i++) T.lhi[i] = 0;
     for (int s = 0; s < n; s++) B.tmp[nib_get(B.lens4, s)]++;
+    const uint32_t ncodes = (uint32_t)(n - B.tmp[0]), n1 = B.tmp[1];
     B.tmp[0] = 0;
     int left = 1;
     uint32_t first = 0, index = 0;
@@ -139,6 +143,7 @@ __device__ __forceinline__ int lane_build_litlen(LaneTables &T, LaneBuild &B, in
         index += c;
         first = (first + c) << 1;
     }
+    if (left > 0 && !infl_incomplete_ok(rule, ncodes, n1)) return 1;
     for (int s = 0; s < n; s++) {
         const uint32_t l = nib_get(B.lens4, s);
         if (l) {
@@ -215,6 +220,7 @@ __device__ __forceinline__ int zlib_inflate_lane(LaneTables &T, const uint8_t *i
             lb_get(b, b.cnt & 7);
             lb_need32(b);
             const uint32_t len = lb_get(b, 16), nlen = lb_get(b, 16);
+            if (lb_consumed(b) > total_bits) return INF_ERR_TRUNC;   // (LEN / NLEN from behind the stream's end: as inflate_dev.h)
             if ((len ^ 0xFFFFu) != nlen) return INF_ERR_DATA;
             const uint64_t pos = lb_consumed(b) >> 3;
             if (8 * pos > total_bits || pos + len > in_len - 6) return INF_ERR_TRUNC;
@@ -228,7 +234,7 @@ __device__ __forceinline__ int zlib_inflate_lane(LaneTables &T, const uint8_t *i
             for (int s = 0; s < 288; s++) nib_set(B.lens4, s, s < 144 ? 8u : s < 256 ? 9u : s < 280 ? 7u : 8u);
             nl = 288;
             nd = 30;
-            if (lane_build_small([](int) { return 5u; }, nd, B.dcount, B.dsym)) return INF_ERR_DATA;
+            if (lane_build_small([](int) { return 5u; }, nd, B.dcount, B.dsym, INF_CODE_FIXED)) return INF_ERR_DATA;
         } else {
             lb_need32(b);
             const uint32_t hd = lb_get(b, 14);
@@ -244,7 +250,8 @@ __device__ __forceinline__ int zlib_inflate_lane(LaneTables &T, const uint8_t *i
                 const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
                 for (int i = 0; i < ncl; i++) { lb_need32(b); cl[order[i]] = (uint8_t)lb_get(b, 3); }
             }
-            if (lane_build_small([&](int s) { return (uint32_t)cl[s]; }, 19, B.dcount, B.dsym)) return INF_ERR_DATA;
+            if (lb_consumed(b) > total_bits) return INF_ERR_TRUNC;   // (code lengths from behind the stream's end: as inflate_dev.h)
+            if (lane_build_small([&](int s) { return (uint32_t)cl[s]; }, 19, B.dcount, B.dsym, INF_CODE_CL)) return INF_ERR_DATA;
             uint32_t prev = 0;
             int idx = 0;
             const int tot = nl + nd;
@@ -267,9 +274,9 @@ __device__ __forceinline__ int zlib_inflate_lane(LaneTables &T, const uint8_t *i
             if (lb_consumed(b) > total_bits) return INF_ERR_TRUNC;
             if (nib_get(B.lens4, 256) == 0) return INF_ERR_DATA;
             // distance tables (their lengths sit behind the lit/len ones)
-            if (lane_build_small([&](int s) { return nib_get(B.lens4, nl + s); }, nd, B.dcount, B.dsym)) return INF_ERR_DATA;
+            if (lane_build_small([&](int s) { return nib_get(B.lens4, nl + s); }, nd, B.dcount, B.dsym, INF_CODE_DATA)) return INF_ERR_DATA;
         }
-        if (lane_build_litlen(T, B, nl, lim)) return INF_ERR_DATA;
+        if (lane_build_litlen(T, B, nl, lim, type == 2 ? INF_CODE_DATA : INF_CODE_FIXED)) return INF_ERR_DATA;
         for (;;) {
             lb_need32(b);
             int sym = lane_litlen(b, T, lim);
@@ -307,7 +314,7 @@ __device__ __forceinline__ int zlib_inflate_lane(LaneTables &T, const uint8_t *i
     const uint8_t *t = in + in_len - 4;
     const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
     if (o > cap) return INF_ERR_OVERFLOW;
-    if (((adB << 16) | adA) != want) return INF_ERR_ADLER;
+    if (((adB << 16) | adA) != want || ((lb_consumed(b) + 7) >> 3) != in_len - 6) return INF_ERR_ADLER;   // (bytes between the last block and the trailer: as inflate_dev.h)
     return INF_OK;
 }
 
