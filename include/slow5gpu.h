@@ -912,6 +912,75 @@ int s5gpu_pileup_add_batch(void *handle, uint32_t n, const void *const *rec, con
 /* Downloads the accumulator to acc_out (HOST memory, s5gpu_pileup_bytes(R); may be NULL) and ends the handle, whatever it returns. */
 int s5gpu_pileup_close(void *handle, void *acc_out);
 
+/* ---- refine: per-read level rescaling from the path, and a windowed realign (docs/codecs.md §4.20) ----
+ * The query of a read and the reference were normalised apart (§4.16).  refine fits the line r = a q + b by least squares over the cells
+ * (i, j), lo[i] <= j <= hi[i], of the read's path, requantises the query q'[i] = clamp(rint(a q[i] + b), -clip, clip), and aligns q' again
+ * in the window [start - pad, end + pad] of the reference (clipped to [0, R - 1]), `iters` times, each round from the query that came in and
+ * along the path of the round before.  The reference stays as it is, so costs before and after compare.  Everything is reproducible bit
+ * for bit: the sums are exact integers, the solve is in double with every operation rounded on its own (§4.20 gives the order). */
+#define S5GPU_STATUS_FIT_FLAT 21      /* status[i]: fewer than min_cells cells, or a query without variance along the path: no fit */
+#define S5GPU_STATUS_FIT_RANGE 22     /* status[i]: the slope is not finite or outside [a_min, a_max], or |b| > b_max: the fit is refused */
+typedef struct s5gpu_refine_params {  /* 40 bytes */
+    double a_min, a_max;       /* the slopes that are accepted: finite, 0 < a_min <= a_max; 0.5 and 2.0 */
+    double b_max;              /* the largest |b| that is accepted: finite, >= 0; 64.0                   */
+    int32_t clip;              /* q' is clamped to +-clip: 1 .. 32767; 127                               */
+    uint32_t pad;              /* columns added on either side of [start, end]: 0 .. 65535; 16           */
+    uint32_t min_cells;        /* the fewest cells that are fitted: >= 2; 16                             */
+    uint32_t iters;            /* rounds of s5gpu_refine_dev and s5gpu_refine_batch: 1 .. 4; 2           */
+} s5gpu_refine_params_t;
+typedef struct s5gpu_fit {     /* 64 bytes */
+    double a, b;               /* 1 and 0 where the read was not fitted or the fit was refused */
+    int64_t n, sq, sr, sqq, sqr, srr;   /* the cells, and the sums of q, r, q^2, q r, r^2 over them; 0 where the read has no path to fit */
+} s5gpu_fit_t;
+/* The fit of n reads along their paths: queries, qpitch, qlen, ref, R, lo, hi as s5gpu_sdtw_path_dev took and left them, status_in what it
+ * wrote (or any caller's: a read whose status_in is not 0 is passed over and keeps it), all DEVICE arrays; params a HOST struct (pad and
+ * iters are checked, not used).  A read is fitted iff status_in = 0, it has a query, every row passes the rules of s5gpu_pileup_accum_dev
+ * (else S5GPU_STATUS_PATH_ROW) and the path spans at most wmax columns (else S5GPU_STATUS_PATH_WIDE).  fit_out[i]: a, b and the sums;
+ * queries_out (may be NULL; [n, qpitch]): q', zeros behind qlen; status_out[i]: 0, S5GPU_STATUS_FIT_FLAT or S5GPU_STATUS_FIT_RANGE (a = 1,
+ * b = 0, the sums as they are, and q' a copy of q), or the status of a read that was not fitted (a = 1, b = 0, sums 0, q' zeros).  Nothing
+ * else is written.  n = 0: S5GPU_OK, nothing launched.  S5GPU_ERR_ARG (nothing launched): the cases of s5gpu_sdtw_path_dev, a parameter
+ * outside its range, a NULL or misaligned pointer (fit_out: 16 bytes; lo, hi, the statuses: 4; queries: 2).  Asynchronous on hip_stream. */
+int s5gpu_path_fit_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, const int32_t *lo,
+                       const int32_t *hi, const int32_t *status_in, uint32_t wmax, const s5gpu_refine_params_t *params, s5gpu_fit_t *fit_out,
+                       int16_t *queries_out, int32_t *status_out, void *hip_stream);
+/* sDTW and its path in one call, in a window of the reference around a row that is known: for each read with a query, ws = max(0, start -
+ * pad), we = min(R - 1, end + pad) of rows_in[i]; rows_out[i] = (cost', qlen, start', end') and lo, hi are §4.16's alignment and §4.17's path
+ * of the query against r[ws .. we] (a free start anywhere in it, the smallest column of least cost as the end), in absolute columns.
+ * status[i]: 0; S5GPU_STATUS_PATH_ROW (rows_in[i] is unusable, as in s5gpu_sdtw_path_dev); S5GPU_STATUS_PATH_WIDE (we - ws + 1 > wmax).  A
+ * read with another status than 0, or without a query (status 0), has the empty row (0xFFFFFFFF, 0, -1, -1) and -1 in lo and hi.  scratch,
+ * scratch_bytes and the groups as in s5gpu_sdtw_path_dev (slots of s5gpu_sdtw_path_slot_bytes(qpitch, wmax)); rows_out must not be
+ * rows_in.  S5GPU_ERR_ARG (nothing launched): the cases of s5gpu_sdtw_path_dev, pad > 65535.  Asynchronous on hip_stream. */
+int s5gpu_sdtw_window_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R,
+                          const s5gpu_map_row_t *rows_in, uint32_t pad, uint32_t wmax, void *scratch, size_t scratch_bytes,
+                          s5gpu_map_row_t *rows_out, int32_t *lo, int32_t *hi, int32_t *status, void *hip_stream);
+/* The bytes of `work` that s5gpu_refine_dev needs for n reads of pitch qpitch (a trial round's query, row, path, fit and statuses); 0 for
+ * a qpitch the call refuses. */
+size_t s5gpu_refine_work_bytes(uint32_t n, uint32_t qpitch);
+/* params->iters rounds of the two calls above on DEVICE buffers; nothing comes to the host in between.  Round k + 1 fits the query that came
+ * in along the path of round k (round 0: lo_in, hi_in), requantises from the query that came in, and realigns in the window around round
+ * k's row (round 0: rows_in).  A round succeeds for a read when the fit is accepted and the window is at most wmax wide; its outputs then
+ * become the round's.  A read that fails a round (S5GPU_STATUS_FIT_FLAT, S5GPU_STATUS_FIT_RANGE, S5GPU_STATUS_PATH_WIDE) keeps the outputs
+ * of the last round that succeeded (none yet: copies of what came in, a = 1, b = 0), takes no further part, and has that status;
+ * rounds_out[i]: the rounds that succeeded.  A read with status_in != 0, without a query, or whose lo_in, hi_in do not pass
+ * s5gpu_path_fit_dev's checks has zeros in queries_out, the empty row, -1 in lo_out and hi_out, a = 1, b = 0, 0 rounds, and status_in or that
+ * check's status.  What comes out feeds s5gpu_pileup_accum_dev as it is.  work: s5gpu_refine_work_bytes(n, qpitch) bytes, 16-byte
+ * aligned; no output may be an input.  S5GPU_ERR_ARG (nothing launched): the cases of the two calls above.  Asynchronous on hip_stream. */
+int s5gpu_refine_dev(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R,
+                     const s5gpu_map_row_t *rows_in, const int32_t *lo_in, const int32_t *hi_in, const int32_t *status_in, uint32_t wmax,
+                     const s5gpu_refine_params_t *params, void *scratch, size_t scratch_bytes, void *work, size_t work_bytes, int16_t *queries_out,
+                     s5gpu_map_row_t *rows_out, int32_t *lo_out, int32_t *hi_out, s5gpu_fit_t *fit_out, int32_t *status_out, uint32_t *rounds_out,
+                     void *hip_stream);
+/* The chain of s5gpu_align_batch, then s5gpu_refine_dev, on the FIRST device in use; one download brings back rows_out[0 .. n) (the first
+ * mapping), rows_refined_out[0 .. n), fit_out[0 .. n), lo_out and hi_out ([n, qmax]: the refined path), events_out (may be NULL) as in
+ * s5gpu_align_batch, status_out (may be NULL: the statuses of s5gpu_align_batch, S5GPU_STATUS_FIT_FLAT, S5GPU_STATUS_FIT_RANGE) and
+ * rounds_out (may be NULL).  A corrupt record: as in s5gpu_align_batch, its refined row the empty row and its fit a = 1, b = 0.
+ * S5GPU_ERR_ARG before anything is launched: the cases of s5gpu_align_batch, a refine parameter outside its range, a NULL output. */
+int s5gpu_refine_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                       const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, uint32_t wmax,
+                       const s5gpu_refine_params_t *refine_params, const int16_t *ref_host, uint32_t R, s5gpu_map_row_t *rows_out,
+                       s5gpu_map_row_t *rows_refined_out, s5gpu_fit_t *fit_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out,
+                       int32_t *status_out, uint32_t *rounds_out);
+
 #ifdef __cplusplus
 }
 #endif

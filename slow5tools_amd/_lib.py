@@ -125,6 +125,19 @@ PileCol = np.dtype([("depth", "<u4"), ("n_events", "<u4"), ("n_samples", "<u8"),
 PileTotal = np.dtype([("reads_used", "<u8"), ("reads_skipped", "<u8"), ("reads_bad", "<u8"), ("cells", "<u8"), ("cost", "<u8"), ("R", "<u4"),
                       ("reserved", "<u4", (5,))])
 assert PileCol.itemsize == 48 and PileTotal.itemsize == 64
+STATUS_FIT_FLAT, STATUS_FIT_RANGE = 21, 22
+# s5gpu_fit_t: the fit of "refine" (slow5tools_amd/refine.py)
+Fit = np.dtype([("a", "<f8"), ("b", "<f8"), ("n", "<i8"), ("sq", "<i8"), ("sr", "<i8"), ("sqq", "<i8"), ("sqr", "<i8"), ("srr", "<i8")])
+assert Fit.itemsize == 64
+
+
+class RefineParams(C.Structure):
+    """s5gpu_refine_params_t"""
+    _fields_ = [("a_min", C.c_double), ("a_max", C.c_double), ("b_max", C.c_double), ("clip", C.c_int32), ("pad", C.c_uint32), ("min_cells", C.c_uint32),
+                ("iters", C.c_uint32)]
+
+
+assert C.sizeof(RefineParams) == 40
 
 
 class S5GpuError(RuntimeError):
@@ -271,6 +284,15 @@ def lib():
     L.s5gpu_pileup_open.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), u32, vp, u32]
     L.s5gpu_pileup_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp]
     L.s5gpu_pileup_close.argtypes = [vp, vp]
+    # refine: the fit along a path, the windowed realign, their rounds on the device, and records anywhere in host memory
+    L.s5gpu_path_fit_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, vp, vp, u32, C.POINTER(RefineParams), vp, vp, vp, vp]
+    L.s5gpu_sdtw_window_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, u32, u32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    L.s5gpu_refine_work_bytes.argtypes = [u32, u32]
+    L.s5gpu_refine_work_bytes.restype = C.c_size_t
+    L.s5gpu_refine_dev.argtypes = [u32, vp, u32, vp, vp, u32, vp, vp, vp, vp, u32, C.POINTER(RefineParams), vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp,
+                                   vp, vp, vp]
+    L.s5gpu_refine_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), u32, C.POINTER(RefineParams), vp, u32, vp, vp, vp,
+                                     vp, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -300,4 +322,5 @@ EXPORTS = [
     "s5gpu_refseq_close",
     "s5gpu_sdtw_path_slot_bytes", "s5gpu_sdtw_path_dev", "s5gpu_align_batch",
     "s5gpu_pileup_bytes", "s5gpu_pileup_reset_dev", "s5gpu_pileup_accum_dev", "s5gpu_pileup_open", "s5gpu_pileup_add_batch", "s5gpu_pileup_close",
+    "s5gpu_path_fit_dev", "s5gpu_sdtw_window_dev", "s5gpu_refine_work_bytes", "s5gpu_refine_dev", "s5gpu_refine_batch",
 ]

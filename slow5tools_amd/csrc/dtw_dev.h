@@ -1,7 +1,7 @@
 // dtw_dev.h — what dtw_kernels.hip, dtw_path_kernels.hip and their host sides share: the quantiser, the sDTW cell, a lane's step of the
 // systolic scheme, the packing of a path's decisions and the walk back through them, and the launchers (docs/codecs.md §4.16, §4.17).
 // With S5_DTW_HOST defined only the quantiser, the lane code and the path code are declared, as plain C++: tests/test_map.py,
-// tests/test_map_second.py and tests/test_align.py compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
+// tests/test_map_second.py, tests/test_align.py and tests/test_refine.py (path_walk_from, §4.20) compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
 // against the restatement, without a device.
 #pragma once
 #include <math.h>
@@ -288,6 +288,39 @@ DTW_HD int32_t path_walk(const uint32_t *words, uint32_t slot_words, uint32_t G,
         i--;
         if (code == 0u) j--;
         hi[i] = start + (int32_t)j;
+    }
+    return S5GPU_STATUS_PATH_ROW;
+}
+
+// path_walk's sibling for a window that is wider than the path (§4.20): from (Q - 1, jend), jend < W, to row 0, where it may arrive in any
+// column of the window; that column (absolute, as lo and hi: `base` is the window's first) goes to *start_out.  Every bound of path_walk is
+// kept: at most Q + W trips; i < Q and j < W checked before each use; a word index clamped to the slot; a code of 3 or a step out of the
+// window ends the walk.  -> 0, or S5GPU_STATUS_PATH_ROW (*start_out = -1; lo and hi hold a partial path: the caller overwrites them)
+DTW_HD int32_t path_walk_from(const uint32_t *words, uint32_t slot_words, uint32_t G, uint32_t Q, uint32_t W, int32_t base, uint32_t jend, int32_t *lo,
+                              int32_t *hi, int32_t *start_out) {
+    *start_out = -1;
+    if (Q == 0 || W == 0 || slot_words == 0 || jend >= W) return S5GPU_STATUS_PATH_ROW;
+    const uint32_t top = slot_words * 64u - 1u;
+    uint32_t i = Q - 1, j = jend, at = 0xFFFFFFFFu, word = 0;
+    hi[i] = base + (int32_t)j;
+    for (uint32_t trip = 0; trip < Q + W; trip++) {
+        if (i >= Q || j >= W) break;
+        if (i == 0) {
+            lo[0] = base + (int32_t)j;
+            *start_out = base + (int32_t)j;
+            return 0;
+        }
+        uint32_t shift;
+        uint32_t x = path_cell(G, i, j, &shift);
+        x = x < top ? x : top;
+        if (x != at) { word = words[x]; at = x; }
+        const uint32_t code = (word >> shift) & 3u;
+        if (code == 3u || (code != 1u && j == 0)) break;
+        if (code == 2u) { j--; continue; }
+        lo[i] = base + (int32_t)j;
+        i--;
+        if (code == 0u) j--;
+        hi[i] = base + (int32_t)j;
     }
     return S5GPU_STATUS_PATH_ROW;
 }
