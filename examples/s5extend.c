@@ -1,0 +1,254 @@
+/*
+ * s5extend.c — where a WHOLE read lies on a reference squiggle: the first events of the read are mapped by subsequence DTW (s5map), and from
+ * the column where they start the path of all its events is followed in tiles over a band of the reference that moves with it, on the GPU
+ * (k_sdtw, k_ev_query_long, k_sdtw_band, k_sdtw_band_trace; docs/codecs.md §4.21).
+ *
+ *   s5extend [-K batch] [--rna] [--skip S] [--events Q] [--min-events M] [--tile T] [--band B] [--max-events N] [--per-event] ref.txt file.blow5
+ *       <read_id>\t<events_used>\t<cost>\t<cost_per_event>\t<ref_start>\t<ref_end>\t<tiles>\t<anchor>      one line per read, in file order
+ *   ref.txt, S, Q, M, the event parameters and the read ids are those of s5map: Q events behind the first S are mapped, and their start is
+ *   the anchor.  The long query is the events behind the first S, at most N (default and most 2^20) and at least M; T (64, 128, 256, 512 or
+ *   1024; default 256) rows make a tile, B (a multiple of 64 in 64 .. 4096; default 512) columns its window.  cost is the sum of
+ *   |query - reference| over the path, cost_per_event = cost / events_used as %.3f; ref_start .. ref_end (inclusive) the reference positions
+ *   of the first and the last event.  The band is a heuristic: a read whose true path leaves it is aligned worse, not refused, and
+ *   cost_per_event is the only sign.  A read without a path prints `*` in every column behind its id, and why goes to stderr: `short`
+ *   (fewer than M events), `row` (no anchor, or the walk failed), `wide` (the read's scratch alone is above 1 GiB).
+ *   --per-event prints s5align's lines instead, for every event of the whole read:
+ *       <read_id>\t<event>\t<sample_start>\t<sample_end>\t<mean>\t<ref_lo>\t<ref_hi>
+ *   Exit 0; 1 when a record is corrupt (its read id, or its number in the file when the id cannot be read, goes to stderr; the other reads
+ *   are printed); 2 on any other error (an empty or unparsable reference, an unreadable or damaged file, a .slow5 argument: text input is
+ *   not built, convert it first).
+ *
+ * At most K records (default 4096) go to one s5gpu_extend_batch call: compressed bytes go up; the rows, lo, hi and the event rows come
+ * back in one download, ragged.  The read ids come as in s5map.
+ */
+#define _GNU_SOURCE
+#include <inttypes.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "slow5_compat.h"
+#include "slow5gpu.h"
+
+enum { EXIT_CORRUPT = 1, EXIT_ERROR = 2, PITCH = 128 };
+
+static int die(const char *what) {
+    fprintf(stderr, "s5extend: %s (%s)\n", what, s5gpu_last_error());
+    return EXIT_ERROR;
+}
+/* a status of the decoder's, not one of map's or align's */
+static int corrupt_status(int32_t s) { return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW; }
+static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
+static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
+
+/* --rid's layout of s5skim.c: the aux fields' types only, every role "." — a skim line is only needed for its first column */
+static int rid_layout(const char *h, size_t len, s5gpu_skim_layout_t *L) {
+    size_t b = 0;
+    while (b < len) {
+        const char *e = (const char *)memchr(h + b, '\n', len - b);
+        const size_t l = e ? (size_t)(e - h) - b : len - b;
+        if (l >= 6 && memcmp(h + b, "#char*", 6) == 0) {
+            const int k = s5gpu_aux_types_parse(h + b, l, L->type, S5GPU_SKIM_MAX_AUX);
+            if (k < 0) return -1;
+            L->n_aux = (uint32_t)k;
+            for (int a = 0; a < k; a++) L->role[a] = S5GPU_SKIM_DOT;
+            L->n_unhandled = (uint32_t)k;
+            return 0;
+        }
+        b += l + 1;
+    }
+    return -1;
+}
+
+/* one number per line; NULL (and a message) when the file cannot be read, holds no number or a line is no number */
+static float *read_reference(const char *path, size_t *n_out) {
+    FILE *f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "s5extend: cannot open %s\n", path); return NULL; }
+    size_t n = 0, cap = 1024, line_cap = 0, line_no = 0;
+    float *v = (float *)malloc(sizeof(float) * cap);
+    char *line = NULL;
+    ssize_t l;
+    while (v && (l = getline(&line, &line_cap, f)) >= 0) {
+        line_no++;
+        while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r' || line[l - 1] == ' ' || line[l - 1] == '\t')) line[--l] = 0;
+        if (l == 0 || line[0] == '#') continue;
+        char *end = NULL;
+        const double x = strtod(line, &end);
+        if (end == line || *end != 0) {
+            fprintf(stderr, "s5extend: %s line %zu is not a number\n", path, line_no);
+            free(v); free(line); fclose(f);
+            return NULL;
+        }
+        if (n == cap) { cap *= 2; v = (float *)realloc(v, sizeof(float) * cap); }
+        if (v) v[n++] = (float)x;
+    }
+    free(line);
+    fclose(f);
+    if (!v) { fprintf(stderr, "s5extend: out of memory\n"); return NULL; }
+    if (n == 0 || n > 0x7FFFFFFFu) { fprintf(stderr, "s5extend: %s holds %s\n", path, n ? "too many numbers" : "no number"); free(v); return NULL; }
+    *n_out = n;
+    return v;
+}
+
+int main(int argc, char **argv) {
+    long K = 4096, skip = 0, qmax = 250, qmin = 50, tile = 256, band = 512, emax = 1l << 20;
+    int rna = 0, bad = 0, per_event = 0;
+    const char *ref_path = NULL, *path = NULL;
+    for (int i = 1; i < argc; i++) {
+        if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--skip") && i + 1 < argc) skip = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--events") && i + 1 < argc) qmax = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--min-events") && i + 1 < argc) qmin = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--tile") && i + 1 < argc) tile = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--band") && i + 1 < argc) band = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--max-events") && i + 1 < argc) emax = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--rna")) rna = 1;
+        else if (!strcmp(argv[i], "--per-event")) per_event = 1;
+        else if (argv[i][0] != '-' && !ref_path) ref_path = argv[i];
+        else if (argv[i][0] != '-' && !path) path = argv[i];
+        else bad = 1;
+    }
+    const int tile_ok = tile == 64 || tile == 128 || tile == 256 || tile == 512 || tile == 1024;
+    if (bad || !path || K < 1 || K > (1l << 24) || skip < 0 || skip > 0x7FFFFFFFl || qmax < 1 || qmax > 1024 || qmin < 1 || qmin > qmax || !tile_ok ||
+        band < 64 || band > 4096 || band % 64 != 0 || emax < qmin || emax > (1l << 20)) {
+        fprintf(stderr, "usage: s5extend [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--tile T (64, 128, 256, 512, 1024)]\n"
+                        "                [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] [--per-event] ref.txt file.blow5\n");
+        return EXIT_ERROR;
+    }
+    const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
+    const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
+    size_t R = 0;
+    float *levels = read_reference(ref_path, &R);
+    if (!levels) return EXIT_ERROR;
+    int16_t *ref = (int16_t *)malloc(sizeof(int16_t) * R);
+    if (!ref) return die("out of memory");
+    if (s5gpu_quantise_host(levels, R, M.scale, M.clip, ref) != S5GPU_OK) return die("the reference cannot be quantised");
+    free(levels);
+    if (s5gpu_init(0) != S5GPU_OK) return die("no GPU");
+    slow5_file_t *in = slow5_open(path, "r");
+    if (!in) { fprintf(stderr, "s5extend: cannot open %s\n", path); return EXIT_ERROR; }
+    if (in->format != SLOW5_FORMAT_BINARY) { fprintf(stderr, "s5extend: %s is SLOW5 text: convert it to BLOW5 first\n", path); return EXIT_ERROR; }
+    const int rec = rec_code_of(in->compress->record_press->method), sig = sig_code_of(in->compress->signal_press->method);
+    const s5gpu_event_params_t dna = {3, 6, 1.4, 9.0, 0.2}, rnap = {7, 14, 2.5, 9.0, 1.0};
+    const s5gpu_event_params_t *P = rna ? &rnap : &dna;
+    static char obuf[1 << 20];
+    setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+
+    void **mem = (void **)calloc((size_t)K, sizeof(void *));
+    size_t *len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
+    uint64_t *rec_pos = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)K);
+    uint32_t *rec_len = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)K);
+    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K), *ist = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
+    char *ids = (char *)malloc((size_t)K * PITCH);
+    uint16_t *id_len = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)K);
+    void **line = (void **)calloc((size_t)K, sizeof(void *));
+    size_t *line_len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
+    s5gpu_map_row_t *map_rows = (s5gpu_map_row_t *)malloc(sizeof(s5gpu_map_row_t) * (size_t)K);
+    s5gpu_ext_row_t *rows = (s5gpu_ext_row_t *)malloc(sizeof(s5gpu_ext_row_t) * (size_t)K);
+    uint64_t *first = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)K + 1));
+    if (!mem || !len || !rec_pos || !rec_len || !st || !ist || !ids || !id_len || !line || !line_len || !map_rows || !rows || !first) return die("out of memory");
+    size_t chunk_cap = 0, cap = 0;
+    int32_t *lo = NULL, *hi = NULL;
+    s5gpu_event_t *ev = NULL;
+    uint8_t *chunk = NULL;
+    s5gpu_skim_layout_t *L = NULL;
+    int code = EXIT_SUCCESS, at_end = 0;
+    uint64_t n_done = 0;
+    while (!at_end) {
+        uint32_t n = 0;
+        size_t bytes = 0;
+        while (n < (uint32_t)K) {
+            mem[n] = slow5_get_next_mem(&len[n], in);
+            if (!mem[n]) {
+                if (slow5_errno != SLOW5_ERR_EOF) { fprintf(stderr, "s5extend: cannot read record %" PRIu64 " of %s\n", n_done + n, path); return EXIT_ERROR; }
+                at_end = 1;
+                break;
+            }
+            if (len[n] > 0xFFFFFF00u) { fprintf(stderr, "s5extend: record %" PRIu64 " is too large\n", n_done + n); return EXIT_ERROR; }
+            bytes += 8 + len[n];
+            n++;
+        }
+        if (n == 0) break;
+        int rc = S5GPU_ERR_NOMEM;
+        for (int attempt = 0; attempt < 2 && rc == S5GPU_ERR_NOMEM; attempt++) {                       /* the second time with the room the first asked for */
+            rc = s5gpu_extend_batch(n, (const void *const *)mem, len, rec, sig, P, &M, &B, 0, ref, (uint32_t)R, map_rows, rows, first, lo, hi,
+                                    per_event ? ev : NULL, cap, st);
+            if (rc != S5GPU_ERR_NOMEM || first[0] <= cap) break;
+            cap = (size_t)first[0];
+            free(lo); free(hi); free(ev);
+            lo = (int32_t *)malloc(sizeof(int32_t) * cap); hi = (int32_t *)malloc(sizeof(int32_t) * cap);
+            ev = per_event ? (s5gpu_event_t *)malloc(sizeof(s5gpu_event_t) * cap) : NULL;
+            if (!lo || !hi || (per_event && !ev)) return die("out of memory");
+        }
+        if (rc != S5GPU_OK && rc != S5GPU_ERR_DATA) return die("alignment failed");
+        /* the ids: the device id path over the records framed in one buffer; what it leaves (zstd, long ids) is the first column of a skim line */
+        for (uint32_t i = 0; i < n; i++) ist[i] = 5;
+        if (rec != S5GPU_REC_ZSTD) {
+            if (bytes + 64 > chunk_cap) {
+                if (chunk) s5gpu_host_free(chunk);
+                chunk_cap = bytes + bytes / 4 + 64;
+                chunk = (uint8_t *)s5gpu_host_alloc(chunk_cap);
+                if (!chunk) return die("out of memory");
+            }
+            size_t p = 0;
+            for (uint32_t i = 0; i < n; i++) {
+                const uint64_t sz = len[i];
+                memcpy(chunk + p, &sz, 8);
+                memcpy(chunk + p + 8, mem[i], len[i]);
+                rec_pos[i] = p + 8; rec_len[i] = (uint32_t)len[i];
+                p += 8 + len[i];
+            }
+            if (s5gpu_record_ids_stream(n, chunk, p, rec_pos, rec_len, rec, PITCH, ids, id_len, ist) != S5GPU_OK) return die("read ids failed");
+        }
+        for (uint32_t i = 0; i < n; i++) {
+            line[i] = NULL;
+            if (ist[i] == 0 || corrupt_status(st[i])) continue;                                        /* (a corrupt record has no skim line either) */
+            if (!L) {
+                L = (s5gpu_skim_layout_t *)calloc(1, sizeof *L);
+                if (!L) return die("out of memory");
+                if (rid_layout(in->header->data, in->header->data_len, L) != 0) return die("the header names no column types");
+            }
+            const void *r1 = mem[i];
+            int32_t s1 = 0;
+            if (s5gpu_skim_batch(1, &r1, &len[i], rec, sig, L, &line[i], &line_len[i], &s1) != S5GPU_OK || !line[i]) return die("read ids failed");
+        }
+        for (uint32_t i = 0; i < n; i++) {
+            const char *id = NULL;
+            size_t idl = 0;
+            if (ist[i] == 0) { id = ids + (size_t)i * PITCH; idl = id_len[i]; }
+            else if (line[i]) {
+                const char *tab = (const char *)memchr(line[i], '\t', line_len[i]);
+                id = (const char *)line[i]; idl = tab ? (size_t)(tab - id) : line_len[i];
+            }
+            if (corrupt_status(st[i])) {
+                if (id) fprintf(stderr, "s5extend: read %.*s is corrupt (status %d)\n", (int)idl, id, st[i]);
+                else fprintf(stderr, "s5extend: record %" PRIu64 " of the file is corrupt (status %d)\n", n_done + i, st[i]);
+                code = EXIT_CORRUPT;
+            } else if (st[i] != 0) {
+                const char *why = st[i] == S5GPU_STATUS_QUERY_SHORT ? "short" : st[i] == S5GPU_STATUS_PATH_WIDE ? "wide" : "row";
+                fprintf(stderr, "s5extend: read %.*s has no path: %s\n", (int)idl, id, why);
+                printf(per_event ? "%.*s\t*\t*\t*\t*\t*\t*\n" : "%.*s\t*\t*\t*\t*\t*\t*\t*\n", (int)idl, id);
+            } else if (per_event) {
+                const size_t at = (size_t)first[i];
+                for (uint32_t k = 0; k < rows[i].qlen; k++) {
+                    const s5gpu_event_t *e = &ev[at + k];
+                    printf("%.*s\t%" PRIu64 "\t%u\t%" PRIu64 "\t%.6g\t%d\t%d\n", (int)idl, id, (uint64_t)skip + k, e->start, (uint64_t)e->start + e->length,
+                           (double)e->mean, lo[at + k], hi[at + k]);
+                }
+            } else {
+                printf("%.*s\t%u\t%" PRIu64 "\t%.3f\t%d\t%d\t%u\t%d\n", (int)idl, id, rows[i].qlen, rows[i].cost, (double)rows[i].cost / (double)rows[i].qlen,
+                       rows[i].start, rows[i].end, rows[i].tiles, map_rows[i].start);
+            }
+            free(line[i]);
+            free(mem[i]);
+            mem[i] = NULL;
+        }
+        n_done += n;
+    }
+    if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5extend: write failed\n"); return EXIT_ERROR; }
+    if (chunk) s5gpu_host_free(chunk);
+    slow5_close(in);
+    free(mem); free(len); free(rec_pos); free(rec_len); free(st); free(ist); free(ids); free(id_len); free(line); free(line_len);
+    free(map_rows); free(rows); free(first); free(lo); free(hi); free(ev); free(L); free(ref);
+    return code;
+}

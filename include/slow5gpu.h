@@ -981,6 +981,72 @@ int s5gpu_refine_batch(uint32_t n, const void *const *rec, const size_t *rec_len
                        s5gpu_map_row_t *rows_refined_out, s5gpu_fit_t *fit_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out,
                        int32_t *status_out, uint32_t *rounds_out);
 
+/* ---- extend: whole-read banded alignment in tiles from a known anchor (docs/codecs.md §4.21) ----
+ * map, align and refine stop at the first 1024 events of a read.  extend follows the path of ALL of a read's events (up to 2^20) from the
+ * column where its prefix mapped: the query is cut into tiles of tile_rows rows, each tile is §4.16's recurrence over a window of `band`
+ * reference columns, the window of the next tile is placed around the column where this tile's last row is cheapest, and the last row is
+ * carried into the next tile less its minimum.  The cost is O(events x band) whatever R is.  The band is a heuristic: where the true path
+ * leaves it the result is a worse alignment, not an error; cost / qlen is the only sign.  Integer throughout, reproducible bit for bit. */
+typedef struct s5gpu_band_params {    /* 32 bytes */
+    uint32_t skip;             /* event rows passed over at the head of a read: >= 0                          */
+    uint32_t emin, emax;       /* the fewest rows that make a query, and the most that are used: 1 <= emin <= emax <= 2^20 */
+    uint32_t tile_rows;        /* rows of a tile: 64, 128, 256, 512 or 1024; 256                              */
+    uint32_t band;             /* columns of a tile's window: a multiple of 64 in 64 .. 4096; 512             */
+    int32_t clip;              /* as in s5gpu_map_params_t: 1 .. 32767                                         */
+    double scale;              /* as in s5gpu_map_params_t: finite, > 0                                        */
+} s5gpu_band_params_t;
+typedef struct s5gpu_ext_row {        /* 32 bytes; a read without a path: ~0, 0, 0, -1, -1, -1, status */
+    uint64_t cost;             /* the sum of |q - r| over the cells of the path                                */
+    uint32_t qlen, tiles;      /* the rows of the query, and its tiles                                         */
+    int32_t start, end;        /* the columns of the path in row 0 and in row qlen - 1                         */
+    int32_t a_last;            /* the first column of the last tile's window                                   */
+    int32_t status;            /* 0, the status that came in, or S5GPU_STATUS_PATH_ROW                         */
+} s5gpu_ext_row_t;
+/* The long queries of n reads from their event rows: Q_i = min(emax, max(E_i - skip, 0)) with E_i = first[i + 1] - first[i]; Q_i < emin: no
+ * query, qlen = 0, S5GPU_STATUS_QUERY_SHORT; a read whose ev_status (may be NULL) is not 0 has no query and keeps that status.  The query is
+ * §4.16's quant of the means of rows [skip, skip + Q_i) and lives at queries[first[i] .. first[i] + Q_i), zeros behind it up to
+ * first[i + 1]: the layout is ragged, `first` (n + 1 entries, as s5gpu_signal_events_dev leaves it) is its index, total_rows the length of
+ * `queries`.  A read whose rows do not lie in [0, total_rows) is treated as one without rows.  params: a HOST struct (tile_rows and band
+ * are checked, not used); everything else DEVICE arrays.  S5GPU_ERR_ARG (nothing launched): a parameter outside its range, a NULL or
+ * misaligned pointer (rows: 16 bytes).  n = 0: S5GPU_OK.  Asynchronous on hip_stream. */
+int s5gpu_event_queries_long_dev(uint32_t n, const s5gpu_event_t *rows, const uint64_t *first, const int32_t *ev_status,
+                                 const s5gpu_band_params_t *params, uint64_t total_rows, int16_t *queries, uint32_t *qlen, int32_t *status,
+                                 void *hip_stream);
+/* The scratch s5gpu_sdtw_band_dev needs for n reads of total_rows rows in all: floor(total_rows / tile_rows) + n slots of
+ * s5gpu_sdtw_path_slot_bytes(tile_rows, band), and 4 bytes a slot (rounded up to 16) for the tiles' first columns.  0 for a tile_rows or a
+ * band the call refuses. */
+size_t s5gpu_sdtw_band_scratch_bytes(uint32_t n, uint64_t total_rows, uint32_t tile_rows, uint32_t band);
+/* The banded alignment of n long queries (queries, first, qlen, total_rows as s5gpu_event_queries_long_dev left them) against ref[0 .. R)
+ * from anchor[i], a column 0 <= anchor[i] < R (in the chain: `start` of the read's prefix mapping made with the same skip).  rows_out[i]:
+ * the result row; lo, hi ([total_rows], at first[i] as the query): the first and last column of every row of the path, -1 behind qlen up to
+ * first[i + 1].  A read whose status_in is not 0 has no path and that status; one with a query whose anchor is out of range, or whose walk
+ * fails, S5GPU_STATUS_PATH_ROW; one without a query and with status 0 has the empty row with status 0.  All reads are handled in one group:
+ * scratch (16-byte aligned) has at least s5gpu_sdtw_band_scratch_bytes(n, total_rows, tile_rows, band) bytes, else S5GPU_ERR_NOMEM and
+ * nothing is written.  Nothing but rows_out, lo, hi and the scratch is written.  params: a HOST struct (only tile_rows and band are used).
+ * S5GPU_ERR_ARG (nothing launched): a parameter outside its range, R outside 1 .. 2^31 - 1, a NULL or misaligned pointer (rows_out,
+ * scratch: 16 bytes; first: 8).  n = 0: S5GPU_OK.  Asynchronous on hip_stream.
+ * s5gpu_set_option (tests, tools): "sdtw_band_passes" (1 .. 3, default 3): 1 launches k_sdtw_band only, 2 the walk only, over what an
+ * earlier call left in the scratch and in rows_out. */
+int s5gpu_sdtw_band_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows, const int16_t *ref,
+                        uint32_t R, const int32_t *anchor, const int32_t *status_in, const s5gpu_band_params_t *params, void *scratch,
+                        size_t scratch_bytes, s5gpu_ext_row_t *rows_out, int32_t *lo, int32_t *hi, void *hip_stream);
+/* The chain on the FIRST device in use: the front of s5gpu_map_batch (map_params->want_start is taken as on), sDTW of the prefix query, the
+ * long queries from the event rows that are resident already (a read is segmented once), the banded alignment from anchor = the prefix
+ * row's start, one download.  band_params->skip, scale and clip must equal map_params' (else S5GPU_ERR_ARG).  map_rows_out[0 .. n): the
+ * prefix mapping; rows_out[0 .. n): the result rows.  The paths come back ragged: ev_first_out (n + 1 entries) is the prefix of
+ * rows_out[i].qlen, and lo_out, hi_out and events_out (may be NULL; the query's event rows [skip, skip + qlen) of the read) hold the rows of
+ * record i at [ev_first_out[i], ev_first_out[i + 1]); rows_cap: their room in rows.  Too little room: S5GPU_ERR_NOMEM and ev_first_out[0] =
+ * the rows that suffice (the sum of the reads' Q).  The reads are aligned in groups of consecutive reads whose scratch is at most
+ * scratch_max bytes (0: 1 GiB); a read whose scratch alone is above it has S5GPU_STATUS_PATH_WIDE and no path, the others stay valid.
+ * status_out (may be NULL): 0, S5GPU_STATUS_QUERY_SHORT, S5GPU_STATUS_PATH_ROW (a read with a long query but no anchor: emin below
+ * map_params->qmin), S5GPU_STATUS_PATH_WIDE or the decoder's.  A corrupt record fails the call with S5GPU_ERR_DATA as in
+ * s5gpu_align_batch: its rows are empty, the other reads' outputs are valid.  S5GPU_ERR_ARG before a device is needed: the cases of
+ * s5gpu_map_batch, a band parameter outside its range, a NULL output. */
+int s5gpu_extend_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                       const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const s5gpu_band_params_t *band_params,
+                       size_t scratch_max, const int16_t *ref_host, uint32_t R, s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *rows_out,
+                       uint64_t *ev_first_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out, size_t rows_cap, int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,15 @@ class RefineParams(C.Structure):
 assert C.sizeof(RefineParams) == 40
 
 
+class BandParams(C.Structure):
+    """s5gpu_band_params_t"""
+    _fields_ = [("skip", C.c_uint32), ("emin", C.c_uint32), ("emax", C.c_uint32), ("tile_rows", C.c_uint32), ("band", C.c_uint32), ("clip", C.c_int32),
+                ("scale", C.c_double)]
+
+
+assert C.sizeof(BandParams) == 32
+
+
 class S5GpuError(RuntimeError):
     pass
 
@@ -293,6 +302,13 @@ def lib():
                                    vp, vp, vp]
     L.s5gpu_refine_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), u32, C.POINTER(RefineParams), vp, u32, vp, vp, vp,
                                      vp, vp, vp, vp, vp]
+    # extend: the long queries of event rows, and the banded alignment in tiles from an anchor, on the device
+    L.s5gpu_event_queries_long_dev.argtypes = [u32, vp, vp, vp, C.POINTER(BandParams), u64, vp, vp, vp, vp]
+    L.s5gpu_sdtw_band_scratch_bytes.argtypes = [u32, u64, u32, u32]
+    L.s5gpu_sdtw_band_scratch_bytes.restype = C.c_size_t
+    L.s5gpu_sdtw_band_dev.argtypes = [u32, vp, vp, vp, u64, vp, u32, vp, vp, C.POINTER(BandParams), vp, C.c_size_t, vp, vp, vp, vp]
+    L.s5gpu_extend_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32, vp, vp,
+                                     vp, vp, vp, vp, C.c_size_t, vp]
     _LIB = L
     return L
 
@@ -323,4 +339,5 @@ EXPORTS = [
     "s5gpu_sdtw_path_slot_bytes", "s5gpu_sdtw_path_dev", "s5gpu_align_batch",
     "s5gpu_pileup_bytes", "s5gpu_pileup_reset_dev", "s5gpu_pileup_accum_dev", "s5gpu_pileup_open", "s5gpu_pileup_add_batch", "s5gpu_pileup_close",
     "s5gpu_path_fit_dev", "s5gpu_sdtw_window_dev", "s5gpu_refine_work_bytes", "s5gpu_refine_dev", "s5gpu_refine_batch",
+    "s5gpu_event_queries_long_dev", "s5gpu_sdtw_band_scratch_bytes", "s5gpu_sdtw_band_dev", "s5gpu_extend_batch",
 ]

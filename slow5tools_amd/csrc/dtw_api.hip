@@ -146,6 +146,7 @@ int dtwk::map_front(uint32_t n, const void *const *rec, const size_t *rec_len, i
     if ((rc = dtwk::launch_queries(m, args_of(d_rows, d_first, d_est, mp, d_q, d_ql, d_qst), c->st))) return rc;
     F.d_rows = d_rows; F.d_first = d_first; F.d_q = d_q; F.d_ql = d_ql; F.d_ref = d_ref;
     F.d_out = (s5gpu_map_row_t *)(dp + o_out);
+    F.d_est = d_est; F.total = total;
     return S5GPU_OK;
 }
 

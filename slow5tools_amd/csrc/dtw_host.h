@@ -23,6 +23,8 @@ struct MapFront : s5host::Resident {
     uint32_t *d_ql = nullptr;
     int16_t *d_ref = nullptr;
     s5gpu_map_row_t *d_out = nullptr;
+    const int32_t *d_est = nullptr;                                        // the events' statuses [m]
+    uint64_t total = 0;                                                    // the event rows of the m reads: first[m], which the host knows
 };
 // the S5GPU_ERR_ARG cases of s5gpu_map_batch, before a device is needed; outputs: the caller's own output pointers are there
 int map_front_check(const char *who, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
