@@ -9,10 +9,13 @@
  *   stdv, min and max are over the quantised event levels (mean = sum / events, stdv = sqrt(max(sumsq / events - mean^2, 0))) and mean_cost
  *   is the mean |level - ref_level|, all three as %.6g.  The totals (reads used, skipped, bad; cells; cost) go to stderr as one line.  A
  *   read without a path is skipped, and why goes to stderr as in s5align.
+ *   s5pileup --whole [--tile T] [--band B] [--max-events N] ... : the same ten columns from ALL of a read's events (docs/codecs.md §4.22): the
+ *   prefix of Q events finds the anchor as above, then up to N events (default 2^20) are aligned in tiles of T rows (default 256) over
+ *   windows of B columns (default 512) as in s5extend, and the whole path is added to the table.  --max-span does not count then.
  *   Exit 0; 1 when a record is corrupt (its read id, or its number in the file when the id cannot be read, goes to stderr; the other reads
  *   are counted); 2 on any other error.
  *
- * One handle (s5gpu_pileup_open), one s5gpu_pileup_add_batch per K records (default 4096) and one s5gpu_pileup_close: compressed bytes go
+ * One handle (s5gpu_pileup_open, or s5gpu_pileup_open_whole), one s5gpu_pileup_add_batch (or _whole) per K records (default 4096) and one s5gpu_pileup_close: compressed bytes go
  * up; a status per read comes back, and the table once at the end.  The read ids come as in s5map, for the reads that are
  * named on stderr only.
  */
@@ -87,8 +90,8 @@ static float *read_reference(const char *path, size_t *n_out) {
 }
 
 int main(int argc, char **argv) {
-    long K = 4096, skip = 0, qmax = 250, qmin = 50, wmax = -1, min_depth = 1;
-    int rna = 0, bad = 0;
+    long K = 4096, skip = 0, qmax = 250, qmin = 50, wmax = -1, min_depth = 1, tile = -1, band = -1, emax = -1;
+    int rna = 0, bad = 0, whole = 0;
     const char *ref_path = NULL, *path = NULL;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
@@ -98,14 +101,25 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rna")) rna = 1;
         else if (!strcmp(argv[i], "--max-span") && i + 1 < argc) wmax = atol(argv[++i]);
         else if (!strcmp(argv[i], "--min-depth") && i + 1 < argc) min_depth = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--whole")) whole = 1;
+        else if (!strcmp(argv[i], "--tile") && i + 1 < argc) { tile = atol(argv[++i]); bad |= tile == -1; }
+        else if (!strcmp(argv[i], "--band") && i + 1 < argc) { band = atol(argv[++i]); bad |= band == -1; }
+        else if (!strcmp(argv[i], "--max-events") && i + 1 < argc) { emax = atol(argv[++i]); bad |= emax == -1; }
         else if (argv[i][0] != '-' && !ref_path) ref_path = argv[i];
         else if (argv[i][0] != '-' && !path) path = argv[i];
         else bad = 1;
     }
     if (wmax == -1) wmax = 4 * qmax;
+    if (!whole && (tile != -1 || band != -1 || emax != -1)) bad = 1;      /* (they belong to --whole) */
+    if (tile == -1) tile = 256;
+    if (band == -1) band = 512;
+    if (emax == -1) emax = 1l << 20;
+    if (tile != 64 && tile != 128 && tile != 256 && tile != 512 && tile != 1024) bad = 1;
+    if (band < 64 || band > 4096 || band % 64 || emax < qmin || emax > (1l << 20)) bad = 1;
     if (bad || !path || K < 1 || K > (1l << 24) || skip < 0 || skip > 0x7FFFFFFFl || qmax < 1 || qmax > 1024 || qmin < 1 || qmin > qmax || wmax < 1 ||
         wmax > (1l << 20) || min_depth < 1 || min_depth > 0xFFFFFFFFl) {
         fprintf(stderr, "usage: s5pileup [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--max-span W (1 .. 2^20)] [--min-depth D (>= 1)] ref.txt file.blow5\n");
+        fprintf(stderr, "       s5pileup --whole [--tile T (64, 128, 256, 512, 1024)] [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] ... : the table of whole reads\n");
         return EXIT_ERROR;
     }
     const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
@@ -141,7 +155,8 @@ int main(int argc, char **argv) {
     uint8_t *chunk = NULL;
     s5gpu_skim_layout_t *L = NULL;
     if (!acc) return die("out of memory");
-    void *pile = s5gpu_pileup_open(P, &M, (uint32_t)wmax, ref, (uint32_t)R);
+    const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
+    void *pile = whole ? s5gpu_pileup_open_whole(P, &M, &B, 0, ref, (uint32_t)R) : s5gpu_pileup_open(P, &M, (uint32_t)wmax, ref, (uint32_t)R);
     if (!pile) return die("the table cannot be opened");
     int code = EXIT_SUCCESS, at_end = 0;
     uint64_t n_done = 0;
@@ -160,7 +175,8 @@ int main(int argc, char **argv) {
             n++;
         }
         if (n == 0) break;
-        const int rc = s5gpu_pileup_add_batch(pile, n, (const void *const *)mem, len, rec, sig, NULL, st);
+        const int rc = whole ? s5gpu_pileup_add_batch_whole(pile, n, (const void *const *)mem, len, rec, sig, NULL, NULL, st)
+                             : s5gpu_pileup_add_batch(pile, n, (const void *const *)mem, len, rec, sig, NULL, st);
         if (rc != S5GPU_OK && rc != S5GPU_ERR_DATA) return die("alignment failed");
         int named = 0;                                                                                 /* the ids: only where a read is named */
         for (uint32_t i = 0; i < n; i++) named |= st[i] != 0;

@@ -1047,6 +1047,34 @@ int s5gpu_extend_batch(uint32_t n, const void *const *rec, const size_t *rec_len
                        size_t scratch_max, const int16_t *ref_host, uint32_t R, s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *rows_out,
                        uint64_t *ev_first_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out, size_t rows_cap, int32_t *status_out);
 
+/* ---- pileup of whole reads: the ragged paths of extend added to the table (docs/codecs.md §4.22) ----
+ * The accumulator is that of "pileup" above; fixed-pitch and ragged calls may add to one accumulator in any order and on several streams.
+ * The inputs are laid out as s5gpu_sdtw_band_dev leaves them: read k's rows at [first[k], first[k] + qlen[k]) of queries, lo and hi
+ * ([total_rows] each).  Read k is SKIPPED iff status[k] != 0 or qlen[k] == 0; else BAD iff qlen[k] > 2^20, first[k] > first[k + 1],
+ * first[k + 1] > total_rows, qlen[k] + ev_skip > first[k + 1] - first[k], or a row fails the path rule of "pileup" against the row before
+ * it in the ragged array; else USED, with the cells of "pileup", i the row within the read.  Nothing of a read is accumulated unless every
+ * row of it passed.  events (may be NULL; ev_skip then counts as 0): the samples of row i of read k are
+ * events[first[k] + ev_skip + i].length.  For reads of at most 1024 rows the table is byte for byte s5gpu_pileup_accum_dev's. */
+/* The bytes of the work area of a ragged call (0: total_rows above 2^40). */
+size_t s5gpu_pileup_long_work_bytes(uint32_t n, uint64_t total_rows);
+/* Asynchronous on hip_stream; writes nothing but acc and work (DEVICE memory, 16-byte aligned; a work area per call in flight).
+ * n = 0: S5GPU_OK and nothing is launched.  S5GPU_ERR_ARG, nothing launched: a NULL or misaligned pointer (first: 8 bytes; events, work,
+ * acc: 16), R outside 1 .. 2^26, total_rows above 2^40.  S5GPU_ERR_NOMEM, nothing written: work_bytes below
+ * s5gpu_pileup_long_work_bytes(n, total_rows). */
+int s5gpu_pileup_accum_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows,
+                                const int16_t *ref, uint32_t R, const int32_t *lo, const int32_t *hi, const int32_t *status,
+                                const s5gpu_event_t *events, uint32_t ev_skip, void *work, size_t work_bytes, void *acc, void *hip_stream);
+/* A per-file handle as s5gpu_pileup_open's, for whole reads: s5gpu_pileup_add_batch_whole runs the device side of s5gpu_extend_batch
+ * (band_params and map_params must agree as there; scratch_max as there) and adds the ragged paths; s5gpu_pileup_close serves both kinds.
+ * The add of the other kind returns S5GPU_ERR_ARG and leaves the handle usable.  NULL: the S5GPU_ERR_ARG cases of s5gpu_extend_batch,
+ * R > 2^26, no device, no memory. */
+void *s5gpu_pileup_open_whole(const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params,
+                              const s5gpu_band_params_t *band_params, size_t scratch_max, const int16_t *ref_host, uint32_t R);
+/* map_rows_out, ext_rows_out and status_out ([n] each, may be NULL) are what s5gpu_extend_batch returns for the batch; the paths never
+ * leave the device.  Records that never reached the device count in reads_skipped; a corrupt record behaves as in s5gpu_pileup_add_batch. */
+int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                                 s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,13 @@ def lib():
     L.s5gpu_sdtw_band_dev.argtypes = [u32, vp, vp, vp, u64, vp, u32, vp, vp, C.POINTER(BandParams), vp, C.c_size_t, vp, vp, vp, vp]
     L.s5gpu_extend_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32, vp, vp,
                                      vp, vp, vp, vp, C.c_size_t, vp]
+    # pileup of whole reads: the ragged call, and the per-file handle over extend's chain
+    L.s5gpu_pileup_long_work_bytes.argtypes = [u32, u64]
+    L.s5gpu_pileup_long_work_bytes.restype = C.c_size_t
+    L.s5gpu_pileup_accum_long_dev.argtypes = [u32, vp, vp, vp, u64, vp, u32, vp, vp, vp, vp, u32, vp, C.c_size_t, vp, vp]
+    L.s5gpu_pileup_open_whole.restype = vp
+    L.s5gpu_pileup_open_whole.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32]
+    L.s5gpu_pileup_add_batch_whole.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, vp]
     _LIB = L
     return L
 
@@ -340,4 +347,5 @@ EXPORTS = [
     "s5gpu_pileup_bytes", "s5gpu_pileup_reset_dev", "s5gpu_pileup_accum_dev", "s5gpu_pileup_open", "s5gpu_pileup_add_batch", "s5gpu_pileup_close",
     "s5gpu_path_fit_dev", "s5gpu_sdtw_window_dev", "s5gpu_refine_work_bytes", "s5gpu_refine_dev", "s5gpu_refine_batch",
     "s5gpu_event_queries_long_dev", "s5gpu_sdtw_band_scratch_bytes", "s5gpu_sdtw_band_dev", "s5gpu_extend_batch",
+    "s5gpu_pileup_long_work_bytes", "s5gpu_pileup_accum_long_dev", "s5gpu_pileup_open_whole", "s5gpu_pileup_add_batch_whole",
 ]

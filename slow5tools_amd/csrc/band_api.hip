@@ -4,12 +4,9 @@
 // the banded alignment from `start`, in groups of consecutive reads whose scratch fits -> one download.
 #include <vector>
 
-#include "dtw_host.h"
-#include "band_dev.h"
+#include "band_host.h"
 
-namespace {
-
-int check_band_params(const char *who, const s5gpu_band_params_t *p) {
+int bandk::check_band_params(const char *who, const s5gpu_band_params_t *p) {
     if (!p) { s5gpu_set_error("%s: NULL band parameters", who); return S5GPU_ERR_ARG; }
     if (!bandk::params_ok(*p)) {
         s5gpu_set_error("%s: band parameters emin %u emax %u (1 <= emin <= emax <= %u) tile_rows %u (64, 128, 256, 512, 1024) band %u (a multiple of 64 in "
@@ -18,6 +15,18 @@ int check_band_params(const char *who, const s5gpu_band_params_t *p) {
     }
     return S5GPU_OK;
 }
+
+int bandk::check_band_agrees(const char *who, const s5gpu_map_params_t *mp, const s5gpu_band_params_t *bp) {
+    if (bp->skip != mp->skip || bp->scale != mp->scale || bp->clip != mp->clip) {
+        s5gpu_set_error("%s: skip, scale and clip of the band parameters are not those of the map parameters (the anchor is a column of the same query)", who);
+        return S5GPU_ERR_ARG;
+    }
+    return S5GPU_OK;
+}
+
+using bandk::check_band_params;
+
+namespace {
 
 bool mis(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
 
@@ -80,6 +89,81 @@ extern "C" int s5gpu_sdtw_band_dev(uint32_t n, const int16_t *queries, const uin
     return bandk::launch_band(n, A, (hipStream_t)stream);
 }
 
+// The device side of s5gpu_extend_batch behind a front with m >= 1 reads (band_host.h), queued on the front's stream
+int bandk::extend_tail(const char *who, dtwk::MapFront &F, const s5gpu_map_params_t *mp, const s5gpu_band_params_t *bp, size_t scratch_max, uint32_t R,
+                       bool events, bool paths_back, size_t rows_cap, size_t scan_min, uint64_t *room_out, ExtTail &E) {
+    int rc;
+    Ctx *c = F.hold.c;
+    const uint32_t m = F.m, T = bp->tile_rows;
+    const uint64_t total = F.total;
+    const uint32_t slot_words = dtwk::path_slot_words(T, bp->band);
+    if (scratch_max == 0) scratch_max = (size_t)1 << 30;
+    E.first.assign(m + 1u, 0);
+    E.too_big.assign(m, 0);
+    std::vector<uint64_t> &first = E.first;
+    E.o_map = up(32ull * m, 16); E.o_lo = E.o_map + up(16ull * m, 16); E.o_hi = E.o_lo + up(4ull * total, 16); E.o_ev = E.o_hi + up(4ull * total, 16);
+    E.back = E.o_ev + (events ? 16ull * total : 0); E.o_q = up(E.back, 16); E.o_ql = E.o_q + up(2ull * total, 16); E.o_st = E.o_ql + up(4ull * m, 16);
+    // the host has to know the reads' rows: the room the caller needs, and the groups
+    HIP_TRY(hipMemcpyAsync(first.data(), F.d_first, 8ull * (m + 1u), hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    uint64_t room = 0;
+    for (uint32_t k = 0; k < m; k++) room += bandk::long_qlen(first[k + 1] - first[k], bp->skip, bp->emin, bp->emax);
+    if (room > rows_cap) {
+        *room_out = room;
+        s5gpu_set_error("%s: room for %zu rows, %llu may be needed", who, rows_cap, (unsigned long long)room);
+        return S5GPU_ERR_NOMEM;
+    }
+    if ((rc = c->d_gather.reserve(E.o_st + 4ull * m + 64)) || (rc = c->h_out.reserve((paths_back ? E.back : E.o_lo + 4ull * m) + 64))) return rc;
+    uint8_t *dg = (uint8_t *)c->d_gather.p;
+    s5gpu_ext_row_t *d_rows = (s5gpu_ext_row_t *)dg;
+    s5gpu_map_row_t *d_map = (s5gpu_map_row_t *)(dg + E.o_map);
+    int32_t *d_lo = (int32_t *)(dg + E.o_lo), *d_hi = (int32_t *)(dg + E.o_hi), *d_st = (int32_t *)(dg + E.o_st);
+    int16_t *d_q = (int16_t *)(dg + E.o_q);
+    uint32_t *d_ql = (uint32_t *)(dg + E.o_ql);
+    if ((rc = dtwk::launch_sdtw(m, F.d_q, mp->qmax, F.d_ql, F.d_ref, R, true, d_map, c->st)) ||
+        (rc = s5gpu_event_queries_long_dev(m, F.d_rows, F.d_first, F.d_est, bp, total, d_q, d_ql, d_st, c->st)))
+        return rc;
+    // consecutive reads while their scratch fits; a read that does not fit alone is passed over
+    size_t most = scan_min;
+    std::vector<uint32_t> cut(1, 0);
+    for (uint32_t b = 0; b < m;) {
+        uint32_t e = b;
+        size_t need = 0;
+        while (e < m) {
+            const size_t nx = (size_t)bandk::scratch_bytes(bandk::slot_count(first[e + 1] - first[b], T, e + 1u - b), slot_words);
+            if (nx > scratch_max) break;
+            need = nx;
+            e++;
+        }
+        if (e == b) { E.too_big[b] = 1; e = b + 1; }
+        most = need > most ? need : most;
+        cut.push_back(e);
+        b = e;
+    }
+    if ((rc = c->d_scan.reserve(most + 64))) return rc;
+    for (size_t g = 0; g + 1 < cut.size(); g++) {
+        const uint32_t b = cut[g], e = cut[g + 1];
+        if (E.too_big[b]) continue;
+        bandk::BandArgs A;
+        A.queries = d_q; A.first = F.d_first + b; A.qlen = d_ql + b; A.total_rows = total; A.ref = F.d_ref; A.R = R;
+        A.anchor = &d_map[b].start; A.anchor_stride = sizeof(s5gpu_map_row_t) / sizeof(int32_t); A.status_in = d_st + b; A.row0 = first[b];
+        A.T = T; A.band = bp->band; A.scratch = (uint32_t *)c->d_scan.p; A.slots = bandk::slot_count(first[e] - first[b], T, e - b);
+        A.slot_words = slot_words; A.tile_a = (int32_t *)((uint8_t *)c->d_scan.p + A.slots * ((uint64_t)slot_words * 256u));
+        A.rows_out = d_rows + b; A.lo = d_lo; A.hi = d_hi;
+        if ((rc = bandk::launch_band(e - b, A, c->st))) return rc;         // (the stream orders the groups: the scratch is used again)
+    }
+    return S5GPU_OK;
+}
+
+void bandk::scatter_ext_rows(dtwk::MapFront &F, uint32_t n, const ExtTail &E, const uint8_t *h, s5gpu_ext_row_t *rows_out) {
+    for (uint32_t i = 0; i < n; i++) rows_out[i] = bandk::row_none(F.status[i]);
+    for (uint32_t k = 0; k < F.m; k++) {
+        const uint32_t i = F.cur[k];
+        rows_out[i] = E.too_big[k] ? bandk::row_none(S5GPU_STATUS_PATH_WIDE) : ((const s5gpu_ext_row_t *)h)[k];
+        if (rows_out[i].status != 0) F.status[i] = rows_out[i].status;
+    }
+}
+
 extern "C" int s5gpu_extend_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method, const s5gpu_event_params_t *ep,
                                   const s5gpu_map_params_t *mp_in, const s5gpu_band_params_t *bp, size_t scratch_max, const int16_t *ref_host, uint32_t R,
                                   s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *rows_out, uint64_t *ev_first_out, int32_t *lo_out, int32_t *hi_out,
@@ -90,90 +174,32 @@ extern "C" int s5gpu_extend_batch(uint32_t n, const void *const *rec, const size
         (rc = check_band_params(who, bp)))
         return rc;
     if (!ev_first_out || (rows_cap && (!lo_out || !hi_out))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
-    if (bp->skip != mp_in->skip || bp->scale != mp_in->scale || bp->clip != mp_in->clip) {
-        s5gpu_set_error("%s: skip, scale and clip of the band parameters are not those of the map parameters (the anchor is a column of the same query)", who);
-        return S5GPU_ERR_ARG;
-    }
+    if ((rc = bandk::check_band_agrees(who, mp_in, bp))) return rc;
     if (n == 0) { ev_first_out[0] = 0; return S5GPU_OK; }
     if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
-    if (scratch_max == 0) scratch_max = (size_t)1 << 30;
     s5gpu_map_params_t mp = *mp_in;
     mp.want_start = 1;                                                     // the anchor is the start
     dtwk::MapFront F;
     if ((rc = dtwk::map_front(n, rec, rec_len, rec_method, sig_method, ep, &mp, ref_host, R, F))) return rc;
     Ctx *c = F.hold.c;
-    const uint32_t m = F.m, T = bp->tile_rows;
+    const uint32_t m = F.m;
     const uint64_t total = F.total;
-    const uint32_t slot_words = dtwk::path_slot_words(T, bp->band);
-    std::vector<uint64_t> first(m + 1u, 0);
-    std::vector<uint8_t> too_big(m, 0);
     // in c->d_gather: the rows, the prefix rows, lo, hi and (wanted) a copy of the event rows, which come back in one copy; behind them the
     // long queries, their lengths and statuses, which do not
-    const size_t o_map = up(32ull * m, 16), o_lo = o_map + up(16ull * m, 16), o_hi = o_lo + up(4ull * total, 16), o_ev = o_hi + up(4ull * total, 16);
-    const size_t back = o_ev + (events_out ? 16ull * total : 0), o_q = up(back, 16), o_ql = o_q + up(2ull * total, 16), o_st = o_ql + up(4ull * m, 16);
+    bandk::ExtTail E;
     const uint8_t *h = nullptr;
     if (m) {
-        // the host has to know the reads' rows: the room the caller needs, and the groups
-        HIP_TRY(hipMemcpyAsync(first.data(), F.d_first, 8ull * (m + 1u), hipMemcpyDeviceToHost, c->st));
-        HIP_TRY(hipStreamSynchronize(c->st));
-        uint64_t room = 0;
-        for (uint32_t k = 0; k < m; k++) room += bandk::long_qlen(first[k + 1] - first[k], bp->skip, bp->emin, bp->emax);
-        if (room > rows_cap) {
-            ev_first_out[0] = room;
-            s5gpu_set_error("%s: room for %zu rows, %llu may be needed", who, rows_cap, (unsigned long long)room);
-            return S5GPU_ERR_NOMEM;
-        }
-        if ((rc = c->d_gather.reserve(o_st + 4ull * m + 64)) || (rc = c->h_out.reserve(back + 64))) return rc;
+        if ((rc = bandk::extend_tail(who, F, &mp, bp, scratch_max, R, events_out != nullptr, true, rows_cap, 0, &ev_first_out[0], E))) return rc;
         uint8_t *dg = (uint8_t *)c->d_gather.p;
-        s5gpu_ext_row_t *d_rows = (s5gpu_ext_row_t *)dg;
-        s5gpu_map_row_t *d_map = (s5gpu_map_row_t *)(dg + o_map);
-        int32_t *d_lo = (int32_t *)(dg + o_lo), *d_hi = (int32_t *)(dg + o_hi), *d_st = (int32_t *)(dg + o_st);
-        int16_t *d_q = (int16_t *)(dg + o_q);
-        uint32_t *d_ql = (uint32_t *)(dg + o_ql);
-        if ((rc = dtwk::launch_sdtw(m, F.d_q, mp.qmax, F.d_ql, F.d_ref, R, true, d_map, c->st)) ||
-            (rc = s5gpu_event_queries_long_dev(m, F.d_rows, F.d_first, F.d_est, bp, total, d_q, d_ql, d_st, c->st)))
-            return rc;
-        // consecutive reads while their scratch fits; a read that does not fit alone is passed over
-        size_t most = 0;
-        std::vector<uint32_t> cut(1, 0);
-        for (uint32_t b = 0; b < m;) {
-            uint32_t e = b;
-            size_t need = 0;
-            while (e < m) {
-                const size_t nx = (size_t)bandk::scratch_bytes(bandk::slot_count(first[e + 1] - first[b], T, e + 1u - b), slot_words);
-                if (nx > scratch_max) break;
-                need = nx;
-                e++;
-            }
-            if (e == b) { too_big[b] = 1; e = b + 1; }
-            most = need > most ? need : most;
-            cut.push_back(e);
-            b = e;
-        }
-        if ((rc = c->d_scan.reserve(most + 64))) return rc;
-        for (size_t g = 0; g + 1 < cut.size(); g++) {
-            const uint32_t b = cut[g], e = cut[g + 1];
-            if (too_big[b]) continue;
-            bandk::BandArgs A;
-            A.queries = d_q; A.first = F.d_first + b; A.qlen = d_ql + b; A.total_rows = total; A.ref = F.d_ref; A.R = R;
-            A.anchor = &d_map[b].start; A.anchor_stride = sizeof(s5gpu_map_row_t) / sizeof(int32_t); A.status_in = d_st + b; A.row0 = first[b];
-            A.T = T; A.band = bp->band; A.scratch = (uint32_t *)c->d_scan.p; A.slots = bandk::slot_count(first[e] - first[b], T, e - b);
-            A.slot_words = slot_words; A.tile_a = (int32_t *)((uint8_t *)c->d_scan.p + A.slots * ((uint64_t)slot_words * 256u));
-            A.rows_out = d_rows + b; A.lo = d_lo; A.hi = d_hi;
-            if ((rc = bandk::launch_band(e - b, A, c->st))) return rc;         // (the stream orders the groups: the scratch is used again)
-        }
-        if (events_out && total) HIP_TRY(hipMemcpyAsync(dg + o_ev, F.d_rows, 16ull * total, hipMemcpyDeviceToDevice, c->st));
-        HIP_TRY(hipMemcpyAsync(c->h_out.p, dg, back, hipMemcpyDeviceToHost, c->st));
+        if (events_out && total) HIP_TRY(hipMemcpyAsync(dg + E.o_ev, F.d_rows, 16ull * total, hipMemcpyDeviceToDevice, c->st));
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, dg, E.back, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
         h = (const uint8_t *)c->h_out.p;
     }
+    const std::vector<uint64_t> &first = E.first;
+    const size_t o_map = E.o_map, o_lo = E.o_lo, o_hi = E.o_hi, o_ev = E.o_ev;
     dtwk::scatter_rows(F, n, h ? (const s5gpu_map_row_t *)(h + o_map) : nullptr, nullptr, map_rows_out);
-    for (uint32_t i = 0; i < n; i++) rows_out[i] = bandk::row_none(F.status[i]);
-    for (uint32_t k = 0; k < m; k++) {
-        const uint32_t i = F.cur[k];
-        rows_out[i] = too_big[k] ? bandk::row_none(S5GPU_STATUS_PATH_WIDE) : ((const s5gpu_ext_row_t *)h)[k];
-        if (rows_out[i].status != 0) F.status[i] = rows_out[i].status;
-    }
+    bandk::scatter_ext_rows(F, n, E, h, rows_out);
     uint64_t at = 0;                                                       // the rows of record i: [ev_first_out[i], ev_first_out[i + 1]), in record order
     std::vector<uint32_t> of(n, 0xFFFFFFFFu);
     for (uint32_t k = 0; k < m; k++) of[F.cur[k]] = k;

@@ -2,12 +2,17 @@
 // checks and launches of the two device entry points, and the per-file handle: s5gpu_pileup_add_batch runs the chain of s5gpu_align_batch
 // (the front of dtw_host.h -> sDTW with the start -> the paths -> the query's event rows gathered) and adds the batch to the handle's
 // accumulator with k_pileup; the rows and statuses are all that comes back.  s5gpu_pileup_close makes the one download of the table.
-#include "dtw_host.h"
+// Whole reads (§4.22): the ragged call, and a handle of a second kind whose add runs the device side of s5gpu_extend_batch (band_host.h)
+// and adds the ragged paths it leaves on the device.
+#include "band_host.h"
 #include "pileup_dev.h"
 
 namespace {
 
 struct Handle {
+    bool whole = false;                                                    // opened by s5gpu_pileup_open_whole: bp and scratch_max count, wmax does not
+    s5gpu_band_params_t bp;
+    size_t scratch_max = 0;
     void *d_acc = nullptr;
     s5gpu_event_params_t ep;
     s5gpu_map_params_t mp;
@@ -71,6 +76,7 @@ extern "C" int s5gpu_pileup_add_batch(void *handle, uint32_t n, const void *cons
     const char *who = "s5gpu_pileup_add_batch";
     Handle *h = (Handle *)handle;
     if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
+    if (h->whole) { s5gpu_set_error("%s: the handle is one of s5gpu_pileup_open_whole", who); return S5GPU_ERR_ARG; }
     const uint32_t R = (uint32_t)h->ref.size(), qmax = h->mp.qmax;
     int rc;
     if ((rc = dtwk::map_front_check(who, n, rec, rec_len, rec_method, sig_method, &h->ep, &h->mp, h->ref.data(), R, true))) return rc;
@@ -105,4 +111,96 @@ extern "C" int s5gpu_pileup_close(void *handle, void *acc_out) {
     const int rc = s5host::acc_close(h->d_acc, s5gpu_pileup_bytes((uint32_t)h->ref.size()), acc_out, true);
     delete h;
     return rc;
+}
+
+extern "C" size_t s5gpu_pileup_long_work_bytes(uint32_t n, uint64_t total_rows) {
+    if (total_rows > pilek::LONG_ROWS_MAX) return 0;
+    return (size_t)pilek::long_work(n, total_rows).bytes;
+}
+
+extern "C" int s5gpu_pileup_accum_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows, const int16_t *ref,
+                                           uint32_t R, const int32_t *lo, const int32_t *hi, const int32_t *status, const s5gpu_event_t *events, uint32_t ev_skip,
+                                           void *work, size_t work_bytes, void *acc, void *stream) {
+    const char *who = "s5gpu_pileup_accum_long_dev";
+    if (!acc_ok(who, acc, R)) return S5GPU_ERR_ARG;
+    if (!ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
+    if (total_rows > pilek::LONG_ROWS_MAX) { s5gpu_set_error("%s: %llu rows in all (at most 2^40)", who, (unsigned long long)total_rows); return S5GPU_ERR_ARG; }
+    if (n == 0) return S5GPU_OK;
+    if (!first || !qlen || !status || !work || (total_rows && (!queries || !lo || !hi))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+    if (((uintptr_t)queries & 1u) || ((uintptr_t)first & 7u) || ((uintptr_t)qlen & 3u) || ((uintptr_t)ref & 1u) || ((uintptr_t)lo & 3u) || ((uintptr_t)hi & 3u) ||
+        ((uintptr_t)status & 3u) || ((uintptr_t)events & 15u) || ((uintptr_t)work & 15u)) {
+        s5gpu_set_error("%s: misaligned argument (first: 8 bytes; events, work: 16)", who);
+        return S5GPU_ERR_ARG;
+    }
+    const uint64_t need = pilek::long_work(n, total_rows).bytes;
+    if ((uint64_t)work_bytes < need) {
+        s5gpu_set_error("%s: a work area of %zu bytes, %llu are needed", who, work_bytes, (unsigned long long)need);
+        return S5GPU_ERR_NOMEM;
+    }
+    pilek::PileLongArgs A;
+    A.n = n; A.queries = queries; A.first = first; A.qlen = qlen; A.total_rows = total_rows; A.ref = ref; A.R = R; A.lo = lo; A.hi = hi; A.status = status;
+    A.events = events; A.ev_skip = events ? ev_skip : 0u; A.work = work; A.acc = acc;
+    return pilek::launch_pileup_long(A, (hipStream_t)stream);
+}
+
+extern "C" void *s5gpu_pileup_open_whole(const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const s5gpu_band_params_t *bp, size_t scratch_max,
+                                         const int16_t *ref_host, uint32_t R) {
+    const char *who = "s5gpu_pileup_open_whole";
+    if (dtwk::map_front_check(who, 0, nullptr, nullptr, S5GPU_REC_NONE, S5GPU_SIG_NONE, ep, mp, ref_host, R, true)) return nullptr;
+    if (bandk::check_band_params(who, bp) || bandk::check_band_agrees(who, mp, bp)) return nullptr;
+    if (R > pilek::RMAX) { s5gpu_set_error("%s: a table of %u columns (1 .. 2^26)", who, R); return nullptr; }
+    if (s5host::n_devices() == 0) { s5gpu_set_error("%s: no device", who); return nullptr; }
+    Handle *h = new Handle;
+    h->whole = true; h->ep = *ep; h->mp = *mp; h->mp.want_start = 1; h->bp = *bp; h->scratch_max = scratch_max;
+    h->ref.assign(ref_host, ref_host + R);
+    h->d_acc = s5host::acc_open(who, s5gpu_pileup_bytes(R), [R](void *acc, hipStream_t st) { return pilek::launch_reset(acc, R, st); });
+    if (!h->d_acc) { delete h; return nullptr; }
+    return h;
+}
+
+extern "C" int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                                            s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out) {
+    const char *who = "s5gpu_pileup_add_batch_whole";
+    Handle *h = (Handle *)handle;
+    if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
+    if (!h->whole) { s5gpu_set_error("%s: the handle is one of s5gpu_pileup_open", who); return S5GPU_ERR_ARG; }
+    const uint32_t R = (uint32_t)h->ref.size();
+    int rc;
+    if ((rc = dtwk::map_front_check(who, n, rec, rec_len, rec_method, sig_method, &h->ep, &h->mp, h->ref.data(), R, true))) return rc;
+    if (n == 0) return S5GPU_OK;
+    if (s5host::n_devices() == 0) return S5GPU_ERR_NODEV;
+    dtwk::MapFront F;
+    if ((rc = dtwk::map_front(n, rec, rec_len, rec_method, sig_method, &h->ep, &h->mp, h->ref.data(), R, F))) return rc;
+    Ctx *c = F.hold.c;
+    const uint32_t m = F.m;
+    bandk::ExtTail E;
+    const uint8_t *hb = nullptr;
+    if (m) {
+        // the chain of s5gpu_extend_batch; its scratch serves as the work area afterwards (the stream orders them)
+        const size_t work_bytes = (size_t)pilek::long_work(m, F.total).bytes;
+        uint64_t room = 0;
+        if ((rc = bandk::extend_tail(who, F, &h->mp, &h->bp, h->scratch_max, R, false, false, ~(size_t)0, work_bytes, &room, E))) return rc;
+        uint8_t *dg = (uint8_t *)c->d_gather.p;
+        HIP_TRY(hipMemcpyAsync(c->h_out.p, dg, E.o_lo, hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        // a read's status is its result row's, which the host has to complete for the reads that were passed over: up again, over the long
+        // queries' statuses, which have served
+        hb = (const uint8_t *)c->h_out.p;
+        int32_t *h_st = (int32_t *)((uint8_t *)c->h_out.p + E.o_lo);
+        for (uint32_t k = 0; k < m; k++) h_st[k] = E.too_big[k] ? S5GPU_STATUS_PATH_WIDE : ((const s5gpu_ext_row_t *)hb)[k].status;
+        HIP_TRY(hipMemcpyAsync(dg + E.o_st, h_st, 4ull * m, hipMemcpyHostToDevice, c->st));
+        if ((rc = s5gpu_pileup_accum_long_dev(m, (const int16_t *)(dg + E.o_q), F.d_first, (const uint32_t *)(dg + E.o_ql), F.total, F.d_ref, R,
+                                              (const int32_t *)(dg + E.o_lo), (const int32_t *)(dg + E.o_hi), (const int32_t *)(dg + E.o_st), F.d_rows, h->bp.skip,
+                                              c->d_scan.p, work_bytes, h->d_acc, c->st)))
+            return rc;
+    }
+    if ((rc = pilek::launch_add_skipped(h->d_acc, n - m, c->st))) return rc;     // the records that were dropped
+    HIP_TRY(hipStreamSynchronize(c->st));                                  // the next holder of this context overwrites the batch
+    dtwk::scatter_rows(F, n, hb ? (const s5gpu_map_row_t *)(hb + E.o_map) : nullptr, nullptr, map_rows_out);
+    std::vector<s5gpu_ext_row_t> own;
+    if (!ext_rows_out) { own.resize(n); ext_rows_out = own.data(); }      // (the statuses come from the rows)
+    bandk::scatter_ext_rows(F, n, E, hb, ext_rows_out);
+    if (status_out) memcpy(status_out, F.status, sizeof(int32_t) * n);
+    if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0; it counts in reads_skipped)", who); return S5GPU_ERR_DATA; }
+    return S5GPU_OK;
 }

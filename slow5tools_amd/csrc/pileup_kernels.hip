@@ -14,6 +14,25 @@
 //   4. queries, lo, hi and events are read at [read * qpitch + row] for row < Q only, qlen and status at [read] for read < n;
 //   5. the only barriers are those around the LDS reset and the flush, reached by every thread: no thread returns early;
 //   6. vector stores and HIP atomics only, no inline assembly.
+// Whole reads (§4.22): the ragged layout of s5gpu_sdtw_band_dev, the unit of work a segment of S rows of one read.
+//   k_pileup_long_plan  : one workgroup: the layout checks of every read -> its verdict word; P, the exclusive prefix of the reads' segments
+//   k_pileup_long_check : a wave per segment validates its rows (the first against the row before it in the ragged array); a failure ORs
+//                         V_BAD into the read's verdict.  The kernel boundary makes the verdicts final.  With the sort on it also counts
+//                         the segments by the column block of their first lo.
+//   k_pileup_long_scan  : the rest of the counting sort: the counts' prefix, then k_pileup_long_check once more (pass 1) as the scatter
+//                         that writes the segments (read, segment) in the order of that key
+//   k_pileup_long_accum : k_pileup over a slice of the (ordered) segments, a wave per segment at a time; segments of reads whose verdict
+//                         is not V_USED are passed over; the reads are counted once each, from the verdicts
+// Their rules, beside 2, 3 (per row), 5 and 6 above:
+//   7. first, qlen and status are read at [read] (first also at [read + 1]) for read < n; a read has segments only behind long_verdict:
+//      first[k] + Q + ev_skip <= first[k + 1] <= total_rows, Q <= 2^20, so queries, lo, hi at [first[k] + i] and events at
+//      [first[k] + ev_skip + i] are inside their arrays for every i < Q, and hi[first[k] + i - 1] for 0 < i;
+//   8. trip counts come from qlen, R, S, n and total_rows: a segment has at most S rows, segment numbers run below P[n], the sum of
+//      ceil(Q / S), and a step from one segment's read to the next's takes at most n trips in all;
+//   9. nothing of a read is accumulated unless k_pileup_long_check has passed every row of every one of its segments;
+//  10. the sort's key is clamped below LONG_KEYS and indexes the counts only; a position in the ordered list is used behind `< cap`, and
+//      a list that would not fit (P[n] > cap: only a layout whose reads overlap) is not made: the segments are then walked in P's order;
+//  11. branches on a read's or a segment's fate are wave-uniform: they depend on values every lane of the wave reads from the same address.
 #include <string.h>
 
 #include "dev_common.h"
@@ -27,6 +46,12 @@ namespace {
 
 uint32_t g_cols = MAX_COLS;        // option "pileup_lds_cols"
 uint32_t g_grid = MAX_GRID;        // option "pileup_grid"
+uint32_t g_long_seg = 256;         // option "pileup_long_seg"
+uint32_t g_long_cols = MAX_COLS;   // option "pileup_long_cols"
+uint32_t g_long_sort = 1;          // option "pileup_long_sort"
+uint32_t g_long_grid = MAX_GRID;   // option "pileup_long_grid"
+uint32_t g_long_passes = 7;        // option "pileup_long_passes"
+int set_option_long(const char *key, long value);
 
 struct DevOps {
     static __device__ __forceinline__ void add64(uint64_t *p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
@@ -136,7 +161,7 @@ int pilek::set_option(const char *key, long value) {
         return S5GPU_OK;
     }
     if (strcmp(key, "pileup_grid") == 0 && value >= 1 && value <= (long)MAX_GRID) { g_grid = (uint32_t)value; return S5GPU_OK; }
-    return S5GPU_ERR_ARG;
+    return set_option_long(key, value);
 }
 
 int pilek::launch_reset(void *acc, uint32_t R, hipStream_t st) {
@@ -161,5 +186,242 @@ int pilek::launch_pileup(uint32_t n, const PileArgs &A, hipStream_t st) {
     const uint32_t grid = (uint32_t)(((uint64_t)n + per - 1) / per);
     hipLaunchKernelGGL(k_pileup, dim3(grid), dim3(s5::NT), (size_t)cols * sizeof(s5gpu_pile_col_t), st, n, per, A, cols);
     PILE_LAUNCH_CHECK("k_pileup");
+    return S5GPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- whole reads (§4.22)
+
+namespace {
+
+struct LongPtrs {
+    uint32_t *verdict;               // [n]
+    uint64_t *P;                     // [n + 1]
+    uint32_t *hist, *cursor;         // [LONG_KEYS] each
+    uint64_t *order;                 // [cap]: read << 32 | segment
+    uint64_t cap;
+};
+
+// the slice [*b, *e) of `total` items that part `who` of `parts` takes
+__device__ __forceinline__ void slice_of(uint64_t total, uint64_t who, uint64_t parts, uint64_t *b, uint64_t *e) {
+    const uint64_t per = (total + parts - 1u) / parts;
+    *b = who * per < total ? who * per : total;
+    *e = *b + per < total ? *b + per : total;
+}
+
+}  // namespace
+
+// One workgroup.  verdict[k] and P for every read; the sort's counts zeroed.
+__global__ __launch_bounds__(s5::NT) void k_pileup_long_plan(PileLongArgs A, uint32_t S, LongPtrs L) {
+    __shared__ uint32_t s_scan[s5::NT];
+    __shared__ uint64_t s_carry;
+    for (uint32_t t = threadIdx.x; t < LONG_KEYS; t += s5::NT) L.hist[t] = 0u;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (uint64_t c = 0; c < A.n; c += s5::NT) {                           // (the same trips for every thread)
+        const uint64_t k = c + threadIdx.x;
+        uint32_t segs = 0;
+        if (k < A.n) {
+            const uint32_t Q = A.qlen[k];
+            const uint32_t v = long_verdict(A.first[k], A.first[k + 1], Q, A.status[k], A.total_rows, A.ev_skip);
+            L.verdict[k] = v;
+            segs = v == V_USED ? segs_of(Q, S) : 0u;
+        }
+        s_scan[threadIdx.x] = segs;
+        __syncthreads();
+        for (uint32_t d = 1; d < (uint32_t)s5::NT; d <<= 1) {               // inclusive, Hillis and Steele: at most 256 * 2^14
+            const uint32_t add = threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0u;
+            __syncthreads();
+            s_scan[threadIdx.x] += add;
+            __syncthreads();
+        }
+        const uint64_t carry = s_carry;
+        if (k < A.n) L.P[k] = carry + s_scan[threadIdx.x] - segs;
+        __syncthreads();
+        if (threadIdx.x == s5::NT - 1) s_carry = carry + s_scan[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) L.P[A.n] = s_carry;
+}
+
+// A wave per segment, each wave a slice of the segments in P's order.  pass 0: the rows validated, and (sort) the segment counted under its
+// key; pass 1 (sort only, behind k_pileup_long_scan): the segment put at its place in the ordered list.
+__global__ __launch_bounds__(s5::NT) void k_pileup_long_check(PileLongArgs A, uint32_t S, LongPtrs L, uint32_t sort, uint32_t pass) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t total = L.P[A.n];
+    const bool sorted = sort && total <= L.cap;
+    if (pass == 1 && !sorted) return;                                      // (no barrier in this kernel)
+    uint64_t g, end;
+    slice_of(total, (uint64_t)blockIdx.x * s5::NW + (threadIdx.x >> 6), (uint64_t)gridDim.x * s5::NW, &g, &end);
+    uint32_t k = g < end ? seg_find(L.P, A.n, g) : 0u;
+    for (; g < end; g++) {
+        k = seg_next(L.P, A.n, k, g);
+        const uint32_t Q = A.qlen[k], s = (uint32_t)(g - L.P[k]);
+        if (s >= segs_of(Q < LONG_QMAX ? Q : LONG_QMAX, S)) continue;      // (cannot be: P was made of these)
+        uint32_t r0, r1;
+        seg_rows(Q, S, s, &r0, &r1);
+        const uint64_t f = A.first[k];
+        const int32_t *lo = A.lo + f, *hi = A.hi + f;
+        if (pass == 0) {
+            const bool ok = seg_rows_ok(r0, r1, lane, 64u, lo, hi, A.R);
+            if (!__all(ok ? 1 : 0) && lane == 0) atomicOr(&L.verdict[k], V_BAD);
+        }
+        if (sorted && lane == 0) {
+            const uint32_t key = seg_key(lo[r0], A.R);
+            if (pass == 0) atomicAdd(&L.hist[key], 1u);
+            else {
+                const uint64_t at = atomicAdd(&L.cursor[key], 1u);
+                if (at < L.cap) L.order[at] = (uint64_t)k << 32 | s;
+            }
+        }
+    }
+}
+
+// One workgroup of LONG_KEYS threads: cursor = the exclusive prefix of hist (32-bit counts: launch_pileup_long sorts below 2^32 segments only);
+// hist is left zeroed, as the plan leaves it: a check pass launched again on its own (pileup_long_passes) counts from nothing
+__global__ __launch_bounds__(LONG_KEYS) void k_pileup_long_scan(LongPtrs L) {
+    __shared__ uint32_t s_scan[LONG_KEYS];
+    const uint32_t own = L.hist[threadIdx.x];
+    L.hist[threadIdx.x] = 0u;
+    s_scan[threadIdx.x] = own;
+    __syncthreads();
+    for (uint32_t d = 1; d < LONG_KEYS; d <<= 1) {
+        const uint32_t add = threadIdx.x >= d ? s_scan[threadIdx.x - d] : 0u;
+        __syncthreads();
+        s_scan[threadIdx.x] += add;
+        __syncthreads();
+    }
+    L.cursor[threadIdx.x] = s_scan[threadIdx.x] - own;
+}
+
+namespace {
+// Item `it` of the list the accumulate kernel walks -> *k, and the rows [*r0, *r1) of its segment; false: nothing of it is accumulated (its
+// read is not V_USED).  Unsorted, *k comes in as the read of an earlier item of the same wave, or as n before its first.
+__device__ __forceinline__ bool long_item(const PileLongArgs &A, uint32_t S, const LongPtrs &L, bool sorted, uint64_t it, uint32_t *k, uint32_t *r0, uint32_t *r1) {
+    uint32_t s;
+    if (sorted) {
+        const uint64_t e = L.order[it];                                    // (it < P[n] <= cap)
+        *k = (uint32_t)(e >> 32);
+        s = (uint32_t)e;
+        if (*k >= A.n) return false;
+    } else {
+        *k = *k < A.n ? seg_next(L.P, A.n, *k, it) : seg_find(L.P, A.n, it);
+        s = (uint32_t)(it - L.P[*k]);
+    }
+    const uint32_t Q = A.qlen[*k];
+    if (L.verdict[*k] != V_USED || Q > LONG_QMAX || s >= segs_of(Q, S)) return false;   // (the last two cannot be: the list was made of P)
+    seg_rows(Q, S, s, r0, r1);
+    return true;
+}
+}  // namespace
+
+// per workgroup a slice of the (ordered) segments, a wave per segment at a time; cols as in k_pileup
+__global__ __launch_bounds__(s5::NT) void k_pileup_long_accum(PileLongArgs A, uint32_t S, LongPtrs L, uint32_t sort, uint32_t cols) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t pile_win[];   // cols columns of COL_WORDS words
+    __shared__ uint32_t s_lo;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (uint32_t t = threadIdx.x; t < cols * COL_WORDS; t += s5::NT) pile_win[t] = t % COL_WORDS == 5 ? EMPTY_MINMAX : 0ull;
+    if (threadIdx.x == 0) s_lo = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint64_t total = L.P[A.n];
+    const bool sorted = sort && total <= L.cap;
+    uint64_t base, end;
+    slice_of(total, blockIdx.x, gridDim.x, &base, &end);
+    // the anchor: the smallest first lo of the segments the four waves meet first (where it lies changes the time, never the result)
+    uint32_t k = A.n, r0, r1;
+    if (cols && base + wave < end && long_item(A, S, L, sorted, base + wave, &k, &r0, &r1)) {
+        const int32_t l0 = A.lo[A.first[k] + r0];
+        if (lane == 0 && l0 >= 0 && (uint32_t)l0 < A.R) atomicMin(&s_lo, (uint32_t)l0);
+    }
+    __syncthreads();
+    Window W;
+    W.lo = s_lo == 0xFFFFFFFFu ? 0u : s_lo;
+    W.cols = cols;
+    s5gpu_pile_col_t *win = reinterpret_cast<s5gpu_pile_col_t *>(pile_win);
+    uint64_t *head = reinterpret_cast<uint64_t *>(A.acc);
+    s5gpu_pile_col_t *table = reinterpret_cast<s5gpu_pile_col_t *>(head + HEAD_WORDS);
+    uint64_t cells = 0, cost = 0;                                          // this lane's
+    k = A.n;
+    for (uint64_t it = base + wave; it < end; it += s5::NW) {
+        if (!long_item(A, S, L, sorted, it, &k, &r0, &r1)) continue;       // (the wave's branch)
+        const uint64_t f = A.first[k];
+        seg_cells<DevOps>(r0, r1, lane, 64u, A.lo + f, A.hi + f, A.queries + f, A.events ? A.events + f + A.ev_skip : nullptr, A.ref, A.R, W, win, table,
+                          &cells, &cost);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < cols; b += s5::NT) {               // the flush: the non-empty columns of the window
+        const uint32_t j = W.lo + b;
+        if (j >= W.lo && j < A.R) col_merge<DevOps>(table + j, win + b);
+    }
+    // the reads, once each
+    uint64_t used = 0, skipped = 0, bad = 0;
+    for (uint64_t k = (uint64_t)blockIdx.x * s5::NT + threadIdx.x; k < A.n; k += (uint64_t)gridDim.x * s5::NT) {
+        const uint32_t v = L.verdict[k];
+        if (v & V_SKIPPED) skipped++;
+        else if (v & V_BAD) bad++;
+        else used++;
+    }
+    used = wave_sum(used);
+    skipped = wave_sum(skipped);
+    bad = wave_sum(bad);
+    cells = wave_sum(cells);
+    cost = wave_sum(cost);
+    if (lane == 0) {
+        if (used) DevOps::add64(head + 0, used);
+        if (skipped) DevOps::add64(head + 1, skipped);
+        if (bad) DevOps::add64(head + 2, bad);
+        if (cells) DevOps::add64(head + 3, cells);
+        if (cost) DevOps::add64(head + 4, cost);
+    }
+}
+
+namespace {
+int set_option_long(const char *key, long value) {
+    const bool pow2 = value > 0 && (value & (value - 1)) == 0;
+    if (strcmp(key, "pileup_long_seg") == 0 && pow2 && value >= (long)SEG_MIN && value <= (long)SEG_MAX) { g_long_seg = (uint32_t)value; return S5GPU_OK; }
+    if (strcmp(key, "pileup_long_cols") == 0 && (value == 0 || (pow2 && value >= (long)MIN_COLS && value <= (long)MAX_COLS))) {
+        g_long_cols = (uint32_t)value;
+        return S5GPU_OK;
+    }
+    if (strcmp(key, "pileup_long_sort") == 0 && (value == 0 || value == 1)) { g_long_sort = (uint32_t)value; return S5GPU_OK; }
+    if (strcmp(key, "pileup_long_grid") == 0 && value >= 1 && value <= (long)MAX_GRID) { g_long_grid = (uint32_t)value; return S5GPU_OK; }
+    // which kernels a ragged call launches: 1 the plan, 2 the check (and the sort), 4 the accumulate, over what an earlier call left in the
+    // work area; 7 all (the default).  For tools/pileup_long_time.py: the passes are timed apart (as "sdtw_band_passes").
+    if (strcmp(key, "pileup_long_passes") == 0 && value >= 1 && value <= 7) { g_long_passes = (uint32_t)value; return S5GPU_OK; }
+    return S5GPU_ERR_ARG;
+}
+}  // namespace
+
+int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) {
+    if (A.n == 0) return S5GPU_OK;
+    const uint32_t S = g_long_seg, cols = g_long_cols;
+    const LongWork w = long_work(A.n, A.total_rows);
+    uint8_t *wk = (uint8_t *)A.work;
+    LongPtrs L;
+    L.verdict = (uint32_t *)(wk + w.o_verdict); L.P = (uint64_t *)(wk + w.o_prefix); L.hist = (uint32_t *)(wk + w.o_hist);
+    L.cursor = (uint32_t *)(wk + w.o_cursor); L.order = (uint64_t *)(wk + w.o_order); L.cap = long_order_cap(A.n, A.total_rows);
+    // (the sort's counts are 32-bit: a list that 2^32 segments might not fit is walked in P's order)
+    const uint32_t sort = g_long_sort && L.cap < ((uint64_t)1 << 32) ? 1u : 0u;
+    const uint64_t most = A.total_rows / S + A.n, quads = (most + 3u) / 4u;  // the segments of a well-formed layout, at most
+    const uint32_t grid = (uint32_t)(quads < g_long_grid ? quads : g_long_grid);
+    const uint32_t passes = g_long_passes;
+    if (passes & 1u) {
+        hipLaunchKernelGGL(k_pileup_long_plan, dim3(1), dim3(s5::NT), 0, st, A, S, L);
+        PILE_LAUNCH_CHECK("k_pileup_long_plan");
+    }
+    if (passes & 2u) {
+        hipLaunchKernelGGL(k_pileup_long_check, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sort, 0u);
+        PILE_LAUNCH_CHECK("k_pileup_long_check");
+    }
+    if (sort && (passes & 2u)) {
+        hipLaunchKernelGGL(k_pileup_long_scan, dim3(1), dim3(LONG_KEYS), 0, st, L);
+        PILE_LAUNCH_CHECK("k_pileup_long_scan");
+        hipLaunchKernelGGL(k_pileup_long_check, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sort, 1u);
+        PILE_LAUNCH_CHECK("k_pileup_long_check (scatter)");
+    }
+    if (passes & 4u) {
+        hipLaunchKernelGGL(k_pileup_long_accum, dim3(grid), dim3(s5::NT), (size_t)cols * sizeof(s5gpu_pile_col_t), st, A, S, L, sort, cols);
+        PILE_LAUNCH_CHECK("k_pileup_long_accum");
+    }
     return S5GPU_OK;
 }

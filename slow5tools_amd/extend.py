@@ -108,15 +108,17 @@ def band_dev(queries, first, qlen, ref_tensor, anchor, status=None, params=None,
     return rows[:n], lo[:total], hi[:total]
 
 
-def extend_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=EMAX, tile_rows=TILE_ROWS, band=BAND, host=True):
+def extend_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=EMAX, tile_rows=TILE_ROWS, band=BAND, host=True,
+               events=None):
     """events, the prefix queries, sDTW with the start, the long queries and the banded alignment from `start`, on what
     press.decode_to_device left on the device -> (MAP_ROW array of the prefix mapping, Extended(rows, first, queries, qlen, lo, hi)).
     host=True: numpy arrays (rows an EXT_ROW array, first uint64); False: the device tensors, and the prefix rows as an [n, 4] int32 tensor.
     ref: the quantised reference, an int16 numpy array or a device tensor.  The prefix query is rows [skip, skip + qmax) of a read, at least
-    qmin of them; the long query rows [skip, skip + emax), with the same skip, scale and clip."""
+    qmin of them; the long query rows [skip, skip + emax), with the same skip, scale and clip.  events: the (rows, first) that
+    events.events_dev(dec, event_params, "raw") returned, for a caller that has them already."""
     import torch
 
-    ev, first = _events.events_dev(dec, event_params, "raw")
+    ev, first = _events.events_dev(dec, event_params, "raw") if events is None else events
     fst = dec.t_fields.view(torch.int32).view(-1, 16)[:dec.n, 0].contiguous()          # s5gpu_rec_fields_t.status
     q, ql, st = _map.queries_dev(ev, first, fst, skip, qmax, qmin, scale, clip)
     r = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int16))

@@ -12,6 +12,13 @@ batches or streams.
   pileup_dev  : a DecodedDev -> events, queries, sDTW, paths, then accum_dev
   Pileup      : records -> a per-file handle (s5gpu_pileup_add_batch); close() makes the one download
   file_pileup : a .blow5 file and a reference file -> a PILE_LINE array through the s5pileup tool
+
+Whole reads (§4.22): the same table from all of a read's events, over the ragged paths of extend (extend.py).
+  work_bytes_long  : the bytes of the work area of a ragged call
+  accum_long_dev   : queries, first, qlen, lo, hi and status as extend.band_dev left them, into an accumulator tensor
+  pileup_whole_dev : a DecodedDev -> extend.extend_dev(host=False), then accum_long_dev
+  PileupWhole      : records -> a per-file handle (s5gpu_pileup_add_batch_whole)
+  file_pileup(whole=True) : s5pileup --whole
 """
 import ctypes as C
 import os
@@ -23,6 +30,7 @@ from . import _lib
 from . import align as _align
 from . import build as _build
 from . import events as _events
+from . import extend as _extend
 from . import map as _map
 from ._lib import REC_ZLIB, SIG_SVB_ZD, check
 from .events import DNA, RNA  # noqa: F401  (RNA: for callers)
@@ -121,6 +129,63 @@ def pileup_dev(dec, ref, acc, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN,
     return acc, st
 
 
+def work_bytes_long(n, total_rows):
+    """s5gpu_pileup_long_work_bytes (0: a total_rows the call refuses)"""
+    return int(_lib.lib().s5gpu_pileup_long_work_bytes(int(n), int(total_rows)))
+
+
+def accum_long_dev(queries, first, qlen, ref_tensor, lo, hi, status, acc, events=None, ev_skip=0):
+    """The ragged accumulate: queries [total_rows] int16, first [n + 1] int64 (the prefix events.events_dev returns), qlen [n] int32,
+    ref_tensor [R] int16, lo and hi [total_rows] int32, status [n] int32 and, when given, events [total_rows, 4] int32 (the reads' event rows;
+    the samples of row i of read k are those of row first[k] + ev_skip + i), all on the device of acc, an accumulator of R columns.
+    Asynchronous, on the current stream.  Returns acc."""
+    import torch
+
+    if queries.dtype != torch.int16 or ref_tensor.dtype != torch.int16 or queries.dim() != 1 or ref_tensor.dim() != 1:
+        raise ValueError("accum_long_dev: queries [total_rows] and ref_tensor [R] are int16 tensors")
+    n, total, R = int(first.numel()) - 1, int(queries.numel()), int(ref_tensor.numel())
+    if first.dtype != torch.int64 or n < 0 or int(qlen.numel()) != n or int(status.numel()) != n:
+        raise ValueError("accum_long_dev: first is an [n + 1] int64 tensor, qlen and status have n entries")
+    if lo.dtype != torch.int32 or hi.dtype != torch.int32 or tuple(lo.shape) != (total,) or tuple(hi.shape) != (total,):
+        raise ValueError("accum_long_dev: lo and hi are [total_rows] int32 tensors")
+    if acc.dtype != torch.uint8 or int(acc.numel()) != acc_bytes(R):
+        raise ValueError("accum_long_dev: acc is not an accumulator of %d columns" % R)
+    if events is not None and (events.dtype != torch.int32 or tuple(events.shape) != (total, 4)):
+        raise ValueError("accum_long_dev: events is a [total_rows, 4] int32 tensor")
+    queries, first, ref_tensor, lo, hi = queries.contiguous(), first.contiguous(), ref_tensor.contiguous(), lo.contiguous(), hi.contiguous()
+    qlen, status = qlen.to(torch.int32).contiguous(), status.to(torch.int32).contiguous()
+    events = events.contiguous() if events is not None else None
+    dev = acc.device
+    need = work_bytes_long(n, total)
+    work = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+    check(_lib.lib().s5gpu_pileup_accum_long_dev(n, ptr(queries), first.data_ptr(), ptr(qlen), total, ptr(ref_tensor), R, ptr(lo), ptr(hi), ptr(status),
+                                                 ptr(events), int(ev_skip), work.data_ptr(), need, acc.data_ptr(),
+                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_pileup_accum_long_dev")
+    for t in (queries, first, ref_tensor, lo, hi, qlen, status, events, work):
+        if t is not None:
+            t.record_stream(torch.cuda.current_stream(dev))
+    return acc
+
+
+def pileup_whole_dev(dec, ref, acc, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX,
+                     tile_rows=_extend.TILE_ROWS, band=_extend.BAND):
+    """extend.extend_dev(host=False) on what press.decode_to_device left on the device, then accum_long_dev of all of every read's rows into
+    acc; nothing comes to the host.  Returns (acc, status, ext_rows): the [n] int32 statuses of the reads (0: the read was offered to the
+    table) and the [n, 4] int64 tensor of EXT_ROW records, both on the device."""
+    import torch
+
+    ev, first = _events.events_dev(dec, event_params, "raw")               # (kept: the samples of a row are its event's length)
+    r = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int16))
+    r = r.to(dec.dev)
+    _, x = _extend.extend_dev(dec, r, event_params, skip, qmax, qmin, scale, clip, emax, tile_rows, band, host=False, events=(ev, first))
+    st = (x.rows[:, 3] >> 32).to(torch.int32)                              # EXT_ROW.status
+    accum_long_dev(x.queries, x.first, x.qlen, r, x.lo, x.hi, st, acc, ev, skip)
+    return acc, st, x.rows
+
+
 class Pileup:
     """One file's table on the first device in use: add(records) per batch, close() -> (total, cols) and the end of the handle.  ref: the
     quantised reference (int16).  Also a context manager: leaving it abandons a handle that was not closed."""
@@ -171,14 +236,51 @@ class Pileup:
         return False
 
 
-def file_pileup(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, wmax=None, min_depth=1, raise_on_corrupt=True):
+class PileupWhole(Pileup):
+    """Pileup for whole reads: add(records) runs extend's chain (s5gpu_pileup_add_batch_whole) and returns (rc, MAP_ROW array of the prefix
+    mapping, EXT_ROW array, status).  close, abandon and the context manager are Pileup's."""
+
+    def __init__(self, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX, tile_rows=_extend.TILE_ROWS,
+                 band=_extend.BAND, scratch_max=0):
+        r = np.ascontiguousarray(ref, dtype=np.int16)
+        ep, mp = _events._params(event_params), _map._params(skip, qmax, qmin, scale, clip, True)
+        bp = _extend.BandParams(skip, qmin, emax, tile_rows, band, clip, scale)
+        self.R = len(r)
+        self._h = _lib.lib().s5gpu_pileup_open_whole(C.byref(ep), C.byref(mp), C.byref(bp), int(scratch_max), r.ctypes.data_as(C.c_void_p), len(r))
+        if not self._h:
+            raise _lib.S5GpuError("s5gpu_pileup_open_whole failed: %s" % _lib.lib().s5gpu_last_error().decode(errors="replace"))
+
+    def add(self, records, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, raise_on_error=True):
+        if self._h is None:
+            raise _lib.S5GpuError("pileup handle: already closed")
+        n = len(records)
+        vp = C.c_void_p
+        rb = [bytes(x) for x in records]
+        rbuf = [C.create_string_buffer(x, max(len(x), 1)) for x in rb]
+        rec_p = (vp * max(n, 1))(*[C.addressof(b) for b in rbuf])
+        rl = (C.c_size_t * max(n, 1))(*[len(x) for x in rb])
+        map_rows, rows, status = np.zeros(n, dtype=MAP_ROW), np.zeros(n, dtype=_extend.EXT_ROW), np.zeros(n, dtype=np.int32)
+        rc = _lib.lib().s5gpu_pileup_add_batch_whole(self._h, n, rec_p, rl, rec_method, sig_method, map_rows.ctypes.data_as(vp), rows.ctypes.data_as(vp),
+                                                     status.ctypes.data_as(vp))
+        if rc != 0 and (raise_on_error or rc != ERR_DATA):
+            check(rc, "s5gpu_pileup_add_batch_whole")
+        return rc, map_rows, rows, status
+
+
+def file_pileup(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, wmax=None, min_depth=1, raise_on_corrupt=True, whole=False, emax=None,
+                tile_rows=None, band=None):
     """The table of a .blow5 file against the levels of ref_path (one number per line) as a PILE_LINE array, a row per reference position of
     depth >= min_depth.  Runs the s5pileup tool (examples/s5pileup.c), `batch` records per device call.  A corrupt record raises; with
-    raise_on_corrupt=False it is left out."""
+    raise_on_corrupt=False it is left out.  whole=True: the table of whole reads (--whole), with emax, tile_rows and band as in
+    extend.file_extend; wmax does not count then."""
     if not os.path.exists(S5PILEUP):
         _build.build()
     cmd = [S5PILEUP, "-K", str(int(batch)), "--skip", str(int(skip)), "--events", str(int(qmax)), "--min-events", str(int(qmin)), "--min-depth", str(int(min_depth))]
-    cmd += (["--rna"] if rna else []) + (["--max-span", str(int(wmax))] if wmax is not None else []) + [os.fspath(ref_path), os.fspath(path)]
+    cmd += (["--rna"] if rna else []) + (["--max-span", str(int(wmax))] if wmax is not None else [])
+    if whole:
+        cmd += ["--whole"] + (["--max-events", str(int(emax))] if emax is not None else [])
+        cmd += (["--tile", str(int(tile_rows))] if tile_rows is not None else []) + (["--band", str(int(band))] if band is not None else [])
+    cmd += [os.fspath(ref_path), os.fspath(path)]
     p = subprocess.run(cmd, capture_output=True)
     if p.returncode != 0 and (raise_on_corrupt or p.returncode != 1):
         raise _lib.S5GpuError("s5pileup %s failed (exit %d): %s" % (path, p.returncode, p.stderr.decode(errors="replace").strip()))
