@@ -1,8 +1,9 @@
 // band_kernels.hip — whole-read banded alignment in tiles from a known anchor, on the device (docs/codecs.md §4.21):
 //   k_ev_query_long   : a lane per read, as k_ev_query: the quantised means of event rows [skip, skip + Q) at queries[first[i] ..), ragged.
 //   k_sdtw_band<G>    : the hot path.  A wave per read, four reads a workgroup; the wave loops over its read's tiles of T = 64 G rows.  Within
-//                       a tile it is k_sdtw_win's systolic scheme over the tile's window of W <= band columns (lane l owns G rows, DPP shifts,
-//                       no predicate in a step, decision words in §4.17's [word][lane] layout, one slot a tile).  What differs: lane 0's "cell
+//                       a tile it is k_sdtw_win's systolic scheme over the tile's window of W <= band columns (dirs_walk of dtw_dev.h: lane l
+//                       owns G rows, DPP shifts, no predicate in a step, decision words in §4.17's [word][lane] layout, one slot a tile) with
+//                       a Carry.  What differs: lane 0's "cell
 //                       above" comes from the carried row, fetched 64 columns at a time and handed out by v_readlane as the reference values
 //                       are; the lane that holds a full tile's last row stores that row, a word a step, for the next tile; at the tile's end
 //                       the minimum, its smallest column and the next window are made scalar.  The carried row lives in LDS, band + 1 words a
@@ -41,14 +42,7 @@ __global__ __launch_bounds__(256) void k_ev_query_long(uint32_t n, LongQueryArgs
     if (st != 0) ql = 0;
     else if (ql == 0) st = S5GPU_STATUS_QUERY_SHORT;
     int16_t *q = A.queries + f0;
-    if (ql) {
-        const float *m = &A.rows[f0 + A.skip].mean;
-        const size_t stride = sizeof(s5gpu_event_t) / sizeof(float);
-        double mu, sd;
-        quant_stats(m, stride, ql, &mu, &sd);
-        const bool ok = quant_ok(sd);
-        for (uint32_t j = 0; j < ql; j++) q[j] = ok ? quant_one(m[j * stride], mu, sd, A.scale, A.clip) : (int16_t)0;
-    }
+    if (ql) quant_row(&A.rows[f0 + A.skip].mean, sizeof(s5gpu_event_t) / sizeof(float), ql, A.scale, A.clip, q);
     for (uint64_t j = ql; j < E; j++) q[j] = 0;
     A.qlen[i] = ql;
     A.status[i] = st;
@@ -56,55 +50,28 @@ __global__ __launch_bounds__(256) void k_ev_query_long(uint32_t n, LongQueryArgs
 
 namespace {
 
-__device__ __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// what a tile takes from the one before: S and how to read it (band_dev.h, carry_index / carry_value)
+// what a tile takes from the one before: S and how to read it (band_dev.h, carry_index / carry_value), as dirs_walk asks for it
 struct Carry {
     uint32_t *S;                     // the wave's band + 1 words
     uint32_t delta, wprev, pmin;
     bool first;
-};
-__device__ __forceinline__ uint32_t carry_at(const Carry &C, uint32_t x) {
-    bool in;
-    const uint32_t at = carry_index(C.delta, x, C.wprev, &in);
-    return carry_value(C.first ? 0u : C.S[at], in, C.pmin, C.first);
-}
-
-// The steps of one tile: whole words, every lane at every step, the candidate of the lane's row KB (win_walk of refine_kernels.hip); lane
-// `wl` (64: none) stores its row KB, the tile's last, into the carried row
-template <int G, int KB>
-__device__ __forceinline__ void tile_walk(Lane<G, false> &L, const int16_t *__restrict__ ref, uint32_t W, uint32_t nw, uint32_t *slot, uint32_t lane,
-                                          const Carry &C, uint32_t wl) {
-    constexpr uint32_t SPW = 16 / G, WPB = 64 / SPW;                       // steps per word; words per block of 64 columns
-    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
-    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
-    for (uint32_t w0 = 0; w0 < nw; w0 += WPB) {
-        const uint32_t at = w0 * SPW + lane;                               // the wave's block of columns, zeros and "no cell" behind the window
-        const uint32_t rblk = biased(at < W ? ref[at] : (int16_t)0);
-        const uint32_t cblk = at < W ? carry_at(C, at + 1u) : FAR;
-        const uint32_t cnt = nw - w0 < WPB ? nw - w0 : WPB;
-        for (uint32_t wi = 0; wi < cnt; wi++) {
-            uint32_t word = 0;
-#pragma unroll
-            for (uint32_t s = 0; s < SPW; s++) {
-                const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)(wi * SPW + s));
-                const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)cblk, (int)(wi * SPW + s));
-                rcur = shift_up1(rcur, r0);
-                const uint32_t up = shift_up1(L.d[G - 1], c0);
-                word = path_pack(word, lane_step_dirs(L, rcur, up), s, G);
-                lane_best<G, false, KB>(L, j, W);
-                if (lane == wl && j < W) C.S[j + 1u] = L.d[KB];
-                j++;
-            }
-            slot[(uint64_t)(w0 + wi) * 64u] = word;
-        }
+    // the cell above this tile's window column x - 1 (x = 0: the diagonal of column 0)
+    __device__ __forceinline__ uint32_t at(uint32_t x) const {
+        bool in;
+        const uint32_t i = carry_index(delta, x, wprev, &in);
+        return carry_value(first ? 0u : S[i], in, pmin, first);
     }
-}
+    // the bottom cell of this tile's window column j, for the next tile
+    __device__ __forceinline__ void store(uint32_t j, uint32_t cell) const { S[j + 1u] = cell; }
+};
+
+// kb -> the walk compiled for it.  The kernel's own dispatch, not with_kb of dtw_dev.h: with the Carry in a closure the compiler allocates
+// 6 to 10 more VGPRs at G = 2, 4 and 8, and k_sdtw_band<4> measured 1.4 to 2.2 % slower on the device
 template <int G, int KB = 0>
 struct TileWalk {
     static __device__ __forceinline__ void run(int kb, Lane<G, false> &L, const int16_t *__restrict__ ref, uint32_t W, uint32_t nw, uint32_t *slot,
                                                uint32_t lane, const Carry &C, uint32_t wl) {
-        if (kb == KB) tile_walk<G, KB>(L, ref, W, nw, slot, lane, C, wl);
+        if (kb == KB) dirs_walk<G, KB, true>(L, ref, W, nw, slot, lane, C, wl);
         else if constexpr (KB + 1 < G) TileWalk<G, KB + 1>::run(kb, L, ref, W, nw, slot, lane, C, wl);
     }
 };
@@ -116,7 +83,7 @@ __global__ __launch_bounds__(256) void k_sdtw_band(uint32_t n, BandArgs A) {
     extern __shared__ uint32_t lds[];
     constexpr uint32_t T = 64u * G;
     const uint32_t lane = threadIdx.x & 63u, wave = sgpr(threadIdx.x >> 6);
-    const uint64_t read = (uint64_t)blockIdx.x * 4u + wave;
+    const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
     if (read >= n) return;                                                // (the wave's branch)
     const uint64_t f0 = A.first[read], f1 = A.first[read + 1];
     const bool lies = f0 <= f1 && f1 <= A.total_rows;
@@ -124,8 +91,8 @@ __global__ __launch_bounds__(256) void k_sdtw_band(uint32_t n, BandArgs A) {
     uint32_t Q = A.qlen[read];
     Q = Q < EMAX ? Q : EMAX;
     Q = sgpr((uint64_t)Q < E ? Q : (uint32_t)E);
-    int32_t st = __builtin_amdgcn_readfirstlane(A.status_in[read]);
-    const int32_t anchor = __builtin_amdgcn_readfirstlane(A.anchor[read * A.anchor_stride]);
+    int32_t st = (int32_t)sgpr((uint32_t)A.status_in[read]);
+    const int32_t anchor = (int32_t)sgpr((uint32_t)A.anchor[read * A.anchor_stride]);
     const uint32_t K = tiles_of(Q, T);
     const uint64_t slot0 = slot_first(f0 >= A.row0 ? f0 - A.row0 : 0, T, read);
     if (st == 0 && Q != 0 && (f0 < A.row0 || anchor < 0 || (uint32_t)anchor >= A.R || slot0 + K > A.slots)) st = S5GPU_STATUS_PATH_ROW;
@@ -151,17 +118,13 @@ __global__ __launch_bounds__(256) void k_sdtw_band(uint32_t n, BandArgs A) {
         const int kb = (int)(Qk - 1u - last * G);
         Lane<G, false> L;
         lane_init(L, false);
-        if (lane == 0) L.dg = carry_at(C, 0u);                             // the diagonal of column 0
+        if (lane == 0) L.dg = C.at(0u);                                    // the diagonal of column 0
 #pragma unroll
-        for (int kk = 0; kk < G; kk++) {
-            const uint32_t row = k * T + lane * G + kk;
-            L.q[kk] = biased(row < Q ? q[row] : (int16_t)0);
-        }
-        uint32_t nw = path_words(G, W + last);
-        nw = nw < A.slot_words ? nw : A.slot_words;                        // (never less: slot_words holds band + 63 steps)
+        for (int kk = 0; kk < G; kk++) L.q[kk] = query_value(q, k * T + lane * G + kk, Q);
+        const uint32_t nw = walk_words<G>(W, last, A.slot_words), wl = k + 1u < K ? 63u : 64u;   // a full tile's last row is lane 63's
         uint32_t *slot = A.scratch + (slot0 + k) * ((uint64_t)A.slot_words * 64u) + lane;
         if (lane == 0) A.tile_a[slot0 + k] = (int32_t)a;
-        TileWalk<G>::run(kb, L, A.ref + a, W, nw, slot, lane, C, k + 1u < K ? 63u : 64u);
+        TileWalk<G>::run(kb, L, A.ref + a, W, nw, slot, lane, C, wl);
         const uint32_t mn = (uint32_t)__builtin_amdgcn_readlane((int)L.best, (int)last);
         const uint32_t m = (uint32_t)__builtin_amdgcn_readlane(L.best_end, (int)last);
         if (m >= W || mn >= FAR) {                                         // (cannot be: column m_k of the tile before carries 0 into this one)
@@ -207,19 +170,10 @@ __global__ __launch_bounds__(64) void k_sdtw_band_trace(uint32_t n, BandArgs A) 
     A.rows_out[read] = row;
 }
 
-#define BAND_LAUNCH_CHECK(what)                                                           \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int bandk::launch_queries_long(uint32_t n, const LongQueryArgs &A, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_ev_query_long, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, st, n, A);
-    BAND_LAUNCH_CHECK("k_ev_query_long");
+    S5_LAUNCH_CHECK("k_ev_query_long");
     return S5GPU_OK;
 }
 
@@ -235,7 +189,7 @@ static int launch_band_class(uint32_t n, const BandArgs &A, hipStream_t st) {
         }
     }
     hipLaunchKernelGGL((k_sdtw_band<G>), dim3((uint32_t)(((uint64_t)n + 3u) / 4u)), dim3(256), lds, st, n, A);
-    BAND_LAUNCH_CHECK("k_sdtw_band");
+    S5_LAUNCH_CHECK("k_sdtw_band");
     return S5GPU_OK;
 }
 
@@ -260,6 +214,6 @@ int bandk::launch_band(uint32_t n, const BandArgs &A, hipStream_t st) {
     }
     if (rc || !(g_band_passes & 2u)) return rc;
     hipLaunchKernelGGL(k_sdtw_band_trace, dim3((uint32_t)(((uint64_t)n + 63u) / 64u)), dim3(64), 0, st, n, A);
-    BAND_LAUNCH_CHECK("k_sdtw_band_trace");
+    S5_LAUNCH_CHECK("k_sdtw_band_trace");
     return S5GPU_OK;
 }

@@ -4,6 +4,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// behind a kernel launch, in a function that returns a library code: the launch's own error -> the error text and S5GPU_ERR_HIP
+// (the file declares s5gpu_set_error and includes slow5gpu.h)
+// The dtw, path, refine, band and pileup kernel files use it.  diff, event, signal, fstats and skim_kernels.hip still carry a copy of
+// their own (DF_, EV_, SIG_, FS_, SKIM_LAUNCH_CHECK; skim's differs by a `const`): to be folded in here later.
+#define S5_LAUNCH_CHECK(what)                                                             \
+    do {                                                                                  \
+        hipError_t e_ = hipGetLastError();                                                \
+        if (e_ != hipSuccess) {                                                           \
+            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
+            return S5GPU_ERR_HIP;                                                         \
+        }                                                                                 \
+    } while (0)
+
 namespace s5 {
 
 constexpr int NT = 256;          // threads per workgroup

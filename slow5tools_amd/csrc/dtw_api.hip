@@ -41,16 +41,12 @@ int dtwk::check_ref(const char *who, uint32_t R) {
 }
 
 extern "C" int s5gpu_quantise_host(const float *m, size_t L, double scale, int32_t clip, int16_t *q) {
-    DTW_NO_CONTRACT
     const char *who = "s5gpu_quantise_host";
     int rc;
     if ((rc = check_quant(who, scale, clip))) return rc;
     if (L == 0) return S5GPU_OK;
     if (!m || !q) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
-    double mu, sd;
-    dtwk::quant_stats(m, 1, L, &mu, &sd);
-    const bool ok = dtwk::quant_ok(sd);
-    for (size_t j = 0; j < L; j++) q[j] = ok ? dtwk::quant_one(m[j], mu, sd, scale, clip) : (int16_t)0;
+    dtwk::quant_row(m, 1, L, scale, clip, q);
     return S5GPU_OK;
 }
 

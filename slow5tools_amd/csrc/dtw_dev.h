@@ -1,5 +1,7 @@
-// dtw_dev.h — what dtw_kernels.hip, dtw_path_kernels.hip and their host sides share: the quantiser, the sDTW cell, a lane's step of the
-// systolic scheme, the packing of a path's decisions and the walk back through them, and the launchers (docs/codecs.md §4.16, §4.17).
+// dtw_dev.h — what dtw_kernels.hip, dtw_path_kernels.hip, refine_kernels.hip, band_kernels.hip and their host sides share: the quantiser,
+// the sDTW cell, a lane's step of the systolic scheme, the packing of a path's decisions and the walk back through them, and, for the device
+// only, the wave's side of the scheme (the pieces of a kernel's head, the two walks over the steps, one launch per lane height) and the launchers
+// (docs/codecs.md §4.16, §4.17).
 // With S5_DTW_HOST defined only the quantiser, the lane code and the path code are declared, as plain C++: tests/test_map.py,
 // tests/test_map_second.py, tests/test_align.py and tests/test_refine.py (path_walk_from, §4.20) compile them for the CPU and run the very code a lane runs, 64 lanes in a loop with the lane exchange passed in,
 // against the restatement, without a device.
@@ -13,6 +15,8 @@
 #define DTW_HD static inline
 #else
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 #define DTW_HD __host__ __device__ __forceinline__
 #endif
 
@@ -58,6 +62,20 @@ DTW_HD int16_t quant_one(float x, double mu, double sd, double scale, int32_t cl
     const double z = ((double)x - mu) / sd;
     const double r = rint(z * scale), c = (double)clip;
     return (int16_t)(int32_t)(r < -c ? -c : r > c ? c : r);
+}
+
+// q[0 .. L) of m[0 .. L) read at a stride of `stride` floats, L >= 1: the quantiser of one read, zeros where sd is not usable
+DTW_HD void quant_row(const float *m, size_t stride, size_t L, double scale, int32_t clip, int16_t *q) {
+    double mu, sd;
+    quant_stats(m, stride, L, &mu, &sd);
+    const bool ok = quant_ok(sd);
+    for (size_t j = 0; j < L; j++) q[j] = ok ? quant_one(m[j * stride], mu, sd, scale, clip) : (int16_t)0;
+}
+
+// the rows of a read that count: qlen clamped to the pitch and to QMAX
+DTW_HD uint32_t rows_of(uint32_t qlen, uint32_t qpitch) {
+    const uint32_t q = qlen < qpitch ? qlen : qpitch;
+    return q < QMAX ? q : QMAX;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- a lane of k_sdtw
@@ -260,42 +278,11 @@ DTW_HD int32_t path_row_check(const U4 &row, uint32_t Q, uint32_t R, uint32_t wm
     return 0;
 }
 
-// The walk: from (Q - 1, W - 1) along the decisions to row 0, which it has to reach in window column 0.  lo[i], hi[i] (i < Q) get the first
-// and last column of row i, as absolute columns.  A decision read from memory chooses the next word, so everything is bounded here: at
-// most Q + W trips; i < Q and j < W checked before each use; a word index is clamped to the slot; a code of 3, a step out of the window or
-// an arrival in row 0 right of column 0 ends the walk.  -> 0, or S5GPU_STATUS_PATH_ROW (lo and hi then hold a partial path: the caller
-// overwrites them)
-DTW_HD int32_t path_walk(const uint32_t *words, uint32_t slot_words, uint32_t G, uint32_t Q, uint32_t W, int32_t start, int32_t *lo, int32_t *hi) {
-    if (Q == 0 || W == 0 || slot_words == 0) return S5GPU_STATUS_PATH_ROW;
-    const uint32_t top = slot_words * 64u - 1u;
-    uint32_t i = Q - 1, j = W - 1, at = 0xFFFFFFFFu, word = 0;
-    hi[i] = start + (int32_t)j;
-    for (uint32_t trip = 0; trip < Q + W; trip++) {
-        if (i >= Q || j >= W) break;
-        if (i == 0) {
-            if (j != 0) break;
-            lo[0] = start;
-            return 0;
-        }
-        uint32_t shift;
-        uint32_t x = path_cell(G, i, j, &shift);
-        x = x < top ? x : top;
-        if (x != at) { word = words[x]; at = x; }                          // (a word holds 16 / G steps of G rows: most moves stay in it)
-        const uint32_t code = (word >> shift) & 3u;
-        if (code == 3u || (code != 1u && j == 0)) break;
-        if (code == 2u) { j--; continue; }
-        lo[i] = start + (int32_t)j;
-        i--;
-        if (code == 0u) j--;
-        hi[i] = start + (int32_t)j;
-    }
-    return S5GPU_STATUS_PATH_ROW;
-}
-
-// path_walk's sibling for a window that is wider than the path (§4.20): from (Q - 1, jend), jend < W, to row 0, where it may arrive in any
-// column of the window; that column (absolute, as lo and hi: `base` is the window's first) goes to *start_out.  Every bound of path_walk is
-// kept: at most Q + W trips; i < Q and j < W checked before each use; a word index clamped to the slot; a code of 3 or a step out of the
-// window ends the walk.  -> 0, or S5GPU_STATUS_PATH_ROW (*start_out = -1; lo and hi hold a partial path: the caller overwrites them)
+// The walk: from (Q - 1, jend), jend < W, along the decisions to row 0, where it may arrive in any column of the window (§4.20: a window
+// wider than the path); that column goes to *start_out.  lo[i], hi[i] (i < Q) get the first and last column of row i, as absolute columns
+// (`base` is the window's first).  A decision read from memory chooses the next word, so everything is bounded here: at most Q + W trips;
+// i < Q and j < W checked before each use; a word index is clamped to the slot; a code of 3 or a step out of the window ends the walk.
+// -> 0, or S5GPU_STATUS_PATH_ROW (*start_out = -1; lo and hi hold a partial path: the caller overwrites them)
 DTW_HD int32_t path_walk_from(const uint32_t *words, uint32_t slot_words, uint32_t G, uint32_t Q, uint32_t W, int32_t base, uint32_t jend, int32_t *lo,
                               int32_t *hi, int32_t *start_out) {
     *start_out = -1;
@@ -313,7 +300,7 @@ DTW_HD int32_t path_walk_from(const uint32_t *words, uint32_t slot_words, uint32
         uint32_t shift;
         uint32_t x = path_cell(G, i, j, &shift);
         x = x < top ? x : top;
-        if (x != at) { word = words[x]; at = x; }
+        if (x != at) { word = words[x]; at = x; }                          // (a word holds 16 / G steps of G rows: most moves stay in it)
         const uint32_t code = (word >> shift) & 3u;
         if (code == 3u || (code != 1u && j == 0)) break;
         if (code == 2u) { j--; continue; }
@@ -323,6 +310,13 @@ DTW_HD int32_t path_walk_from(const uint32_t *words, uint32_t slot_words, uint32
         hi[i] = base + (int32_t)j;
     }
     return S5GPU_STATUS_PATH_ROW;
+}
+// ... for the window [start, end] of a row of k_sdtw (§4.17), W columns from `start`: from (Q - 1, W - 1), and row 0 has to be reached in
+// window column 0.  An arrival right of it is refused after lo[0] was written: like every partial path, the callers overwrite it with -1.
+DTW_HD int32_t path_walk(const uint32_t *words, uint32_t slot_words, uint32_t G, uint32_t Q, uint32_t W, int32_t start, int32_t *lo, int32_t *hi) {
+    int32_t got;
+    const int32_t rc = path_walk_from(words, slot_words, G, Q, W, start, W - 1u, lo, hi, &got);          // (W = 0: jend >= W, refused)
+    return rc == 0 && got != start ? S5GPU_STATUS_PATH_ROW : rc;
 }
 
 #ifndef S5_DTW_HOST
@@ -335,6 +329,121 @@ __device__ __forceinline__ uint32_t shift_up1(uint32_t v, uint32_t fill) {
 __device__ __forceinline__ uint32_t shift_up1_zero(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
 }
+// a value that is the same in every lane, as a scalar
+__device__ __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// ---------------------------------------------------------------------------------------------------------------- the wave's side
+// What k_sdtw, k_sdtw2, k_sdtw_dirs, k_sdtw_win and k_sdtw_band are made of.  A wave per read, four reads a workgroup: the wave's read ...
+__device__ __forceinline__ uint64_t wave_read(uint32_t block_x, uint32_t tid) { return (uint64_t)block_x * 4u + sgpr(tid >> 6); }
+// ... and its rows, the same in every lane: every trip count and every branch on Q is the wave's
+__device__ __forceinline__ uint32_t wave_rows(uint32_t qlen, uint32_t qpitch) { return sgpr(rows_of(qlen, qpitch)); }
+// is a read of Q rows another launch's?  The launch of lane height G takes Q in (32 G, 64 G], that of G = 1 everything up to 64, Q = 0 too
+template <int G>
+__device__ __forceinline__ bool other_launch(uint32_t Q) { return Q > 64u * G || (G > 1 && Q <= 32u * G); }
+// a query value of a lane: row `row` of q, zero at and beyond Q (cells nobody reads).  One value, returned: a helper that fills L.q through
+// a reference makes the compiler turn the candidate updates of the walks into chains of selects, 4 to 5 % slower on the device
+__device__ __forceinline__ uint32_t query_value(const int16_t *q, uint32_t row, uint32_t Q) { return biased(row < Q ? q[row] : (int16_t)0); }
+// kb -> f(std::integral_constant<int, KB>()) for the KB that equals it: a walk is compiled per KB (lane_best), and kb is the same in every
+// lane and fixed over a read, so these are scalar branches taken once per read.  f is taken by value: a closure handed down by reference
+// keeps what it captured in memory until late in the compilation, which cost 2 % more vector instructions in an inner loop
+template <int G, int KB = 0, class F>
+__device__ __forceinline__ void with_kb(int kb, F f) {
+    if (kb == KB) f(std::integral_constant<int, KB>());
+    else if constexpr (KB + 1 < G) with_kb<G, KB + 1>(kb, f);
+}
+
+// The steps of one read, the cost family (k_sdtw): lane `last` holds row Q - 1 as its row KB and does column R - 1 at step R - 1 + last
+// (R < 2^31).  Every lane steps at every step (FAR): the shifts need every lane, and no step has a branch.  Lane 0 gets the reference value
+// by v_readlane from the block of 64 that the wave loads together, zeros behind R.  (k_sdtw2 has a walk of its own, dtw_kernels.hip.)
+template <int G, bool WS, int KB>
+__device__ __forceinline__ void sdtw_walk(Lane<G, WS> &L, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane) {
+    const uint32_t steps = R + last;
+    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
+    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
+    auto step = [&](uint32_t rblk, uint32_t k, uint32_t t) {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)k);
+        rcur = shift_up1(rcur, r0);
+        const uint32_t up = shift_up1_zero(L.d[G - 1]);
+        const int32_t sup = WS ? (int32_t)shift_up1((uint32_t)L.s[G - 1], t + 1) : -1;
+        lane_step(L, rcur, up, sup);
+        lane_best<G, WS, KB>(L, j, R);
+        j++;
+    };
+    constexpr int UNROLL = G >= 8 ? 2 : 8;                                 // (a step of 16 rows is long enough in itself)
+    uint32_t tb = 0;
+    for (; tb + 64 <= steps; tb += 64) {
+        const uint32_t at = tb + lane;                                     // the wave's block of reference values, zeros behind R
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+#pragma unroll UNROLL
+        for (uint32_t k = 0; k < 64; k++) step(rblk, k, tb + k);
+    }
+    if (tb < steps) {
+        const uint32_t at = tb + lane;
+        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
+        for (uint32_t k = 0; k < steps - tb; k++) step(rblk, k, tb + k);
+    }
+}
+
+// The steps of one window, the decision family (k_sdtw_dirs; with BEST k_sdtw_win; with BEST and a carry k_sdtw_band): the same lanes and
+// shifts over the W columns from ref on, FAR left of the window, zeros behind it.  A lane packs the 2 G bits of 16 / G steps into a word and
+// stores it at [word][lane] of the slot (`slot` is the lane's own word 0): the walk steps whole words, nw of them, up to 16 / G - 1 steps
+// behind column W - 1 + last, whose codes nobody reads.  BEST: the (cost, end) candidate of the lane's row KB, guarded by j < W.
+// A carry (band_kernels.hip) gives lane 0's cell above from the row the tile before left, C.at(x + 1) for window column x, fetched a block of
+// 64 columns at a time and handed out by v_readlane as the reference values are, "no cell" behind the window; and lane `wl` (64: none)
+// stores its row KB of every column j < W it does with C.store(j, cell).  Without one lane 0's cell above is 0, the free start.
+struct NoCarry {};
+template <int G, int KB, bool BEST, class CarryT = NoCarry>
+__device__ __forceinline__ void dirs_walk(Lane<G, false> &L, const int16_t *__restrict__ ref, uint32_t W, uint32_t nw, uint32_t *slot, uint32_t lane,
+                                          const CarryT &C = CarryT(), uint32_t wl = 64u) {
+    constexpr bool CARRY = !std::is_same<CarryT, NoCarry>::value;
+    constexpr uint32_t SPW = 16 / G, WPB = 64 / SPW;                       // steps per word; words per block of 64 columns
+    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
+    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
+    for (uint32_t w0 = 0; w0 < nw; w0 += WPB) {
+        const uint32_t at = w0 * SPW + lane;                               // the wave's block of columns
+        const uint32_t rblk = biased(at < W ? ref[at] : (int16_t)0);
+        uint32_t cblk = 0;
+        if constexpr (CARRY) cblk = at < W ? C.at(at + 1u) : FAR;
+        const uint32_t cnt = nw - w0 < WPB ? nw - w0 : WPB;
+        for (uint32_t wi = 0; wi < cnt; wi++) {
+            uint32_t word = 0;
+#pragma unroll
+            for (uint32_t s = 0; s < SPW; s++) {
+                const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)(wi * SPW + s));
+                rcur = shift_up1(rcur, r0);
+                uint32_t up;
+                if constexpr (CARRY) up = shift_up1(L.d[G - 1], (uint32_t)__builtin_amdgcn_readlane((int)cblk, (int)(wi * SPW + s)));
+                else up = shift_up1_zero(L.d[G - 1]);
+                word = path_pack(word, lane_step_dirs(L, rcur, up), s, G);
+                if constexpr (BEST) lane_best<G, false, KB>(L, j, W);
+                if constexpr (CARRY) { if (lane == wl && j < W) C.store(j, L.d[KB]); }
+                j++;
+            }
+            slot[(uint64_t)(w0 + wi) * 64u] = word;
+        }
+    }
+}
+// the words of the walk over W columns of a read or tile whose last row is in lane `last`: it does column W - 1 at step W - 1 + last.
+// Clamped to the slot (never less: slot_words holds the widest window + 63 steps of the pitch's G)
+template <int G>
+__device__ __forceinline__ uint32_t walk_words(uint32_t W, uint32_t last, uint32_t slot_words) {
+    const uint32_t nw = path_words(G, W + last);
+    return nw < slot_words ? nw : slot_words;
+}
+
+// A launch per lane height that a query of at most qpitch rows can need: f(std::integral_constant<int, G>()) for G = 1 and every further G
+// with 32 G < qpitch, up to the first that does not return 0.  A wave whose read belongs to another launch returns at once (other_launch).
+template <class F>
+inline int for_each_lane_height(uint32_t qpitch, F &&f) {
+    int rc = f(std::integral_constant<int, 1>());
+    if (!rc && qpitch > 64) rc = f(std::integral_constant<int, 2>());
+    if (!rc && qpitch > 128) rc = f(std::integral_constant<int, 4>());
+    if (!rc && qpitch > 256) rc = f(std::integral_constant<int, 8>());
+    if (!rc && qpitch > 512) rc = f(std::integral_constant<int, 16>());
+    return rc;
+}
+// the grid of a kernel with a wave per read and four reads a workgroup of 256
+inline dim3 wave_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + 3u) / 4u)); }
 
 struct QueryArgs {
     const s5gpu_event_t *rows;
@@ -349,7 +458,7 @@ struct QueryArgs {
 };
 // k_ev_query over n reads, on st
 int launch_queries(uint32_t n, const QueryArgs &A, hipStream_t st);
-// k_sdtw over n reads, on st: a launch per class of lane height that qpitch allows
+// k_sdtw over n reads, on st: a launch per lane height that qpitch allows (for_each_lane_height)
 int launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
                 s5gpu_map_row_t *out, hipStream_t st);
 // k_sdtw2 likewise: the same rows, and the second-best hit of every read with blocks of 2^bshift columns (6 .. 30)

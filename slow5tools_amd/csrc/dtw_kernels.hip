@@ -8,6 +8,8 @@
 // step earlier is the diagonal) and the reference value, one DPP wave shift each; lane 0 gets the reference value by v_readlane from a
 // 64-value block that the wave loads together every 64 steps.  A cell is min3, absolute difference, add on uint32: D < 2^26 (§4.16).
 // Every lane steps at every step, before its column 0 and behind column R - 1 too (dtw_dev.h, FAR): no step has a predicate.
+// The pieces of the kernels' head, the walk over the steps and the launch per lane height are dtw_dev.h's (wave_read, wave_rows,
+// other_launch, query_value; sdtw_walk; for_each_lane_height): the path kernels share them.  k_sdtw2 alone keeps its own head and walk.
 // Nothing can index outside what it owns by construction (the rules of signal_kernels.hip):
 //   1. trip counts come from R and qlen only (qlen clamped to the pitch and to 64 G);
 //   2. no sample, cost or position forms an address: `end` and `start` are written as values;
@@ -32,69 +34,20 @@ __global__ __launch_bounds__(256) void k_ev_query(uint32_t n, QueryArgs A) {
     if (st != 0) ql = 0;                                                  // the rows of a failed record or an overflowed slot are no query
     else if (ql < A.qmin) { ql = 0; st = S5GPU_STATUS_QUERY_SHORT; }
     int16_t *q = A.queries + i * A.qmax;
-    if (ql) {
-        const float *m = &A.rows[f0 + A.skip].mean;
-        const size_t stride = sizeof(s5gpu_event_t) / sizeof(float);
-        double mu, sd;
-        quant_stats(m, stride, ql, &mu, &sd);
-        const bool ok = quant_ok(sd);
-        for (uint32_t j = 0; j < ql; j++) q[j] = ok ? quant_one(m[j * stride], mu, sd, A.scale, A.clip) : (int16_t)0;
-    }
+    if (ql) quant_row(&A.rows[f0 + A.skip].mean, sizeof(s5gpu_event_t) / sizeof(float), ql, A.scale, A.clip, q);
     for (uint32_t j = ql; j < A.qmax; j++) q[j] = 0;
     A.qlen[i] = ql;
     A.status[i] = st;
 }
 
-// (the wave shifts shift_up1 and shift_up1_zero: dtw_dev.h)
-// The steps of one read: lane `last` holds row Q - 1 as its row KB and does column R - 1 at step R - 1 + last (R < 2^31).  Every lane
-// steps at every step (dtw_dev.h, FAR): the shifts need every lane, and no step has a branch.
-template <int G, bool WS, int KB>
-__device__ __forceinline__ void sdtw_walk(Lane<G, WS> &L, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane) {
-    const uint32_t steps = R + last;
-    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
-    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
-    auto step = [&](uint32_t rblk, uint32_t k, uint32_t t) {
-        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)k);
-        rcur = shift_up1(rcur, r0);
-        const uint32_t up = shift_up1_zero(L.d[G - 1]);
-        const int32_t sup = WS ? (int32_t)shift_up1((uint32_t)L.s[G - 1], t + 1) : -1;
-        lane_step(L, rcur, up, sup);
-        lane_best<G, WS, KB>(L, j, R);
-        j++;
-    };
-    constexpr int UNROLL = G >= 8 ? 2 : 8;                                 // (a step of 16 rows is long enough in itself)
-    uint32_t tb = 0;
-    for (; tb + 64 <= steps; tb += 64) {
-        const uint32_t at = tb + lane;                                     // the wave's block of reference values, zeros behind R
-        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
-#pragma unroll UNROLL
-        for (uint32_t k = 0; k < 64; k++) step(rblk, k, tb + k);
-    }
-    if (tb < steps) {
-        const uint32_t at = tb + lane;
-        const uint32_t rblk = biased(at < R ? ref[at] : (int16_t)0);
-        for (uint32_t k = 0; k < steps - tb; k++) step(rblk, k, tb + k);
-    }
-}
-// kb -> the walk compiled for it (kb is the same in every lane: scalar branches, once per read)
-template <int G, bool WS, int KB = 0>
-struct Walk {
-    static __device__ __forceinline__ void run(int kb, Lane<G, WS> &L, const int16_t *__restrict__ ref, uint32_t R, uint32_t last, uint32_t lane) {
-        if (kb == KB) sdtw_walk<G, WS, KB>(L, ref, R, last, lane);
-        else if constexpr (KB + 1 < G) Walk<G, WS, KB + 1>::run(kb, L, ref, R, last, lane);
-    }
-};
-
 template <int G, bool WS>
 __global__ __launch_bounds__(256) void k_sdtw(uint32_t n, const int16_t *__restrict__ queries, uint32_t qpitch, const uint32_t *__restrict__ qlen,
                                               const int16_t *__restrict__ ref, uint32_t R, U4 *__restrict__ out) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t read = (uint64_t)blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
     if (read >= n) return;                                                // (the wave's branch: `read` is the same in its 64 lanes)
-    uint32_t Q = qlen[read];
-    Q = Q < qpitch ? Q : qpitch;
-    Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Q < QMAX ? Q : QMAX));
-    if (Q > 64u * G || (G > 1 && Q <= 32u * G)) return;                    // another launch's read
+    const uint32_t Q = wave_rows(qlen[read], qpitch);
+    if (other_launch<G>(Q)) return;
     if (Q == 0) {
         if (lane == 0) out[read] = result_row(NO_COST, 0, -1, -1);
         return;
@@ -103,17 +56,16 @@ __global__ __launch_bounds__(256) void k_sdtw(uint32_t n, const int16_t *__restr
     lane_init(L, lane == 0);
     const int16_t *q = queries + read * qpitch;
 #pragma unroll
-    for (int k = 0; k < G; k++) {
-        const uint32_t row = lane * G + k;
-        L.q[k] = biased(row < Q ? q[row] : (int16_t)0);                    // rows at or beyond Q: cells nobody reads
-    }
+    for (int k = 0; k < G; k++) L.q[k] = query_value(q, lane * G + k, Q);
     const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1 ...
     const int kb = (int)(Q - 1 - last * G);                                // ... and which of its rows it is
-    Walk<G, WS>::run(kb, L, ref, R, last, lane);
+    with_kb<G>(kb, [&](auto KB) { sdtw_walk<G, WS, decltype(KB)::value>(L, ref, R, last, lane); });
     if (lane == last) out[read] = result_row(L.best, Q, WS ? L.best_start : -1, L.best_end);
 }
 
-// ---- k_sdtw2: k_sdtw with the second-best hit (§4.19).  The walk of sdtw_walk with lane_second beside lane_best, and second_flush where the
+// ---- k_sdtw2: k_sdtw with the second-best hit (§4.19).  It keeps its kernel text, walk and dispatch to itself: on the shared ones
+// (sdtw_walk behind `if constexpr`, with_kb) it measured 0.2 to 0.4 % behind, the loop laid out differently, the cause not found.
+// The walk of sdtw_walk with lane_second beside lane_best, and second_flush where the
 // lane of row Q - 1 has done the last column of a block: it does column t - last at step t, both the same in the whole wave, and a block is at
 // least the 64 steps of a reference block long, so in every 64 steps there is at most one such step, kf, found once: a scalar compare and
 // branch per step, taken once per block, every lane with it (the other lanes' lists are never read).
@@ -191,63 +143,35 @@ __global__ __launch_bounds__(256) void k_sdtw2(uint32_t n, const int16_t *__rest
     if (lane == last) { out[read] = result_row(L.best, Q, WS ? L.best_start : -1, L.best_end); out2[read] = second_row(S, bshift); }
 }
 
-#define DTW_LAUNCH_CHECK(what)                                                           \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int dtwk::launch_queries(uint32_t n, const QueryArgs &A, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_ev_query, dim3((uint32_t)(((uint64_t)n + 255u) / 256u)), dim3(256), 0, st, n, A);
-    DTW_LAUNCH_CHECK("k_ev_query");
+    S5_LAUNCH_CHECK("k_ev_query");
     return S5GPU_OK;
 }
 
-template <int G>
-static int launch_class(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
-                        U4 *out, hipStream_t st) {
-    const dim3 grid((uint32_t)(((uint64_t)n + 3u) / 4u)), block(256);
-    if (want_start) hipLaunchKernelGGL((k_sdtw<G, true>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, out);
-    else hipLaunchKernelGGL((k_sdtw<G, false>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, out);
-    DTW_LAUNCH_CHECK("k_sdtw");
-    return S5GPU_OK;
-}
-
-template <int G>
-static int launch_class2(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
-                         uint32_t bshift, U4 *out, U4 *out2, hipStream_t st) {
-    const dim3 grid((uint32_t)(((uint64_t)n + 3u) / 4u)), block(256);
-    if (want_start) hipLaunchKernelGGL((k_sdtw2<G, true>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, bshift, out, out2);
-    else hipLaunchKernelGGL((k_sdtw2<G, false>), grid, block, 0, st, n, queries, qpitch, qlen, ref, R, bshift, out, out2);
-    DTW_LAUNCH_CHECK("k_sdtw2");
-    return S5GPU_OK;
+int dtwk::launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
+                      s5gpu_map_row_t *out, hipStream_t st) {
+    if (n == 0) return S5GPU_OK;
+    U4 *o = reinterpret_cast<U4 *>(out);
+    return for_each_lane_height(qpitch, [&](auto g) -> int {
+        constexpr int G = decltype(g)::value;
+        if (want_start) hipLaunchKernelGGL((k_sdtw<G, true>), wave_grid(n), dim3(256), 0, st, n, queries, qpitch, qlen, ref, R, o);
+        else hipLaunchKernelGGL((k_sdtw<G, false>), wave_grid(n), dim3(256), 0, st, n, queries, qpitch, qlen, ref, R, o);
+        S5_LAUNCH_CHECK("k_sdtw");
+        return S5GPU_OK;
+    });
 }
 
 int dtwk::launch_sdtw2(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
                        uint32_t bshift, s5gpu_map_row_t *out, s5gpu_map_second_t *out2, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     U4 *o = reinterpret_cast<U4 *>(out), *o2 = reinterpret_cast<U4 *>(out2);
-    int rc = launch_class2<1>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
-    if (!rc && qpitch > 64) rc = launch_class2<2>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
-    if (!rc && qpitch > 128) rc = launch_class2<4>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
-    if (!rc && qpitch > 256) rc = launch_class2<8>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
-    if (!rc && qpitch > 512) rc = launch_class2<16>(n, queries, qpitch, qlen, ref, R, want_start, bshift, o, o2, st);
-    return rc;
-}
-
-// A launch per lane height that a query of at most qpitch rows can need; a wave whose read belongs to another launch returns at once.
-int dtwk::launch_sdtw(uint32_t n, const int16_t *queries, uint32_t qpitch, const uint32_t *qlen, const int16_t *ref, uint32_t R, bool want_start,
-                      s5gpu_map_row_t *out, hipStream_t st) {
-    if (n == 0) return S5GPU_OK;
-    U4 *o = reinterpret_cast<U4 *>(out);
-    int rc = launch_class<1>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
-    if (!rc && qpitch > 64) rc = launch_class<2>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
-    if (!rc && qpitch > 128) rc = launch_class<4>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
-    if (!rc && qpitch > 256) rc = launch_class<8>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
-    if (!rc && qpitch > 512) rc = launch_class<16>(n, queries, qpitch, qlen, ref, R, want_start, o, st);
-    return rc;
+    return for_each_lane_height(qpitch, [&](auto g) -> int {
+        constexpr int G = decltype(g)::value;
+        if (want_start) hipLaunchKernelGGL((k_sdtw2<G, true>), wave_grid(n), dim3(256), 0, st, n, queries, qpitch, qlen, ref, R, bshift, o, o2);
+        else hipLaunchKernelGGL((k_sdtw2<G, false>), wave_grid(n), dim3(256), 0, st, n, queries, qpitch, qlen, ref, R, bshift, o, o2);
+        S5_LAUNCH_CHECK("k_sdtw2");
+        return S5GPU_OK;
+    });
 }

@@ -4,9 +4,10 @@
 //   k_sdtw_trace : per read, the walk back through these decisions from (Q - 1, end) to (0, start): lo[i], hi[i] of every query row
 //   k_ev_gather  : per read, the event rows of its query as a row of an [n, qmax] matrix (for the batch call: the tool prints their samples)
 // k_sdtw_dirs is the scheme of k_sdtw (dtw_kernels.hip): a wave per read, lane l owning G rows, DPP shifts, FAR left of the window, no
-// predicate in a step; it carries neither S nor a (cost, end) candidate.  A lane packs the 2 G bits of 16 / G steps into a word and stores
-// it at [word][lane]: a wave's store is 256 contiguous bytes.  It steps whole words: up to 16 / G - 1 steps behind column W - 1 + last, and
-// like the rows at or beyond Q and the columns left of the window their codes are whatever falls out; nobody reads them.
+// predicate in a step; it carries neither S nor a (cost, end) candidate.  Its steps are dirs_walk of dtw_dev.h, which the window and band
+// kernels run too: a lane packs the 2 G bits of 16 / G steps into a word and stores it at [word][lane], a wave's store is 256 contiguous
+// bytes.  It steps whole words: up to 16 / G - 1 steps behind column W - 1 + last, and like the rows at or beyond Q and the columns left of
+// the window their codes are whatever falls out; nobody reads them.
 // k_sdtw_trace is a SEPARATE launch on the same stream: the kernel boundary is what makes the words visible to its loads (a fence of
 // workgroup scope would not).  A lane per read: the walk is one chain of dependent loads, and 64 chains a wave are what hides their latency.
 // It is the one place in this code base where a value read from memory chooses the next address.  The rules:
@@ -28,14 +29,11 @@ using namespace dtwk;
 
 template <int G>
 __global__ __launch_bounds__(256) void k_sdtw_dirs(uint32_t n, PathArgs A) {
-    constexpr uint32_t SPW = 16 / G, WPB = 64 / SPW;                       // steps per word; words per block of 64 reference values
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t read = (uint64_t)blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
     if (read >= n) return;                                                // (the wave's branch: `read` is the same in its 64 lanes)
-    uint32_t Q = A.qlen[read];
-    Q = Q < A.qpitch ? Q : A.qpitch;
-    Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Q < QMAX ? Q : QMAX));
-    if (Q > 64u * G || (G > 1 && Q <= 32u * G)) return;                    // another launch's read
+    const uint32_t Q = wave_rows(A.qlen[read], A.qpitch);
+    if (other_launch<G>(Q)) return;
     uint32_t W = 0, start = 0;
     int32_t st = 0;
     if (Q) {
@@ -43,9 +41,9 @@ __global__ __launch_bounds__(256) void k_sdtw_dirs(uint32_t n, PathArgs A) {
         st = path_row_check(row, Q, A.R, A.wmax, &W);
         start = row.z;
     }
-    st = __builtin_amdgcn_readfirstlane(st);
-    W = (uint32_t)__builtin_amdgcn_readfirstlane((int)W);
-    start = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
+    st = (int32_t)sgpr((uint32_t)st);
+    W = sgpr(W);
+    start = sgpr(start);
     const bool path = Q != 0 && st == 0;
     int32_t *lo = A.lo + read * A.qpitch, *hi = A.hi + read * A.qpitch;
     for (uint32_t x = (path ? Q : 0u) + lane; x < A.qpitch; x += 64u) { lo[x] = -1; hi[x] = -1; }
@@ -55,40 +53,16 @@ __global__ __launch_bounds__(256) void k_sdtw_dirs(uint32_t n, PathArgs A) {
     lane_init(L, lane == 0);
     const int16_t *q = A.queries + read * A.qpitch;
 #pragma unroll
-    for (int k = 0; k < G; k++) {
-        const uint32_t row = lane * G + k;
-        L.q[k] = biased(row < Q ? q[row] : (int16_t)0);
-    }
-    const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1: it does column W - 1 at step W - 1 + last
-    uint32_t nw = path_words(G, W + last);
-    nw = nw < A.slot_words ? nw : A.slot_words;                            // (never less: slot_words holds wmax + 63 steps of the pitch's G)
-    const int16_t *ref = A.ref + start;
+    for (int k = 0; k < G; k++) L.q[k] = query_value(q, lane * G + k, Q);
+    const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1
     uint32_t *slot = A.scratch + read * ((uint64_t)A.slot_words * 64u) + lane;
-    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
-    for (uint32_t w0 = 0; w0 < nw; w0 += WPB) {
-        const uint32_t at = w0 * SPW + lane;                               // the wave's block of reference values, zeros behind the window
-        const uint32_t rblk = biased(at < W ? ref[at] : (int16_t)0);
-        const uint32_t cnt = nw - w0 < WPB ? nw - w0 : WPB;
-        for (uint32_t wi = 0; wi < cnt; wi++) {
-            uint32_t word = 0;
-#pragma unroll
-            for (uint32_t s = 0; s < SPW; s++) {
-                const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)(wi * SPW + s));
-                rcur = shift_up1(rcur, r0);
-                const uint32_t up = shift_up1_zero(L.d[G - 1]);
-                word = path_pack(word, lane_step_dirs(L, rcur, up), s, G);
-            }
-            slot[(uint64_t)(w0 + wi) * 64u] = word;
-        }
-    }
+    dirs_walk<G, 0, false>(L, A.ref + start, W, walk_words<G>(W, last, A.slot_words), slot, lane);   // (no candidate: KB is not used)
 }
 
 __global__ __launch_bounds__(64) void k_sdtw_trace(uint32_t n, PathArgs A) {
     const uint64_t read = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (read >= n) return;
-    uint32_t Q = A.qlen[read];
-    Q = Q < A.qpitch ? Q : A.qpitch;
-    Q = Q < QMAX ? Q : QMAX;
+    const uint32_t Q = rows_of(A.qlen[read], A.qpitch);
     if (Q == 0) return;
     const U4 row = A.rows[read];
     uint32_t W;
@@ -116,36 +90,18 @@ __global__ __launch_bounds__(64) void k_ev_gather(uint32_t n, const U4 *__restri
     }
 }
 
-#define DTW_LAUNCH_CHECK(what)                                                            \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
-template <int G>
-static int launch_dirs_class(uint32_t n, const PathArgs &A, hipStream_t st) {
-    hipLaunchKernelGGL((k_sdtw_dirs<G>), dim3((uint32_t)(((uint64_t)n + 3u) / 4u)), dim3(256), 0, st, n, A);
-    DTW_LAUNCH_CHECK("k_sdtw_dirs");
-    return S5GPU_OK;
-}
-
-// The dirs pass: a launch per lane height that a query of at most qpitch rows can need, as launch_sdtw; then the trace.
+// The dirs pass: a launch per lane height that a query of at most qpitch rows can need; then the trace.
 int dtwk::launch_path(uint32_t n, const PathArgs &A, hipStream_t st, int which) {
     if (n == 0) return S5GPU_OK;
     int rc = S5GPU_OK;
-    if (which & 1) {
-        rc = launch_dirs_class<1>(n, A, st);
-        if (!rc && A.qpitch > 64) rc = launch_dirs_class<2>(n, A, st);
-        if (!rc && A.qpitch > 128) rc = launch_dirs_class<4>(n, A, st);
-        if (!rc && A.qpitch > 256) rc = launch_dirs_class<8>(n, A, st);
-        if (!rc && A.qpitch > 512) rc = launch_dirs_class<16>(n, A, st);
-    }
+    if (which & 1) rc = for_each_lane_height(A.qpitch, [&](auto g) -> int {
+        hipLaunchKernelGGL((k_sdtw_dirs<decltype(g)::value>), wave_grid(n), dim3(256), 0, st, n, A);
+        S5_LAUNCH_CHECK("k_sdtw_dirs");
+        return S5GPU_OK;
+    });
     if (!rc && (which & 2)) {
         hipLaunchKernelGGL(k_sdtw_trace, dim3((uint32_t)(((uint64_t)n + 63u) / 64u)), dim3(64), 0, st, n, A);
-        DTW_LAUNCH_CHECK("k_sdtw_trace");
+        S5_LAUNCH_CHECK("k_sdtw_trace");
     }
     return rc;
 }
@@ -154,6 +110,6 @@ int dtwk::launch_event_gather(uint32_t n, const s5gpu_event_t *rows, const uint6
                               s5gpu_event_t *out, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_ev_gather, dim3(n), dim3(64), 0, st, n, reinterpret_cast<const U4 *>(rows), first, qlen, skip, qmax, reinterpret_cast<U4 *>(out));
-    DTW_LAUNCH_CHECK("k_ev_gather");
+    S5_LAUNCH_CHECK("k_ev_gather");
     return S5GPU_OK;
 }

@@ -4,20 +4,17 @@
 // compile it for the CPU and run the very code a lane runs, with plain adds in place of the atomics, against the restatements, without a
 // device.
 #pragma once
-#include <stdint.h>
-
-#include "../../include/slow5gpu.h"
-
-#ifdef S5_PILEUP_HOST
-#define PILE_HD static inline
-#else
-#include <hip/hip_runtime.h>
-#define PILE_HD __host__ __device__ __forceinline__
+#if defined(S5_PILEUP_HOST) && !defined(S5_DTW_HOST)
+#define S5_DTW_HOST
 #endif
+#include "dtw_dev.h"
+
+#define PILE_HD DTW_HD
 
 namespace pilek {
 
-constexpr uint32_t QMAX = 1024;              // rows of the largest query (dtwk::QMAX)
+using dtwk::QMAX;                            // rows of the largest query
+using dtwk::rows_of;                         // the rows of a read that count: qlen clamped to the pitch and to QMAX
 constexpr uint32_t RMAX = 1u << 26;          // columns of the largest table: 3 GiB
 constexpr uint32_t MIN_COLS = 64, MAX_COLS = 1024;   // the LDS window: 48 bytes a column
 constexpr uint32_t MAX_GRID = 1024;
@@ -25,12 +22,6 @@ constexpr uint32_t HEAD_WORDS = 8, COL_WORDS = 6;    // 64-bit words of the tota
 constexpr uint64_t EMPTY_MINMAX = (uint64_t)32767u | ((uint64_t)(uint32_t)-32768 << 32);   // word 5 of an empty column: min_q | max_q
 
 static_assert(sizeof(s5gpu_pile_col_t) == 8 * COL_WORDS && sizeof(s5gpu_pile_total_t) == 8 * HEAD_WORDS, "include/slow5gpu.h fixes these layouts");
-
-// the rows of a read that count: qlen clamped to the pitch and to QMAX
-PILE_HD uint32_t rows_of(uint32_t qlen, uint32_t qpitch) {
-    const uint32_t q = qlen < qpitch ? qlen : qpitch;
-    return q < QMAX ? q : QMAX;
-}
 
 // Row i of a read: 0 <= lo <= hi < R, and behind row 0 lo - hi_prev in {0, 1} (hi_prev = hi[i - 1]: whatever it holds, its own row's check
 // decides on it; the difference is taken in 64 bits).  A read is used iff every row i < Q passes.

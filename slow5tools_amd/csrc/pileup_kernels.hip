@@ -145,15 +145,6 @@ __global__ __launch_bounds__(s5::NT) void k_pileup(uint32_t n, uint64_t per, Pil
     }
 }
 
-#define PILE_LAUNCH_CHECK(what)                                                           \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int pilek::set_option(const char *key, long value) {
     if (!key) return S5GPU_ERR_ARG;
     if (strcmp(key, "pileup_lds_cols") == 0 && (value == 0 || (value >= (long)MIN_COLS && value <= (long)MAX_COLS && (value & (value - 1)) == 0))) {
@@ -167,14 +158,14 @@ int pilek::set_option(const char *key, long value) {
 int pilek::launch_reset(void *acc, uint32_t R, hipStream_t st) {
     const uint64_t words = HEAD_WORDS + (uint64_t)COL_WORDS * R, blocks = (words + s5::NT - 1) / s5::NT;
     hipLaunchKernelGGL(k_pileup_reset, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(s5::NT), 0, st, reinterpret_cast<uint64_t *>(acc), R);
-    PILE_LAUNCH_CHECK("k_pileup_reset");
+    S5_LAUNCH_CHECK("k_pileup_reset");
     return S5GPU_OK;
 }
 
 int pilek::launch_add_skipped(void *acc, uint32_t k, hipStream_t st) {
     if (k == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_pileup_add_skipped, dim3(1), dim3(64), 0, st, reinterpret_cast<uint64_t *>(acc), k);
-    PILE_LAUNCH_CHECK("k_pileup_add_skipped");
+    S5_LAUNCH_CHECK("k_pileup_add_skipped");
     return S5GPU_OK;
 }
 
@@ -185,7 +176,7 @@ int pilek::launch_pileup(uint32_t n, const PileArgs &A, hipStream_t st) {
     const uint64_t per = (uint64_t)((quads + want - 1) / want) * 4u;
     const uint32_t grid = (uint32_t)(((uint64_t)n + per - 1) / per);
     hipLaunchKernelGGL(k_pileup, dim3(grid), dim3(s5::NT), (size_t)cols * sizeof(s5gpu_pile_col_t), st, n, per, A, cols);
-    PILE_LAUNCH_CHECK("k_pileup");
+    S5_LAUNCH_CHECK("k_pileup");
     return S5GPU_OK;
 }
 
@@ -407,21 +398,21 @@ int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) {
     const uint32_t passes = g_long_passes;
     if (passes & 1u) {
         hipLaunchKernelGGL(k_pileup_long_plan, dim3(1), dim3(s5::NT), 0, st, A, S, L);
-        PILE_LAUNCH_CHECK("k_pileup_long_plan");
+        S5_LAUNCH_CHECK("k_pileup_long_plan");
     }
     if (passes & 2u) {
         hipLaunchKernelGGL(k_pileup_long_check, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sort, 0u);
-        PILE_LAUNCH_CHECK("k_pileup_long_check");
+        S5_LAUNCH_CHECK("k_pileup_long_check");
     }
     if (sort && (passes & 2u)) {
         hipLaunchKernelGGL(k_pileup_long_scan, dim3(1), dim3(LONG_KEYS), 0, st, L);
-        PILE_LAUNCH_CHECK("k_pileup_long_scan");
+        S5_LAUNCH_CHECK("k_pileup_long_scan");
         hipLaunchKernelGGL(k_pileup_long_check, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sort, 1u);
-        PILE_LAUNCH_CHECK("k_pileup_long_check (scatter)");
+        S5_LAUNCH_CHECK("k_pileup_long_check (scatter)");
     }
     if (passes & 4u) {
         hipLaunchKernelGGL(k_pileup_long_accum, dim3(grid), dim3(s5::NT), (size_t)cols * sizeof(s5gpu_pile_col_t), st, A, S, L, sort, cols);
-        PILE_LAUNCH_CHECK("k_pileup_long_accum");
+        S5_LAUNCH_CHECK("k_pileup_long_accum");
     }
     return S5GPU_OK;
 }

@@ -2,9 +2,10 @@
 //   k_path_fit        : a wave per read, four reads a workgroup (the shape of k_pileup).  The wave validates the WHOLE path (each lane its rows
 //                       i = lane, lane + 64, ..., one vote), then the lanes sum their rows' cells, the six int64 sums are reduced across the
 //                       wave, the line is solved, a and b are made wave-uniform, and each lane writes its rows of q'; lane 0 writes the fit.
-//   k_sdtw_win<G>     : the systolic wave of k_sdtw_dirs over the read's own window ref + ws of W' columns; in the same pass it carries the
-//                       (cost, end) candidate of k_sdtw: lane_best on the lane that holds row Q - 1, compiled per KB, guarded by j < W'.  No
-//                       S.  It writes the decision words in the slot layout of §4.17 and the row (cost', qlen, -1, end').
+//   k_sdtw_win<G>     : the systolic wave of k_sdtw_dirs over the read's own window ref + ws of W' columns (dirs_walk of dtw_dev.h with
+//                       BEST); in the same pass it carries the (cost, end) candidate of k_sdtw: lane_best on the lane that holds row Q - 1,
+//                       compiled per KB, guarded by j < W'.  No S.  It writes the decision words in the slot layout of §4.17 and the row
+//                       (cost', qlen, -1, end').
 //   k_sdtw_trace_win  : a SEPARATE launch (the kernel boundary makes the words visible), a lane per read: path_walk_from from
 //                       (Q - 1, end' - ws) to wherever it arrives in row 0; that column is start', written into the row.
 //   k_refine_round    : the bookkeeping of s5gpu_refine_dev between rounds: a trial round is taken over where it succeeded.
@@ -43,9 +44,6 @@ __device__ __forceinline__ double wave_first(double v) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
     return __longlong_as_double((long long)((uint64_t)lo | ((uint64_t)hi << 32)));
 }
-__device__ __forceinline__ uint64_t wave_read(uint32_t block_x, uint32_t tid) {
-    return (uint64_t)block_x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-}
 
 }  // namespace
 
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(256) void k_path_fit(uint32_t n, FitArgs A) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
     if (read >= n) return;                                                // (the wave's branch)
-    const uint32_t Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)pilek::rows_of(A.qlen[read], A.qpitch));
+    const uint32_t Q = wave_rows(A.qlen[read], A.qpitch);
     int32_t st = __builtin_amdgcn_readfirstlane(A.status_in[read]);
     const int32_t *lo = A.lo + read * A.qpitch, *hi = A.hi + read * A.qpitch;
     const int16_t *q = A.queries + read * A.qpitch;
@@ -91,36 +89,12 @@ __global__ __launch_bounds__(256) void k_path_fit(uint32_t n, FitArgs A) {
     }
 }
 
-// The steps of one read's window: whole words, every lane at every step (k_sdtw_dirs), and the candidate of the lane's row KB (k_sdtw)
-template <int G, int KB>
-__device__ __forceinline__ void win_walk(Lane<G, false> &L, const int16_t *__restrict__ ref, uint32_t W, uint32_t nw, uint32_t *slot, uint32_t lane) {
-    constexpr uint32_t SPW = 16 / G, WPB = 64 / SPW;                       // steps per word; words per block of 64 reference values
-    uint32_t rcur = 0;                                                     // the reference value of the column this lane did last
-    uint32_t j = 0u - lane;                                                // the column this lane does next (modulo 2^32 before its column 0)
-    for (uint32_t w0 = 0; w0 < nw; w0 += WPB) {
-        const uint32_t at = w0 * SPW + lane;                               // the wave's block of reference values, zeros behind the window
-        const uint32_t rblk = biased(at < W ? ref[at] : (int16_t)0);
-        const uint32_t cnt = nw - w0 < WPB ? nw - w0 : WPB;
-        for (uint32_t wi = 0; wi < cnt; wi++) {
-            uint32_t word = 0;
-#pragma unroll
-            for (uint32_t s = 0; s < SPW; s++) {
-                const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)rblk, (int)(wi * SPW + s));
-                rcur = shift_up1(rcur, r0);
-                const uint32_t up = shift_up1_zero(L.d[G - 1]);
-                word = path_pack(word, lane_step_dirs(L, rcur, up), s, G);
-                lane_best<G, false, KB>(L, j, W);
-                j++;
-            }
-            slot[(uint64_t)(w0 + wi) * 64u] = word;
-        }
-    }
-}
-// kb -> the walk compiled for it (kb is the same in every lane: scalar branches, once per read)
+// kb -> the walk compiled for it.  The kernel's own dispatch, as k_sdtw_band's TileWalk, not with_kb of dtw_dev.h: through the closure the
+// window call measured 0.5 to 1 % slower; with this struct the kernel has the instruction counts it had with a walk of its own
 template <int G, int KB = 0>
 struct WinWalk {
     static __device__ __forceinline__ void run(int kb, Lane<G, false> &L, const int16_t *__restrict__ ref, uint32_t W, uint32_t nw, uint32_t *slot, uint32_t lane) {
-        if (kb == KB) win_walk<G, KB>(L, ref, W, nw, slot, lane);
+        if (kb == KB) dirs_walk<G, KB, true>(L, ref, W, nw, slot, lane);
         else if constexpr (KB + 1 < G) WinWalk<G, KB + 1>::run(kb, L, ref, W, nw, slot, lane);
     }
 };
@@ -129,17 +103,15 @@ template <int G>
 __global__ __launch_bounds__(256) void k_sdtw_win(uint32_t n, WinArgs A) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
-    if (read >= n) return;                                                // (the wave's branch)
-    uint32_t Q = A.qlen[read];
-    Q = Q < A.qpitch ? Q : A.qpitch;
-    Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(Q < QMAX ? Q : QMAX));
-    if (Q > 64u * G || (G > 1 && Q <= 32u * G)) return;                    // another launch's read
+    if (read >= n) return;                                                // (the wave's branch: `read` is the same in its 64 lanes)
+    const uint32_t Q = wave_rows(A.qlen[read], A.qpitch);
+    if (other_launch<G>(Q)) return;
     int32_t st = A.gate ? A.gate[read] : 0;
     uint32_t W = 0, ws = 0;
     if (st == 0 && Q) st = win_row_check(A.rows_in[read], Q, A.R, A.pad, A.wmax, &ws, &W);
-    st = __builtin_amdgcn_readfirstlane(st);
-    W = (uint32_t)__builtin_amdgcn_readfirstlane((int)W);
-    ws = (uint32_t)__builtin_amdgcn_readfirstlane((int)ws);
+    st = (int32_t)sgpr((uint32_t)st);
+    W = sgpr(W);
+    ws = sgpr(ws);
     const bool path = Q != 0 && st == 0;
     int32_t *lo = A.lo + read * A.qpitch, *hi = A.hi + read * A.qpitch;
     for (uint32_t x = (path ? Q : 0u) + lane; x < A.qpitch; x += 64u) { lo[x] = -1; hi[x] = -1; }
@@ -152,14 +124,10 @@ __global__ __launch_bounds__(256) void k_sdtw_win(uint32_t n, WinArgs A) {
     lane_init(L, lane == 0);
     const int16_t *q = A.queries + read * A.qpitch;
 #pragma unroll
-    for (int k = 0; k < G; k++) {
-        const uint32_t row = lane * G + k;
-        L.q[k] = biased(row < Q ? q[row] : (int16_t)0);
-    }
-    const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1: it does column W - 1 at step W - 1 + last
-    const int kb = (int)(Q - 1 - last * G);
-    uint32_t nw = path_words(G, W + last);
-    nw = nw < A.slot_words ? nw : A.slot_words;                            // (never less: slot_words holds wmax + 63 steps of the pitch's G)
+    for (int k = 0; k < G; k++) L.q[k] = query_value(q, lane * G + k, Q);
+    const uint32_t last = (Q - 1) / G;                                     // the lane of row Q - 1 ...
+    const int kb = (int)(Q - 1 - last * G);                                // ... and which of its rows it is
+    const uint32_t nw = walk_words<G>(W, last, A.slot_words);
     uint32_t *slot = A.scratch + read * ((uint64_t)A.slot_words * 64u) + lane;
     WinWalk<G>::run(kb, L, A.ref + ws, W, nw, slot, lane);
     if (lane == last) A.rows_out[read] = result_row(L.best, Q, -1, (int32_t)ws + L.best_end);
@@ -168,9 +136,7 @@ __global__ __launch_bounds__(256) void k_sdtw_win(uint32_t n, WinArgs A) {
 __global__ __launch_bounds__(64) void k_sdtw_trace_win(uint32_t n, WinArgs A) {
     const uint64_t read = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (read >= n) return;
-    uint32_t Q = A.qlen[read];
-    Q = Q < A.qpitch ? Q : A.qpitch;
-    Q = Q < QMAX ? Q : QMAX;
+    const uint32_t Q = rows_of(A.qlen[read], A.qpitch);
     if (Q == 0 || (A.gate && A.gate[read] != 0)) return;
     uint32_t W, ws;
     if (win_row_check(A.rows_in[read], Q, A.R, A.pad, A.wmax, &ws, &W) != 0) return;   // (k_sdtw_win wrote the status, the empty row and the -1s)
@@ -196,7 +162,7 @@ __global__ __launch_bounds__(256) void k_refine_round(uint32_t n, RoundArgs A, u
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t read = wave_read(blockIdx.x, threadIdx.x);
     if (read >= n) return;
-    const uint32_t Q = (uint32_t)__builtin_amdgcn_readfirstlane((int)pilek::rows_of(A.qlen[read], A.qpitch));
+    const uint32_t Q = wave_rows(A.qlen[read], A.qpitch);
     const uint64_t at = read * A.qpitch;
     int mode;                                                             // 0 nothing, 1 from what came in, 2 from the trial, 3 no result
     int32_t st = 0;
@@ -229,46 +195,30 @@ __global__ __launch_bounds__(256) void k_refine_round(uint32_t n, RoundArgs A, u
     }
 }
 
-#define REF_LAUNCH_CHECK(what)                                                            \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int refk::launch_fit(uint32_t n, const FitArgs &A, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_path_fit, dim3((uint32_t)(((uint64_t)n + 3u) / 4u)), dim3(256), 0, st, n, A);
-    REF_LAUNCH_CHECK("k_path_fit");
+    S5_LAUNCH_CHECK("k_path_fit");
     return S5GPU_OK;
 }
 
-template <int G>
-static int launch_win_class(uint32_t n, const WinArgs &A, hipStream_t st) {
-    hipLaunchKernelGGL((k_sdtw_win<G>), dim3((uint32_t)(((uint64_t)n + 3u) / 4u)), dim3(256), 0, st, n, A);
-    REF_LAUNCH_CHECK("k_sdtw_win");
-    return S5GPU_OK;
-}
-
-// a launch per lane height that a query of at most qpitch rows can need, as launch_path; then the trace
+// a launch per lane height that a query of at most qpitch rows can need; then the trace
 int refk::launch_window(uint32_t n, const WinArgs &A, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
-    int rc = launch_win_class<1>(n, A, st);
-    if (!rc && A.qpitch > 64) rc = launch_win_class<2>(n, A, st);
-    if (!rc && A.qpitch > 128) rc = launch_win_class<4>(n, A, st);
-    if (!rc && A.qpitch > 256) rc = launch_win_class<8>(n, A, st);
-    if (!rc && A.qpitch > 512) rc = launch_win_class<16>(n, A, st);
+    const int rc = for_each_lane_height(A.qpitch, [&](auto g) -> int {
+        hipLaunchKernelGGL((k_sdtw_win<decltype(g)::value>), wave_grid(n), dim3(256), 0, st, n, A);
+        S5_LAUNCH_CHECK("k_sdtw_win");
+        return S5GPU_OK;
+    });
     if (rc) return rc;
     hipLaunchKernelGGL(k_sdtw_trace_win, dim3((uint32_t)(((uint64_t)n + 63u) / 64u)), dim3(64), 0, st, n, A);
-    REF_LAUNCH_CHECK("k_sdtw_trace_win");
+    S5_LAUNCH_CHECK("k_sdtw_trace_win");
     return S5GPU_OK;
 }
 
 int refk::launch_round(uint32_t n, const RoundArgs &A, uint32_t round, hipStream_t st) {
     if (n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_refine_round, dim3((uint32_t)(((uint64_t)n + 3u) / 4u)), dim3(256), 0, st, n, A, round);
-    REF_LAUNCH_CHECK("k_refine_round");
+    S5_LAUNCH_CHECK("k_refine_round");
     return S5GPU_OK;
 }

@@ -17,6 +17,7 @@ import pytest
 
 import oracle_bind as ob
 from blow5_fixture import Blow5, golden
+from test_map import last_lane_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DNA = (3, 6, 1.4, 9.0, 0.2)
@@ -322,7 +323,20 @@ static int one_case(FILE *f, FILE *o) {
     return 0;
 }
 
+// A decision buffer whose walk reaches row 0 right of window column 0: Q = 3 rows in a window of W = 2 columns, every code 1 ((i - 1, j)),
+// so from (2, 1) it goes straight up to (0, 1).  Prints path_walk's status, and what path_walk_from says of the same buffer.
+static int row0_case(void) {
+    const uint32_t G = 1, Q = 3, W = 2, slot_words = path_words(G, W + 63);
+    std::vector<uint32_t> slot((size_t)slot_words * 64, 0x55555555u);
+    int32_t lo[3] = {-7, -7, -7}, hi[3] = {-7, -7, -7}, lo2[3], hi2[3], start = -7;
+    const int32_t st = path_walk(slot.data(), slot_words, G, Q, W, 10, lo, hi);
+    const int32_t st2 = path_walk_from(slot.data(), slot_words, G, Q, W, 10, W - 1, lo2, hi2, &start);
+    printf("%d %d %d\n", st, st2, start);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 2 && strcmp(argv[1], "row0") == 0) return row0_case();
     if (argc != 3) return 1;
     FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
     if (!f || !o) return 1;
@@ -426,6 +440,8 @@ def test_the_path_code_compiled_for_the_cpu_matches_the_restatement(tmp_path):
     assert at == len(raw) and {1, 2, 63, 64, 65, 129} <= widths
     for (q, r, lo, hi), case in zip(HAND_MADE, cases[-len(HAND_MADE):]):
         assert path_ref(case[0], case[1])[1].tolist() == lo
+    # a walk that arrives in row 0 right of window column 0 is refused by path_walk; path_walk_from takes it, and names the column (10 + 1)
+    assert subprocess.check_output([exe, "row0"], text=True).split() == [str(PATH_ROW), "0", "11"]
 
 
 def test_refused_arguments_are_refused_before_a_device_is_needed():
@@ -585,6 +601,15 @@ def test_path_is_exact_on_a_mixed_batch(gpu, mixed, name, R):
     assert st[0] == 0 and (lo[0] == -1).all() and (hi[0] == -1).all()      # qlen = 0: status 0 and no path
     for i, Q in enumerate(QLENS):
         assert (lo[i, Q:] == -1).all() and (hi[i, Q:] == -1).all() and (lo[i, :Q] >= 0).all()
+
+
+@pytest.mark.gpu
+def test_path_every_row_of_the_last_lane(gpu):
+    qm, ql = last_lane_batch()
+    ref = np.random.default_rng(42).integers(-127, 128, 129).astype(np.int16)
+    want = _want(qm, ql, ref, 1024)
+    assert want[2]["qlen"].tolist() == ql and (want[2]["cost"] < 2 ** 26).all() and (want[0][:, 0] >= 0).all()      # every read has a path
+    _check(_run_path(gpu, qm, ql, ref, wmax=129), want, "every row of the last lane")
 
 
 @pytest.mark.gpu

@@ -286,7 +286,7 @@ static uint32_t carry_at(const Carry &C, uint32_t x) {
     return carry_value(C.first ? 0u : C.S[at], in, C.pmin, C.first);
 }
 
-// a tile's steps: tile_walk of band_kernels.hip, the block fetch at every 64th step included
+// a tile's steps: dirs_walk of dtw_dev.h with band_kernels.hip's Carry, the block fetch at every 64th step included
 template <int G, int KB>
 static void tile(std::vector<Lane<G, false> > &L, const int16_t *ref, uint32_t W, uint32_t nw, uint32_t *slot, const Carry &C, uint32_t wl) {
     const uint32_t SPW = 16 / G;
@@ -735,6 +735,21 @@ def test_band_is_exact_on_a_mixed_batch(gpu, R, T, band):
     st = got[2]
     assert st[7] == 7 and st[36] == QUERY_SHORT and st[37] == QUERY_SHORT and (st == 0).sum() == 37
     assert got[3]["status"][7] == 7 and got[3]["cost"][7] == NO_COST64 and got[3]["status"][36] == QUERY_SHORT
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 2, 4, 8, 16])
+def test_band_every_row_of_the_last_lane(gpu, G):
+    """tiles of T = 64 G rows: reads of T - k rows, k < G (one tile, no row carried out), and of 2 T - k (two tiles), so that the last row of
+    the last tile is every row (Qk - 1) % G of the lane that holds it: the walks are compiled per such row"""
+    T, band = 64 * G, 64
+    qs = [T - k for k in range(G)] + [2 * T - k for k in range(G)]
+    assert {(Q - 1) % G for Q in qs[:G]} == set(range(G)) and {(Q - T - 1) % G for Q in qs[G:]} == set(range(G))
+    rd = Reads(300, qs, skip=3, seed=950 + G)
+    wants = {(i, T, band, rd.anchor[i]): band_ref(rd.q[i], rd.ref, rd.anchor[i], T, band) for i in range(rd.n)}
+    assert [w["row"][1:3] for w in wants.values()] == [(Q, 1 + (i >= G)) for i, Q in enumerate(qs)]
+    assert all(w["row"][6] == 0 and w["row"][0] < NO_COST64 and w["lo"][0] >= 0 for w in wants.values())       # every read has a result
+    _check_band(rd, _run_band(gpu, rd, T, band), T, band, wants=wants)
 
 
 @pytest.mark.gpu

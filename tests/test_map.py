@@ -284,10 +284,7 @@ int main(int argc, char **argv) {
             std::vector<float> m((size_t)L * stride + 1);
             std::vector<int16_t> q(L + 1);
             if (fread(m.data(), 4, (size_t)L * stride, f) != (size_t)L * stride) return 1;
-            double mu = 0, sd = 0;
-            if (L) quant_stats(m.data(), stride, L, &mu, &sd);
-            const bool ok = L && quant_ok(sd);
-            for (uint32_t j = 0; j < L; j++) q[j] = ok ? quant_one(m[(size_t)j * stride], mu, sd, scale, clip) : (int16_t)0;
+            if (L) quant_row(m.data(), stride, L, scale, clip, q.data());
             fwrite(q.data(), 2, L, o);
         }
     }
@@ -422,6 +419,20 @@ def mixed_batches():
     return {"pm127": _mixed(rng, -127, 127), "ties": _mixed(rng, -1, 1)}
 
 
+def last_lane_batch(seed=41):
+    """Every row of the last lane: for each lane height G the queries of Q = 64 G - k rows, k < G, whose last row is row (Q - 1) % G of the
+    lane that holds it (the walks are compiled per such row), and for G > 1 the smallest query of the class, 32 G + 1.  -> (the [35, 1024]
+    matrix of +-127, 9999 behind each query; the 35 lengths).  That every row of every lane height occurs is asserted here."""
+    ql = [64 * g - k for g in (1, 2, 4, 8, 16) for k in range(g)] + [32 * g + 1 for g in (2, 4, 8, 16)]
+    for g in (1, 2, 4, 8, 16):
+        assert {(Q - 1) % g for Q in ql if _g_of(Q) == g} == set(range(g)), g
+    rng = np.random.default_rng(seed)
+    qm = np.full((len(ql), 1024), 9999, dtype=np.int16)
+    for i, n in enumerate(ql):
+        qm[i, :n] = rng.integers(-127, 128, n)
+    return qm, ql
+
+
 def _check_rows(got, want, what):
     for col in ("cost", "qlen", "start", "end"):
         bad = np.nonzero(got[col] != want[col])[0]
@@ -440,6 +451,19 @@ def test_sdtw_is_exact_on_a_mixed_batch(gpu, mixed_batches, R):
         if not ws:
             w["start"] = -1
         _check_rows(_run_sdtw(gpu, qm, QLENS, ref, ws), w, (R, ws))
+
+
+@pytest.mark.gpu
+def test_sdtw_every_row_of_the_last_lane(gpu):
+    qm, ql = last_lane_batch()
+    ref = np.random.default_rng(42).integers(-127, 128, 129).astype(np.int16)
+    want = rows_ref(qm, ql, ref, True)
+    assert want["qlen"].tolist() == ql and (want["cost"] < 2 ** 26).all() and (want["start"] >= 0).all()       # every read has a result
+    for ws in (False, True):
+        w = want.copy()
+        if not ws:
+            w["start"] = -1
+        _check_rows(_run_sdtw(gpu, qm, ql, ref, ws), w, ("every row of the last lane", ws))
 
 
 @pytest.mark.gpu

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from blow5_fixture import Blow5, golden
-from test_map import DNA, EVENT, MAP_ROW, NO_COST, QLENS, QUERY_SHORT, RS, _lines, _mixed, quant_ref, sdtw_ref
+from test_map import DNA, EVENT, MAP_ROW, NO_COST, QLENS, QUERY_SHORT, RS, _lines, _mixed, last_lane_batch, quant_ref, sdtw_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAP_SECOND = np.dtype([("cost2", "<u4"), ("end2", "<i4"), ("mapq", "<u4"), ("zero", "<u4")])
@@ -552,6 +552,20 @@ def test_sdtw2_is_exact_on_the_mixed_batch(gpu, mixed_batches, R, kind, lo, hi):
         assert (np.abs((want["end2"][1:] >> 6) - (rows["end"][1:] >> 6)) >= 2).all()
         got7 = _run_sdtw2(gpu, qm, QLENS, ref, False, bshift=7)[1]
         _check_second(got7, seconds_ref(qm, QLENS, ref, 7), (R, kind, "bshift 7"))
+
+
+@pytest.mark.gpu
+def test_sdtw2_every_row_of_the_last_lane(gpu):
+    qm, ql = last_lane_batch()
+    ref = np.random.default_rng(43).integers(-127, 128, 300).astype(np.int16)
+    last = [last_rows(qm[i, :n], ref) for i, n in enumerate(ql)]
+    want = np.array([second_ref(L, 6) for L in last], dtype=MAP_SECOND)
+    assert (want["end2"] >= 0).all() and (want["cost2"] < 2 ** 26).all()                                       # every read has a runner-up
+    for ws in (False, True):
+        rows, sec = _run_sdtw2(gpu, qm, ql, ref, ws)
+        _check_second(sec, want, ("every row of the last lane", ws))
+        assert rows["qlen"].tolist() == ql and (rows["start"] >= 0).all() == ws
+        assert rows["cost"].tolist() == [int(L.min()) for L in last] and rows["end"].tolist() == [int(L.argmin()) for L in last]
 
 
 @pytest.mark.gpu

@@ -16,6 +16,7 @@ import pytest
 
 import oracle_bind as ob
 from blow5_fixture import Blow5, golden
+from test_map import last_lane_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DNA = (3, 6, 1.4, 9.0, 0.2)
@@ -847,6 +848,16 @@ def test_window_is_exact_on_a_mixed_batch(gpu, mixed, R, pad):
     want = _want_window(B, rows, pad, int(W.max()))                        # every read in its window
     assert (want[3] == 0).sum() == B.n - 1
     _same(_run_window(gpu, B, rows, pad, int(W.max())), want, (R, pad, "all"))
+
+
+@pytest.mark.gpu
+def test_window_every_row_of_the_last_lane(gpu):
+    qm, ql = last_lane_batch()
+    B = Batch(gpu, qm, ql, np.random.default_rng(42).integers(-127, 128, 129).astype(np.int16))
+    want = _want_window(B, B.rows, 1, 129)
+    assert not want[3].any() and want[0]["qlen"].tolist() == ql and (want[0]["cost"] < 2 ** 26).all()          # every read has a result
+    assert (want[1][:, 0] >= 0).all()
+    _same(_run_window(gpu, B, B.rows, 1, 129), want, "every row of the last lane")
 
 
 @pytest.mark.gpu
