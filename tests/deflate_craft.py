@@ -10,11 +10,17 @@ block of literals and varies its HEADER:
 The second (Stream, py_inflate, catalogue; tests/test_inflate_craft.py) writes whole streams token by token — stored, fixed and dynamic
 blocks at any bit offset, any symbol and extra-bit choice, any code lengths, complete or not, any zlib wrapper — executes its own tokens to
 know what a valid stream holds, and restates inflate in plain Python from the RFCs, with zlib's rules for the code tables.
+
+A third part, for the ENCODER (tests/test_deflate_encode_craft.py), stands at the end: parse_blocks reads a stream down to header fields,
+code-length entries and tokens; rle_tokens, cl_rle and the cost functions restate the encoder's rules; encode_catalogue names record
+payloads that reach its edges.
 """
 import collections
 import functools
 import heapq
+import re
 import struct
+import types
 import zlib
 
 import numpy as np
@@ -933,3 +939,601 @@ def catalogue():
 
 def by_name():
     return {e.name: e for e in catalogue()}
+
+
+# ================================================================ the ENCODER's side: what a record's stream holds, token by token
+# (tests/test_deflate_encode_craft.py).  parse_blocks reads a zlib stream down to its header fields, code-length entries and tokens;
+# rle_tokens, cl_rle and the cost functions restate what csrc/deflate2_dev.h and cl_header_wave (csrc/deflate_dev.h) promise in their
+# comments — the rule, in plain Python over bytes and lists, not the kernels' mask arithmetic —; encode_catalogue names the smallest
+# record payloads that reach each edge of the encoder.
+BLOCK = 16384                    # DEFL_BLK: payload bytes of one DEFLATE block (the staged form cuts there; the fused kernels take one block)
+SLAB = 256                       # positions of a wave step: slab k covers [256 k - 2, 256 k + 254), a lane four of them
+DEFL2_LIST_CAP = 640             # tokens of the list in S.freq
+DEFL2_LISTB_MIN = 64             # the list's second pool (staged form) never reaches below this word of the bit buffer
+STAGED_OBUF_WORDS = (BLOCK + 64) // 4          # staged_shape(): words of the staged kernel's bit buffer
+STAGED_WF_AT = STAGED_OBUF_WORDS - 4 * 288     # ... below its four per-wave histograms: the second pool grows down from here
+LIST_CAP_STAGED = DEFL2_LIST_CAP + (STAGED_WF_AT - DEFL2_LISTB_MIN) * 2
+# the two static code-length codes of cl_header_wave, as data: lengths of symbols 0 .. 18
+CLA_LENS = [3, 7, 7, 7, 7, 5, 5, 5, 5, 5, 3, 2, 2, 7, 0, 0, 5, 6, 7]      # HCLEN 18 (symbol 15 stands last in ORDER and has no code)
+CLB_LENS = [3, 6, 7, 7, 6, 5, 4, 5, 5, 4, 3, 3, 2, 7, 7, 7, 4, 6, 7]      # HCLEN 19
+CL_EXTRA = {16: 2, 17: 3, 18: 7}
+
+
+def _peek_table(lengths):
+    """([(symbol, length) or None] indexed by the next m bits of the stream, m = the longest length) of a canonical code"""
+    m = max(lengths) if lengths else 0
+    tab = [None] * (1 << m)
+    for s, (c, l) in enumerate(zip(canonical(list(lengths)), lengths)):
+        if l:
+            r = int(format(c, "0%db" % l)[::-1], 2)
+            for k in range(r, 1 << m, 1 << l):
+                tab[k] = (s, l)
+    return tab, m
+
+
+@functools.lru_cache(maxsize=None)          # (the routes hand in the same streams again and again; the result is read, never changed)
+def parse_blocks(stream):
+    """RFC 1950 / 1951 on `stream`, keeping what py_inflate throws away.  -> namespace(header, blocks, data, adler, trailing); a block:
+    btype, bfinal, first_bit, end_bit (bit positions in the deflate data: the block is [first_bit, end_bit)), at (bytes out in front of
+    it), data (the bytes it produces); stored: pad (the bits up to the byte boundary); Huffman: tokens [("L", byte) | ("M", length,
+    distance)], tokens_at; dynamic: hlit, hdist, hclen, cll (the 19 code-length-code lengths), entries [(symbol, extra value)] of the
+    code-length sequence as sent, litlens, dlens.  adler: the four bytes behind the last block as a number, trailing: what follows them.
+    ValueError on anything that is not a stream."""
+    if len(stream) < 6 or (stream[0] & 15) != 8 or (stream[0] >> 4) > 7 or (stream[0] * 256 + stream[1]) % 31 or stream[1] & 0x20:
+        raise ValueError("zlib header")
+    d = stream[2:]
+    nbits = 8 * len(d)
+
+    def peek(pos, n):                          # n <= 25
+        return (int.from_bytes(d[pos >> 3:(pos >> 3) + 4], "little") >> (pos & 7)) & ((1 << n) - 1)
+
+    pos, out, blocks = 0, bytearray(), []
+    while True:
+        b = types.SimpleNamespace(first_bit=pos, at=len(out))
+        b.bfinal, b.btype = peek(pos, 1), peek(pos + 1, 2)
+        pos += 3
+        if b.btype == 3:
+            raise ValueError("block type 3")
+        if b.btype == 0:
+            padn = -pos & 7
+            b.pad = peek(pos, padn)
+            pos += padn
+            ln, nl = peek(pos, 16), peek(pos + 16, 16)
+            pos += 32
+            if ln ^ nl != 0xFFFF or (pos >> 3) + ln > len(d):
+                raise ValueError("stored block")
+            out += d[pos >> 3:(pos >> 3) + ln]
+            pos += 8 * ln
+        else:
+            if b.btype == 1:
+                ll, dl = FIXED_LL, FIXED_DL
+            else:
+                b.hlit, b.hdist, b.hclen = peek(pos, 5) + 257, peek(pos + 5, 5) + 1, peek(pos + 10, 4) + 4
+                pos += 14
+                if b.hlit > 286 or b.hdist > 30:
+                    raise ValueError("HLIT / HDIST")
+                b.cll = [0] * 19
+                for k in range(b.hclen):
+                    b.cll[ORDER[k]] = peek(pos, 3)
+                    pos += 3
+                if sum(1 << (7 - l) for l in b.cll if l) != 128:
+                    raise ValueError("code-length code")
+                ct, cm = _peek_table(b.cll)
+                b.entries, lens = [], []
+                while len(lens) < b.hlit + b.hdist:
+                    s, l = ct[peek(pos, cm)]
+                    pos += l
+                    x = peek(pos, CL_EXTRA.get(s, 0))
+                    pos += CL_EXTRA.get(s, 0)
+                    if s == 16 and not lens:
+                        raise ValueError("repeat with nothing in front")
+                    lens += [s] if s < 16 else [lens[-1]] * (3 + x) if s == 16 else [0] * ((3 if s == 17 else 11) + x)
+                    b.entries.append((s, x))
+                if len(lens) > b.hlit + b.hdist or pos > nbits:
+                    raise ValueError("code-length sequence")
+                ll, dl = b.litlens, b.dlens = lens[:b.hlit], lens[b.hlit:]
+            lt, lm = _peek_table(ll)
+            dt, dm = _peek_table(dl)
+            b.tokens_at, b.tokens = pos, []
+            while True:
+                e = lt[peek(pos, lm)]
+                if e is None or pos > nbits:
+                    raise ValueError("lit/len code")
+                pos += e[1]
+                s = e[0]
+                if s < 256:
+                    b.tokens.append(("L", s))
+                    out.append(s)
+                elif s == 256:
+                    break
+                else:
+                    if s > 285:
+                        raise ValueError("lit/len symbol %d" % s)
+                    length = LBASE[s - 257] + peek(pos, LEXT[s - 257])
+                    pos += LEXT[s - 257]
+                    e = dt[peek(pos, dm)] if dm else None
+                    if e is None or e[0] >= 30:
+                        raise ValueError("distance code")
+                    pos += e[1]
+                    dist = DBASE[e[0]] + peek(pos, DEXT[e[0]])
+                    pos += DEXT[e[0]]
+                    if dist > len(out):
+                        raise ValueError("distance %d with %d bytes out" % (dist, len(out)))
+                    b.tokens.append(("M", length, dist))
+                    if dist >= length:
+                        out += out[len(out) - dist:len(out) - dist + length]
+                    else:
+                        for _ in range(length):
+                            out.append(out[-dist])
+        if pos > nbits:
+            raise ValueError("truncated")
+        b.end_bit, b.data = pos, bytes(out[b.at:])
+        blocks.append(b)
+        if b.bfinal:
+            break
+    end = (pos + 7) >> 3
+    if len(d) < end + 4:
+        raise ValueError("truncated")
+    return types.SimpleNamespace(header=bytes(stream[:2]), blocks=blocks, data=bytes(out), adler=struct.unpack(">I", d[end:end + 4])[0], trailing=bytes(d[end + 4:]))
+
+
+def as_stream_tokens(tokens):
+    """parse_blocks' tokens as Stream's"""
+    return [lit(t[1]) if t[0] == "L" else match(t[1], t[2]) for t in tokens]
+
+
+def emit_blocks(p):
+    """the stream that parse_blocks read, written again from what it returned: canonical codes from the lengths, the code-length
+    entries as sent, every token with the one symbol and extra-bit choice an encoder makes"""
+    w = Bits()
+    for b in p.blocks:
+        w.put(b.bfinal, 1)
+        w.put(b.btype, 2)
+        if b.btype == 0:
+            if w.n:
+                w.put(b.pad, 8 - w.n)
+            w.put(len(b.data), 16)
+            w.put(len(b.data) ^ 0xFFFF, 16)
+            w.out += b.data
+            continue
+        ll, dl = FIXED_LL, FIXED_DL
+        if b.btype == 2:
+            ll, dl = b.litlens, b.dlens
+            w.put(b.hlit - 257, 5); w.put(b.hdist - 1, 5); w.put(b.hclen - 4, 4)
+            for k in range(b.hclen):
+                w.put(b.cll[ORDER[k]], 3)
+            cc = _codes(b.cll)
+            for s, x in b.entries:
+                w.put(*cc[s])
+                w.put(x, CL_EXTRA.get(s, 0))
+        lc, dc = _codes(ll), _codes(dl)
+        for t in as_stream_tokens(b.tokens):
+            if t[0] == "lit":
+                w.put(*lc[t[1]])
+            else:
+                w.put(*lc[t[3]]); w.put(t[4], LEXT[t[3] - 257]); w.put(*dc[t[5]]); w.put(t[6], DEXT[t[5]])
+        w.put(*lc[256])
+    return p.header + w.done() + struct.pack(">I", p.adler) + p.trailing
+
+
+# ---------------------------------------------------------------- the tokeniser, restated from the head comment of csrc/deflate2_dev.h
+def runs_of(data):
+    """[(first position, length)] of the maximal runs of equal bytes"""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    if not len(a):
+        return []
+    starts = np.concatenate([[0], np.flatnonzero(a[1:] != a[:-1]) + 1])
+    return list(zip(starts.tolist(), np.diff(np.concatenate([starts, [len(a)]])).tolist()))
+
+
+def rle_tokens(block_bytes):
+    """the tokens of ONE block: a run of R <= 3 equal bytes is R literals; a run of R >= 4 is one literal, (R - 1) // 258 matches
+    (258, distance 1), and for rem = (R - 1) % 258 one match (rem, 1) if rem >= 3, else rem literals"""
+    out = []
+    for s, r in runs_of(block_bytes):
+        v = block_bytes[s]
+        if r <= 3:
+            out += [("L", v)] * r
+            continue
+        out.append(("L", v))
+        out += [("M", 258, 1)] * ((r - 1) // 258)
+        rem = (r - 1) % 258
+        out += [("M", rem, 1)] if rem >= 3 else [("L", v)] * rem
+    return out
+
+
+def pieces(payload):
+    """the blocks of a payload: the staged form cuts at every 16384 bytes (a payload of at most one block is one block; an empty one too)"""
+    return [payload[i:i + BLOCK] for i in range(0, len(payload), BLOCK)] or [b""]
+
+
+def expand(tokens):
+    out = bytearray()
+    for t in tokens:
+        if t[0] == "L":
+            out.append(t[1])
+        else:
+            for _ in range(t[1]):
+                out.append(out[-t[2]])
+    return bytes(out)
+
+
+def slab_token_counts(block_bytes):
+    """{slab: tokens} of the GENERAL slabs of a block, the ones whose tokens pass 1 puts on the list: slab k covers positions
+    [256 k - 2, 256 k + 254); it is general if one of its positions lies in a run of >= 4 bytes behind that run's first byte.  A literal
+    counts at its own position, what a run sends behind its first byte at the run's LAST position."""
+    general, count = set(), collections.Counter()
+    for s, r in runs_of(block_bytes):
+        if r <= 3:
+            for p in range(s, s + r):
+                count[(p + 2) // SLAB] += 1
+            continue
+        count[(s + 2) // SLAB] += 1
+        rem = (r - 1) % 258
+        count[(s + r - 1 + 2) // SLAB] += (r - 1) // 258 + (1 if rem >= 3 else rem)
+        general.update(range((s + 1 + 2) // SLAB, (s + r - 1 + 2) // SLAB + 1))
+    return {k: count[k] for k in sorted(general)}
+
+
+# ---------------------------------------------------------------- costs, from a token list: exact integer arithmetic
+def token_symbol(t):
+    """(lit/len symbol, extra bits) of a token"""
+    if t[0] == "L":
+        return t[1], 0
+    k = 28 if t[1] == 258 else max(s for s in range(28) if LBASE[s] <= t[1])
+    return 257 + k, LEXT[k]
+
+
+def _dist_symbol(dist):
+    return max(s for s in range(30) if DBASE[s] <= dist)
+
+
+def token_freq(tokens):
+    """occurrences of the 286 lit/len symbols, the end-of-block code counted once"""
+    f = [0] * 286
+    for t in tokens:
+        f[token_symbol(t)[0]] += 1
+    f[256] += 1
+    return f
+
+
+def _side_bits(tokens, fixed):
+    """length extra bits + what the distances take: 5 bits + extra under the fixed code, 1 bit under the encoder's two 1-bit codes"""
+    n = 0
+    for t in tokens:
+        if t[0] == "M":
+            n += token_symbol(t)[1] + (5 + DEXT[_dist_symbol(t[2])] if fixed else 1)
+    return n
+
+
+def fixed_bits(tokens):
+    """a fixed block: 3 + body under the fixed code + 7"""
+    return 3 + sum(FIXED_LL[token_symbol(t)[0]] for t in tokens) + _side_bits(tokens, True) + 7
+
+
+def stored_bits(at_bit, n):
+    """a stored block of n bytes whose header starts at bit at_bit: 3 + pad to the byte + 32 + 8 n"""
+    return 3 + (-(at_bit + 3) & 7) + 32 + 8 * n
+
+
+def shannon_lengths(freq):
+    """ceil(log2(N / f)) per symbol in use, N = sum(freq): the smallest l with f << l >= N (where assign_lengths_wave starts; <= 15 for
+    N <= 32768)"""
+    N = sum(freq)
+    return [0 if not f else next(l for l in range(1, 32) if (f << l) >= N) for f in freq]
+
+
+def shannon_body_bits(tokens):
+    """sum over the tokens' symbols of f * ceil(log2(N / f)), N = tokens + one end-of-block, + the matches' extra and distance bits (the
+    end-of-block code itself is not in it)"""
+    f = token_freq(tokens)
+    ls = shannon_lengths(f)
+    f[256] -= 1
+    return sum(a * b for a, b in zip(f, ls)) + _side_bits(tokens, False)
+
+
+def dyn_upper(tokens, hlit=286):
+    """what the encoder's own dynamic block costs at most: 17 header bits, 19 code-length-code lengths, <= 7 bits per code length
+    described (an entry of either static code-length code costs at most that per length it covers), the body at its Shannon start
+    (assign_lengths_wave only shortens the codes of symbols in use), an end-of-block code of <= 15 bits"""
+    return 17 + 3 * 19 + 7 * (hlit + 2) + shannon_body_bits(tokens) + 15
+
+
+def huffman_body_bits(tokens):
+    """the body under an optimal Huffman code of the tokens' symbols and end-of-block (no dynamic block has a smaller body; nor has the
+    fixed one), the matches' extra and distance bits as the encoder's dynamic block sends them"""
+    f = token_freq(tokens)
+    ls = huff_lengths(f, 15) if sum(1 for x in f if x) >= 2 else [1 if x else 0 for x in f]
+    return sum(a * b for a, b in zip(f, ls)) + _side_bits(tokens, False)
+
+
+def dyn_lower(tokens):
+    """what ANY dynamic block of this encoder costs at least: 17 header bits, 18 code-length-code lengths (either static code sends 18
+    or 19), one bit per symbol that needs a code (the cheapest description of a nonzero length is a share of a symbol-16 entry: 4 + 2
+    bits for six of them), and the body under an optimal Huffman code, end-of-block included"""
+    return 17 + 3 * 18 + sum(1 for f in token_freq(tokens) if f) + huffman_body_bits(tokens)
+
+
+def pinned_type(tokens, n):
+    """the block type that the arithmetic alone pins for a block of n bytes, wherever its header starts in a byte: 2 if the dynamic
+    block's upper bound beats the fixed block and the shortest stored one (the encoder takes the dynamic block unless one of the others
+    is no larger); 0 if the longest stored block is no larger than the fixed block and than dyn_lower (stored wins ties); else None"""
+    if dyn_upper(tokens) < min(fixed_bits(tokens), stored_bits(5, n)):
+        return 2
+    if stored_bits(6, n) <= min(fixed_bits(tokens), dyn_lower(tokens)):
+        return 0
+    return None
+
+
+def cl_rle(lengths):
+    """the header's run-length rule as [(symbol, extra value)]: zeros in chunks of 138 — a chunk of >= 11 one symbol-18 entry, of 3 .. 10
+    one symbol-17 entry, a shorter one plain zeros; of a run of a nonzero value the first goes plain and the rest in chunks of 6 — a chunk
+    of >= 3 one symbol-16 entry, a shorter one plain"""
+    out, i, n = [], 0, len(lengths)
+    while i < n:
+        j = i
+        while j < n and lengths[j] == lengths[i]:
+            j += 1
+        v, run = lengths[i], j - i
+        if v == 0:
+            for c in [138] * (run // 138) + [run % 138]:
+                out += [(18, c - 11)] if c >= 11 else [(17, c - 3)] if c >= 3 else [(0, 0)] * c
+        else:
+            out.append((v, 0))
+            for c in [6] * ((run - 1) // 6) + [(run - 1) % 6]:
+                out += [(16, c - 3)] if c >= 3 else [(v, 0)] * c
+        i = j
+    return out
+
+
+def cl_cost(entries, cl_lens):
+    """bits of the code-length sequence under one of the static codes; None if it lacks a symbol"""
+    if any(cl_lens[s] == 0 for s, _ in entries):
+        return None
+    return sum(cl_lens[s] + CL_EXTRA.get(s, 0) for s, _ in entries)
+
+
+# ================================================================ the encoder's catalogue: the smallest payload per edge
+# A record's payload is [u16 id length][read id][u32 read group][4 doubles][u64 blob length][signal blob][aux bytes]; the aux bytes are
+# copied verbatim, so everything behind the head is the test's to choose.  An entry is a dict: name, signal, read_id, fields (read group
+# and the four doubles), aux, why; and what the CPU test holds it to — runs [(last position, length)] of the payload, pin (the block type
+# per block that the arithmetic must pin, or None), plus per-family keys named where they are made.
+SIG4 = (3, 4, 5, 4)                                  # four samples: blob 04 00 00 00 | 00 | 06 02 02 01
+FIELDS2 = (0, 2.0, 2.0, 2.0, 2.0)                   # 2.0 = 00 00 00 00 00 00 00 40: small bytes only
+ALPHA16 = bytes(range(0x61, 0x71))                  # the background's 16 values
+RUN_BYTES = bytes(range(0xE0, 0xF0))                # planted runs: outside the background, neighbours differ
+
+
+def enc_hdr(e):
+    """the record bytes in front of the u64 blob length (press.pack_hdr)"""
+    return struct.pack("<H", len(e["read_id"])) + e["read_id"] + struct.pack("<Idddd", *e["fields"])
+
+
+def enc_payload(e, sig_method=1):
+    """the oracle's payload of an entry (sig_method 1 svb-zd, 2 ex-zd)"""
+    key = (e["name"], sig_method)
+    if key not in _PAYLOADS:
+        import oracle_bind as ob
+        r, keep = ob.make_rec(e["read_id"], *e["fields"], np.asarray(e["signal"], dtype=np.int16), e["aux"])
+        _PAYLOADS[key] = ob.rec_pack(r, sig_method)
+    return _PAYLOADS[key]
+
+
+_PAYLOADS = {}
+
+
+def background(rng, n, alphabet=ALPHA16):
+    """n bytes over the alphabet with no run of four"""
+    x = rng.integers(0, len(alphabet), n)
+    for i in range(3, n):
+        if x[i] == x[i - 1] == x[i - 2] == x[i - 3]:
+            x[i] = (x[i] + 1) % len(alphabet)
+    return bytearray(bytes(alphabet[int(v)] for v in x))
+
+
+def flat_bytes(rng, n):
+    """n bytes (a multiple of 256), every value equally often, in a shuffled order without a run of four"""
+    while True:
+        x = bytes(rng.permutation(np.repeat(np.arange(256, dtype=np.uint8), n // 256)))
+        if all(r < 4 for _, r in runs_of(x)):
+            return bytearray(x)
+
+
+@functools.lru_cache(maxsize=None)
+def encode_catalogue():
+    """[entry dict] (needs the CPU oracle: the head of every payload is the oracle's)"""
+    E = []
+
+    def head_of(signal, read_id, fields):
+        e = dict(name="head:%r%r%r" % (tuple(signal), read_id, fields), signal=signal, read_id=read_id, fields=fields, aux=b"")
+        return enc_payload(e)
+
+    def add(name, why, plen=None, runs=(), aux=None, signal=SIG4, read_id=b"craft0001", fields=FIELDS2, pin=2, bg=None, **more):
+        """plen and runs are in PAYLOAD positions: the aux bytes are a background of plen - head bytes with the runs (last position,
+        length) planted in it, run i of byte RUN_BYTES[i % 16]; or aux as given"""
+        head = head_of(tuple(signal), read_id, fields)
+        if aux is None:
+            rng = _rng(name)
+            pay = bytearray(head) + (background(rng, plen - len(head)) if bg is None else bg(rng, plen - len(head)))
+            for i, (end, r) in enumerate(runs):
+                assert end - r + 1 >= len(head) and end < plen, (name, end, r)
+                pay[end - r + 1:end + 1] = bytes([RUN_BYTES[i % 16]]) * r
+            aux = bytes(pay[len(head):])
+        e = dict(name=name, why=why, signal=tuple(signal), read_id=read_id, fields=fields, aux=bytes(aux), runs=list(runs), pin=pin, head=len(head))
+        e.update(more)
+        E.append(e)
+        return e
+
+    P9 = 2250                                            # nine slabs, the last one partly filled: positions up to 2249 of [2046, 2302)
+    # ---- runs against the frame geometry
+    for off in range(-2, 6):
+        where = "slot %d of lane 63 in front of it" % (off + 4) if off < 0 else "slot %d of lane %d" % (off % 4, off // 4)
+        for back in (3, 4, 5):
+            add("slab_end%+d_back%d" % (off, back), "at every slab boundary 256 k - 2, k = 1 .. 8, a run of %d that ends %+d from it (%s)" % (back + 1, off, where),
+                P9, [(SLAB * k - 2 + off, back + 1) for k in range(1, 9)])
+        for par, ks in (("odd", (1, 3, 5, 7)), ("even", (2, 4, 6, 8))):
+            add("slab_end%+d_back260_%s" % (off, par), "a run that starts in front of the slab it ends in (find_break_before), ending %+d from the boundary of slab %s: 261 "
+                "bytes (slab 1: 150, it cannot start in the head)" % (off, ", ".join(map(str, ks))), P9, [(SLAB * k - 2 + off, 261 if k > 1 else 150) for k in ks])
+    # (the entries above hold a run in every slab: more tokens of general slabs than the list takes, so WHICH of their slabs are sent from the list
+    # and which are redone from the bytes depends on the order in which the waves ask.  These hold one such run, and a run of 180 that
+    # leaves slab 0 some 40 tokens: at most 43 + 254 + 254 listed tokens, all of them in S.freq on every route)
+    for k in range(1, 9):
+        for off in range(-2, 6):
+            add("alone_slab%d_end%+d" % (k, off), "a run of 5 that ends %+d from the boundary of slab %d and no other but one in slab 0: every general slab is sent from the list" %
+                (off, k), P9, [(243, 180), (SLAB * k - 2 + off, 5)], listed=True)
+    P9L = 2300                                           # the last slab filled up to slot 1 of lane 63
+    for lane, slab in ((62, 0), (63, 0), (0, 8), (1, 8), (62, 8), (63, 8)):
+        for slot in range(4):
+            end = SLAB * slab - 2 + 4 * lane + slot
+            if end >= P9L:
+                continue
+            for back in (3, 4, 5):
+                add("lane%d_slot%d_slab%d_back%d" % (lane, slot, slab, back), "a run of %d that ends in slot %d of lane %d of %s" %
+                    (back + 1, slot, lane, "slab 0" if slab == 0 else "the last, partly filled slab (payload of %d bytes)" % P9L), P9L, [(end, back + 1)])
+    add("lane1_slot3_slab0", "a run of 4 in positions 2 .. 5 (the read id): lane 1 of slab 0, whose lane 0 holds positions -2 .. 1", P9, [], read_id=b"AAAAcraft")["runs"] = [(5, 4)]
+    for j in (2, 3, 4):
+        add("from_position_0_to_%d" % (j + 1), "a run from position 0: an id length of 257 = 01 01 and a read id that starts with %d bytes 01 (slot %d of lane %d of slab 0)" %
+            (j, (j + 3) % 4, (j + 3) // 4), 2600, [], read_id=b"\x01" * j + b"craftcraf" * 28 + b"cra"[:257 - j - 252])["runs"] = [(j + 1, j + 2)]
+    add("from_position_0_whole_id", "a run of 263 from position 0: id length 01 01, 257 id bytes 01, read group 01 01 01 01", 2600, [], read_id=b"\x01" * 257,
+        fields=(0x01010101, 2.0, 2.0, 2.0, 2.0))["runs"] = [(262, 263)]
+    for plen in (2250, 2251, 2252, 2253, 2301, 2302, 2303, 2304, 2305, 2306):
+        add("length_%d" % plen, "a payload of %d bytes (%d mod 4, %d mod 256), no run at its end" % (plen, plen % 4, plen % 256), plen, [(1200, 5)])
+        add("length_%d_run_to_the_end" % plen, "a payload of %d bytes (%d mod 4, %d mod 256) that ends with a run of 5" % (plen, plen % 4, plen % 256), plen, [(plen - 1, 5)])
+    add("run_261_to_the_end", "a run that starts two slabs in front of the payload's last byte", P9, [(P9 - 1, 261)])
+    # ---- run lengths
+    rl = (3, 4, 5, 6, 259, 260, 261, 262, 517, 518, 519, 520)
+    at, runs = 100, []
+    for r in rl:
+        runs.append((at + r - 1, r))
+        at += r + 37
+    add("run_lengths_around_258", "runs of %s bytes: rem = (R - 1) mod 258 of 0, 1, 2 and 3 behind no, one and two matches of 258" % ", ".join(map(str, rl)), at + 50, runs, rl=rl, pin=None)
+    at, runs = 100, []
+    for k in range(29):
+        runs.append((at + LBASE[k], LBASE[k] + 1))
+        at += LBASE[k] + 1 + 23
+    add("length_symbols_all_29", "one run of base length + 1 per length symbol 257 .. 285", at + 50, runs, pin=None)
+    add("run_16000", "one run of 16000 bytes: 62 matches of 258 from one lane (nfull = 62) and a match of 3", 16200, [(16100, 16000)], pin=None)
+    # ---- the run-heavy front (gen_hint): four samples above; here a constant signal of 2000 samples = 499 zero key bytes + 1999 zero data bytes
+    const = (1234,) * 2000
+    h2 = len(head_of(const, b"craft0001", FIELDS2))
+    k2 = (h2 + 2) // SLAB + 2                            # a slab well inside the aux bytes, behind the hinted front
+    add("const2000_plain_aux", "constant signal: 499 zero key bytes and 1999 zero data bytes, the first 3 slabs hinted as run-heavy; aux without a run: plain slabs taken in pairs", h2 + 2300, [], signal=const)
+    add("const2000_run_in_a_plain_pair", "... and one run of 5 in the second slab of a pair that pass 1 takes for plain", h2 + 2300, [(SLAB * (k2 + 1) + 100, 5)], signal=const)
+    add("const2000_runs_at_slab_edges", "... and a run of 5 ending on the first slot of every slab behind the front", h2 + 2300,
+        [(SLAB * k - 2, 5) for k in range(k2, (h2 + 2300) // SLAB)], signal=const)
+    add("const2000_run_from_the_front", "... whose zero run of the signal continues 300 bytes into the aux bytes", h2 + 2300, [], signal=const,
+        aux=b"\x00" * 300 + bytes(background(_rng("c2f"), 2000)))
+    # ---- the token list
+    for name, plen in (("list_8k_run_in_every_slab", 8192), ("list_16k_run_in_every_slab", BLOCK)):
+        add(name, "%d bytes, a run of 4 in every slab: ~254 tokens per general slab, DEFL2_LIST_CAP = %d is full after two or three slabs — fused: the rest take SEG_REDO; staged: "
+            "the list straddles entry %d into pool B%s" % (plen, DEFL2_LIST_CAP, DEFL2_LIST_CAP,
+            ", fills its %d entries (%d + 2 x (wf_at %d - DEFL2_LISTB_MIN %d)) and leaves the block's ~8 KiB of bits %d words: !list_ok" %
+            (LIST_CAP_STAGED, DEFL2_LIST_CAP, STAGED_WF_AT, DEFL2_LISTB_MIN, DEFL2_LISTB_MIN) if plen == BLOCK else ""),
+            plen, [(SLAB * k + 130, 4) for k in range(plen // SLAB)], list_over=LIST_CAP_STAGED if plen == BLOCK else DEFL2_LIST_CAP)
+    add("poolb_list_ok_dynamic", "16384 bytes, a run of 4 in slabs 0 .. 5 only: ~1500 listed tokens straddle entry %d and take ~%d words of pool B below word %d; the block's bits "
+        "(58 plain slabs of 4-bit literals: ~2100 words) end below them: list_ok, and the block stays dynamic" % (DEFL2_LIST_CAP, (1500 - DEFL2_LIST_CAP) // 2, STAGED_WF_AT),
+        BLOCK, [(SLAB * k + 130, 4) for k in range(6)], list_over=DEFL2_LIST_CAP, list_ok=True)
+    # ---- code lengths and header
+    def two_and_rares(rng, n):
+        x = bytearray(b"\x61\x62" * (n // 2 + 1))[:n]
+        for i in range(n // 250):
+            x[100 + 250 * i] = 0x80 + i % 60
+        return x
+    add("cl14_two_bytes_and_rares", "16384 bytes, two bytes alternating and 60 bytes that occur once or twice: the head's zero runs leave N just below 2^14, the Shannon start holds "
+        "lengths of 14, which code-length code A cannot describe", BLOCK, [], bg=two_and_rares)
+    add("cl15_later_block", "the same in two blocks: the second has no run at all, N = 16385 > 2^14 and a Shannon start with lengths of 15 (staged form only)", 2 * BLOCK, [],
+        bg=two_and_rares)
+    at, runs = 400, []
+    for k in range(29):
+        runs.append((at + LBASE[k], LBASE[k] + 1))
+        at += LBASE[k] + 1 + 9
+    add("all_286_symbols", "every literal 0 .. 255 and every length symbol in use: no unused symbol is left to absorb the slack", at + 600, runs,
+        bg=lambda rng, n: bytearray(bytes(range(256)) * (n // 256 + 1))[:n], all_symbols=True, pin=None)
+    # used symbols of these: 0 (the head's zeros), 0x20 .. 0x2F (every other head byte: id length 32, id, read group, doubles, 32 samples with deltas +16 / -17), 256, and the
+    # length symbols of the head's zero runs; symbols 1 .. 31 stay unused BELOW the gaps of interest: the slack absorption takes the lowest unused symbols, at most 15 of them
+    zsig = tuple(int(v) for v in np.cumsum(np.tile([16, -17], 16)))
+    zfields = (0x20212223, ) + tuple(struct.unpack("<d", bytes([0x28 + i, 0x21, 0x22, 0x23, 0x24, 0x25, 0x26, 0x27]))[0] for i in range(4))
+    for gaps in ((2, 10, 138), (3, 11, 139), (140,)):
+        used, s = list(range(0x20, 0x30)), 0x30
+        for g in gaps:
+            s += g
+            used.append(s)
+            s += 1
+        used += list(range(s, 256))
+        add("zero_runs_" + "_".join(map(str, gaps)), "lit/len symbols in use: 0, 0x20 .. 0x2F, then gaps of exactly %s unused symbols (above symbols 1 .. 31, which the slack "
+            "absorption may take), then everything up to 255" % ", ".join(map(str, gaps)), 1800, [], signal=zsig, read_id=b"\x21" * 32, fields=zfields,
+            bg=lambda rng, n, used=used: background(rng, n, bytes(used)), zero_runs=gaps)
+    for rep in (4, 7, 8, 10):
+        alpha = bytes(range(0x80, 0x80 + rep))
+        add("cl_repeat_%d" % rep, "%d neighbouring symbols 0x80 .. of one frequency between unused ones: a run of %d equal code lengths" % (rep, rep), 64 + 40 * rep, [],
+            bg=lambda rng, n, alpha=alpha: bytearray((alpha * (n // len(alpha) + 1))[:n // len(alpha) * len(alpha)] + b"\x7e" * (n % len(alpha))), pin=None, repeat=rep)
+    add("hlit_286_only_match_258", "a run of 259: the only match behind the head's is one of 258, symbol 285, HLIT = 286", 900, [(700, 259)], pin=None)
+    add("no_match_behind_the_head", "no run of four behind the head (its u64 blob length always holds one: no record's first block has HLIT = 257)", 900, [])
+    # ---- block choice
+    add("shortest_record", "the shortest payload a record can have: empty signal, one-character read id, no aux (51 bytes)", aux=b"", signal=(), read_id=b"r", pin=None)
+    for plen in (100, 300):
+        add("payload_%d" % plen, "a payload of %d bytes" % plen, plen, [], pin=None)
+    rnd = lambda rng, n: bytearray(_rb(rng, n))
+    add("random_with_three_runs", "8100 random bytes with three planted runs: stored (a random payload of a few KB has an optimal Huffman body well below 8 bits per byte: only from "
+        "~8 KB on does the arithmetic pin the stored block)", 8100, [(400, 5), (4800, 4), (7300, 6)], bg=rnd, pin=0)
+    add("random_1500_with_three_runs", "1500 random bytes with three planted runs", 1500, [(400, 5), (800, 4), (1300, 6)], bg=rnd, pin=None)
+    add("half_random_half_constant", "1000 random bytes, then 1000 equal ones", 2064, [(2063, 1000)], bg=rnd, pin=None)
+    # a stored block that the fixed block misses by less than its length extra bits.  A shuffled cycle of all 256 values keeps a dynamic block at
+    # 8 bits per literal plus its header; zero doubles in the head (a run of up to 35 zeros: a match with 3 extra bits) and a run or two save
+    # the fixed block a few hundred bits, every literal of 144 and more costs it one; high literals are added until the fixed block is half
+    # its matches' extra bits larger than the stored one.  (That the dynamic block is larger than both rests on its header of some 500 bits:
+    # the arithmetic of the restatement does not pin it.  Three cycles and one run of 12 is the shape at which dyn_lower comes closest to the
+    # stored block; with four cycles and a run of 20 the encoder's dynamic block already wins.  So the entry's stored block is an OBSERVED pin,
+    # key `observed`: the GPU tests assert it on the svb-zd routes, and if a change to the length assignment ever makes the dynamic block win
+    # there, they say that this entry no longer does its job.)
+    def near_fixed(name, fields, cycles, nruns, r):
+        rng = _rng(name)
+        head = head_of(SIG4, b"craft0001", fields)
+        pay = bytearray(head)
+        for i in range(nruns):
+            pay += bytes(rng.permutation(256).astype(np.uint8)[:24]) + bytes([RUN_BYTES[i % 16]]) * r
+        for _ in range(cycles):
+            pay += flat_bytes(rng, 256)
+        toks = rle_tokens(bytes(pay))
+        extra = sum(token_symbol(t)[1] for t in toks)
+        more = extra // 2 - (fixed_bits(toks) - stored_bits(0, len(pay)))
+        assert 0 <= more <= 112, (name, more)
+        pay += bytes([144 + (7 * i) % 112 for i in range(more)])
+        add(name, "%d bytes of every byte value about equally often, zero doubles in the head and %d run(s) of %d: the fixed block is %d bits larger than the stored one and holds %d "
+            "length extra bits; left out of its cost they make it look smaller" % (len(pay), nruns, r, extra // 2, extra), aux=bytes(pay[len(head):]), fields=fields, pin=None, near_fixed=extra, observed=0)
+    near_fixed("fixed_near_stored", (0, 0.0, 0.0, 0.0, 0.0), 3, 1, 12)
+    # small payloads over alphabets of 3 .. 42 values with skewed frequencies: code-length headers of many shapes (the choice between the two static
+    # code-length codes is checked on every one; among so many, some cost the same under both)
+    def skewed(k):
+        def make(rng, n):
+            alpha = rng.permutation(256)[:3 + k]
+            p = 0.85 ** np.arange(3 + k)
+            x = rng.choice(3 + k, n, p=p / p.sum())
+            for i in range(3, n):
+                if x[i] == x[i - 1] == x[i - 2] == x[i - 3]:
+                    x[i] = (x[i] + 1) % (3 + k)
+            return bytearray(bytes(int(alpha[v]) for v in x))
+        return make
+    for k in range(40):
+        add("skewed_%02d" % k, "%d bytes over %d values of geometric frequencies" % (500 + 60 * k, 3 + k), 500 + 60 * k, [], bg=skewed(k), pin=None)
+    # ---- block edges (staged form: more than one block)
+    for plen in (16383, 16384, 16385, 16386, 16387, 32768, 32769):
+        add("payload_%d" % plen, "a payload of %d bytes: blocks of %s" % (plen, " + ".join(str(len(x)) for x in pieces(bytes(plen)))), plen, [(5000, 5)], pin=None)
+    add("run_3_before_to_3_behind_the_cut", "a run of 6 across the cut at 16384: three literals at the end of one block, three at the start of the next", 17000, [(BLOCK + 2, 6)])
+    add("run_600_across_the_cut", "a run of 600 across the cut at 16384: 300 bytes in either block, starting anew behind the cut", 19500, [(BLOCK + 299, 600)])
+    add("stored_then_dynamic", "16384 random bytes, then 3000 compressible ones: the dynamic block's carry word and bit offset come from a stored block", BLOCK + 3000, [],
+        bg=lambda rng, n: bytearray(_rb(rng, n - 3000)) + background(rng, 3000), pin=(0, 2))
+    add("dynamic_then_stored", "16384 compressible bytes, then every byte value 64 times in a shuffled order: the stored block's pad bits depend on the dynamic block in front; "
+        "the second block's optimal Huffman BODY alone is larger than the stored block", 2 * BLOCK, [],
+        bg=lambda rng, n: background(rng, n - BLOCK) + flat_bytes(rng, BLOCK), pin=(2, 0), flat_block=1)
+    assert len({e["name"] for e in E}) == len(E)
+    return E
+
+
+def enc_family(name):
+    """the name with its numbers taken out: the entries of one loop of the catalogue"""
+    return re.sub(r"[+-]?\d+", "#", name)
+
+
+def enc_by_name():
+    return {e["name"]: e for e in encode_catalogue()}
