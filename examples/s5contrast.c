@@ -1,0 +1,184 @@
+/*
+ * s5contrast.c — where two samples differ: per reference position, the level histograms of the whole-read alignments of two files held
+ * against each other on the GPU (k_pile_hist_accum, k_pile_contrast; docs/codecs.md §4.23).
+ *
+ *   s5contrast [-K batch] [--rna] [--skip S] [--events Q] [--min-events M] [--tile T] [--band B] [--max-events N] [--min-depth D] [--q0 V] [--shift S]
+ *              ref.txt a.blow5 b.blow5
+ *       <ref_pos>\t<ref_level>\t<depth_a>\t<depth_b>\t<events_a>\t<events_b>\t<mean_a>\t<mean_b>\t<ks_d>\t<ks_level>\t<tv>\t<med_a>\t<med_b>
+ *   one line per position whose depth is at least D (default 1) in both files.  ref.txt, S, Q, M, T, B, N and the event parameters are those
+ *   of s5extend.  depth, events and mean (sum / events, of the quantised event levels) come from each file's table as in s5pileup --whole.
+ *   The histograms have 64 bins of 2^shift levels from q0 on (defaults -128 and 2: the clip of +-127 in bins of 4).  ks_d is the two-sample
+ *   Kolmogorov-Smirnov statistic of the position's two histograms, ks_num / (events_a events_b), and tv their total-variation distance,
+ *   1 - ov_num / (events_a events_b); ks_level is the lowest level of the bin where the two distributions are furthest apart, med_a and med_b
+ *   the lowest level of each median's bin (q0 + (bin << shift)).  Doubles are printed as %.6g.  ks_d is a statistic, not a probability.
+ *   The totals of both files (reads used, skipped, bad; cells; cost) go to stderr, a line each.
+ *   Exit 0; 1 when a record is corrupt (its file and number go to stderr; the other reads are counted); 2 on any other error.
+ *
+ * One handle (s5gpu_contrast_open), one s5gpu_contrast_add_batch per K records (default 4096) of a.blow5, then of b.blow5, and one
+ * s5gpu_contrast_close: compressed bytes go up; a status per read comes back, and the rows and the two tables once at the end.
+ */
+#define _GNU_SOURCE
+#include <inttypes.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "slow5_compat.h"
+#include "slow5gpu.h"
+
+enum { EXIT_CORRUPT = 1, EXIT_ERROR = 2 };
+
+static int die(const char *what) {
+    fprintf(stderr, "s5contrast: %s (%s)\n", what, s5gpu_last_error());
+    return EXIT_ERROR;
+}
+/* a status of the decoder's, not one of map's or extend's */
+static int corrupt_status(int32_t s) { return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW; }
+static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
+static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
+
+/* one number per line; NULL (and a message) when the file cannot be read, holds no number or a line is no number */
+static float *read_reference(const char *path, size_t *n_out) {
+    FILE *f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "s5contrast: cannot open %s\n", path); return NULL; }
+    size_t n = 0, cap = 1024, line_cap = 0, line_no = 0;
+    float *v = (float *)malloc(sizeof(float) * cap);
+    char *line = NULL;
+    ssize_t l;
+    while (v && (l = getline(&line, &line_cap, f)) >= 0) {
+        line_no++;
+        while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r' || line[l - 1] == ' ' || line[l - 1] == '\t')) line[--l] = 0;
+        if (l == 0 || line[0] == '#') continue;
+        char *end = NULL;
+        const double x = strtod(line, &end);
+        if (end == line || *end != 0) {
+            fprintf(stderr, "s5contrast: %s line %zu is not a number\n", path, line_no);
+            free(v); free(line); fclose(f);
+            return NULL;
+        }
+        if (n == cap) { cap *= 2; v = (float *)realloc(v, sizeof(float) * cap); }
+        if (v) v[n++] = (float)x;
+    }
+    free(line);
+    fclose(f);
+    if (!v) { fprintf(stderr, "s5contrast: out of memory\n"); return NULL; }
+    if (n == 0 || n > (1u << 22)) { fprintf(stderr, "s5contrast: %s holds %s\n", path, n ? "too many numbers (at most 2^22)" : "no number"); free(v); return NULL; }
+    *n_out = n;
+    return v;
+}
+
+/* the batches of one file into `side` of the handle; 0, EXIT_CORRUPT or EXIT_ERROR */
+static int add_file(void *h, int side, const char *path, long K, void **mem, size_t *len, int32_t *st) {
+    slow5_file_t *in = slow5_open(path, "r");
+    if (!in) { fprintf(stderr, "s5contrast: cannot open %s\n", path); return EXIT_ERROR; }
+    if (in->format != SLOW5_FORMAT_BINARY) { fprintf(stderr, "s5contrast: %s is SLOW5 text: convert it to BLOW5 first\n", path); return EXIT_ERROR; }
+    const int rec = rec_code_of(in->compress->record_press->method), sig = sig_code_of(in->compress->signal_press->method);
+    int code = EXIT_SUCCESS, at_end = 0;
+    uint64_t n_done = 0;
+    while (!at_end) {
+        uint32_t n = 0;
+        while (n < (uint32_t)K) {
+            mem[n] = slow5_get_next_mem(&len[n], in);
+            if (!mem[n]) {
+                if (slow5_errno != SLOW5_ERR_EOF) { fprintf(stderr, "s5contrast: cannot read record %" PRIu64 " of %s\n", n_done + n, path); return EXIT_ERROR; }
+                at_end = 1;
+                break;
+            }
+            if (len[n] > 0xFFFFFF00u) { fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is too large\n", n_done + n, path); return EXIT_ERROR; }
+            n++;
+        }
+        if (n == 0) break;
+        const int rc = s5gpu_contrast_add_batch(h, side, n, (const void *const *)mem, len, rec, sig, NULL, NULL, st);
+        if (rc != S5GPU_OK && rc != S5GPU_ERR_DATA) return die("alignment failed");
+        for (uint32_t i = 0; i < n; i++) {
+            if (corrupt_status(st[i])) {
+                fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is corrupt (status %d)\n", n_done + i, path, st[i]);
+                code = EXIT_CORRUPT;
+            }
+            free(mem[i]);
+            mem[i] = NULL;
+        }
+        n_done += n;
+    }
+    slow5_close(in);
+    return code;
+}
+
+int main(int argc, char **argv) {
+    long K = 4096, skip = 0, qmax = 250, qmin = 50, min_depth = 1, tile = 256, band = 512, emax = 1l << 20, q0 = -128, shift = 2;
+    int rna = 0, bad = 0;
+    const char *ref_path = NULL, *path[2] = {NULL, NULL};
+    for (int i = 1; i < argc; i++) {
+        if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--skip") && i + 1 < argc) skip = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--events") && i + 1 < argc) qmax = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--min-events") && i + 1 < argc) qmin = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--rna")) rna = 1;
+        else if (!strcmp(argv[i], "--min-depth") && i + 1 < argc) min_depth = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--tile") && i + 1 < argc) tile = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--band") && i + 1 < argc) band = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--max-events") && i + 1 < argc) emax = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--q0") && i + 1 < argc) q0 = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--shift") && i + 1 < argc) shift = atol(argv[++i]);
+        else if (argv[i][0] != '-' && !ref_path) ref_path = argv[i];
+        else if (argv[i][0] != '-' && !path[0]) path[0] = argv[i];
+        else if (argv[i][0] != '-' && !path[1]) path[1] = argv[i];
+        else bad = 1;
+    }
+    if (tile != 64 && tile != 128 && tile != 256 && tile != 512 && tile != 1024) bad = 1;
+    if (band < 64 || band > 4096 || band % 64 || emax < qmin || emax > (1l << 20)) bad = 1;
+    if (q0 < -32768 || q0 > 32767 || shift < 0 || shift > 10) bad = 1;
+    if (bad || !path[1] || K < 1 || K > (1l << 24) || skip < 0 || skip > 0x7FFFFFFFl || qmax < 1 || qmax > 1024 || qmin < 1 || qmin > qmax || min_depth < 1 ||
+        min_depth > 0xFFFFFFFFl) {
+        fprintf(stderr, "usage: s5contrast [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--tile T (64, 128, 256, 512, 1024)]\n"
+                        "                  [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] [--min-depth D (>= 1)]\n"
+                        "                  [--q0 V (-32768 .. 32767)] [--shift S (0 .. 10)] ref.txt a.blow5 b.blow5\n");
+        return EXIT_ERROR;
+    }
+    const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
+    size_t R = 0;
+    float *levels = read_reference(ref_path, &R);
+    if (!levels) return EXIT_ERROR;
+    int16_t *ref = (int16_t *)malloc(sizeof(int16_t) * R);
+    if (!ref) return die("out of memory");
+    if (s5gpu_quantise_host(levels, R, M.scale, M.clip, ref) != S5GPU_OK) return die("the reference cannot be quantised");
+    free(levels);
+    if (s5gpu_init(0) != S5GPU_OK) return die("no GPU");
+    const s5gpu_event_params_t dna = {3, 6, 1.4, 9.0, 0.2}, rnap = {7, 14, 2.5, 9.0, 1.0};
+    const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
+    static char obuf[1 << 20];
+    setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+
+    void **mem = (void **)calloc((size_t)K, sizeof(void *));
+    size_t *len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
+    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
+    uint8_t *acc[2] = {(uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R)), (uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R))};
+    s5gpu_pile_contrast_t *rows = (s5gpu_pile_contrast_t *)malloc(sizeof *rows * R);
+    if (!mem || !len || !st || !acc[0] || !acc[1] || !rows) return die("out of memory");
+    void *h = s5gpu_contrast_open(rna ? &rnap : &dna, &M, &B, 0, ref, (uint32_t)R, (int32_t)q0, (uint32_t)shift);
+    if (!h) return die("the tables cannot be opened");
+    int code = EXIT_SUCCESS;
+    for (int side = 0; side < 2; side++) {
+        const int c = add_file(h, side, path[side], K, mem, len, st);
+        if (c == EXIT_ERROR) return EXIT_ERROR;
+        if (c) code = c;
+    }
+    if (s5gpu_contrast_close(h, acc[0], acc[1], rows) != S5GPU_OK) return die("the rows cannot be fetched");
+    const s5gpu_pile_col_t *ca = (const s5gpu_pile_col_t *)(acc[0] + sizeof(s5gpu_pile_total_t)), *cb = (const s5gpu_pile_col_t *)(acc[1] + sizeof(s5gpu_pile_total_t));
+    for (size_t j = 0; j < R; j++) {
+        const s5gpu_pile_contrast_t *r = &rows[j];
+        if (r->depth_a < (uint64_t)min_depth || r->depth_b < (uint64_t)min_depth) continue;
+        const double nn = (double)r->n_a * (double)r->n_b;
+        printf("%zu\t%d\t%u\t%u\t%u\t%u\t%.6g\t%.6g\t%.6g\t%ld\t%.6g\t%ld\t%ld\n", j, (int)ref[j], r->depth_a, r->depth_b, ca[j].n_events, cb[j].n_events,
+               (double)ca[j].sum_q / (double)ca[j].n_events, (double)cb[j].sum_q / (double)cb[j].n_events, (double)r->ks_num / nn, q0 + ((long)r->ks_bin << shift),
+               1.0 - (double)r->ov_num / nn, q0 + ((long)r->med_a << shift), q0 + ((long)r->med_b << shift));
+    }
+    for (int side = 0; side < 2; side++) {
+        const s5gpu_pile_total_t *T = (const s5gpu_pile_total_t *)acc[side];
+        fprintf(stderr, "s5contrast: %s: reads used %" PRIu64 ", skipped %" PRIu64 ", bad %" PRIu64 "; cells %" PRIu64 ", cost %" PRIu64 "; %zu positions\n", path[side],
+                T->reads_used, T->reads_skipped, T->reads_bad, T->cells, T->cost, R);
+    }
+    if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5contrast: write failed\n"); return EXIT_ERROR; }
+    free(mem); free(len); free(st); free(acc[0]); free(acc[1]); free(rows); free(ref);
+    return code;
+}

@@ -1075,6 +1075,69 @@ void *s5gpu_pileup_open_whole(const s5gpu_event_params_t *event_params, const s5
 int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
                                  s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out);
 
+/* ---- contrast: per-position level histograms and a two-sample comparison of them (docs/codecs.md §4.23) ----
+ * A histogram is a head and R columns of 64 uint32_t counts that stay on the device beside (or without) the table of "pileup".  The bin of a
+ * quantised level q: d = (int32)q - q0; bin = d < 0 ? 0 : min(d >> shift, 63), q0 in -32768 .. 32767, shift in 0 .. 10.  Which reads are
+ * USED, SKIPPED and BAD and which cells (i, j) a used read has is "pileup of whole reads"' rule with ev_skip = 0; column j, bin b counts the
+ * cells (i, j) of used reads with bin(q[i]) = b.  Every member is an integer sum: the bytes do not depend on the order of reads, segments,
+ * calls, streams or atomics, and fed the same reads the bins of column j add up to the table's n_events[j], the head's counts to its totals. */
+typedef struct s5gpu_pile_hist_head {  /* 64 bytes in front of the columns */
+    uint64_t cells;                    /* the cells counted: the sum of every bin */
+    uint64_t reads_used, reads_skipped, reads_bad;
+    uint32_t R;
+    int32_t q0;
+    uint32_t shift, bins;              /* bins: 64 */
+    uint64_t reserved[2];
+} s5gpu_pile_hist_head_t;
+typedef struct s5gpu_pile_contrast {   /* 40 bytes: column j of two histograms A and B held against each other.  c*_b: the inclusive prefix sums */
+    uint32_t n_a, n_b;                 /* nA, nB: the columns' cells (0xFFFFFFFF: that or more) */
+    uint32_t depth_a, depth_b;         /* the tables' depth (0 without tables) */
+    uint64_t ks_num;                   /* max_b |cA_b nB - cB_b nA|: the two-sample Kolmogorov-Smirnov statistic is D = ks_num / (nA nB) */
+    uint64_t ov_num;                   /* sum_b min(A_b nB, B_b nA): 1 - ov_num / (nA nB) is the total-variation distance */
+    uint16_t ks_bin;                   /* the smallest b that attains ks_num */
+    uint16_t med_a, med_b;             /* the smallest b with 2 c_b >= n (0 for an empty column) */
+    uint16_t flags;                    /* S5GPU_CONTRAST_* */
+} s5gpu_pile_contrast_t;
+#define S5GPU_CONTRAST_EMPTY_A 1u      /* nA = 0 */
+#define S5GPU_CONTRAST_EMPTY_B 2u      /* nB = 0 */
+#define S5GPU_CONTRAST_A_LOWER 4u      /* at ks_bin cA_b nB > cB_b nA: A's levels lie lower */
+#define S5GPU_CONTRAST_BIG 8u          /* nA or nB >= 2^31: the products would not fit; ks_num = ov_num = 0 and ks_bin = 0, the rest filled */
+#define S5GPU_CONTRAST_TABLE_A 16u     /* a table was given and its n_events is not nA */
+#define S5GPU_CONTRAST_TABLE_B 32u     /* ... nB */
+#define S5GPU_CONTRAST_HEADS 128u      /* the two heads disagree (R, q0, shift, bins): set in every row, and nothing else is */
+/* 64 + 256 R, the bytes of a histogram of R columns; 0 for R = 0 or R > 2^22 (1 GiB). */
+size_t s5gpu_pile_hist_bytes(uint32_t R);
+/* Writes the empty histogram (zeros and the head) to hist (DEVICE memory, 16-byte aligned, s5gpu_pile_hist_bytes(R)).  Asynchronous on
+ * hip_stream.  S5GPU_ERR_ARG: R, q0 or shift outside its range, a NULL or misaligned pointer. */
+int s5gpu_pile_hist_reset_dev(void *hist, uint32_t R, int32_t q0, uint32_t shift, void *hip_stream);
+/* Adds n reads in the ragged layout of s5gpu_pileup_accum_long_dev (neither a reference nor events are needed) to hist, which
+ * s5gpu_pile_hist_reset_dev wrote for the same R; q0 and shift are the reset's.  Asynchronous on hip_stream; writes nothing but hist and
+ * work (s5gpu_pileup_long_work_bytes(n, total_rows); a work area per call in flight).  Calls on several streams may share a histogram.
+ * n = 0: S5GPU_OK and nothing is launched.  S5GPU_ERR_ARG, nothing launched: a NULL or misaligned pointer (first: 8 bytes; work, hist: 16),
+ * R outside 1 .. 2^22, total_rows above 2^40.  S5GPU_ERR_NOMEM, nothing written: a short work area.
+ * s5gpu_set_option (tests, tools): "pile_hist_cols" (0, or a power of two 16 .. 256; default 256): the columns a workgroup keeps in LDS, 256
+ * bytes each (0: every cell is a global atomic); "pile_hist_grid" (1 .. 1024, default 1024); "pileup_long_seg" and "pileup_long_sort" count
+ * as they do for the table.  None changes the result. */
+int s5gpu_pile_hist_accum_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows, uint32_t R,
+                                   const int32_t *lo, const int32_t *hi, const int32_t *status, void *work, size_t work_bytes, void *hist,
+                                   void *hip_stream);
+/* Writes R rows to out (DEVICE memory, 8-byte aligned) from two histograms of R columns and, when given, the two tables of the same reads
+ * (acc_a and acc_b: both or neither).  The heads are read on the device.  Asynchronous on hip_stream; all integer and exact for
+ * nA, nB < 2^31.  S5GPU_ERR_ARG: R outside 1 .. 2^22, a NULL or misaligned pointer, one table without the other. */
+int s5gpu_pile_contrast_dev(const void *hist_a, const void *hist_b, const void *acc_a, const void *acc_b, uint32_t R, s5gpu_pile_contrast_t *out,
+                            void *hip_stream);
+/* A per-file handle over the chain of s5gpu_pileup_open_whole with two sides: a table and a histogram each, on the first device in use.
+ * NULL: the cases of s5gpu_pileup_open_whole, R > 2^22, q0 or shift outside its range. */
+void *s5gpu_contrast_open(const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const s5gpu_band_params_t *band_params,
+                          size_t scratch_max, const int16_t *ref_host, uint32_t R, int32_t q0, uint32_t shift);
+/* s5gpu_pileup_add_batch_whole into the table and the histogram of side 0 or 1 (any other: S5GPU_ERR_ARG).  Records that never reached the
+ * device count as skipped in both; a corrupt record: S5GPU_ERR_DATA, the rest of the batch added, the handle usable. */
+int s5gpu_contrast_add_batch(void *handle, int side, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                             s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out);
+/* Runs the comparison, downloads the R rows to rows_out and, where not NULL, the two tables (HOST memory, s5gpu_pileup_bytes(R) each), and
+ * ends the handle, whatever it returns.  rows_out NULL: the handle is abandoned. */
+int s5gpu_contrast_close(void *handle, void *acc_a_out, void *acc_b_out, s5gpu_pile_contrast_t *rows_out);
+
 #ifdef __cplusplus
 }
 #endif

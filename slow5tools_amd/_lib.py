@@ -125,6 +125,12 @@ PileCol = np.dtype([("depth", "<u4"), ("n_events", "<u4"), ("n_samples", "<u8"),
 PileTotal = np.dtype([("reads_used", "<u8"), ("reads_skipped", "<u8"), ("reads_bad", "<u8"), ("cells", "<u8"), ("cost", "<u8"), ("R", "<u4"),
                       ("reserved", "<u4", (5,))])
 assert PileCol.itemsize == 48 and PileTotal.itemsize == 64
+# s5gpu_pile_hist_head_t / s5gpu_pile_contrast_t: the head of a level histogram and a row of "contrast" (slow5tools_amd/contrast.py)
+PileHistHead = np.dtype([("cells", "<u8"), ("reads_used", "<u8"), ("reads_skipped", "<u8"), ("reads_bad", "<u8"), ("R", "<u4"), ("q0", "<i4"), ("shift", "<u4"),
+                         ("bins", "<u4"), ("reserved", "<u8", (2,))])
+PileContrast = np.dtype([("n_a", "<u4"), ("n_b", "<u4"), ("depth_a", "<u4"), ("depth_b", "<u4"), ("ks_num", "<u8"), ("ov_num", "<u8"), ("ks_bin", "<u2"),
+                         ("med_a", "<u2"), ("med_b", "<u2"), ("flags", "<u2")])
+assert PileHistHead.itemsize == 64 and PileContrast.itemsize == 40
 STATUS_FIT_FLAT, STATUS_FIT_RANGE = 21, 22
 # s5gpu_fit_t: the fit of "refine" (slow5tools_amd/refine.py)
 Fit = np.dtype([("a", "<f8"), ("b", "<f8"), ("n", "<i8"), ("sq", "<i8"), ("sr", "<i8"), ("sqq", "<i8"), ("sqr", "<i8"), ("srr", "<i8")])
@@ -316,6 +322,16 @@ def lib():
     L.s5gpu_pileup_open_whole.restype = vp
     L.s5gpu_pileup_open_whole.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32]
     L.s5gpu_pileup_add_batch_whole.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, vp]
+    # contrast: per-position level histograms, the comparison of two, and the per-file handle with two sides
+    L.s5gpu_pile_hist_bytes.argtypes = [u32]
+    L.s5gpu_pile_hist_bytes.restype = C.c_size_t
+    L.s5gpu_pile_hist_reset_dev.argtypes = [vp, u32, i32, u32, vp]
+    L.s5gpu_pile_hist_accum_long_dev.argtypes = [u32, vp, vp, vp, u64, u32, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.s5gpu_pile_contrast_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    L.s5gpu_contrast_open.restype = vp
+    L.s5gpu_contrast_open.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32, i32, u32]
+    L.s5gpu_contrast_add_batch.argtypes = [vp, i32, u32, vp, vp, i32, i32, vp, vp, vp]
+    L.s5gpu_contrast_close.argtypes = [vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -348,4 +364,6 @@ EXPORTS = [
     "s5gpu_path_fit_dev", "s5gpu_sdtw_window_dev", "s5gpu_refine_work_bytes", "s5gpu_refine_dev", "s5gpu_refine_batch",
     "s5gpu_event_queries_long_dev", "s5gpu_sdtw_band_scratch_bytes", "s5gpu_sdtw_band_dev", "s5gpu_extend_batch",
     "s5gpu_pileup_long_work_bytes", "s5gpu_pileup_accum_long_dev", "s5gpu_pileup_open_whole", "s5gpu_pileup_add_batch_whole",
+    "s5gpu_pile_hist_bytes", "s5gpu_pile_hist_reset_dev", "s5gpu_pile_hist_accum_long_dev", "s5gpu_pile_contrast_dev", "s5gpu_contrast_open",
+    "s5gpu_contrast_add_batch", "s5gpu_contrast_close",
 ]

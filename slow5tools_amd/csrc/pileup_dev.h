@@ -161,6 +161,55 @@ PILE_HD LongWork long_work(uint32_t n, uint64_t total_rows) {
     return w;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- level histograms (§4.23)
+// Beside the table: R columns of 64 32-bit counts behind a head.  A column is 256 bytes, a lane per bin for one wave.
+constexpr uint32_t HIST_RMAX = 1u << 22;     // columns of the largest histogram: 1 GiB
+constexpr uint32_t HIST_BINS = 64, HIST_SHIFT_MAX = 10;
+constexpr uint32_t HIST_MIN_COLS = 16, HIST_MAX_COLS = 256;   // the LDS window: 256 bytes a column, 64 KB at most
+constexpr uint32_t HIST_HEAD_WORDS = 16;     // 32-bit words of the head
+
+static_assert(sizeof(s5gpu_pile_hist_head_t) == 4 * HIST_HEAD_WORDS && sizeof(s5gpu_pile_contrast_t) == 40, "include/slow5gpu.h fixes these layouts");
+
+// the bin of a level: shift comes from memory and is clamped before it shifts; the bin is below HIST_BINS whatever q, q0 and shift are
+PILE_HD uint32_t hist_bin(int32_t q, int32_t q0, uint32_t shift) {
+    const int64_t d = (int64_t)q - q0;
+    if (d < 0) return 0u;
+    const uint64_t b = (uint64_t)d >> (shift < HIST_SHIFT_MAX ? shift : HIST_SHIFT_MAX);
+    return b < HIST_BINS - 1u ? (uint32_t)b : HIST_BINS - 1u;
+}
+// One cell added to a column's bin.  Ops: add32_win on the window's memory and add32 on the table's (atomics on the device, plain on the host).
+template <class Ops>
+PILE_HD void hist_col_add(uint32_t *col, uint32_t bin, bool in_window) {
+    if (in_window) Ops::add32_win(col + (bin & (HIST_BINS - 1u)), 1u);
+    else Ops::add32(col + (bin & (HIST_BINS - 1u)), 1u);
+}
+// Word t of a window of W.cols columns added to the table (the flush) and emptied; a slot that stands for no column of the table holds nothing
+template <class Ops>
+PILE_HD void hist_flush_word(uint32_t t, const Window &W, uint32_t *win, uint32_t *table, uint32_t R) {
+    const uint32_t j = W.lo + t / HIST_BINS, v = win[t];
+    if (v == 0u || j < W.lo || j >= R) return;
+    Ops::add32(table + (uint64_t)j * HIST_BINS + t % HIST_BINS, v);
+    win[t] = 0u;
+}
+// The cells of a row that passed row_ok with its whole read: columns lo .. hi, the trips and the second `j < R` of row_cells
+template <class Ops>
+PILE_HD void hist_row_cells(int32_t lo, int32_t hi, uint32_t bin, uint32_t R, const Window &W, uint32_t *win, uint32_t *table, uint64_t *cells) {
+    const uint32_t trips = (uint32_t)(hi - lo) + 1u;
+    uint32_t j = (uint32_t)lo;
+    for (uint32_t t = 0; t < trips && t < R && j < R; t++, j++) {
+        uint32_t slot;
+        if (window_slot(W, j, &slot)) hist_col_add<Ops>(win + slot * HIST_BINS, bin, true);
+        else hist_col_add<Ops>(table + (uint64_t)j * HIST_BINS, bin, false);
+        *cells += 1;
+    }
+}
+// the rows of a segment, as seg_cells
+template <class Ops>
+PILE_HD void hist_seg_cells(uint32_t r0, uint32_t r1, uint32_t lane, uint32_t step, const int32_t *lo, const int32_t *hi, const int16_t *q, int32_t q0, uint32_t shift,
+                            uint32_t R, const Window &W, uint32_t *win, uint32_t *table, uint64_t *cells) {
+    for (uint32_t i = r0 + lane; i < r1; i += step) hist_row_cells<Ops>(lo[i], hi[i], hist_bin((int32_t)q[i], q0, shift), R, W, win, table, cells);
+}
+
 #ifndef S5_PILEUP_HOST
 struct PileLongArgs {
     uint32_t n;
@@ -179,6 +228,13 @@ struct PileLongArgs {
 };
 // k_pileup_long_plan, _check, (the sort,) _accum over the reads of a ragged batch, on st
 int launch_pileup_long(const PileLongArgs &A, hipStream_t st);
+// ... and from the same verdicts and segment list k_pile_hist_accum into hist (§4.23), when hist is given; A.acc (with A.ref and A.events)
+// may then be NULL: the histogram alone
+int launch_pileup_long(const PileLongArgs &A, void *hist, hipStream_t st);
+// k_pile_hist_reset; k reads that never reached the device count as skipped in a histogram; k_pile_contrast (contrast_kernels.hip)
+int launch_hist_reset(void *hist, uint32_t R, int32_t q0, uint32_t shift, hipStream_t st);
+int launch_hist_add_skipped(void *hist, uint32_t k, hipStream_t st);
+int launch_contrast(const void *hist_a, const void *hist_b, const void *acc_a, const void *acc_b, uint32_t R, s5gpu_pile_contrast_t *out, hipStream_t st);
 
 struct PileArgs {
     const int16_t *queries;          // [n, qpitch]

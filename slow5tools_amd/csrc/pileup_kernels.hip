@@ -23,6 +23,7 @@
 //                         that writes the segments (read, segment) in the order of that key
 //   k_pileup_long_accum : k_pileup over a slice of the (ordered) segments, a wave per segment at a time; segments of reads whose verdict
 //                         is not V_USED are passed over; the reads are counted once each, from the verdicts
+//   k_pile_hist_accum   : the same walk into the level histograms of §4.23 (further down, with its own note)
 // Their rules, beside 2, 3 (per row), 5 and 6 above:
 //   7. first, qlen and status are read at [read] (first also at [read + 1]) for read < n; a read has segments only behind long_verdict:
 //      first[k] + Q + ev_skip <= first[k + 1] <= total_rows, Q <= 2^20, so queries, lo, hi at [first[k] + i] and events at
@@ -366,9 +367,84 @@ __global__ __launch_bounds__(s5::NT) void k_pileup_long_accum(PileLongArgs A, ui
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- level histograms (§4.23)
+// k_pile_hist_accum: k_pileup_long_accum's walk over the same (ordered) segments and verdicts, into R columns of 64 32-bit bins: a wave per
+// segment at a time, lanes over rows, one add per cell.  The window is `cols` columns of 256 bytes in LDS (32-bit LDS adds), flushed word by
+// word at the end; cells outside it are 32-bit global atomic adds.  Rules 2, 3, 5 to 11 above hold as they stand; the bin is clamped below
+// 64 (hist_bin) and masked where it indexes (hist_col_add); q0 and shift are read from the head the reset wrote, the shift clamped.
 namespace {
+struct HistOps {
+    static __device__ __forceinline__ void add32(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+    static __device__ __forceinline__ void add32_win(uint32_t *p, uint32_t v) { atomicAdd(p, v); }   // (a pointer into LDS: a ds add)
+};
+}  // namespace
+
+__global__ __launch_bounds__(s5::NT) void k_pile_hist_accum(PileLongArgs A, uint32_t S, LongPtrs L, uint32_t sort, uint32_t cols, uint32_t *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t hist_win[];    // cols columns of HIST_BINS words: all of the 64 KB at cols = 256
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (uint32_t t = threadIdx.x; t < cols * HIST_BINS; t += s5::NT) hist_win[t] = 0u;
+    const uint64_t total = L.P[A.n];
+    const bool sorted = sort && total <= L.cap;
+    uint64_t base, end;
+    slice_of(total, blockIdx.x, gridDim.x, &base, &end);
+    // the anchor of k_pileup_long_accum: the smallest first lo of the segments the four waves meet first.  Every thread works it out for
+    // itself (four items), so that no static LDS is needed beside the window.
+    uint32_t k, r0, r1, anchor = 0xFFFFFFFFu;
+    for (uint32_t w = 0; cols && w < (uint32_t)s5::NW && base + w < end; w++) {
+        k = A.n;
+        if (!long_item(A, S, L, sorted, base + w, &k, &r0, &r1)) continue;
+        const int32_t l0 = A.lo[A.first[k] + r0];
+        if (l0 >= 0 && (uint32_t)l0 < A.R && (uint32_t)l0 < anchor) anchor = (uint32_t)l0;
+    }
+    Window W;
+    W.lo = anchor == 0xFFFFFFFFu ? 0u : anchor;
+    W.cols = cols;
+    const int32_t q0 = (int32_t)hist[9];                                   // s5gpu_pile_hist_head_t::q0, ::shift (32-bit words 9 and 10): written by the reset only
+    const uint32_t shift = hist[10];
+    uint32_t *table = hist + HIST_HEAD_WORDS;
+    uint64_t *head = reinterpret_cast<uint64_t *>(hist);
+    __syncthreads();
+    uint64_t cells = 0;                                                    // this lane's
+    k = A.n;
+    for (uint64_t it = base + wave; it < end; it += s5::NW) {
+        if (!long_item(A, S, L, sorted, it, &k, &r0, &r1)) continue;       // (the wave's branch)
+        const uint64_t f = A.first[k];
+        hist_seg_cells<HistOps>(r0, r1, lane, 64u, A.lo + f, A.hi + f, A.queries + f, q0, shift, A.R, W, hist_win, table, &cells);
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < cols * HIST_BINS; t += s5::NT) hist_flush_word<HistOps>(t, W, hist_win, table, A.R);
+    // the reads, once each
+    uint64_t used = 0, skipped = 0, bad = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * s5::NT + threadIdx.x; r < A.n; r += (uint64_t)gridDim.x * s5::NT) {
+        const uint32_t v = L.verdict[r];
+        if (v & V_SKIPPED) skipped++;
+        else if (v & V_BAD) bad++;
+        else used++;
+    }
+    used = wave_sum(used);
+    skipped = wave_sum(skipped);
+    bad = wave_sum(bad);
+    cells = wave_sum(cells);
+    if (lane == 0) {
+        if (cells) DevOps::add64(head + 0, cells);
+        if (used) DevOps::add64(head + 1, used);
+        if (skipped) DevOps::add64(head + 2, skipped);
+        if (bad) DevOps::add64(head + 3, bad);
+    }
+}
+
+namespace {
+uint32_t g_hist_cols = HIST_MAX_COLS;   // option "pile_hist_cols"
+uint32_t g_hist_grid = MAX_GRID;        // option "pile_hist_grid"
+
 int set_option_long(const char *key, long value) {
     const bool pow2 = value > 0 && (value & (value - 1)) == 0;
+    if (strcmp(key, "pile_hist_cols") == 0 && (value == 0 || (pow2 && value >= (long)HIST_MIN_COLS && value <= (long)HIST_MAX_COLS))) {
+        g_hist_cols = (uint32_t)value;
+        return S5GPU_OK;
+    }
+    if (strcmp(key, "pile_hist_grid") == 0 && value >= 1 && value <= (long)MAX_GRID) { g_hist_grid = (uint32_t)value; return S5GPU_OK; }
     if (strcmp(key, "pileup_long_seg") == 0 && pow2 && value >= (long)SEG_MIN && value <= (long)SEG_MAX) { g_long_seg = (uint32_t)value; return S5GPU_OK; }
     if (strcmp(key, "pileup_long_cols") == 0 && (value == 0 || (pow2 && value >= (long)MIN_COLS && value <= (long)MAX_COLS))) {
         g_long_cols = (uint32_t)value;
@@ -383,7 +459,9 @@ int set_option_long(const char *key, long value) {
 }
 }  // namespace
 
-int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) {
+int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) { return launch_pileup_long(A, nullptr, st); }
+
+int pilek::launch_pileup_long(const PileLongArgs &A, void *hist, hipStream_t st) {
     if (A.n == 0) return S5GPU_OK;
     const uint32_t S = g_long_seg, cols = g_long_cols;
     const LongWork w = long_work(A.n, A.total_rows);
@@ -410,9 +488,15 @@ int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) {
         hipLaunchKernelGGL(k_pileup_long_check, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sort, 1u);
         S5_LAUNCH_CHECK("k_pileup_long_check (scatter)");
     }
-    if (passes & 4u) {
+    if ((passes & 4u) && A.acc) {
         hipLaunchKernelGGL(k_pileup_long_accum, dim3(grid), dim3(s5::NT), (size_t)cols * sizeof(s5gpu_pile_col_t), st, A, S, L, sort, cols);
         S5_LAUNCH_CHECK("k_pileup_long_accum");
+    }
+    if ((passes & 4u) && hist) {
+        const uint32_t hcols = g_hist_cols, hgrid = (uint32_t)(quads < g_hist_grid ? quads : g_hist_grid);
+        hipLaunchKernelGGL(k_pile_hist_accum, dim3(hgrid), dim3(s5::NT), (size_t)hcols * HIST_BINS * sizeof(uint32_t), st, A, S, L, sort, hcols,
+                           reinterpret_cast<uint32_t *>(hist));
+        S5_LAUNCH_CHECK("k_pile_hist_accum");
     }
     return S5GPU_OK;
 }
