@@ -3,7 +3,7 @@
  * against each other on the GPU (k_pile_hist_accum, k_pile_contrast; docs/codecs.md §4.23).
  *
  *   s5contrast [-K batch] [--rna] [--skip S] [--events Q] [--min-events M] [--tile T] [--band B] [--max-events N] [--min-depth D] [--q0 V] [--shift S]
- *              ref.txt a.blow5 b.blow5
+ *              [--refine [--iters N] [--slope LO,HI]] ref.txt a.blow5 b.blow5
  *       <ref_pos>\t<ref_level>\t<depth_a>\t<depth_b>\t<events_a>\t<events_b>\t<mean_a>\t<mean_b>\t<ks_d>\t<ks_level>\t<tv>\t<med_a>\t<med_b>
  *   one line per position whose depth is at least D (default 1) in both files.  ref.txt, S, Q, M, T, B, N and the event parameters are those
  *   of s5extend.  depth, events and mean (sum / events, of the quantised event levels) come from each file's table as in s5pileup --whole.
@@ -12,6 +12,9 @@
  *   1 - ov_num / (events_a events_b); ks_level is the lowest level of the bin where the two distributions are furthest apart, med_a and med_b
  *   the lowest level of each median's bin (q0 + (bin << shift)).  Doubles are printed as %.6g.  ks_d is a statistic, not a probability.
  *   The totals of both files (reads used, skipped, bad; cells; cost) go to stderr, a line each.
+ *   --refine [--iters N] [--slope LO,HI]: every read of both files is first put into the reference's units by the rounds of
+ *   s5extend --refine (docs/codecs.md §4.24; s5gpu_contrast_set_refine): a per-read scale error no longer shows as a level difference.  A
+ *   read whose fit is refused is left out and counts as skipped; how many there were goes to stderr behind each file's totals.
  *   Exit 0; 1 when a record is corrupt (its file and number go to stderr; the other reads are counted); 2 on any other error.
  *
  * One handle (s5gpu_contrast_open), one s5gpu_contrast_add_batch per K records (default 4096) of a.blow5, then of b.blow5, and one
@@ -33,7 +36,10 @@ static int die(const char *what) {
     return EXIT_ERROR;
 }
 /* a status of the decoder's, not one of map's or extend's */
-static int corrupt_status(int32_t s) { return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW; }
+static int corrupt_status(int32_t s) {
+    return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW && s != S5GPU_STATUS_FIT_FLAT &&
+           s != S5GPU_STATUS_FIT_RANGE;
+}
 static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
 static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
 
@@ -68,7 +74,7 @@ static float *read_reference(const char *path, size_t *n_out) {
 }
 
 /* the batches of one file into `side` of the handle; 0, EXIT_CORRUPT or EXIT_ERROR */
-static int add_file(void *h, int side, const char *path, long K, void **mem, size_t *len, int32_t *st) {
+static int add_file(void *h, int side, const char *path, long K, void **mem, size_t *len, int32_t *st, uint64_t *n_refused) {
     slow5_file_t *in = slow5_open(path, "r");
     if (!in) { fprintf(stderr, "s5contrast: cannot open %s\n", path); return EXIT_ERROR; }
     if (in->format != SLOW5_FORMAT_BINARY) { fprintf(stderr, "s5contrast: %s is SLOW5 text: convert it to BLOW5 first\n", path); return EXIT_ERROR; }
@@ -95,6 +101,7 @@ static int add_file(void *h, int side, const char *path, long K, void **mem, siz
                 fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is corrupt (status %d)\n", n_done + i, path, st[i]);
                 code = EXIT_CORRUPT;
             }
+            if (st[i] == S5GPU_STATUS_FIT_FLAT || st[i] == S5GPU_STATUS_FIT_RANGE) (*n_refused)++;
             free(mem[i]);
             mem[i] = NULL;
         }
@@ -106,7 +113,9 @@ static int add_file(void *h, int side, const char *path, long K, void **mem, siz
 
 int main(int argc, char **argv) {
     long K = 4096, skip = 0, qmax = 250, qmin = 50, min_depth = 1, tile = 256, band = 512, emax = 1l << 20, q0 = -128, shift = 2;
-    int rna = 0, bad = 0;
+    long iters = 2;
+    double a_lo = 0.5, a_hi = 2.0;
+    int rna = 0, bad = 0, refine = 0;
     const char *ref_path = NULL, *path[2] = {NULL, NULL};
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
@@ -120,10 +129,17 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--max-events") && i + 1 < argc) emax = atol(argv[++i]);
         else if (!strcmp(argv[i], "--q0") && i + 1 < argc) q0 = atol(argv[++i]);
         else if (!strcmp(argv[i], "--shift") && i + 1 < argc) shift = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--refine")) refine = 1;
+        else if (!strcmp(argv[i], "--iters") && i + 1 < argc) iters = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--slope") && i + 1 < argc) { if (sscanf(argv[++i], "%lf,%lf", &a_lo, &a_hi) != 2) bad = 1; }
         else if (argv[i][0] != '-' && !ref_path) ref_path = argv[i];
         else if (argv[i][0] != '-' && !path[0]) path[0] = argv[i];
         else if (argv[i][0] != '-' && !path[1]) path[1] = argv[i];
         else bad = 1;
+    }
+    if (iters < 1 || iters > 4 || !(a_lo > 0.0) || !(a_lo <= a_hi) || !(a_hi <= 1e300)) {
+        fprintf(stderr, "s5contrast: --iters N (1 .. 4), --slope LO,HI (0 < LO <= HI)\n");
+        return EXIT_ERROR;
     }
     if (tile != 64 && tile != 128 && tile != 256 && tile != 512 && tile != 1024) bad = 1;
     if (band < 64 || band > 4096 || band % 64 || emax < qmin || emax > (1l << 20)) bad = 1;
@@ -132,7 +148,8 @@ int main(int argc, char **argv) {
         min_depth > 0xFFFFFFFFl) {
         fprintf(stderr, "usage: s5contrast [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--tile T (64, 128, 256, 512, 1024)]\n"
                         "                  [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] [--min-depth D (>= 1)]\n"
-                        "                  [--q0 V (-32768 .. 32767)] [--shift S (0 .. 10)] ref.txt a.blow5 b.blow5\n");
+                        "                  [--q0 V (-32768 .. 32767)] [--shift S (0 .. 10)]\n"
+                        "                  [--refine [--iters N (1 .. 4)] [--slope LO,HI (0 < LO <= HI)]] ref.txt a.blow5 b.blow5\n");
         return EXIT_ERROR;
     }
     const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
@@ -157,9 +174,12 @@ int main(int argc, char **argv) {
     if (!mem || !len || !st || !acc[0] || !acc[1] || !rows) return die("out of memory");
     void *h = s5gpu_contrast_open(rna ? &rnap : &dna, &M, &B, 0, ref, (uint32_t)R, (int32_t)q0, (uint32_t)shift);
     if (!h) return die("the tables cannot be opened");
+    const s5gpu_refine_params_t RP = {a_lo, a_hi, 64.0, 127, 16, 16, (uint32_t)iters};
+    if (refine && s5gpu_contrast_set_refine(h, &RP) != S5GPU_OK) return die("the rounds cannot be turned on");
+    uint64_t n_refused[2] = {0, 0};
     int code = EXIT_SUCCESS;
     for (int side = 0; side < 2; side++) {
-        const int c = add_file(h, side, path[side], K, mem, len, st);
+        const int c = add_file(h, side, path[side], K, mem, len, st, &n_refused[side]);
         if (c == EXIT_ERROR) return EXIT_ERROR;
         if (c) code = c;
     }
@@ -177,6 +197,7 @@ int main(int argc, char **argv) {
         const s5gpu_pile_total_t *T = (const s5gpu_pile_total_t *)acc[side];
         fprintf(stderr, "s5contrast: %s: reads used %" PRIu64 ", skipped %" PRIu64 ", bad %" PRIu64 "; cells %" PRIu64 ", cost %" PRIu64 "; %zu positions\n", path[side],
                 T->reads_used, T->reads_skipped, T->reads_bad, T->cells, T->cost, R);
+        if (refine) fprintf(stderr, "s5contrast: %s: reads refused by the fit %" PRIu64 " (they count as skipped)\n", path[side], n_refused[side]);
     }
     if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5contrast: write failed\n"); return EXIT_ERROR; }
     free(mem); free(len); free(st); free(acc[0]); free(acc[1]); free(rows); free(ref);

@@ -12,6 +12,9 @@
  *   s5pileup --whole [--tile T] [--band B] [--max-events N] ... : the same ten columns from ALL of a read's events (docs/codecs.md §4.22): the
  *   prefix of Q events finds the anchor as above, then up to N events (default 2^20) are aligned in tiles of T rows (default 256) over
  *   windows of B columns (default 512) as in s5extend, and the whole path is added to the table.  --max-span does not count then.
+ *   s5pileup --whole --refine [--iters N] [--slope LO,HI] ... : every read is first put into the reference's units by the rounds of
+ *   s5extend --refine (docs/codecs.md §4.24; s5gpu_pileup_set_refine), so mean, stdv, min and max are in the reference's units; a read
+ *   whose fit is refused is left out and counts as skipped, and how many there were goes to stderr behind the totals.
  *   Exit 0; 1 when a record is corrupt (its read id, or its number in the file when the id cannot be read, goes to stderr; the other reads
  *   are counted); 2 on any other error.
  *
@@ -36,7 +39,10 @@ static int die(const char *what) {
     return EXIT_ERROR;
 }
 /* a status of the decoder's, not one of map's or align's */
-static int corrupt_status(int32_t s) { return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW; }
+static int corrupt_status(int32_t s) {
+    return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW && s != S5GPU_STATUS_FIT_FLAT &&
+           s != S5GPU_STATUS_FIT_RANGE;
+}
 static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
 static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
 
@@ -90,8 +96,9 @@ static float *read_reference(const char *path, size_t *n_out) {
 }
 
 int main(int argc, char **argv) {
-    long K = 4096, skip = 0, qmax = 250, qmin = 50, wmax = -1, min_depth = 1, tile = -1, band = -1, emax = -1;
-    int rna = 0, bad = 0, whole = 0;
+    long K = 4096, skip = 0, qmax = 250, qmin = 50, wmax = -1, min_depth = 1, tile = -1, band = -1, emax = -1, iters = 2;
+    double a_lo = 0.5, a_hi = 2.0;
+    int rna = 0, bad = 0, whole = 0, refine = 0;
     const char *ref_path = NULL, *path = NULL;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
@@ -102,6 +109,9 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--max-span") && i + 1 < argc) wmax = atol(argv[++i]);
         else if (!strcmp(argv[i], "--min-depth") && i + 1 < argc) min_depth = atol(argv[++i]);
         else if (!strcmp(argv[i], "--whole")) whole = 1;
+        else if (!strcmp(argv[i], "--refine")) refine = 1;
+        else if (!strcmp(argv[i], "--iters") && i + 1 < argc) iters = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--slope") && i + 1 < argc) { if (sscanf(argv[++i], "%lf,%lf", &a_lo, &a_hi) != 2) bad = 1; }
         else if (!strcmp(argv[i], "--tile") && i + 1 < argc) { tile = atol(argv[++i]); bad |= tile == -1; }
         else if (!strcmp(argv[i], "--band") && i + 1 < argc) { band = atol(argv[++i]); bad |= band == -1; }
         else if (!strcmp(argv[i], "--max-events") && i + 1 < argc) { emax = atol(argv[++i]); bad |= emax == -1; }
@@ -109,6 +119,11 @@ int main(int argc, char **argv) {
         else if (argv[i][0] != '-' && !path) path = argv[i];
         else bad = 1;
     }
+    if (iters < 1 || iters > 4 || !(a_lo > 0.0) || !(a_lo <= a_hi) || !(a_hi <= 1e300)) {
+        fprintf(stderr, "s5pileup: --iters N (1 .. 4), --slope LO,HI (0 < LO <= HI)\n");
+        return EXIT_ERROR;
+    }
+    if (refine && !whole) bad = 1;                                         /* (it belongs to --whole) */
     if (wmax == -1) wmax = 4 * qmax;
     if (!whole && (tile != -1 || band != -1 || emax != -1)) bad = 1;      /* (they belong to --whole) */
     if (tile == -1) tile = 256;
@@ -120,6 +135,7 @@ int main(int argc, char **argv) {
         wmax > (1l << 20) || min_depth < 1 || min_depth > 0xFFFFFFFFl) {
         fprintf(stderr, "usage: s5pileup [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--max-span W (1 .. 2^20)] [--min-depth D (>= 1)] ref.txt file.blow5\n");
         fprintf(stderr, "       s5pileup --whole [--tile T (64, 128, 256, 512, 1024)] [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] ... : the table of whole reads\n");
+        fprintf(stderr, "       s5pileup --whole --refine [--iters N (1 .. 4)] [--slope LO,HI (0 < LO <= HI)] ... : every read rescaled to the reference's units first\n");
         return EXIT_ERROR;
     }
     const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
@@ -158,6 +174,9 @@ int main(int argc, char **argv) {
     const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
     void *pile = whole ? s5gpu_pileup_open_whole(P, &M, &B, 0, ref, (uint32_t)R) : s5gpu_pileup_open(P, &M, (uint32_t)wmax, ref, (uint32_t)R);
     if (!pile) return die("the table cannot be opened");
+    const s5gpu_refine_params_t RP = {a_lo, a_hi, 64.0, 127, 16, 16, (uint32_t)iters};
+    if (refine && s5gpu_pileup_set_refine(pile, &RP) != S5GPU_OK) return die("the rounds cannot be turned on");
+    uint64_t n_refused = 0;
     int code = EXIT_SUCCESS, at_end = 0;
     uint64_t n_done = 0;
     while (!at_end) {
@@ -223,6 +242,9 @@ int main(int argc, char **argv) {
                 if (id) fprintf(stderr, "s5pileup: read %.*s is corrupt (status %d)\n", (int)idl, id, st[i]);
                 else fprintf(stderr, "s5pileup: record %" PRIu64 " of the file is corrupt (status %d)\n", n_done + i, st[i]);
                 code = EXIT_CORRUPT;
+            } else if (st[i] == S5GPU_STATUS_FIT_FLAT || st[i] == S5GPU_STATUS_FIT_RANGE) {
+                fprintf(stderr, "s5pileup: read %.*s is left out: its fit is refused (%s)\n", (int)idl, id, st[i] == S5GPU_STATUS_FIT_FLAT ? "flat" : "range");
+                n_refused++;
             } else if (st[i] != 0) {
                 const char *why = st[i] == S5GPU_STATUS_QUERY_SHORT ? "short" : st[i] == S5GPU_STATUS_PATH_WIDE ? "wide" : "row";
                 fprintf(stderr, "s5pileup: read %.*s has no path: %s\n", (int)idl, id, why);
@@ -245,6 +267,7 @@ int main(int argc, char **argv) {
     }
     fprintf(stderr, "s5pileup: reads used %" PRIu64 ", skipped %" PRIu64 ", bad %" PRIu64 "; cells %" PRIu64 ", cost %" PRIu64 "; %zu positions\n", T->reads_used,
             T->reads_skipped, T->reads_bad, T->cells, T->cost, R);
+    if (refine) fprintf(stderr, "s5pileup: reads refused by the fit %" PRIu64 " (they count as skipped)\n", n_refused);
     if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5pileup: write failed\n"); return EXIT_ERROR; }
     if (chunk) s5gpu_host_free(chunk);
     slow5_close(in);

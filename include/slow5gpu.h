@@ -1075,6 +1075,68 @@ void *s5gpu_pileup_open_whole(const s5gpu_event_params_t *event_params, const s5
 int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
                                  s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out);
 
+/* ---- refine, whole reads: the fit along extend's ragged paths, and rounds of the banded alignment (docs/codecs.md §4.24) ----
+ * "refine" above works on the fixed-pitch matrices of at most 1024 events.  These calls do the same on the ragged layout of "extend": read
+ * k's rows at [first[k], first[k] + qlen[k]) of queries, lo and hi ([total_rows] each), qlen[k] <= 2^20.  Who is fitted is decided as in
+ * "pileup of whole reads" with ev_skip = 0: a read whose status_in is not 0 or whose qlen is 0 is SKIPPED (it keeps its status and has no
+ * fit); one with a flaw in its layout or a row that fails the path rule is BAD (S5GPU_STATUS_PATH_ROW, no fit); the others are fitted over
+ * all the cells of their paths, whole or not at all.  There is no wmax.  The sums are exact in int64, the solve is that of "refine":
+ * S5GPU_STATUS_FIT_FLAT and S5GPU_STATUS_FIT_RANGE as there.  refine_params->pad must be in its range and is not used: the band is the
+ * window.  Integer-exact but for the one solve in double; reproducible bit for bit whatever the launch shape. */
+/* The bytes of the work area of s5gpu_path_fit_long_dev (0: total_rows above 2^40). */
+size_t s5gpu_path_fit_long_work_bytes(uint32_t n, uint64_t total_rows);
+/* fit_out[k]: a, b and the six sums (a = 1, b = 0 and zeros for a read that is not fitted; a = 1, b = 0 and its sums for one whose fit is
+ * refused); status_out[k]: 0, the status that came in, S5GPU_STATUS_PATH_ROW, S5GPU_STATUS_FIT_FLAT or S5GPU_STATUS_FIT_RANGE; queries_out
+ * (may be NULL; [total_rows]): q' = clamp(rint(a q + b), -clip, clip) at the rows of the reads whose status_out is 0, zeros everywhere
+ * else.  Asynchronous on hip_stream; writes nothing but the outputs and work (DEVICE memory, 16-byte aligned, a work area per call in
+ * flight).  refine_params: a HOST struct.  n = 0: S5GPU_OK and nothing is launched.  S5GPU_ERR_ARG, nothing launched: a refine parameter
+ * outside its range, R outside 1 .. 2^31 - 1, total_rows above 2^40, a NULL or misaligned pointer (first: 8 bytes; fit_out, work: 16),
+ * queries_out == queries.  S5GPU_ERR_NOMEM, nothing written: work_bytes below s5gpu_path_fit_long_work_bytes(n, total_rows).
+ * s5gpu_set_option (tests, tools): "refine_long_passes" (1 .. 63, default 63) says which kernels these calls launch: 1 the plan and the
+ * check, 2 the sums, 4 the solve, 8 the requantiser, 16 the bookkeeping of the rounds, 32 the band call. */
+int s5gpu_path_fit_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows,
+                            const int16_t *ref, uint32_t R, const int32_t *lo, const int32_t *hi, const int32_t *status_in,
+                            const s5gpu_refine_params_t *refine_params, void *work, size_t work_bytes, s5gpu_fit_t *fit_out,
+                            int16_t *queries_out, int32_t *status_out, void *hip_stream);
+/* The bytes of the work area of s5gpu_extend_refine_dev: the fit's and a trial round (0: total_rows above 2^40). */
+size_t s5gpu_extend_refine_work_bytes(uint32_t n, uint64_t total_rows);
+/* refine_params->iters rounds on device buffers, nothing downloaded in between.  What comes in is what s5gpu_sdtw_band_dev left: the long
+ * queries, rows_in (a read's status_in is rows_in[k].status), lo_in, hi_in.  Round 0 makes the outputs copies of what came in, with a = 1,
+ * b = 0 and rounds 0; a SKIPPED or BAD read has "no result": zeros in queries_out, -1 in lo_out and hi_out, the empty row with its
+ * status, and takes no part.  Round j >= 1: the fit of the query that CAME IN along the path the read has, q' from it, and the banded
+ * alignment of q' (band_params->tile_rows and band; anchor: `start` of the row the read has) into a trial; where both succeed the trial
+ * becomes the read's result and rounds_out[k] = j; a read that gets a fit status or a band status keeps the last round that succeeded,
+ * takes no further part, and reports that status in rows_out[k].status.  queries_out holds zeros and lo_out, hi_out -1 at every row that
+ * is behind a read's query or belongs to no read.  What comes out feeds s5gpu_pileup_accum_long_dev as it is (status: rows_out[k].status).
+ * scratch: that of s5gpu_sdtw_band_scratch_bytes(n, total_rows, tile_rows, band), used again every round; too small: S5GPU_ERR_NOMEM and
+ * nothing is written, as with a work area below s5gpu_extend_refine_work_bytes(n, total_rows).  S5GPU_ERR_ARG, nothing launched: a band
+ * or refine parameter outside its range, R outside 1 .. 2^31 - 1, total_rows above 2^40, a NULL or misaligned pointer (rows, fit_out,
+ * scratch, work: 16 bytes; first: 8), an output that is an input.  n = 0: S5GPU_OK.  Asynchronous on hip_stream. */
+int s5gpu_extend_refine_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows,
+                            const int16_t *ref, uint32_t R, const s5gpu_ext_row_t *rows_in, const int32_t *lo_in, const int32_t *hi_in,
+                            const s5gpu_band_params_t *band_params, const s5gpu_refine_params_t *refine_params, void *scratch,
+                            size_t scratch_bytes, void *work, size_t work_bytes, int16_t *queries_out, s5gpu_ext_row_t *rows_out,
+                            int32_t *lo_out, int32_t *hi_out, s5gpu_fit_t *fit_out, uint32_t *rounds_out, void *hip_stream);
+/* s5gpu_extend_batch with the rounds behind each group's band call: rows_first_out[0 .. n) are the rows of the first alignment (what
+ * s5gpu_extend_batch returns), rows_out, lo_out, hi_out the refined ones (ev_first_out: the prefix of rows_out[i].qlen), queries_out (may
+ * be NULL) the refined long queries laid out as lo_out, fit_out[0 .. n) and rounds_out (may be NULL) the fits and the rounds that
+ * succeeded.  status_out (may be NULL): those of s5gpu_extend_batch, S5GPU_STATUS_FIT_FLAT, S5GPU_STATUS_FIT_RANGE.  The results do not
+ * depend on how scratch_max cuts the groups.  S5GPU_ERR_ARG before a device is needed: the cases of s5gpu_extend_batch, a refine
+ * parameter outside its range, a NULL rows_first_out or fit_out. */
+int s5gpu_extend_refine_batch(uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                              const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params,
+                              const s5gpu_band_params_t *band_params, const s5gpu_refine_params_t *refine_params, size_t scratch_max,
+                              const int16_t *ref_host, uint32_t R, s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *rows_first_out,
+                              s5gpu_ext_row_t *rows_out, uint64_t *ev_first_out, int32_t *lo_out, int32_t *hi_out, s5gpu_event_t *events_out,
+                              int16_t *queries_out, size_t rows_cap, s5gpu_fit_t *fit_out, uint32_t *rounds_out, int32_t *status_out);
+/* Refinement inside the whole-read handles: behind this call s5gpu_pileup_add_batch_whole (s5gpu_contrast_add_batch) runs the rounds and
+ * feeds the table (and the histograms) with the refined queries, paths and statuses: the table's sums of levels and the histograms' bins
+ * are then in the reference's units, and a read whose rounds ended with a status is skipped.  ext_rows_out of the add are the refined
+ * rows.  NULL turns refinement off.  S5GPU_ERR_ARG: a NULL handle, a handle that is not a whole-read one, one that has added a batch
+ * already, a parameter outside its range. */
+int s5gpu_pileup_set_refine(void *handle, const s5gpu_refine_params_t *refine_params);
+int s5gpu_contrast_set_refine(void *handle, const s5gpu_refine_params_t *refine_params);
+
 /* ---- contrast: per-position level histograms and a two-sample comparison of them (docs/codecs.md §4.23) ----
  * A histogram is a head and R columns of 64 uint32_t counts that stay on the device beside (or without) the table of "pileup".  The bin of a
  * quantised level q: d = (int32)q - q0; bin = d < 0 ? 0 : min(d >> shift, 63), q0 in -32768 .. 32767, shift in 0 .. 10.  Which reads are

@@ -332,6 +332,18 @@ def lib():
     L.s5gpu_contrast_open.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32, i32, u32]
     L.s5gpu_contrast_add_batch.argtypes = [vp, i32, u32, vp, vp, i32, i32, vp, vp, vp]
     L.s5gpu_contrast_close.argtypes = [vp, vp, vp, vp]
+    # refine, whole reads: the fit along ragged paths, the rounds of the banded alignment, the chain, and the switch of the whole-read handles
+    L.s5gpu_path_fit_long_work_bytes.argtypes = [u32, u64]
+    L.s5gpu_path_fit_long_work_bytes.restype = C.c_size_t
+    L.s5gpu_path_fit_long_dev.argtypes = [u32, vp, vp, vp, u64, vp, u32, vp, vp, vp, C.POINTER(RefineParams), vp, C.c_size_t, vp, vp, vp, vp]
+    L.s5gpu_extend_refine_work_bytes.argtypes = [u32, u64]
+    L.s5gpu_extend_refine_work_bytes.restype = C.c_size_t
+    L.s5gpu_extend_refine_dev.argtypes = [u32, vp, vp, vp, u64, vp, u32, vp, vp, vp, C.POINTER(BandParams), C.POINTER(RefineParams), vp, C.c_size_t, vp,
+                                          C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    L.s5gpu_extend_refine_batch.argtypes = [u32, vp, vp, i32, i32, C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.POINTER(RefineParams),
+                                            C.c_size_t, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.s5gpu_pileup_set_refine.argtypes = [vp, C.POINTER(RefineParams)]
+    L.s5gpu_contrast_set_refine.argtypes = [vp, C.POINTER(RefineParams)]
     _LIB = L
     return L
 
@@ -366,4 +378,6 @@ EXPORTS = [
     "s5gpu_pileup_long_work_bytes", "s5gpu_pileup_accum_long_dev", "s5gpu_pileup_open_whole", "s5gpu_pileup_add_batch_whole",
     "s5gpu_pile_hist_bytes", "s5gpu_pile_hist_reset_dev", "s5gpu_pile_hist_accum_long_dev", "s5gpu_pile_contrast_dev", "s5gpu_contrast_open",
     "s5gpu_contrast_add_batch", "s5gpu_contrast_close",
+    "s5gpu_path_fit_long_work_bytes", "s5gpu_path_fit_long_dev", "s5gpu_extend_refine_work_bytes", "s5gpu_extend_refine_dev", "s5gpu_extend_refine_batch",
+    "s5gpu_pileup_set_refine", "s5gpu_contrast_set_refine",
 ]

@@ -150,9 +150,10 @@ def rows_to_host(rows):
 
 
 def contrast_whole_dev(dec_a, dec_b, ref, q0=Q0, shift=SHIFT, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX,
-                       tile_rows=_extend.TILE_ROWS, band=_extend.BAND):
+                       tile_rows=_extend.TILE_ROWS, band=_extend.BAND, refine=None):
     """extend.extend_dev(host=False) on two decoded batches, each side's ragged paths into a table and a histogram of its own, then
-    contrast_dev.  Returns (rows, (acc_a, acc_b), (hist_a, hist_b)), all on the device."""
+    contrast_dev.  Returns (rows, (acc_a, acc_b), (hist_a, hist_b)), all on the device.  refine (as in extend.extend_dev): both sides are
+    fed with the refined queries, paths and statuses: the bins are then in the reference's units (§4.24)."""
     import torch
 
     r = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int16))
@@ -161,7 +162,7 @@ def contrast_whole_dev(dec_a, dec_b, ref, q0=Q0, shift=SHIFT, event_params=DNA, 
     accs, hists = [], []
     for dec in (dec_a, dec_b):
         ev, first = _events.events_dev(dec, event_params, "raw")
-        _, x = _extend.extend_dev(dec, r, event_params, skip, qmax, qmin, scale, clip, emax, tile_rows, band, host=False, events=(ev, first))
+        _, x = _extend.extend_dev(dec, r, event_params, skip, qmax, qmin, scale, clip, emax, tile_rows, band, host=False, events=(ev, first), refine=refine)
         st = (x.rows[:, 3] >> 32).to(torch.int32)                          # EXT_ROW.status
         accs.append(_pileup.accum_long_dev(x.queries, x.first, x.qlen, r, x.lo, x.hi, st, _pileup.new_acc(R, dec.dev), ev, skip))
         hists.append(hist_accum_long_dev(x.queries, x.first, x.qlen, x.lo, x.hi, st, new_hist(R, q0, shift, dec.dev)))
@@ -174,7 +175,7 @@ class Contrast:
     handle that was not closed."""
 
     def __init__(self, ref, q0=Q0, shift=SHIFT, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX,
-                 tile_rows=_extend.TILE_ROWS, band=_extend.BAND, scratch_max=0):
+                 tile_rows=_extend.TILE_ROWS, band=_extend.BAND, scratch_max=0, refine=None):
         r = np.ascontiguousarray(ref, dtype=np.int16)
         ep, mp = _events._params(event_params), _map._params(skip, qmax, qmin, scale, clip, True)
         bp = _extend.BandParams(skip, qmin, emax, tile_rows, band, clip, scale)
@@ -182,6 +183,12 @@ class Contrast:
         self._h = _lib.lib().s5gpu_contrast_open(C.byref(ep), C.byref(mp), C.byref(bp), int(scratch_max), r.ctypes.data_as(C.c_void_p), len(r), int(q0), int(shift))
         if not self._h:
             raise _lib.S5GpuError("s5gpu_contrast_open failed: %s" % _lib.lib().s5gpu_last_error().decode(errors="replace"))
+        rp = _extend._refine_params(refine)
+        if rp is not None:
+            rc = _lib.lib().s5gpu_contrast_set_refine(self._h, C.byref(rp))
+            if rc != 0:
+                self.abandon()
+                check(rc, "s5gpu_contrast_set_refine")
 
     def add(self, side, records, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, raise_on_error=True):
         """Adds a batch of records (bytes without the u64 prefix) to side 0 or 1 -> (rc, MAP_ROW array, EXT_ROW array, status).  A corrupt
@@ -226,16 +233,19 @@ class Contrast:
 
 
 def file_contrast(a, b, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, min_depth=1, q0=Q0, shift=SHIFT, emax=None, tile_rows=None, band=None,
-                  raise_on_corrupt=True):
+                  raise_on_corrupt=True, refine=False, iters=None, slope=None):
     """The positions of two .blow5 files against the levels of ref_path (one number per line) as a CONTRAST_LINE array, a row per reference
     position whose depth is at least min_depth in both.  Runs the s5contrast tool (examples/s5contrast.c), `batch` records per device call.
-    A corrupt record raises; with raise_on_corrupt=False it is left out."""
+    A corrupt record raises; with raise_on_corrupt=False it is left out.  refine=True: --refine, with iters and slope as in extend.file_extend."""
     if not os.path.exists(S5CONTRAST):
         _build.build()
     cmd = [S5CONTRAST, "-K", str(int(batch)), "--skip", str(int(skip)), "--events", str(int(qmax)), "--min-events", str(int(qmin)), "--min-depth", str(int(min_depth)),
            "--q0", str(int(q0)), "--shift", str(int(shift))]
     cmd += (["--rna"] if rna else []) + (["--max-events", str(int(emax))] if emax is not None else [])
     cmd += (["--tile", str(int(tile_rows))] if tile_rows is not None else []) + (["--band", str(int(band))] if band is not None else [])
+    if refine:
+        cmd += ["--refine"] + (["--iters", str(int(iters))] if iters is not None else [])
+        cmd += ["--slope", "%.17g,%.17g" % (float(slope[0]), float(slope[1]))] if slope is not None else []
     cmd += [os.fspath(ref_path), os.fspath(a), os.fspath(b)]
     p = subprocess.run(cmd, capture_output=True)
     if p.returncode != 0 and (raise_on_corrupt or p.returncode != 1):

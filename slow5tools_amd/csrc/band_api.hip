@@ -4,7 +4,7 @@
 // the banded alignment from `start`, in groups of consecutive reads whose scratch fits -> one download.
 #include <vector>
 
-#include "band_host.h"
+#include "refine_host.h"
 
 int bandk::check_band_params(const char *who, const s5gpu_band_params_t *p) {
     if (!p) { s5gpu_set_error("%s: NULL band parameters", who); return S5GPU_ERR_ARG; }
@@ -91,7 +91,7 @@ extern "C" int s5gpu_sdtw_band_dev(uint32_t n, const int16_t *queries, const uin
 
 // The device side of s5gpu_extend_batch behind a front with m >= 1 reads (band_host.h), queued on the front's stream
 int bandk::extend_tail(const char *who, dtwk::MapFront &F, const s5gpu_map_params_t *mp, const s5gpu_band_params_t *bp, size_t scratch_max, uint32_t R,
-                       bool events, bool paths_back, size_t rows_cap, size_t scan_min, uint64_t *room_out, ExtTail &E) {
+                       bool events, bool paths_back, size_t rows_cap, size_t scan_min, uint64_t *room_out, ExtTail &E, const s5gpu_refine_params_t *rp) {
     int rc;
     Ctx *c = F.hold.c;
     const uint32_t m = F.m, T = bp->tile_rows;
@@ -113,7 +113,14 @@ int bandk::extend_tail(const char *who, dtwk::MapFront &F, const s5gpu_map_param
         s5gpu_set_error("%s: room for %zu rows, %llu may be needed", who, rows_cap, (unsigned long long)room);
         return S5GPU_ERR_NOMEM;
     }
-    if ((rc = c->d_gather.reserve(E.o_st + 4ull * m + 64)) || (rc = c->h_out.reserve((paths_back ? E.back : E.o_lo + 4ull * m) + 64))) return rc;
+    size_t gather = E.o_st + 4ull * m, host = paths_back ? E.back : E.o_lo + 4ull * m;
+    if (rp) {
+        E.r_base = E.r_rows = up(gather, 64); E.r_fit = E.r_rows + 32ull * m; E.r_rnd = E.r_fit + 64ull * m; E.r_lo = E.r_rnd + up(4ull * m, 16);
+        E.r_hi = E.r_lo + up(4ull * total, 16); E.r_q = E.r_hi + up(4ull * total, 16); E.r_back = E.r_q + up(2ull * total, 16); E.r_work = E.r_back;
+        gather = E.r_work + (size_t)refk::refine_long_work(m, total).bytes;
+        host = paths_back ? E.r_back : host + 32ull * m + 16;
+    }
+    if ((rc = c->d_gather.reserve(gather + 64)) || (rc = c->h_out.reserve(host + 64))) return rc;
     uint8_t *dg = (uint8_t *)c->d_gather.p;
     s5gpu_ext_row_t *d_rows = (s5gpu_ext_row_t *)dg;
     s5gpu_map_row_t *d_map = (s5gpu_map_row_t *)(dg + E.o_map);
@@ -141,6 +148,7 @@ int bandk::extend_tail(const char *who, dtwk::MapFront &F, const s5gpu_map_param
         b = e;
     }
     if ((rc = c->d_scan.reserve(most + 64))) return rc;
+    if (rp && (rc = refk::long_rounds_fill((int16_t *)(dg + E.r_q), (int32_t *)(dg + E.r_lo), (int32_t *)(dg + E.r_hi), total, c->st))) return rc;
     for (size_t g = 0; g + 1 < cut.size(); g++) {
         const uint32_t b = cut[g], e = cut[g + 1];
         if (E.too_big[b]) continue;
@@ -151,6 +159,13 @@ int bandk::extend_tail(const char *who, dtwk::MapFront &F, const s5gpu_map_param
         A.slot_words = slot_words; A.tile_a = (int32_t *)((uint8_t *)c->d_scan.p + A.slots * ((uint64_t)slot_words * 256u));
         A.rows_out = d_rows + b; A.lo = d_lo; A.hi = d_hi;
         if ((rc = bandk::launch_band(e - b, A, c->st))) return rc;         // (the stream orders the groups: the scratch is used again)
+        if (!rp) continue;
+        refk::LongRounds X;
+        X.n = e - b; X.queries = d_q; X.first = A.first; X.qlen = A.qlen; X.total_rows = total; X.ref = F.d_ref; X.R = R; X.rows_in = d_rows + b; X.lo_in = d_lo;
+        X.hi_in = d_hi; X.row0 = first[b]; X.T = T; X.band = bp->band; X.P = *rp; X.scratch = c->d_scan.p; X.slots = A.slots; X.slot_words = slot_words;
+        X.work = dg + E.r_work; X.queries_out = (int16_t *)(dg + E.r_q); X.rows_out = (s5gpu_ext_row_t *)(dg + E.r_rows) + b; X.lo_out = (int32_t *)(dg + E.r_lo);
+        X.hi_out = (int32_t *)(dg + E.r_hi); X.fit_out = (s5gpu_fit_t *)(dg + E.r_fit) + b; X.rounds_out = (uint32_t *)(dg + E.r_rnd) + b;
+        if ((rc = refk::long_rounds(X, c->st))) return rc;
     }
     return S5GPU_OK;
 }

@@ -180,25 +180,29 @@ int pilek::add_batch_whole(const char *who, const WholeChain &W, void *d_acc, vo
     Ctx *c = F.hold.c;
     const uint32_t m = F.m;
     bandk::ExtTail E;
-    const uint8_t *hb = nullptr;
+    const uint8_t *hb = nullptr, *hrows = nullptr;
     if (m) {
         // the chain of s5gpu_extend_batch; its scratch serves as the work area afterwards (the stream orders them)
         const size_t work_bytes = (size_t)long_work(m, F.total).bytes;
         uint64_t room = 0;
-        if ((rc = bandk::extend_tail(who, F, &W.mp, &W.bp, W.scratch_max, R, false, false, ~(size_t)0, work_bytes, &room, E))) return rc;
+        if ((rc = bandk::extend_tail(who, F, &W.mp, &W.bp, W.scratch_max, R, false, false, ~(size_t)0, work_bytes, &room, E, W.refine ? &W.rp : nullptr))) return rc;
         uint8_t *dg = (uint8_t *)c->d_gather.p;
+        const size_t h_rrows = up(E.o_lo + 4ull * m, 16);                  // (refined: the rows of the rounds, behind the statuses)
         HIP_TRY(hipMemcpyAsync(c->h_out.p, dg, E.o_lo, hipMemcpyDeviceToHost, c->st));
+        if (W.refine) HIP_TRY(hipMemcpyAsync((uint8_t *)c->h_out.p + h_rrows, dg + E.r_rows, 32ull * m, hipMemcpyDeviceToHost, c->st));
         HIP_TRY(hipStreamSynchronize(c->st));
         // a read's status is its result row's, which the host has to complete for the reads that were passed over: up again, over the long
         // queries' statuses, which have served
         hb = (const uint8_t *)c->h_out.p;
         int32_t *h_st = (int32_t *)((uint8_t *)c->h_out.p + E.o_lo);
-        for (uint32_t k = 0; k < m; k++) h_st[k] = E.too_big[k] ? S5GPU_STATUS_PATH_WIDE : ((const s5gpu_ext_row_t *)hb)[k].status;
+        hrows = W.refine ? hb + h_rrows : hb;
+        for (uint32_t k = 0; k < m; k++) h_st[k] = E.too_big[k] ? S5GPU_STATUS_PATH_WIDE : ((const s5gpu_ext_row_t *)hrows)[k].status;
         HIP_TRY(hipMemcpyAsync(dg + E.o_st, h_st, 4ull * m, hipMemcpyHostToDevice, c->st));
         PileLongArgs A;
         A.n = m; A.queries = (const int16_t *)(dg + E.o_q); A.first = F.d_first; A.qlen = (const uint32_t *)(dg + E.o_ql); A.total_rows = F.total; A.ref = F.d_ref;
         A.R = R; A.lo = (const int32_t *)(dg + E.o_lo); A.hi = (const int32_t *)(dg + E.o_hi); A.status = (const int32_t *)(dg + E.o_st); A.events = F.d_rows;
         A.ev_skip = W.bp.skip; A.work = c->d_scan.p; A.acc = d_acc;
+        if (W.refine) { A.queries = (const int16_t *)(dg + E.r_q); A.lo = (const int32_t *)(dg + E.r_lo); A.hi = (const int32_t *)(dg + E.r_hi); }
         if ((rc = accum_long_checked(who, A, work_bytes, d_hist, false, c->st))) return rc;
     }
     if ((rc = launch_add_skipped(d_acc, n - m, c->st))) return rc;         // the records that were dropped
@@ -207,10 +211,26 @@ int pilek::add_batch_whole(const char *who, const WholeChain &W, void *d_acc, vo
     dtwk::scatter_rows(F, n, hb ? (const s5gpu_map_row_t *)(hb + E.o_map) : nullptr, nullptr, map_rows_out);
     std::vector<s5gpu_ext_row_t> own;
     if (!ext_rows_out) { own.resize(n); ext_rows_out = own.data(); }      // (the statuses come from the rows)
-    bandk::scatter_ext_rows(F, n, E, hb, ext_rows_out);
+    bandk::scatter_ext_rows(F, n, E, hrows, ext_rows_out);
     if (status_out) memcpy(status_out, F.status, sizeof(int32_t) * n);
     if (F.corrupt) { s5gpu_set_error("%s: at least one record is corrupt (its status is not 0; it counts in reads_skipped)", who); return S5GPU_ERR_DATA; }
     return S5GPU_OK;
+}
+
+int pilek::whole_set_refine(const char *who, WholeChain &W, const s5gpu_refine_params_t *rp) {
+    if (W.started) { s5gpu_set_error("%s: the handle has added a batch already", who); return S5GPU_ERR_ARG; }
+    if (rp && refk::check_refine_params(who, rp)) return S5GPU_ERR_ARG;
+    W.refine = rp != nullptr;
+    if (rp) W.rp = *rp;
+    return S5GPU_OK;
+}
+
+extern "C" int s5gpu_pileup_set_refine(void *handle, const s5gpu_refine_params_t *rp) {
+    const char *who = "s5gpu_pileup_set_refine";
+    Handle *h = (Handle *)handle;
+    if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
+    if (!h->whole) { s5gpu_set_error("%s: the handle is one of s5gpu_pileup_open", who); return S5GPU_ERR_ARG; }
+    return pilek::whole_set_refine(who, h->c, rp);
 }
 
 extern "C" int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
@@ -219,5 +239,6 @@ extern "C" int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void
     Handle *h = (Handle *)handle;
     if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
     if (!h->whole) { s5gpu_set_error("%s: the handle is one of s5gpu_pileup_open", who); return S5GPU_ERR_ARG; }
+    h->c.started = true;
     return pilek::add_batch_whole(who, h->c, h->d_acc, nullptr, n, rec, rec_len, rec_method, sig_method, map_rows_out, ext_rows_out, status_out);
 }

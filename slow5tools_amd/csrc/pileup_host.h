@@ -1,7 +1,7 @@
 // pileup_host.h — host code that pileup_api.hip and contrast_api.hip share (docs/codecs.md §4.22, §4.23): the checks of a ragged call, and
 // the batch of a whole-read handle, which feeds a table, a histogram or both from one run of extend's chain.
 #pragma once
-#include "band_host.h"
+#include "refine_host.h"
 #include "pileup_dev.h"
 
 namespace pilek {
@@ -17,7 +17,12 @@ struct WholeChain {
     s5gpu_band_params_t bp;
     size_t scratch_max = 0;
     std::vector<int16_t> ref;
+    bool refine = false;                                                   // §4.24: the rounds behind each group's band call; the table and the histogram
+    s5gpu_refine_params_t rp;                                              // are fed with the refined queries, paths and statuses
+    bool started = false;                                                  // a batch has been added: the parameters stay as they are
 };
+// s5gpu_pileup_set_refine and s5gpu_contrast_set_refine on the chain of a whole-read handle
+int whole_set_refine(const char *who, WholeChain &W, const s5gpu_refine_params_t *rp);
 // the checks of s5gpu_pileup_open_whole, but for the device's: a message and S5GPU_ERR_ARG
 int whole_open_check(const char *who, const s5gpu_event_params_t *ep, const s5gpu_map_params_t *mp, const s5gpu_band_params_t *bp, const int16_t *ref_host, uint32_t R);
 // s5gpu_pileup_add_batch_whole on the chain W into d_acc and, when given, d_hist

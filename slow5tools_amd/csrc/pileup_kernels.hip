@@ -24,6 +24,8 @@
 //   k_pileup_long_accum : k_pileup over a slice of the (ordered) segments, a wave per segment at a time; segments of reads whose verdict
 //                         is not V_USED are passed over; the reads are counted once each, from the verdicts
 //   k_pile_hist_accum   : the same walk into the level histograms of §4.23 (further down, with its own note)
+//   k_path_fit_long, k_fit_long_solve, k_requant_long, k_refine_long_gate, k_refine_long_round : refine over whole reads (§4.24), behind
+//                         the same plan and check passes (further down, with their own note)
 // Their rules, beside 2, 3 (per row), 5 and 6 above:
 //   7. first, qlen and status are read at [read] (first also at [read + 1]) for read < n; a read has segments only behind long_verdict:
 //      first[k] + Q + ev_skip <= first[k + 1] <= total_rows, Q <= 2^20, so queries, lo, hi at [first[k] + i] and events at
@@ -38,6 +40,7 @@
 
 #include "dev_common.h"
 #include "pileup_dev.h"
+#include "refine_dev.h"
 
 extern "C" void s5gpu_set_error(const char *fmt, ...);
 
@@ -434,7 +437,131 @@ __global__ __launch_bounds__(s5::NT) void k_pile_hist_accum(PileLongArgs A, uint
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- refine, whole reads (§4.24)
+// The fit of §4.20 along the ragged paths, behind the plan and the check above (no sort: there is no window to keep warm, the segments are
+// walked in P's order), and the bookkeeping of the rounds of s5gpu_extend_refine_dev:
+//   k_path_fit_long    : a wave per segment, each wave a slice of consecutive segments, lanes over rows.  A lane keeps its six partial sums
+//                        while the wave stays in one read; where the read changes (and at the end) the wave reduces them with shuffles and
+//                        lane 0 adds them to the read's Sums with 64-bit atomics: integers, so the bytes depend on nothing but the cells
+//   k_fit_long_solve   : a lane per read: verdict and sums -> fit and status (refk::long_fit_status)
+//   k_requant_long     : over the same segments: q' = requant_one(q0) for the rows of the reads whose fit's status is 0
+//   k_refine_long_gate : a lane per read: the status of a result row as a word of its own (what the plan and the band call read)
+//   k_refine_long_round: over the same segments the rows of q, lo and hi a read takes over (refk::long_round_rule), and a lane per read its
+//                        row, fit, rounds and status.  The statuses are read from one array and written to another: no wave reads what
+//                        another writes.
+// Rules 2, 3 (per row), 6 to 9 and 11 hold as they stand: nothing of a read is summed, requantised or copied unless its verdict is V_USED
+// behind the check pass (in round 0 that of the path that came in), so first[k] + i lies inside the ragged arrays for i < Q; ref[j] is read
+// behind j < R (row_sums); a[], b[] and the statuses are read at [read] for read < n.  No barrier, no LDS; branches on a read's fate are
+// wave-uniform, and every shuffle is executed by all 64 lanes.
 namespace {
+__device__ __forceinline__ int64_t wave_sum_i(int64_t v) { return (int64_t)wave_sum((uint64_t)v); }
+// the wave's partial sums of read `k` added to its Sums, and emptied (k = n: no read yet)
+__device__ __forceinline__ void fit_flush(refk::Sums *sums, uint32_t k, uint32_t n, refk::Sums &acc, uint32_t lane) {
+    if (k >= n) return;                                                    // (wave-uniform)
+    const int64_t cnt = wave_sum_i(acc.n), sq = wave_sum_i(acc.sq), sr = wave_sum_i(acc.sr), sqq = wave_sum_i(acc.sqq), sqr = wave_sum_i(acc.sqr),
+                  srr = wave_sum_i(acc.srr);
+    if (lane == 0 && cnt != 0) {
+        uint64_t *w = reinterpret_cast<uint64_t *>(sums + k);
+        DevOps::add64(w + 0, (uint64_t)cnt); DevOps::add64(w + 1, (uint64_t)sq); DevOps::add64(w + 2, (uint64_t)sr);
+        DevOps::add64(w + 3, (uint64_t)sqq); DevOps::add64(w + 4, (uint64_t)sqr); DevOps::add64(w + 5, (uint64_t)srr);
+    }
+    acc.n = acc.sq = acc.sr = acc.sqq = acc.sqr = acc.srr = 0;
+}
+// the slice of the segments (in P's order) of this wave
+__device__ __forceinline__ void wave_slice(const PileLongArgs &A, const LongPtrs &L, uint64_t *g, uint64_t *end) {
+    slice_of(L.P[A.n], (uint64_t)blockIdx.x * s5::NW + (threadIdx.x >> 6), (uint64_t)gridDim.x * s5::NW, g, end);
+}
+// segment g of the slice -> its read *k (from the read of the segment before) and, behind `true`, its rows [*r0, *r1)
+__device__ __forceinline__ bool wave_seg(const PileLongArgs &A, uint32_t S, const LongPtrs &L, uint64_t g, uint32_t *k, uint32_t *r0, uint32_t *r1) {
+    *k = seg_next(L.P, A.n, *k, g);
+    const uint32_t Q = A.qlen[*k], s = (uint32_t)(g - L.P[*k]);
+    if (Q > LONG_QMAX || s >= segs_of(Q, S)) return false;                 // (cannot be: P was made of these)
+    seg_rows(Q, S, s, r0, r1);
+    return true;
+}
+}  // namespace
+
+__global__ __launch_bounds__(s5::NT) void k_path_fit_long(PileLongArgs A, uint32_t S, LongPtrs L, refk::Sums *sums) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t g, end;
+    wave_slice(A, L, &g, &end);
+    uint32_t k = g < end ? seg_find(L.P, A.n, g) : 0u, held = A.n, r0, r1;
+    refk::Sums acc = {0, 0, 0, 0, 0, 0};
+    for (; g < end; g++) {
+        if (!wave_seg(A, S, L, g, &k, &r0, &r1) || L.verdict[k] != V_USED) continue;   // (the wave's branch)
+        if (k != held) { fit_flush(sums, held, A.n, acc, lane); held = k; }
+        const uint64_t f = A.first[k];
+        refk::seg_sums(r0, r1, lane, 64u, A.lo + f, A.hi + f, A.queries + f, A.ref, A.R, acc);
+    }
+    fit_flush(sums, held, A.n, acc, lane);
+}
+
+__global__ __launch_bounds__(s5::NT) void k_fit_long_solve(uint32_t n, const uint32_t *__restrict__ verdict, const refk::Sums *__restrict__ sums,
+                                                           const int32_t *__restrict__ status_in, s5gpu_refine_params_t P, s5gpu_fit_t *__restrict__ fit,
+                                                           int32_t *__restrict__ status_out) {
+    const uint64_t k = (uint64_t)blockIdx.x * s5::NT + threadIdx.x;
+    if (k < n) {
+        s5gpu_fit_t F;
+        const int32_t st = refk::long_fit_status(verdict[k], status_in[k], sums[k], P, &F);
+        fit[k] = F;
+        status_out[k] = st;
+    }
+}
+
+__global__ __launch_bounds__(s5::NT) void k_requant_long(PileLongArgs A, uint32_t S, LongPtrs L, const int32_t *__restrict__ fit_status,
+                                                         const s5gpu_fit_t *__restrict__ fit, int32_t clip, int16_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t g, end;
+    wave_slice(A, L, &g, &end);
+    uint32_t k = g < end ? seg_find(L.P, A.n, g) : 0u, r0, r1;
+    for (; g < end; g++) {
+        if (!wave_seg(A, S, L, g, &k, &r0, &r1) || L.verdict[k] != V_USED || fit_status[k] != 0) continue;   // (the wave's branch)
+        const uint64_t f = A.first[k];
+        const double a = fit[k].a, b = fit[k].b;
+        for (uint32_t i = r0 + lane; i < r1; i += 64u) out[f + i] = refk::requant_one(A.queries[f + i], a, b, clip);
+    }
+}
+
+__global__ __launch_bounds__(s5::NT) void k_refine_long_gate(uint32_t n, const s5gpu_ext_row_t *__restrict__ rows, int32_t *__restrict__ st) {
+    const uint64_t k = (uint64_t)blockIdx.x * s5::NT + threadIdx.x;
+    if (k < n) st[k] = rows[k].status;
+}
+
+__global__ __launch_bounds__(s5::NT) void k_refine_long_round(refk::RoundLongArgs B, uint32_t round, uint32_t S, LongPtrs L) {
+    const PileLongArgs &A = B.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t g, end;
+    wave_slice(A, L, &g, &end);
+    uint32_t k = g < end ? seg_find(L.P, A.n, g) : 0u, r0, r1;
+    for (; g < end; g++) {
+        if (!wave_seg(A, S, L, g, &k, &r0, &r1)) continue;                 // (the wave's branch, as those below)
+        const uint32_t v = L.verdict[k];
+        if ((v & V_SKIPPED) || (round == 0 && v != V_USED)) continue;      // (a bad path that came in: the fills hold "no result" already)
+        int32_t st;
+        const int mode = refk::long_round_rule(round, v, A.qlen[k], B.cur_in[k], round ? B.t_sf[k] : 0, round ? B.t_rows[k].status : 0, &st);
+        if (mode == 0) continue;
+        const uint64_t f = A.first[k];                                     // (the read has segments: its layout passed this round's plan)
+        for (uint32_t i = r0 + lane; i < r1; i += 64u) {
+            int16_t q = 0;
+            int32_t l = -1, h = -1;
+            if (mode == 1) { q = A.queries[f + i]; l = A.lo[f + i]; h = A.hi[f + i]; }
+            if (mode == 2) { q = B.t_q[f + i]; l = B.t_lo[f + i]; h = B.t_hi[f + i]; }
+            B.q[f + i] = q; B.lo[f + i] = l; B.hi[f + i] = h;
+        }
+    }
+    // the reads, once each
+    for (uint64_t r = (uint64_t)blockIdx.x * s5::NT + threadIdx.x; r < A.n; r += (uint64_t)gridDim.x * s5::NT) {
+        int32_t st;
+        const int mode = refk::long_round_rule(round, L.verdict[r], A.qlen[r], B.cur_in[r], round ? B.t_sf[r] : 0, round ? B.t_rows[r].status : 0, &st);
+        if (round == 0 || B.cur_in[r] == 0) B.rows[r] = refk::long_round_row(mode, st, round ? B.t_rows[r] : B.rows_in[r], B.rows[r]);
+        if (mode == 2) { B.fit[r] = B.t_fit[r]; B.rounds[r] = round; }
+        if (mode == 1 || mode == 3) { B.fit[r] = refk::fit_none(); B.rounds[r] = 0; }
+        B.cur_out[r] = st;
+    }
+}
+
+namespace {
+uint32_t g_refine_passes = 63;          // option "refine_long_passes"
 uint32_t g_hist_cols = HIST_MAX_COLS;   // option "pile_hist_cols"
 uint32_t g_hist_grid = MAX_GRID;        // option "pile_hist_grid"
 
@@ -455,7 +582,26 @@ int set_option_long(const char *key, long value) {
     // which kernels a ragged call launches: 1 the plan, 2 the check (and the sort), 4 the accumulate, over what an earlier call left in the
     // work area; 7 all (the default).  For tools/pileup_long_time.py: the passes are timed apart (as "sdtw_band_passes").
     if (strcmp(key, "pileup_long_passes") == 0 && value >= 1 && value <= 7) { g_long_passes = (uint32_t)value; return S5GPU_OK; }
+    // which kernels the whole-read fit and its rounds launch (§4.24): 1 the plan and the check, 2 the sums, 4 the solve, 8 the requantiser,
+    // 16 the bookkeeping of the rounds, 32 the band call, over what an earlier call left; 63 all (the default).  For
+    // tools/extend_refine_time.py: the passes are timed apart.
+    if (strcmp(key, "refine_long_passes") == 0 && value >= 1 && value <= 63) { g_refine_passes = (uint32_t)value; return S5GPU_OK; }
     return S5GPU_ERR_ARG;
+}
+
+// the places of a ragged call's work area
+LongPtrs long_ptrs(const PileLongArgs &A) {
+    const LongWork w = long_work(A.n, A.total_rows);
+    uint8_t *wk = (uint8_t *)A.work;
+    LongPtrs L;
+    L.verdict = (uint32_t *)(wk + w.o_verdict); L.P = (uint64_t *)(wk + w.o_prefix); L.hist = (uint32_t *)(wk + w.o_hist);
+    L.cursor = (uint32_t *)(wk + w.o_cursor); L.order = (uint64_t *)(wk + w.o_order); L.cap = long_order_cap(A.n, A.total_rows);
+    return L;
+}
+// the workgroups of a walk over the segments of a well-formed layout: four segments each at a time, `most` workgroups at most
+uint32_t long_grid(const PileLongArgs &A, uint32_t S, uint32_t most) {
+    const uint64_t segs = A.total_rows / S + A.n, quads = (segs + 3u) / 4u;
+    return (uint32_t)(quads < most ? quads : most);
 }
 }  // namespace
 
@@ -464,11 +610,7 @@ int pilek::launch_pileup_long(const PileLongArgs &A, hipStream_t st) { return la
 int pilek::launch_pileup_long(const PileLongArgs &A, void *hist, hipStream_t st) {
     if (A.n == 0) return S5GPU_OK;
     const uint32_t S = g_long_seg, cols = g_long_cols;
-    const LongWork w = long_work(A.n, A.total_rows);
-    uint8_t *wk = (uint8_t *)A.work;
-    LongPtrs L;
-    L.verdict = (uint32_t *)(wk + w.o_verdict); L.P = (uint64_t *)(wk + w.o_prefix); L.hist = (uint32_t *)(wk + w.o_hist);
-    L.cursor = (uint32_t *)(wk + w.o_cursor); L.order = (uint64_t *)(wk + w.o_order); L.cap = long_order_cap(A.n, A.total_rows);
+    const LongPtrs L = long_ptrs(A);
     // (the sort's counts are 32-bit: a list that 2^32 segments might not fit is walked in P's order)
     const uint32_t sort = g_long_sort && L.cap < ((uint64_t)1 << 32) ? 1u : 0u;
     const uint64_t most = A.total_rows / S + A.n, quads = (most + 3u) / 4u;  // the segments of a well-formed layout, at most
@@ -498,5 +640,60 @@ int pilek::launch_pileup_long(const PileLongArgs &A, void *hist, hipStream_t st)
                            reinterpret_cast<uint32_t *>(hist));
         S5_LAUNCH_CHECK("k_pile_hist_accum");
     }
+    return S5GPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- refine, whole reads (§4.24)
+
+uint32_t refk::long_passes() { return g_refine_passes; }
+
+int refk::launch_long_verdicts(const PileLongArgs &A, hipStream_t st) {
+    if (A.n == 0 || !(g_refine_passes & 1u)) return S5GPU_OK;
+    const uint32_t S = g_long_seg;
+    const LongPtrs L = long_ptrs(A);
+    hipLaunchKernelGGL(k_pileup_long_plan, dim3(1), dim3(s5::NT), 0, st, A, S, L);
+    S5_LAUNCH_CHECK("k_pileup_long_plan");
+    hipLaunchKernelGGL(k_pileup_long_check, dim3(long_grid(A, S, g_long_grid)), dim3(s5::NT), 0, st, A, S, L, 0u, 0u);
+    S5_LAUNCH_CHECK("k_pileup_long_check");
+    return S5GPU_OK;
+}
+
+int refk::launch_fit_long(const FitLongArgs &F, hipStream_t st) {
+    const PileLongArgs &A = F.A;
+    if (A.n == 0) return S5GPU_OK;
+    int rc;
+    if ((rc = launch_long_verdicts(A, st))) return rc;
+    const uint32_t S = g_long_seg, grid = long_grid(A, S, g_long_grid), per_read = (uint32_t)(((uint64_t)A.n + s5::NT - 1) / s5::NT);
+    const LongPtrs L = long_ptrs(A);
+    refk::Sums *sums = (refk::Sums *)((uint8_t *)A.work + fit_long_work(A.n, A.total_rows).o_sums);
+    if (g_refine_passes & 2u) {
+        const hipError_t e = hipMemsetAsync(sums, 0, sizeof(refk::Sums) * (size_t)A.n, st);
+        if (e != hipSuccess) { s5gpu_set_error("k_path_fit_long: the sums could not be cleared: %s", hipGetErrorString(e)); return S5GPU_ERR_HIP; }
+        hipLaunchKernelGGL(k_path_fit_long, dim3(grid), dim3(s5::NT), 0, st, A, S, L, sums);
+        S5_LAUNCH_CHECK("k_path_fit_long");
+    }
+    if (g_refine_passes & 4u) {
+        hipLaunchKernelGGL(k_fit_long_solve, dim3(per_read), dim3(s5::NT), 0, st, A.n, L.verdict, sums, A.status, F.P, F.fit, F.status_out);
+        S5_LAUNCH_CHECK("k_fit_long_solve");
+    }
+    if (F.queries_out && (g_refine_passes & 8u)) {
+        hipLaunchKernelGGL(k_requant_long, dim3(grid), dim3(s5::NT), 0, st, A, S, L, F.status_out, F.fit, F.P.clip, F.queries_out);
+        S5_LAUNCH_CHECK("k_requant_long");
+    }
+    return S5GPU_OK;
+}
+
+int refk::launch_gate_long(uint32_t n, const s5gpu_ext_row_t *rows, int32_t *st_out, hipStream_t st) {
+    if (n == 0 || !(g_refine_passes & 16u)) return S5GPU_OK;
+    hipLaunchKernelGGL(k_refine_long_gate, dim3((uint32_t)(((uint64_t)n + s5::NT - 1) / s5::NT)), dim3(s5::NT), 0, st, n, rows, st_out);
+    S5_LAUNCH_CHECK("k_refine_long_gate");
+    return S5GPU_OK;
+}
+
+int refk::launch_round_long(const RoundLongArgs &B, uint32_t round, hipStream_t st) {
+    if (B.A.n == 0 || !(g_refine_passes & 16u)) return S5GPU_OK;
+    const uint32_t S = g_long_seg;
+    hipLaunchKernelGGL(k_refine_long_round, dim3(long_grid(B.A, S, g_long_grid)), dim3(s5::NT), 0, st, B, round, S, long_ptrs(B.A));
+    S5_LAUNCH_CHECK("k_refine_long_round");
     return S5GPU_OK;
 }

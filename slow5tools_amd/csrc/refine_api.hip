@@ -1,8 +1,19 @@
 // refine_api.hip — host side of the refine calls (include/slow5gpu.h, "refine"; docs/codecs.md §4.20): argument checks and launches of
 // s5gpu_path_fit_dev and s5gpu_sdtw_window_dev, the rounds of s5gpu_refine_dev, and s5gpu_refine_batch: the chain of s5gpu_align_batch
 // (the front and the path tail of dtw_host.h) -> the rounds -> one download.
-#include "dtw_host.h"
-#include "refine_dev.h"
+#include "refine_host.h"
+
+int refk::check_refine_params(const char *who, const s5gpu_refine_params_t *p) {
+    if (!p) { s5gpu_set_error("%s: NULL refine parameters", who); return S5GPU_ERR_ARG; }
+    if (!refk::params_ok(*p)) {
+        s5gpu_set_error("%s: refine parameters a_min %g a_max %g (finite, 0 < a_min <= a_max) b_max %g (finite, >= 0) clip %d (1 .. 32767) pad %u (0 .. 65535) "
+                        "min_cells %u (>= 2) iters %u (1 .. 4)", who, p->a_min, p->a_max, p->b_max, p->clip, p->pad, p->min_cells, p->iters);
+        return S5GPU_ERR_ARG;
+    }
+    return S5GPU_OK;
+}
+
+using refk::check_refine_params;
 
 namespace {
 
@@ -11,16 +22,6 @@ int check_shape(const char *who, uint32_t qpitch, uint32_t R, uint32_t wmax, con
     int rc;
     if ((rc = dtwk::check_ref(who, R)) || (rc = dtwk::check_wmax(who, wmax))) return rc;
     if (!ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
-    return S5GPU_OK;
-}
-
-int check_refine_params(const char *who, const s5gpu_refine_params_t *p) {
-    if (!p) { s5gpu_set_error("%s: NULL refine parameters", who); return S5GPU_ERR_ARG; }
-    if (!refk::params_ok(*p)) {
-        s5gpu_set_error("%s: refine parameters a_min %g a_max %g (finite, 0 < a_min <= a_max) b_max %g (finite, >= 0) clip %d (1 .. 32767) pad %u (0 .. 65535) "
-                        "min_cells %u (>= 2) iters %u (1 .. 4)", who, p->a_min, p->a_max, p->b_max, p->clip, p->pad, p->min_cells, p->iters);
-        return S5GPU_ERR_ARG;
-    }
     return S5GPU_OK;
 }
 

@@ -8,6 +8,8 @@ not an error; cost / qlen is the only sign.
 
   queries_long_dev : event rows and their prefix -> (queries, qlen, status) on the device, ragged: read i at queries[first[i]:first[i] + qlen[i]]
   band_dev         : long queries, a reference and an anchor column per read -> (rows, lo, hi) on the device
+  fit_long_dev     : long queries, a reference, lo, hi and status as band_dev left them -> (FIT tensor, q', status) on the device (§4.24)
+  refine_long_dev  : ... and the rounds of s5gpu_extend_refine_dev -> RefinedLong(queries, rows, lo, hi, fit, rounds) on the device
   extend_dev       : a DecodedDev -> (MAP_ROW array of the prefix mapping, Extended): events, prefix queries, sDTW with the start, long
                      queries, the banded alignment from `start`
   read_extend      : records -> (map_rows, rows, first, lo, hi, events, status) through s5gpu_extend_batch
@@ -31,6 +33,7 @@ from . import map as _map
 from ._lib import REC_ZLIB, SIG_SVB_ZD, STATUS_PATH_ROW, STATUS_PATH_WIDE, STATUS_QUERY_SHORT, check  # noqa: F401  (for callers)
 from .events import DNA, RNA  # noqa: F401  (RNA: for callers)
 from .map import CLIP, MAP_ROW, QMAX, QMIN, SCALE, SKIP
+from .refine import FIT, RefineParams
 
 EXT_ROW = np.dtype([("cost", "<u8"), ("qlen", "<u4"), ("tiles", "<u4"), ("start", "<i4"), ("end", "<i4"), ("a_last", "<i4"), ("status", "<i4")])
 EVENT = _align.EVENT
@@ -41,6 +44,12 @@ S5EXTEND = os.path.join(os.path.dirname(os.path.abspath(__file__)), "s5extend")
 EMAX = 1 << 20
 TILE_ROWS, BAND = 256, 512
 Extended = collections.namedtuple("Extended", "rows first queries qlen lo hi")
+RefinedLong = collections.namedtuple("RefinedLong", "queries rows lo hi fit rounds")
+# what extend_dev returns with refine=...: Extended's fields are the refined ones, rows_first the rows of the first alignment
+ExtendedRefined = collections.namedtuple("ExtendedRefined", "rows first queries qlen lo hi rows_first fit rounds")
+# the columns s5extend --refine appends to a line (scale and shift nan, the others -1: `*`)
+EXTEND_REFINE_LINE = np.dtype(EXTEND_LINE.descr + [("scale", "<f8"), ("shift", "<f8"), ("rounds", "<i8"), ("cost_refined", "<i8"), ("ref_start_refined", "<i8"),
+                                                   ("ref_end_refined", "<i8"), ("fit", "S8")])
 
 assert EXT_ROW.itemsize == 32
 
@@ -108,14 +117,84 @@ def band_dev(queries, first, qlen, ref_tensor, anchor, status=None, params=None,
     return rows[:n], lo[:total], hi[:total]
 
 
+def _refine_params(refine):
+    """None: no refinement; True: the defaults; else an s5gpu_refine_params_t (refine.RefineParams(...))"""
+    return None if refine is None or refine is False else RefineParams() if refine is True else refine
+
+
+def fit_long_dev(queries, first, qlen, ref_tensor, lo, hi, status=None, params=None, want_queries=True):
+    """k_path_fit_long, k_fit_long_solve and k_requant_long behind the plan and check passes of the whole-read pileup -> (fit, queries',
+    status'): fit an [n, 8] int64 tensor whose rows are FIT records (fit.cpu().numpy().view(FIT)), queries' [total_rows] int16 (q' at the rows
+    of the reads whose status' is 0, zeros elsewhere; None without want_queries), status' [n] int32.  Asynchronous, on the current stream."""
+    import torch
+
+    if queries.dtype != torch.int16 or ref_tensor.dtype != torch.int16 or queries.dim() != 1 or ref_tensor.dim() != 1:
+        raise ValueError("fit_long_dev: queries [total_rows] and ref_tensor [R] are int16 tensors")
+    n, total, dev = int(first.numel()) - 1, int(queries.numel()), queries.device
+    p = params if params is not None else RefineParams()
+    queries, first, ref_tensor = queries.contiguous(), first.contiguous(), ref_tensor.contiguous()
+    qlen, lo, hi = qlen.to(torch.int32).contiguous(), lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if status is None else status.to(torch.int32).contiguous()
+    wb = int(_lib.lib().s5gpu_path_fit_long_work_bytes(n, total))
+    work = torch.empty(max(wb, 16) // 8 + 2, dtype=torch.int64, device=dev)
+    fit = torch.zeros((max(n, 1), 8), dtype=torch.int64, device=dev)
+    q1 = torch.zeros(max(total, 1), dtype=torch.int16, device=dev) if want_queries else None
+    st = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    check(_lib.lib().s5gpu_path_fit_long_dev(n, queries.data_ptr() if total else None, first.data_ptr(), qlen.data_ptr(), total,
+                                             ref_tensor.data_ptr() if ref_tensor.numel() else None, int(ref_tensor.numel()), lo.data_ptr() if total else None,
+                                             hi.data_ptr() if total else None, status.data_ptr(), C.byref(p), work.data_ptr(), wb, fit.data_ptr(),
+                                             q1.data_ptr() if want_queries else None, st.data_ptr(),
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_path_fit_long_dev")
+    for t in (queries, first, ref_tensor, qlen, lo, hi, status, work):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return fit[:n], (q1[:total] if want_queries else None), st[:n]
+
+
+def refine_long_dev(queries, first, qlen, ref_tensor, rows, lo, hi, band_params=None, params=None, scratch_bytes_=None):
+    """s5gpu_extend_refine_dev on what band_dev left on the device -> RefinedLong(queries, rows, lo, hi, fit, rounds), all on the device:
+    queries [total_rows] int16, rows [n, 4] int64 (EXT_ROW records; a read's status is its row's), lo and hi [total_rows] int32, fit
+    [n, 8] int64 (FIT records), rounds [n] int32.  band_params: the BandParams of the band call (tile_rows and band count).
+    scratch_bytes_ (for tests): the size the call is told instead of what it needs.  Asynchronous, on the current stream."""
+    import torch
+
+    if queries.dtype != torch.int16 or ref_tensor.dtype != torch.int16 or queries.dim() != 1 or ref_tensor.dim() != 1:
+        raise ValueError("refine_long_dev: queries [total_rows] and ref_tensor [R] are int16 tensors")
+    n, total, dev = int(first.numel()) - 1, int(queries.numel()), queries.device
+    bp = band_params if band_params is not None else BandParams()
+    p = params if params is not None else RefineParams()
+    queries, first, ref_tensor, rows = queries.contiguous(), first.contiguous(), ref_tensor.contiguous(), rows.contiguous()
+    qlen, lo, hi = qlen.to(torch.int32).contiguous(), lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+    need = scratch_bytes(n, total, bp.tile_rows, bp.band)
+    sb = need if scratch_bytes_ is None else int(scratch_bytes_)
+    scratch = torch.empty(max(need, 16) // 4 + 4, dtype=torch.int32, device=dev)
+    wb = int(_lib.lib().s5gpu_extend_refine_work_bytes(n, total))
+    work = torch.empty(max(wb, 16) // 8 + 2, dtype=torch.int64, device=dev)
+    q1 = torch.zeros(max(total, 1), dtype=torch.int16, device=dev)
+    rows1 = torch.zeros((max(n, 1), 4), dtype=torch.int64, device=dev)
+    lo1 = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+    hi1 = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+    fit = torch.zeros((max(n, 1), 8), dtype=torch.int64, device=dev)
+    rounds = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    check(_lib.lib().s5gpu_extend_refine_dev(n, queries.data_ptr() if total else None, first.data_ptr(), qlen.data_ptr(), total,
+                                             ref_tensor.data_ptr() if ref_tensor.numel() else None, int(ref_tensor.numel()), rows.data_ptr(),
+                                             lo.data_ptr() if total else None, hi.data_ptr() if total else None, C.byref(bp), C.byref(p), scratch.data_ptr(), sb,
+                                             work.data_ptr(), wb, q1.data_ptr(), rows1.data_ptr(), lo1.data_ptr(), hi1.data_ptr(), fit.data_ptr(),
+                                             rounds.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "s5gpu_extend_refine_dev")
+    for t in (queries, first, ref_tensor, rows, qlen, lo, hi, scratch, work):
+        t.record_stream(torch.cuda.current_stream(dev))
+    return RefinedLong(q1[:total], rows1[:n], lo1[:total], hi1[:total], fit[:n], rounds[:n])
+
+
 def extend_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=EMAX, tile_rows=TILE_ROWS, band=BAND, host=True,
-               events=None):
+               events=None, refine=None):
     """events, the prefix queries, sDTW with the start, the long queries and the banded alignment from `start`, on what
     press.decode_to_device left on the device -> (MAP_ROW array of the prefix mapping, Extended(rows, first, queries, qlen, lo, hi)).
     host=True: numpy arrays (rows an EXT_ROW array, first uint64); False: the device tensors, and the prefix rows as an [n, 4] int32 tensor.
     ref: the quantised reference, an int16 numpy array or a device tensor.  The prefix query is rows [skip, skip + qmax) of a read, at least
     qmin of them; the long query rows [skip, skip + emax), with the same skip, scale and clip.  events: the (rows, first) that
-    events.events_dev(dec, event_params, "raw") returned, for a caller that has them already."""
+    events.events_dev(dec, event_params, "raw") returned, for a caller that has them already.  refine (None; True: the defaults; or
+    refine.RefineParams(...)): the rounds of refine_long_dev follow, and an ExtendedRefined comes back in Extended's place: rows, queries, lo
+    and hi are the refined ones, rows_first the rows of the first alignment, fit a FIT array and rounds [n] (§4.24)."""
     import torch
 
     ev, first = _events.events_dev(dec, event_params, "raw") if events is None else events
@@ -127,6 +206,15 @@ def extend_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scal
     p = BandParams(skip, qmin, emax, tile_rows, band, clip, scale)
     lq, lql, lst = queries_long_dev(ev, first, st, p)
     rows, lo, hi = band_dev(lq, first, lql, r, out[:, 2], lst, p)
+    rp = _refine_params(refine)
+    if rp is not None:
+        x = refine_long_dev(lq, first, lql, r, rows, lo, hi, p, rp)
+        if not host:
+            return out, ExtendedRefined(x.rows, first, x.queries, lql, x.lo, x.hi, rows, x.fit, x.rounds)
+        return out.cpu().numpy().view(MAP_ROW).reshape(-1).copy(), ExtendedRefined(
+            x.rows.cpu().numpy().view(EXT_ROW).reshape(-1).copy(), first.cpu().numpy().astype(np.uint64), x.queries.cpu().numpy(), lql.cpu().numpy(),
+            x.lo.cpu().numpy(), x.hi.cpu().numpy(), rows.cpu().numpy().view(EXT_ROW).reshape(-1).copy(), x.fit.cpu().numpy().view(FIT).reshape(-1).copy(),
+            x.rounds.cpu().numpy())
     if not host:
         return out, Extended(rows, first, lq, lql, lo, hi)
     return out.cpu().numpy().view(MAP_ROW).reshape(-1).copy(), Extended(rows.cpu().numpy().view(EXT_ROW).reshape(-1).copy(),
@@ -135,12 +223,15 @@ def extend_dev(dec, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scal
 
 
 def read_extend(records, ref, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP,
-                emax=EMAX, tile_rows=TILE_ROWS, band=BAND, scratch_max=0, raise_on_error=True):
+                emax=EMAX, tile_rows=TILE_ROWS, band=BAND, scratch_max=0, raise_on_error=True, refine=None):
     """A batch of records (bytes without the u64 prefix) against the quantised reference `ref` (int16) through s5gpu_extend_batch ->
     (map_rows, rows, first, lo, hi, events, status): a MAP_ROW array (the prefix mapping), an EXT_ROW array, the [n + 1] uint64 prefix of
     rows["qlen"], and ragged along it lo, hi (int32) and the query's event rows (EVENT); status [n] int32.  scratch_max: the bytes of scratch
-    a group of reads may use (0: 1 GiB).  A corrupt record raises; with raise_on_error=False it has its status and empty outputs."""
+    a group of reads may use (0: 1 GiB).  A corrupt record raises; with raise_on_error=False it has its status and empty outputs.
+    refine (as in extend_dev): through s5gpu_extend_refine_batch -> (map_rows, rows, first, lo, hi, events, status, rows_first, queries, fit,
+    rounds): rows, first, lo and hi are the refined ones, queries the refined long queries laid out as lo."""
     L = _lib.lib()
+    rp = _refine_params(refine)
     n = len(records)
     ep, mp = _events._params(event_params), _map._params(skip, qmax, qmin, scale, clip, True)
     bp = BandParams(skip, qmin, emax, tile_rows, band, clip, scale)
@@ -155,6 +246,16 @@ def read_extend(records, ref, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, event_
     cap = max(sum(len(x) for x in rb) // 16, 64)
     for _ in range(2):
         lo, hi, ev = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=EVENT)
+        if rp is not None:
+            rows_first, q1, fit, rounds = np.zeros(n, dtype=EXT_ROW), np.zeros(cap, dtype=np.int16), np.zeros(n, dtype=FIT), np.zeros(n, dtype=np.uint32)
+            rc = L.s5gpu_extend_refine_batch(n, rec_p, rl, rec_method, sig_method, C.byref(ep), C.byref(mp), C.byref(bp), C.byref(rp), int(scratch_max),
+                                             r.ctypes.data_as(vp), len(r), map_rows.ctypes.data_as(vp), rows_first.ctypes.data_as(vp), rows.ctypes.data_as(vp),
+                                             first.ctypes.data_as(vp), lo.ctypes.data_as(vp), hi.ctypes.data_as(vp), ev.ctypes.data_as(vp), q1.ctypes.data_as(vp),
+                                             cap, fit.ctypes.data_as(vp), rounds.ctypes.data_as(vp), status.ctypes.data_as(vp))
+            if rc != -3 or int(first[0]) <= cap:
+                break
+            cap = int(first[0])
+            continue
         rc = L.s5gpu_extend_batch(n, rec_p, rl, rec_method, sig_method, C.byref(ep), C.byref(mp), C.byref(bp), int(scratch_max), r.ctypes.data_as(vp), len(r),
                                   map_rows.ctypes.data_as(vp), rows.ctypes.data_as(vp), first.ctypes.data_as(vp), lo.ctypes.data_as(vp), hi.ctypes.data_as(vp),
                                   ev.ctypes.data_as(vp), cap, status.ctypes.data_as(vp))
@@ -162,20 +263,27 @@ def read_extend(records, ref, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, event_
             break
         cap = int(first[0])                                                # S5GPU_ERR_NOMEM: first[0] = the rows that suffice
     if rc != 0 and (raise_on_error or rc != -5):
-        check(rc, "s5gpu_extend_batch")
+        check(rc, "s5gpu_extend_batch" if rp is None else "s5gpu_extend_refine_batch")
     t = int(first[n])
+    if rp is not None:
+        return map_rows, rows, first, lo[:t].copy(), hi[:t].copy(), ev[:t].copy(), status, rows_first, q1[:t].copy(), fit, rounds
     return map_rows, rows, first, lo[:t].copy(), hi[:t].copy(), ev[:t].copy(), status
 
 
-def file_extend(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, emax=None, tile_rows=None, band=None, raise_on_corrupt=True):
+def file_extend(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, emax=None, tile_rows=None, band=None, raise_on_corrupt=True,
+                refine=False, iters=None, slope=None):
     """(ids, lines) of a .blow5 file against the levels of ref_path (one number per line), the reads in file order: ids a list of bytes,
     lines an EXTEND_LINE array.  Runs the s5extend tool (examples/s5extend.c), `batch` records per device call.  A corrupt record raises;
-    with raise_on_corrupt=False it is left out."""
+    with raise_on_corrupt=False it is left out.  refine=True: `s5extend --refine` (iters: --iters N; slope: --slope LO,HI as a pair), and
+    lines is an EXTEND_REFINE_LINE array."""
     if not os.path.exists(S5EXTEND):
         _build.build()
     cmd = [S5EXTEND, "-K", str(int(batch)), "--skip", str(int(skip)), "--events", str(int(qmax)), "--min-events", str(int(qmin))]
     cmd += (["--rna"] if rna else []) + (["--max-events", str(int(emax))] if emax is not None else [])
     cmd += (["--tile", str(int(tile_rows))] if tile_rows is not None else []) + (["--band", str(int(band))] if band is not None else [])
+    if refine:
+        cmd += ["--refine"] + (["--iters", str(int(iters))] if iters is not None else [])
+        cmd += ["--slope", "%.17g,%.17g" % (float(slope[0]), float(slope[1]))] if slope is not None else []
     p = subprocess.run(cmd + [os.fspath(ref_path), os.fspath(path)], capture_output=True)
     if p.returncode != 0 and (raise_on_corrupt or p.returncode != 1):
         raise _lib.S5GpuError("s5extend %s failed (exit %d): %s" % (path, p.returncode, p.stderr.decode(errors="replace").strip()))
@@ -187,5 +295,8 @@ def file_extend(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmi
         if ln:
             f = ln.split(b"\t")
             ids.append(f[0])
-            lines.append((num(f[1]), num(f[2]), num(f[3], float, np.nan), num(f[4]), num(f[5]), num(f[6]), num(f[7])))
-    return ids, np.array(lines, dtype=EXTEND_LINE).reshape(-1)
+            line = (num(f[1]), num(f[2]), num(f[3], float, np.nan), num(f[4]), num(f[5]), num(f[6]), num(f[7]))
+            if refine:
+                line += (num(f[8], float, np.nan), num(f[9], float, np.nan), num(f[10]), num(f[11]), num(f[12]), num(f[13]), f[14])
+            lines.append(line)
+    return ids, np.array(lines, dtype=EXTEND_REFINE_LINE if refine else EXTEND_LINE).reshape(-1)

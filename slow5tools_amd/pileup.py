@@ -171,16 +171,17 @@ def accum_long_dev(queries, first, qlen, ref_tensor, lo, hi, status, acc, events
 
 
 def pileup_whole_dev(dec, ref, acc, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX,
-                     tile_rows=_extend.TILE_ROWS, band=_extend.BAND):
+                     tile_rows=_extend.TILE_ROWS, band=_extend.BAND, refine=None):
     """extend.extend_dev(host=False) on what press.decode_to_device left on the device, then accum_long_dev of all of every read's rows into
     acc; nothing comes to the host.  Returns (acc, status, ext_rows): the [n] int32 statuses of the reads (0: the read was offered to the
-    table) and the [n, 4] int64 tensor of EXT_ROW records, both on the device."""
+    table) and the [n, 4] int64 tensor of EXT_ROW records, both on the device.  refine (as in extend.extend_dev): the table is fed with the
+    refined queries, paths and statuses, and ext_rows are the refined rows (§4.24)."""
     import torch
 
     ev, first = _events.events_dev(dec, event_params, "raw")               # (kept: the samples of a row are its event's length)
     r = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.int16))
     r = r.to(dec.dev)
-    _, x = _extend.extend_dev(dec, r, event_params, skip, qmax, qmin, scale, clip, emax, tile_rows, band, host=False, events=(ev, first))
+    _, x = _extend.extend_dev(dec, r, event_params, skip, qmax, qmin, scale, clip, emax, tile_rows, band, host=False, events=(ev, first), refine=refine)
     st = (x.rows[:, 3] >> 32).to(torch.int32)                              # EXT_ROW.status
     accum_long_dev(x.queries, x.first, x.qlen, r, x.lo, x.hi, st, acc, ev, skip)
     return acc, st, x.rows
@@ -241,7 +242,7 @@ class PileupWhole(Pileup):
     mapping, EXT_ROW array, status).  close, abandon and the context manager are Pileup's."""
 
     def __init__(self, ref, event_params=DNA, skip=SKIP, qmax=QMAX, qmin=QMIN, scale=SCALE, clip=CLIP, emax=_extend.EMAX, tile_rows=_extend.TILE_ROWS,
-                 band=_extend.BAND, scratch_max=0):
+                 band=_extend.BAND, scratch_max=0, refine=None):
         r = np.ascontiguousarray(ref, dtype=np.int16)
         ep, mp = _events._params(event_params), _map._params(skip, qmax, qmin, scale, clip, True)
         bp = _extend.BandParams(skip, qmin, emax, tile_rows, band, clip, scale)
@@ -249,6 +250,12 @@ class PileupWhole(Pileup):
         self._h = _lib.lib().s5gpu_pileup_open_whole(C.byref(ep), C.byref(mp), C.byref(bp), int(scratch_max), r.ctypes.data_as(C.c_void_p), len(r))
         if not self._h:
             raise _lib.S5GpuError("s5gpu_pileup_open_whole failed: %s" % _lib.lib().s5gpu_last_error().decode(errors="replace"))
+        rp = _extend._refine_params(refine)                                # (§4.24: the rows add() returns are then the refined ones)
+        if rp is not None:
+            rc = _lib.lib().s5gpu_pileup_set_refine(self._h, C.byref(rp))
+            if rc != 0:
+                self.abandon()
+                check(rc, "s5gpu_pileup_set_refine")
 
     def add(self, records, rec_method=REC_ZLIB, sig_method=SIG_SVB_ZD, raise_on_error=True):
         if self._h is None:
@@ -268,11 +275,11 @@ class PileupWhole(Pileup):
 
 
 def file_pileup(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmin=QMIN, wmax=None, min_depth=1, raise_on_corrupt=True, whole=False, emax=None,
-                tile_rows=None, band=None):
+                tile_rows=None, band=None, refine=False, iters=None, slope=None):
     """The table of a .blow5 file against the levels of ref_path (one number per line) as a PILE_LINE array, a row per reference position of
     depth >= min_depth.  Runs the s5pileup tool (examples/s5pileup.c), `batch` records per device call.  A corrupt record raises; with
     raise_on_corrupt=False it is left out.  whole=True: the table of whole reads (--whole), with emax, tile_rows and band as in
-    extend.file_extend; wmax does not count then."""
+    extend.file_extend; wmax does not count then.  refine=True (with whole): --refine, with iters and slope as in extend.file_extend."""
     if not os.path.exists(S5PILEUP):
         _build.build()
     cmd = [S5PILEUP, "-K", str(int(batch)), "--skip", str(int(skip)), "--events", str(int(qmax)), "--min-events", str(int(qmin)), "--min-depth", str(int(min_depth))]
@@ -280,6 +287,9 @@ def file_pileup(path, ref_path, batch=4096, rna=False, skip=SKIP, qmax=QMAX, qmi
     if whole:
         cmd += ["--whole"] + (["--max-events", str(int(emax))] if emax is not None else [])
         cmd += (["--tile", str(int(tile_rows))] if tile_rows is not None else []) + (["--band", str(int(band))] if band is not None else [])
+    if refine:
+        cmd += ["--refine"] + (["--iters", str(int(iters))] if iters is not None else [])
+        cmd += ["--slope", "%.17g,%.17g" % (float(slope[0]), float(slope[1]))] if slope is not None else []
     cmd += [os.fspath(ref_path), os.fspath(path)]
     p = subprocess.run(cmd, capture_output=True)
     if p.returncode != 0 and (raise_on_corrupt or p.returncode != 1):
