@@ -1,12 +1,21 @@
-// contrast_kernels.hip — the level histograms' reset and the comparison of two of them, column by column (docs/codecs.md §4.23).  The
-// accumulate kernel, k_pile_hist_accum, stands beside k_pileup_long_accum in pileup_kernels.hip: it walks the same segment list.
+// contrast_kernels.hip — the level histograms (docs/codecs.md §4.23): their reset, the accumulate kernel, and the comparison of two of them,
+// column by column.
 //   k_pile_hist_reset : zeros and the head
+//   k_pile_hist_accum : k_pileup_long_accum's walk (ragged_dev.h) over the same (ordered) segments and verdicts, which launch_pileup_long
+//                       (pileup_kernels.hip) leaves in the work area, into R columns of 64 32-bit bins: a wave per segment at a time, lanes
+//                       over rows, one add per cell.  The window is `cols` columns of 256 bytes in LDS (32-bit LDS adds), flushed word by word
+//                       at the end; cells outside it are 32-bit global atomic adds.  Rules 2, 3, 5 and 6 of pileup_kernels.hip and 7 to 11 of
+//                       ragged_dev.h hold as they stand; the bin is clamped below 64 (hist_bin) and masked where it indexes (hist_col_add);
+//                       q0 and shift are read from the head the reset wrote, the shift clamped.
 //   k_pile_contrast   : a wave per column at a time, a lane per bin: the two columns loaded (256 bytes each, coalesced), one wave scan for the
 //                       prefix sums cA, cB, the 64-bit products cA nB and cB nA, and a wave reduction each for the largest difference (with
 //                       its smallest bin), the overlap's sum and the two medians (a ballot).  Lane 0 writes the row as five 64-bit words.
 // All integer: for nA, nB < 2^31 every product is below 2^62 and the sum of the overlap at most nA nB; above that S5GPU_CONTRAST_BIG is set
-// instead.  Values read from memory form no address here: a column is table[j] behind j < R, R an argument; the heads are compared on the
-// device, and where they disagree (with each other or with R) no column is read at all.  No barrier, vector stores only, no inline assembly.
+// instead.  In k_pile_contrast values read from memory form no address: a column is table[j] behind j < R, R an argument; the heads are
+// compared on the device, and where they disagree (with each other or with R) no column is read at all.  No barrier there, vector stores
+// only, no inline assembly.
+#include <string.h>
+
 #include "dev_common.h"
 #include "pileup_dev.h"
 
@@ -31,6 +40,42 @@ __global__ void k_pile_hist_add_skipped(uint64_t *hist, uint32_t k) {
 }
 
 namespace {
+uint32_t g_hist_cols = HIST_MAX_COLS;   // option "pile_hist_cols"
+uint32_t g_hist_grid = MAX_GRID;        // option "pile_hist_grid"
+
+struct HistOps {
+    static __device__ __forceinline__ void add32(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+    static __device__ __forceinline__ void add32_win(uint32_t *p, uint32_t v) { atomicAdd(p, v); }   // (a pointer into LDS: a ds add)
+};
+}  // namespace
+
+// per workgroup a slice of the (ordered) segments, a wave per segment at a time; cols: the window's columns, 0 or a power of two
+__global__ __launch_bounds__(s5::NT) void k_pile_hist_accum(PileLongArgs A, uint32_t S, LongPtrs L, uint32_t sort, uint32_t cols, uint32_t *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t hist_win[];    // cols columns of HIST_BINS words: all of the 64 KB at cols = 256
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t t = threadIdx.x; t < cols * HIST_BINS; t += s5::NT) hist_win[t] = 0u;
+    const GroupSlice G = group_slice(A, L, sort);
+    Window W;
+    const uint32_t l0 = cols ? group_anchor(A, S, L, G, 0u, s5::NW) : ANCHOR_NONE;
+    W.lo = l0 == ANCHOR_NONE ? 0u : l0;
+    W.cols = cols;
+    const int32_t q0 = (int32_t)hist[9];                                   // s5gpu_pile_hist_head_t::q0, ::shift (32-bit words 9 and 10): written by the reset only
+    const uint32_t shift = hist[10];
+    uint32_t *table = hist + HIST_HEAD_WORDS;
+    __syncthreads();
+    uint64_t cells = 0;                                                    // this lane's
+    walk_by_group(A, S, L, G, [&](const Seg &g) {
+        const uint64_t f = A.first[g.k];                                   // (loaded beside the verdict: rule 7, k < n)
+        if (L.verdict[g.k] != V_USED) return;                              // (the wave's branch)
+        hist_seg_cells<HistOps>(g.r0, g.r1, lane, 64u, A.lo + f, A.hi + f, A.queries + f, q0, shift, A.R, W, hist_win, table, &cells);
+    });
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < cols * HIST_BINS; t += s5::NT) hist_flush_word<HistOps>(t, W, hist_win, table, A.R);
+    const ReadCounts c = verdict_counts(L.verdict, A.n);
+    head_add(reinterpret_cast<uint64_t *>(hist), {wave_sum(cells), c.used, c.skipped, c.bad});
+}
+
+namespace {
 
 __device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v, uint32_t lane) {
 #pragma unroll
@@ -38,11 +83,6 @@ __device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v, uint32_t lane) {
         const uint64_t t = __shfl_up(v, d);
         if (lane >= (uint32_t)d) v += t;
     }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
     return v;
 }
 // the smallest lane whose flag is set (one is: lane 63's)
@@ -86,7 +126,7 @@ __global__ __launch_bounds__(s5::NT) void k_pile_contrast(const uint32_t *__rest
             ks_bin = at & 63u;
             if (at & 64u) flags |= S5GPU_CONTRAST_A_LOWER;
             const uint64_t ma = a * nb, mb = b * na;
-            ov = wave_sum64(ma < mb ? ma : mb);
+            ov = wave_sum(ma < mb ? ma : mb);
         }
         const uint32_t med_a = first_lane(2u * ca >= na), med_b = first_lane(2u * cb >= nb);
         uint32_t depth_a = 0, depth_b = 0;
@@ -112,6 +152,25 @@ int pilek::launch_hist_reset(void *hist, uint32_t R, int32_t q0, uint32_t shift,
     const uint64_t words = HIST_HEAD_WORDS + (uint64_t)HIST_BINS * R, blocks = (words + s5::NT - 1) / s5::NT;
     hipLaunchKernelGGL(k_pile_hist_reset, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(s5::NT), 0, st, reinterpret_cast<uint32_t *>(hist), R, q0, shift);
     S5_LAUNCH_CHECK("k_pile_hist_reset");
+    return S5GPU_OK;
+}
+
+int pilek::hist_set_option(const char *key, long value) {
+    if (!key) return S5GPU_ERR_ARG;
+    const bool pow2 = value > 0 && (value & (value - 1)) == 0;
+    if (strcmp(key, "pile_hist_cols") == 0 && (value == 0 || (pow2 && value >= (long)HIST_MIN_COLS && value <= (long)HIST_MAX_COLS))) {
+        g_hist_cols = (uint32_t)value;
+        return S5GPU_OK;
+    }
+    if (strcmp(key, "pile_hist_grid") == 0 && value >= 1 && value <= (long)MAX_GRID) { g_hist_grid = (uint32_t)value; return S5GPU_OK; }
+    return S5GPU_ERR_ARG;
+}
+
+int pilek::launch_hist_accum(const PileLongArgs &A, uint32_t S, const LongPtrs &L, uint32_t sort, void *hist, hipStream_t st) {
+    const uint32_t cols = g_hist_cols;
+    hipLaunchKernelGGL(k_pile_hist_accum, dim3(long_grid(A, S, g_hist_grid)), dim3(s5::NT), (size_t)cols * HIST_BINS * sizeof(uint32_t), st, A, S, L, sort, cols,
+                       reinterpret_cast<uint32_t *>(hist));
+    S5_LAUNCH_CHECK("k_pile_hist_accum");
     return S5GPU_OK;
 }
 

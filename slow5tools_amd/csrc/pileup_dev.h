@@ -1,15 +1,11 @@
 // pileup_dev.h — what pileup_kernels.hip and pileup_api.hip share (docs/codecs.md §4.18): the validation of a read's path, the cells of one
-// query row added to a column table, the window of columns a workgroup keeps in LDS, and the launchers.
-// With S5_PILEUP_HOST defined only the plain C++ is declared (the switch of dtw_dev.h): tests/test_pileup.py and tests/test_pileup_long.py
-// compile it for the CPU and run the very code a lane runs, with plain adds in place of the atomics, against the restatements, without a
-// device.
+// query row added to a column table, the window of columns a workgroup keeps in LDS, the level histograms of §4.23, and the launchers.  The
+// ragged layout of whole reads (§4.22), row_ok and the PILE_HD / S5_PILEUP_HOST switch come with ragged_dev.h.
+// With S5_PILEUP_HOST defined only the plain C++ is declared (the switch of dtw_dev.h): tests/test_pileup.py, tests/test_pileup_long.py and
+// tests/test_contrast.py compile it for the CPU and run the very code a lane runs, with plain adds in place of the atomics, against the
+// restatements, without a device.
 #pragma once
-#if defined(S5_PILEUP_HOST) && !defined(S5_DTW_HOST)
-#define S5_DTW_HOST
-#endif
-#include "dtw_dev.h"
-
-#define PILE_HD DTW_HD
+#include "ragged_dev.h"
 
 namespace pilek {
 
@@ -22,15 +18,6 @@ constexpr uint32_t HEAD_WORDS = 8, COL_WORDS = 6;    // 64-bit words of the tota
 constexpr uint64_t EMPTY_MINMAX = (uint64_t)32767u | ((uint64_t)(uint32_t)-32768 << 32);   // word 5 of an empty column: min_q | max_q
 
 static_assert(sizeof(s5gpu_pile_col_t) == 8 * COL_WORDS && sizeof(s5gpu_pile_total_t) == 8 * HEAD_WORDS, "include/slow5gpu.h fixes these layouts");
-
-// Row i of a read: 0 <= lo <= hi < R, and behind row 0 lo - hi_prev in {0, 1} (hi_prev = hi[i - 1]: whatever it holds, its own row's check
-// decides on it; the difference is taken in 64 bits).  A read is used iff every row i < Q passes.
-PILE_HD bool row_ok(uint32_t i, int32_t lo, int32_t hi, int32_t hi_prev, uint32_t R) {
-    if (lo < 0 || lo > hi || (uint32_t)hi >= R) return false;
-    if (i == 0) return true;
-    const int64_t d = (int64_t)lo - (int64_t)hi_prev;
-    return d == 0 || d == 1;
-}
 
 // The window: columns [lo, lo + cols) live in a table of their own (LDS on the device), cols 0 or a power of two.  -> is column j inside,
 // and its slot there: the index is masked behind the range test, so it is inside the table whatever j is.
@@ -88,77 +75,12 @@ PILE_HD void row_cells(uint32_t i, int32_t lo, int32_t hi, int32_t hi_prev, int3
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- whole reads (§4.22)
-// The ragged layout of s5gpu_sdtw_band_dev: read k's rows at [first[k], first[k] + qlen[k]) of queries, lo and hi.  The unit of work is a
-// segment of S consecutive rows of one read.  A read's verdict is a word: 0 used (so far), SKIPPED, or BAD (ORed in by any of its segments).
-constexpr uint32_t LONG_QMAX = 1u << 20;     // rows of the longest read (bandk::EMAX)
-constexpr uint32_t SEG_MIN = 64, SEG_MAX = 1024;
-constexpr uint32_t LONG_KEYS = 1024;         // buckets of the segments' counting sort
-constexpr uint64_t LONG_ROWS_MAX = (uint64_t)1 << 40;
-constexpr uint32_t V_USED = 0, V_SKIPPED = 1, V_BAD = 2;
-
-// the layout checks of read k: f0 = first[k], f1 = first[k + 1].  Behind V_USED every row i < Q of the read, and its event row
-// first[k] + ev_skip + i, lies inside [0, total_rows).
-PILE_HD uint32_t long_verdict(uint64_t f0, uint64_t f1, uint32_t Q, int32_t status, uint64_t total_rows, uint32_t ev_skip) {
-    if (status != 0 || Q == 0) return V_SKIPPED;
-    if (Q > LONG_QMAX || f0 > f1 || f1 > total_rows || (uint64_t)Q + ev_skip > f1 - f0) return V_BAD;
-    return V_USED;
-}
-PILE_HD uint32_t segs_of(uint32_t Q, uint32_t S) { return (Q + S - 1u) / S; }          // (Q <= 2^20)
-// the rows [*r0, *r1) of segment s < segs_of(Q, S)
-PILE_HD void seg_rows(uint32_t Q, uint32_t S, uint32_t s, uint32_t *r0, uint32_t *r1) {
-    *r0 = s * S;
-    *r1 = Q - *r0 < S ? Q : *r0 + S;
-}
-// The segments are numbered along P, the [n + 1] exclusive prefix of the reads' segments (none for a read that is not V_USED after the
-// layout checks): segment g < P[n] belongs to the one read k with P[k] <= g < P[k + 1], as its segment g - P[k].  At most 32 trips.
-PILE_HD uint32_t seg_find(const uint64_t *P, uint32_t n, uint64_t g) {
-    uint32_t a = 0, b = n;
-    for (uint32_t t = 0; t < 32u && b - a > 1u; t++) {
-        const uint32_t mid = a + (b - a) / 2u;
-        if (P[mid] <= g) a = mid; else b = mid;
-    }
-    return a;
-}
-// ... and from a read k0 at or before it: at most n trips
-PILE_HD uint32_t seg_next(const uint64_t *P, uint32_t n, uint32_t k0, uint64_t g) {
-    uint32_t k = k0;
-    while (k + 1u < n && P[k + 1u] <= g) k++;
-    return k;
-}
-// the bucket of a segment whose first row starts at column lo0 (unvalidated: the key is clamped and orders the work, nothing else)
-PILE_HD uint32_t seg_key(int32_t lo0, uint32_t R) {
-    const uint32_t block = (R + LONG_KEYS - 1u) / LONG_KEYS;               // >= 1
-    const uint32_t key = lo0 < 0 ? 0u : (uint32_t)lo0 / block;
-    return key < LONG_KEYS ? key : LONG_KEYS - 1u;
-}
-// Rows r0 + lane, r0 + lane + step, ... < r1 of a read whose lo, hi (and q, ev) point at ITS row 0: hi_prev of a row is the row before it in
-// the ragged array, whichever segment that lies in.  On the device lane < step = 64; on the host (0, 1).
-PILE_HD bool seg_rows_ok(uint32_t r0, uint32_t r1, uint32_t lane, uint32_t step, const int32_t *lo, const int32_t *hi, uint32_t R) {
-    bool ok = true;
-    for (uint32_t i = r0 + lane; i < r1; i += step) ok = ok && row_ok(i, lo[i], hi[i], i ? hi[i - 1] : 0, R);
-    return ok;
-}
+// the rows of a segment of a whole read (ragged_dev.h, §4.22), as seg_rows_ok walks them
 template <class Ops>
 PILE_HD void seg_cells(uint32_t r0, uint32_t r1, uint32_t lane, uint32_t step, const int32_t *lo, const int32_t *hi, const int16_t *q, const s5gpu_event_t *ev,
                        const int16_t *ref, uint32_t R, const Window &W, s5gpu_pile_col_t *win, s5gpu_pile_col_t *cols, uint64_t *cells, uint64_t *cost) {
     for (uint32_t i = r0 + lane; i < r1; i += step)
         row_cells<Ops>(i, lo[i], hi[i], i ? hi[i - 1] : 0, (int32_t)q[i], ev ? ev[i].length : 0u, ref, R, W, win, cols, cells, cost);
-}
-// the work area of a ragged call: verdicts [n], P [n + 1], the sort's counts and cursors, and the ordered segments (a read and a segment
-// each), one for every segment the smallest S makes of a layout whose reads do not overlap: the sum of ceil(Q / S) is at most this
-PILE_HD uint64_t long_order_cap(uint32_t n, uint64_t total_rows) { return total_rows / SEG_MIN + n; }
-PILE_HD uint64_t up16(uint64_t x) { return (x + 15u) & ~(uint64_t)15u; }
-struct LongWork { uint64_t o_verdict, o_prefix, o_hist, o_cursor, o_order, bytes; };
-PILE_HD LongWork long_work(uint32_t n, uint64_t total_rows) {
-    LongWork w;
-    w.o_verdict = 0;
-    w.o_prefix = up16(4ull * n);
-    w.o_hist = w.o_prefix + up16(8ull * ((uint64_t)n + 1u));
-    w.o_cursor = w.o_hist + 4ull * LONG_KEYS;
-    w.o_order = w.o_cursor + 4ull * LONG_KEYS;
-    w.bytes = w.o_order + up16(8ull * long_order_cap(n, total_rows));
-    return w;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- level histograms (§4.23)
@@ -211,27 +133,62 @@ PILE_HD void hist_seg_cells(uint32_t r0, uint32_t r1, uint32_t lane, uint32_t st
 }
 
 #ifndef S5_PILEUP_HOST
-struct PileLongArgs {
-    uint32_t n;
-    const int16_t *queries;          // [total_rows]
-    const uint64_t *first;           // [n + 1]
-    const uint32_t *qlen;
-    uint64_t total_rows;
-    const int16_t *ref;
-    uint32_t R;
-    const int32_t *lo, *hi;          // [total_rows]
-    const int32_t *status;
-    const s5gpu_event_t *events;     // [total_rows], or nullptr
-    uint32_t ev_skip;                // 0 without events
-    void *work;                      // long_work(n, total_rows).bytes
-    void *acc;
+// What the kernels of pileup_kernels.hip, contrast_kernels.hip and refine_long_kernels.hip share beside the walks of ragged_dev.h
+struct DevOps {
+    static __device__ __forceinline__ void add64(uint64_t *p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+    // min_q and max_q only ever move one way, so a value read before (however stale) can only ask for an atomic too many, never one too few:
+    // most cells of a column that holds a few reads already change neither
+    static __device__ __forceinline__ void minmax32(s5gpu_pile_col_t *c, int32_t lo, int32_t hi) {
+        const uint64_t mm = __hip_atomic_load(reinterpret_cast<uint64_t *>(&c->min_q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lo < (int32_t)(uint32_t)mm) atomicMin(&c->min_q, lo);
+        if (hi > (int32_t)(uint32_t)(mm >> 32)) atomicMax(&c->max_q, hi);
+    }
 };
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// the reads of a ragged batch, once each, from their verdicts: the grid's threads share them out; in every lane the wave's counts
+struct ReadCounts { uint64_t used, skipped, bad; };
+__device__ __forceinline__ ReadCounts verdict_counts(const uint32_t *verdict, uint32_t n) {
+    ReadCounts c = {0, 0, 0};
+    for (uint64_t k = (uint64_t)blockIdx.x * s5::NT + threadIdx.x; k < n; k += (uint64_t)gridDim.x * s5::NT) {
+        const uint32_t v = verdict[k];
+        if (v & V_SKIPPED) c.skipped++;
+        else if (v & V_BAD) c.bad++;
+        else c.used++;
+    }
+    c.used = wave_sum(c.used);
+    c.skipped = wave_sum(c.skipped);
+    c.bad = wave_sum(c.bad);
+    return c;
+}
+// a wave's totals v[i] added to word i of a head, by its lane 0, where they are not 0
+template <int N>
+__device__ __forceinline__ void head_add(uint64_t *head, const uint64_t (&v)[N]) {
+    if ((threadIdx.x & 63u) != 0) return;
+#pragma unroll
+    for (int i = 0; i < N; i++)
+        if (v[i]) DevOps::add64(head + i, v[i]);
+}
+
 // k_pileup_long_plan, _check, (the sort,) _accum over the reads of a ragged batch, on st
 int launch_pileup_long(const PileLongArgs &A, hipStream_t st);
 // ... and from the same verdicts and segment list k_pile_hist_accum into hist (§4.23), when hist is given; A.acc (with A.ref and A.events)
 // may then be NULL: the histogram alone
 int launch_pileup_long(const PileLongArgs &A, void *hist, hipStream_t st);
-// k_pile_hist_reset; k reads that never reached the device count as skipped in a histogram; k_pile_contrast (contrast_kernels.hip)
+// the plan and the check alone (no sort): the verdicts and P in A.work, for a walk of another file (refine_long_kernels.hip)
+int launch_long_plan_check(const PileLongArgs &A, hipStream_t st);
+// "pileup_long_seg"; and the workgroups of a walk over the segments of a well-formed layout, four segments each at a time: at most `most`,
+// or "pileup_long_grid" of them
+uint32_t long_seg();
+uint32_t long_grid(const PileLongArgs &A, uint32_t S, uint32_t most);
+uint32_t long_grid(const PileLongArgs &A, uint32_t S);
+// k_pile_hist_accum over the verdicts and the (ordered) segments launch_pileup_long left in L (contrast_kernels.hip, as the four below)
+int launch_hist_accum(const PileLongArgs &A, uint32_t S, const LongPtrs &L, uint32_t sort, void *hist, hipStream_t st);
+int hist_set_option(const char *key, long value);
+// k_pile_hist_reset; k reads that never reached the device count as skipped in a histogram; k_pile_contrast
 int launch_hist_reset(void *hist, uint32_t R, int32_t q0, uint32_t shift, hipStream_t st);
 int launch_hist_add_skipped(void *hist, uint32_t k, hipStream_t st);
 int launch_contrast(const void *hist_a, const void *hist_b, const void *acc_a, const void *acc_b, uint32_t R, s5gpu_pile_contrast_t *out, hipStream_t st);

@@ -1,7 +1,7 @@
 // refine_dev.h — what refine_kernels.hip and refine_api.hip share (docs/codecs.md §4.20): the sums of a path row, the solve, the
 // requantiser, the window around a row, and the launchers.  With S5_REFINE_HOST (or S5_DTW_HOST) defined only the plain C++ is declared
 // (the switch of dtw_dev.h and pileup_dev.h): tests/test_refine.py compiles it for the CPU and runs the very code a lane runs against the
-// restatement, without a device.  Further down: the same for whole reads (§4.24), on the ragged layout and the segments of pileup_dev.h;
+// restatement, without a device.  Further down: the same for whole reads (§4.24), on the ragged layout and the segments of ragged_dev.h;
 // tests/test_extend_refine.py compiles that part behind S5_PILEUP_HOST.
 #pragma once
 #if (defined(S5_REFINE_HOST) || defined(S5_PILEUP_HOST)) && !defined(S5_DTW_HOST)
@@ -99,7 +99,7 @@ DTW_HD s5gpu_fit_t fit_none() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- whole reads (§4.24)
-// The fit along the ragged paths of extend (the layout, the verdicts and the segments of pileup_dev.h, §4.22, with ev_skip = 0), and the
+// The fit along the ragged paths of extend (the layout, the verdicts and the segments of ragged_dev.h, §4.22, with ev_skip = 0), and the
 // bookkeeping of the rounds of s5gpu_extend_refine_dev.  There is no wmax: a row of a path that passed pilek::row_ok in every row has
 // hi - lo + 1 <= R trips, and j < R is checked again before ref[j] is read (row_sums with R for wmax).  A read has fewer than 2^20 + 2^26
 // cells and each term is below 2^30: every sum is below 2^57.
@@ -191,7 +191,8 @@ struct RoundLongArgs {
     s5gpu_fit_t *fit;
     uint32_t *rounds;
 };
-// k_pileup_long_plan and k_pileup_long_check (no sort) over the reads of A: the verdicts and the segments' prefix in A.work
+// The launchers of refine_long_kernels.hip.  launch_long_verdicts: pilek::launch_long_plan_check (k_pileup_long_plan and k_pileup_long_check, no sort) over the
+// reads of A: the verdicts and the segments' prefix in A.work
 int launch_long_verdicts(const pilek::PileLongArgs &A, hipStream_t st);
 // ... then k_path_fit_long, k_fit_long_solve and (queries_out) k_requant_long
 int launch_fit_long(const FitLongArgs &F, hipStream_t st);
@@ -199,8 +200,9 @@ int launch_fit_long(const FitLongArgs &F, hipStream_t st);
 int launch_gate_long(uint32_t n, const s5gpu_ext_row_t *rows, int32_t *st_out, hipStream_t st);
 // k_refine_long_round
 int launch_round_long(const RoundLongArgs &B, uint32_t round, hipStream_t st);
-// which of these the calls launch ("refine_long_passes", pileup_kernels.hip)
+// which of these the calls launch: "refine_long_passes", the one key of s5gpu_set_option here
 uint32_t long_passes();
+int long_set_option(const char *key, long value);
 #endif
 
 #ifndef S5_DTW_HOST

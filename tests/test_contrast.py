@@ -1,10 +1,11 @@
-"""contrast: per-position level histograms and the two-sample comparison of them (docs/codecs.md §4.23; slow5tools_amd/csrc/pileup_kernels.hip,
-contrast_kernels.hip).
+"""contrast: per-position level histograms and the two-sample comparison of them (docs/codecs.md §4.23; slow5tools_amd/csrc/contrast_kernels.hip,
+behind the plan, the check and the sort of pileup_kernels.hip).
 
 The oracles are hist_ref and contrast_ref in contrast_ref.py: the definitions of §4.23 in int64 numpy and Python integers, tied to
 pileup_long_ref of the same case (the bins of a column add up to its n_events, the head to the totals).  Every member is an integer sum, so
 the device is held to them byte for byte, whatever the window, the grid, the sort, the segment length, the calls and the streams.  The
-header's plain C++ (pileup_dev.h) is also compiled for the CPU, once more under the address and undefined-behaviour sanitizers.
+headers' plain C++ (pileup_dev.h, and the walk of ragged_dev.h: every segment is resolved by seg_item, as in the kernels) is also compiled for
+the CPU, once more under the address and undefined-behaviour sanitizers.
 """
 import ctypes as C
 import os
@@ -193,7 +194,8 @@ def test_the_restatements():
 
 HIST_HOST = r'''
 // The histogram code of pileup_dev.h on the CPU, with plain adds in place of the atomics: what k_pileup_long_plan, _check, the sort and
-// k_pile_hist_accum do with it, every table allocated at exactly its size, the segments visited in a shuffled order (or in the sort's).
+// k_pile_hist_accum do with it, every table allocated at exactly its size, the segments visited in a shuffled order (or in the sort's),
+// each resolved by seg_item of ragged_dev.h.
 // in.bin: n, R, S, cols, wlo, sort, seed, q0, shift, pad (uint32), total_rows (uint64), then first, qlen, status, queries, lo, hi;
 // out.bin: the histogram's bytes.
 #define S5_PILEUP_HOST
@@ -230,43 +232,42 @@ int main(int argc, char **argv) {
     int32_t *status = get<int32_t>(f, n);
     int16_t *q = get<int16_t>(f, total_rows);
     int32_t *lo = get<int32_t>(f, total_rows), *hi = get<int32_t>(f, total_rows);
-    uint32_t *verdict = (uint32_t *)malloc(n ? 4ull * n : 1);
-    uint64_t *P = (uint64_t *)malloc(8ull * (n + 1ull));
+    const PileLongArgs A = {n, q, first, qlen, total_rows, nullptr, R, lo, hi, status, nullptr, 0u, nullptr, nullptr};
+    const uint64_t cap = long_order_cap(n, total_rows);
+    uint32_t hist[LONG_KEYS], cursor[LONG_KEYS], *verdict = (uint32_t *)malloc(n ? 4ull * n : 1);
+    uint64_t *P = (uint64_t *)malloc(8ull * (n + 1ull)), *order = (uint64_t *)malloc(cap ? 8 * cap : 1);   // the work area's parts, each at exactly its size
+    const LongPtrs L = {verdict, P, hist, cursor, order, cap};
+    memset(hist, 0, sizeof hist);
     P[0] = 0;
     for (uint32_t k = 0; k < n; k++) {
         verdict[k] = long_verdict(first[k], first[k + 1], qlen[k], status[k], total_rows, 0u);
         P[k + 1] = P[k] + (verdict[k] == V_USED ? segs_of(qlen[k], S) : 0u);
     }
-    const uint64_t total = P[n], cap = long_order_cap(n, total_rows);
+    const uint64_t total = P[n];
     uint64_t *list = (uint64_t *)malloc(total ? 8 * total : 1);
     for (uint64_t g = 0; g < total; g++) list[g] = g;
     shuffle(list, total);
-    uint32_t hist[LONG_KEYS], cursor[LONG_KEYS];
-    memset(hist, 0, sizeof hist);
     const bool sorted = sort && total <= cap;
-    for (uint64_t x = 0; x < total; x++) {
-        const uint64_t g = list[x];
-        const uint32_t k = seg_find(P, n, g), s = (uint32_t)(g - P[k]);
-        uint32_t r0, r1;
-        seg_rows(qlen[k], S, s, &r0, &r1);
-        if (!seg_rows_ok(r0, r1, 0, 1, lo + first[k], hi + first[k], R)) verdict[k] |= V_BAD;
-        if (sorted) hist[seg_key(lo[first[k] + r0], R)]++;
+    for (uint64_t x = 0; x < total; x++) {                                  // every segment through seg_item, the kernels' resolver
+        Seg g = seg_none(n);
+        if (!seg_item(A, S, L, false, list[x], &g)) return 4;
+        if (!seg_rows_ok(g.r0, g.r1, 0, 1, lo + first[g.k], hi + first[g.k], R)) verdict[g.k] |= V_BAD;
+        if (sorted) hist[seg_key(lo[first[g.k] + g.r0], R)]++;
     }
-    uint64_t *order = (uint64_t *)malloc(cap ? 8 * cap : 1);
     if (sorted) {
         uint32_t at = 0;
         for (uint32_t b = 0; b < LONG_KEYS; b++) { cursor[b] = at; at += hist[b]; }
         for (uint64_t x = 0; x < total; x++) {
-            const uint64_t g = list[x];
-            const uint32_t k = seg_find(P, n, g), s = (uint32_t)(g - P[k]);
-            const uint64_t pos = cursor[seg_key(lo[first[k] + s * S], R)]++;
+            Seg g = seg_none(n);
+            if (!seg_item(A, S, L, false, list[x], &g)) return 4;
+            const uint64_t pos = cursor[seg_key(lo[first[g.k] + g.r0], R)]++;
             if (pos >= cap) return 5;
-            order[pos] = (uint64_t)k << 32 | s;
+            order[pos] = (uint64_t)g.k << 32 | g.s;
         }
     } else {
         shuffle(list, total);
     }
-    // the cells: a table of exactly R columns and a window of exactly cols
+    // the cells: a table of exactly R columns and a window of exactly cols; the items of the ordered list, or of P's order shuffled
     uint32_t *table = (uint32_t *)calloc(R ? (size_t)R * HIST_BINS : 1, 4), *win = (uint32_t *)calloc(cols ? (size_t)cols * HIST_BINS : 1, 4);
     Window W;
     W.lo = h[4]; W.cols = cols;
@@ -274,13 +275,10 @@ int main(int argc, char **argv) {
     memset(&T, 0, sizeof T);
     T.R = R; T.q0 = q0; T.shift = shift; T.bins = HIST_BINS;
     for (uint64_t x = 0; x < total; x++) {
-        uint32_t k, s;
-        if (sorted) { k = (uint32_t)(order[x] >> 32); s = (uint32_t)order[x]; }
-        else { k = seg_find(P, n, list[x]); s = (uint32_t)(list[x] - P[k]); }
-        if (verdict[k] != V_USED) continue;
-        uint32_t r0, r1;
-        seg_rows(qlen[k], S, s, &r0, &r1);
-        hist_seg_cells<HostOps>(r0, r1, 0, 1, lo + first[k], hi + first[k], q + first[k], q0, shift, R, W, win, table, &T.cells);
+        Seg g = seg_none(n);
+        if (!seg_item(A, S, L, sorted, sorted ? x : list[x], &g)) return 4;
+        if (verdict[g.k] != V_USED) continue;
+        hist_seg_cells<HostOps>(g.r0, g.r1, 0, 1, lo + first[g.k], hi + first[g.k], q + first[g.k], q0, shift, R, W, win, table, &T.cells);
     }
     for (uint32_t t = 0; t < cols * HIST_BINS; t++) {
         hist_flush_word<HostOps>(t, W, win, table, R);

@@ -1,4 +1,5 @@
-"""refine over whole reads (docs/codecs.md §4.24): the restatement's known answers, the header's plain C++ on the CPU (also under ASan and
+"""refine over whole reads (docs/codecs.md §4.24; slow5tools_amd/csrc/refine_long_kernels.hip): the restatement's known answers, the headers'
+plain C++ (refine_dev.h, and the walk of ragged_dev.h: every segment is resolved by seg_item, as in the kernels) on the CPU (also under ASan and
 UBSan) against it, the planted case, refused arguments, exports; and on the device the fit, the rounds, the chain, pileup and contrast, all
 bit for bit against extend_refine_ref.py."""
 import ctypes as C
@@ -137,7 +138,7 @@ def test_restatement_known_answers():
 # ---------------------------------------------------------------------------------------------------------------- the header's code on the CPU
 
 REFINE_LONG_HOST = r'''
-// The plain C++ of the whole-read refine in refine_dev.h and pileup_dev.h (§4.24) on the CPU, the way the kernels use it.  A batch of in.bin:
+// The plain C++ of the whole-read refine in refine_dev.h and ragged_dev.h (§4.24) on the CPU, the way the kernels use it.  A batch of in.bin:
 // n, S, iters, shuffle, total, R, the 40 bytes of the refine parameters, first[n + 1], qlen[n], q0[total], ref[R], rows_in[n], lo_in[total],
 // hi_in[total], and for every round j = 1 .. iters what the band call left of the trial: t_rows[n], t_lo[total], t_hi[total] (the band
 // kernel is not part of this program).  Every array is allocated at exactly its size with a guard word either side, poisoned under ASan.
@@ -190,10 +191,19 @@ struct Batch {
     uint64_t total;
     const uint64_t *first; const uint32_t *qlen; const int16_t *q0, *ref;
 };
+// segment g of P's order through seg_item of ragged_dev.h, the kernels' resolver (no read carried: the order is shuffled), held to
+// seg_find, seg_next and the rows' bounds every time
+static Seg seg_of(const Batch &B, const uint64_t *P, uint64_t g) {
+    const PileLongArgs A = {B.n, B.q0, B.first, B.qlen, B.total};           // (the rest is not the resolver's)
+    const LongPtrs L = {nullptr, const_cast<uint64_t *>(P)};
+    Seg s = seg_none(B.n);
+    if (!seg_item(A, B.S, L, false, g, &s) || s.k != seg_find(P, B.n, g) || s.k != seg_next(P, B.n, 0u, g) || s.r0 >= s.r1 || s.r1 > B.qlen[s.k] || s.r1 - s.r0 > B.S) abort();
+    return s;
+}
 
 static uint32_t rnd(uint32_t &s) { s = s * 1664525u + 1013904223u; return s >> 8; }
 
-// the plan and the check: verdict[n], P[n + 1]; the segments of the check in shuffled order, found with seg_find
+// the plan and the check: verdict[n], P[n + 1]; the segments of the check in shuffled order, resolved by seg_item
 static void verdicts(const Batch &B, const int32_t *status, const int32_t *lo, const int32_t *hi, uint32_t *verdict, uint64_t *P, std::vector<uint64_t> &order, uint32_t shuffle) {
     uint64_t at = 0;
     for (uint32_t k = 0; k < B.n; k++) {
@@ -207,11 +217,8 @@ static void verdicts(const Batch &B, const int32_t *status, const int32_t *lo, c
     uint32_t s = shuffle;
     for (uint64_t g = at; g > 1; g--) { const uint64_t j = rnd(s) % g; const uint64_t t = order[g - 1]; order[g - 1] = order[j]; order[j] = t; }
     for (uint64_t x = 0; x < at; x++) {
-        const uint64_t g = order[x];
-        const uint32_t k = seg_find(P, B.n, g);
-        if (k != seg_next(P, B.n, 0u, g)) abort();
-        uint32_t r0, r1;
-        seg_rows(B.qlen[k], B.S, (uint32_t)(g - P[k]), &r0, &r1);
+        const Seg s = seg_of(B, P, order[x]);
+        const uint32_t k = s.k, r0 = s.r0, r1 = s.r1;
         const uint64_t f = B.first[k];
         bool ok = true;
         for (uint32_t lane = 0; lane < 64; lane++) ok = seg_rows_ok(r0, r1, lane, 64u, lo + f, hi + f, B.R) && ok;
@@ -225,11 +232,9 @@ static void fit_long(const Batch &B, const s5gpu_refine_params_t &Pm, const int3
     verdicts(B, status, lo, hi, verdict, P, order, shuffle);
     Arr<Sums> sums(B.n);
     for (uint64_t x = 0; x < order.size(); x++) {
-        const uint64_t g = order[x];
-        const uint32_t k = seg_find(P, B.n, g);
+        const Seg s = seg_of(B, P, order[x]);
+        const uint32_t k = s.k, r0 = s.r0, r1 = s.r1;
         if (verdict[k] != V_USED) continue;
-        uint32_t r0, r1;
-        seg_rows(B.qlen[k], B.S, (uint32_t)(g - P[k]), &r0, &r1);
         const uint64_t f = B.first[k];
         Sums part = {0, 0, 0, 0, 0, 0};
         for (uint32_t lane = 0; lane < 64; lane++) seg_sums(r0, r1, lane, 64u, lo + f, hi + f, B.q0 + f, B.ref, B.R, part);
@@ -237,11 +242,9 @@ static void fit_long(const Batch &B, const s5gpu_refine_params_t &Pm, const int3
     }
     for (uint32_t k = 0; k < B.n; k++) st_out[k] = long_fit_status(verdict[k], status[k], sums.p[k], Pm, &fit[k]);
     for (uint64_t x = 0; x < order.size(); x++) {
-        const uint64_t g = order[x];
-        const uint32_t k = seg_find(P, B.n, g);
+        const Seg s = seg_of(B, P, order[x]);
+        const uint32_t k = s.k, r0 = s.r0, r1 = s.r1;
         if (verdict[k] != V_USED || st_out[k] != 0) continue;
-        uint32_t r0, r1;
-        seg_rows(B.qlen[k], B.S, (uint32_t)(g - P[k]), &r0, &r1);
         const uint64_t f = B.first[k];
         for (uint32_t i = r0; i < r1; i++) out[f + i] = requant_one(B.q0[f + i], fit[k].a, fit[k].b, Pm.clip);
     }
@@ -281,14 +284,12 @@ static int one_batch(FILE *f, FILE *o) {
             t_fit.write(o); t_sf.write(o); t_q.write(o);
         }
         for (uint64_t x = 0; x < order.size(); x++) {
-            const uint64_t g = order[x];
-            const uint32_t k = seg_find(P.p, B.n, g), v = verdict.p[k];
+            const Seg sg = seg_of(B, P.p, order[x]);
+            const uint32_t k = sg.k, r0 = sg.r0, r1 = sg.r1, v = verdict.p[k];
             if ((v & V_SKIPPED) || (round == 0 && v != V_USED)) continue;
             int32_t s;
             const int mode = long_round_rule(round, v, qlen.p[k], cur_in[k], round ? t_sf.p[k] : 0, round ? t_rows.p[k].status : 0, &s);
             if (mode == 0) continue;
-            uint32_t r0, r1;
-            seg_rows(qlen.p[k], B.S, (uint32_t)(g - P.p[k]), &r0, &r1);
             const uint64_t at = first.p[k];
             for (uint32_t i = r0; i < r1; i++) {
                 int16_t qq = 0;
@@ -421,8 +422,8 @@ def _check_host_output(raw, batches, traces):
 
 
 def test_the_refine_long_code_compiled_for_the_cpu_matches_the_restatement(tmp_path):
-    """seg_sums, sums_add, long_fit_status, long_round_rule, long_round_row of refine_dev.h behind long_verdict, seg_find, seg_rows and
-    seg_rows_ok of pileup_dev.h, as g++ compiles them, on host_batches(): sums, fits, statuses, q' and the bookkeeping's outputs behind
+    """seg_sums, sums_add, long_fit_status, long_round_rule, long_round_row of refine_dev.h behind long_verdict, seg_item (against seg_find
+    and seg_next) and seg_rows_ok of ragged_dev.h, as g++ compiles them, on host_batches(): sums, fits, statuses, q' and the bookkeeping's outputs behind
     every round equal the restatement's byte for byte, whatever the segment size and the order of the segments; and the same program under
     ASan and UBSan, every array at exactly its size"""
     batches = host_batches()
@@ -604,8 +605,8 @@ def _dev(env, a, dtype=None):
     return env.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
 
 
-def _options(env, seg=tl.DEFAULT_SEG, sort=tl.DEFAULT_SORT):
-    for key, v in ((b"pileup_long_seg", seg), (b"pileup_long_sort", sort)):
+def _options(env, seg=tl.DEFAULT_SEG, sort=tl.DEFAULT_SORT, grid=tl.DEFAULT_GRID):
+    for key, v in ((b"pileup_long_seg", seg), (b"pileup_long_sort", sort), (b"pileup_long_grid", grid)):
         env.lib.check(env.L.s5gpu_set_option(key, v), key.decode())
 
 
@@ -663,8 +664,10 @@ def _flawed(case, rows):
 def test_fit_long_is_exact_on_a_mixed_batch(gpu, R):
     """s5gpu_path_fit_long_dev on 40 ragged reads (every Q of QLENS four times, two reads without a query, 5 and 70 rows) whose paths come from
     band_dev at (64, 128), with a read that comes in with a status, broken rows in a first and in a last segment and a `first` out of
-    range: fits, sums, statuses and q' equal fit_long_ref, the same bytes at segments of 64 and 256 with the sort on and off, with and
-    without queries_out, and on two streams into separate outputs"""
+    range: fits, sums, statuses and q' equal fit_long_ref, the same bytes at segments of 64 and 256 with the sort on and off, at segments
+    of 64 with one workgroup (each of its four waves walks some thirty consecutive segments across the reads' boundaries, the flawed reads
+    among them: the sums held and flushed, the read carried from segment to segment) and with three (most of the twelve waves have a short
+    slice or none), with and without queries_out, and on two streams into separate outputs"""
     t = gpu.torch
     rng = np.random.default_rng(4240 + R)
     ref = np.clip(np.rint(rng.normal(0.0, 40.0, R)), -127, 127).astype(np.int16)
@@ -686,6 +689,10 @@ def test_fit_long_is_exact_on_a_mixed_batch(gpu, R):
             for sort in (1, 0):
                 _options(gpu, seg=seg, sort=sort)
                 _same_fit((R, seg, sort), _fit(gpu, d, P), want)
+        for grid in (1, 3):
+            _options(gpu, seg=64, grid=grid)
+            _same_fit((R, "grid", grid), _fit(gpu, d, P), want)
+        _options(gpu, seg=256, sort=0)
         _same_fit((R, "no queries"), _fit(gpu, d, P, want_queries=False), want)
     finally:
         _options(gpu)
@@ -768,8 +775,8 @@ def test_the_rounds_equal_the_restatement_on_the_planted_reads(gpu, iters):
 @pytest.mark.gpu
 def test_the_rounds_on_a_mixed_batch_where_reads_drop_out(gpu):
     """the mixed batch with its flaws through four rounds with a slope limit that some reads meet in one round and others in a later one:
-    everything equals refine_long_ref, also at segments of 64 without the sort; and a scratch one slot too small is refused with nothing
-    written"""
+    everything equals refine_long_ref, also at segments of 64 without the sort, and there with one workgroup and with three (see
+    test_fit_long_is_exact_on_a_mixed_batch); and a scratch one slot too small is refused with nothing written"""
     t = gpu.torch
     case, rows = mixed_case(64, 128, 300, te.MIXED_Q, 4241)
     case, rows = _flawed(case, rows)
@@ -782,6 +789,9 @@ def test_the_rounds_on_a_mixed_batch_where_reads_drop_out(gpu):
     try:
         _options(gpu, seg=64, sort=0)
         _same_out("mixed, segments of 64", _refine(gpu, case, rows, 64, 128, P), want)
+        for grid in (1, 3):
+            _options(gpu, seg=64, grid=grid)
+            _same_out(("mixed, segments of 64, grid", grid), _refine(gpu, case, rows, 64, 128, P), want)
     finally:
         _options(gpu)
     # a scratch one slot too small

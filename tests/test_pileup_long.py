@@ -1,10 +1,12 @@
-"""pileup of whole reads: the ragged paths of extend added to the table (docs/codecs.md §4.22; slow5tools_amd/csrc/pileup_kernels.hip).
+"""pileup of whole reads: the ragged paths of extend added to the table (docs/codecs.md §4.22; slow5tools_amd/csrc/pileup_kernels.hip, the
+layout and the walk over its segments in ragged_dev.h).
 
 The oracle is pileup_long_ref in this file: the definition of §4.22 in int64 numpy for the ragged layout, read by read, with the invariants
 asserted.  It is tied to §4.18's restatement (test_pileup.pileup_ref) on every case of that file re-laid as ragged.  Every member of the
 table is an integer sum, minimum or maximum, so the device is held to it byte for byte, whatever the segment length, the window, the sort,
-the grid, the calls and the streams.  The header's plain C++ (pileup_dev.h) is also compiled for the CPU, once more under the address and
-undefined-behaviour sanitizers, and held to the same oracle with the segments visited in a shuffled order.
+the grid, the calls and the streams.  The headers' plain C++ (ragged_dev.h, pileup_dev.h) is also compiled for the CPU, once more under the
+address and undefined-behaviour sanitizers, and held to the same oracle with the segments visited in a shuffled order, each resolved by
+seg_item, the one resolver the kernels walk with; seg_item itself is held to a plain double loop over reads and segments.
 """
 import ctypes as C
 import functools
@@ -421,8 +423,9 @@ def test_restatement_on_hand_made_paths_and_against_the_fixed_pitch_one():
 
 
 PILE_LONG_HOST = r'''
-// The whole-read code of pileup_dev.h on the CPU, with plain adds in place of the atomics: what k_pileup_long_plan, _check, the sort and _accum
-// do with it, every table allocated at exactly its size, the segments visited in a shuffled order (or in the sort's).
+// The whole-read code of ragged_dev.h and pileup_dev.h on the CPU, with plain adds in place of the atomics: what k_pileup_long_plan, _check,
+// the sort and _accum do with it, every table allocated at exactly its size, the segments visited in a shuffled order (or in the sort's),
+// every one resolved by seg_item, the kernels' own resolver, which is also held to a plain double loop (brute).
 // in.bin: n, R, events?, ev_skip, S, cols, wlo, sort, seed, pad (uint32), total_rows (uint64), then first, qlen, status, queries, ref, lo, hi,
 // events; out.bin: the accumulator's bytes.
 #define S5_PILEUP_HOST
@@ -430,6 +433,7 @@ PILE_LONG_HOST = r'''
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <vector>
 using namespace pilek;
 struct HostOps {
     static void add64(uint64_t *p, uint64_t v) { *p += v; }
@@ -451,6 +455,29 @@ static uint64_t g_rand;
 static uint64_t rnd() { g_rand = g_rand * 6364136223846793005ull + 1442695040888963407ull; return g_rand >> 33; }
 static void shuffle(uint64_t *v, uint64_t k) { for (uint64_t i = k; i > 1; i--) { const uint64_t j = rnd() % i, t = v[i - 1]; v[i - 1] = v[j]; v[j] = t; } }
 
+// seg_item against a plain double loop over the reads and their segments of S rows (verdict: the layout's): in P's order with "none yet"
+// before each item (0) and with the read carried from the item before (1), and through an ordered list, the double loop's backwards (2)
+static bool brute(const PileLongArgs &A, const uint32_t *verdict, uint32_t S) {
+    std::vector<uint64_t> P(A.n + 1ull), want;
+    for (uint32_t k = 0; k < A.n; k++) {
+        P[k] = want.size();
+        for (uint32_t s = 0; verdict[k] == V_USED && s < segs_of(A.qlen[k], S); s++) want.push_back((uint64_t)k << 32 | s);
+    }
+    P[A.n] = want.size();
+    std::vector<uint64_t> order(want.rbegin(), want.rend());
+    const LongPtrs L = {nullptr, P.data(), nullptr, nullptr, order.data(), order.size()};
+    Seg carried = seg_none(A.n);
+    for (uint64_t it = 0; it < want.size(); it++)
+        for (int mode = 0; mode < 3; mode++) {
+            Seg fresh = seg_none(A.n), *g = mode == 1 ? &carried : &fresh;
+            const uint64_t w = mode == 2 ? order[it] : want[it];
+            const uint32_t k = (uint32_t)(w >> 32), s = (uint32_t)w, r0 = s * S, r1 = A.qlen[k] - r0 < S ? A.qlen[k] : r0 + S;
+            if (!seg_item(A, S, L, mode == 2, it, g) || g->k != k || g->s != s || g->r0 != r0 || g->r1 != r1) return false;
+        }
+    Seg g = seg_none(A.n);
+    return !seg_item(A, S, L, true, order.size(), &g);                       // a place behind the list's end stands for nothing
+}
+
 int main(int argc, char **argv) {
     if (argc != 3) return 1;
     FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
@@ -465,25 +492,28 @@ int main(int argc, char **argv) {
     int16_t *q = get<int16_t>(f, total_rows), *ref = get<int16_t>(f, R);
     int32_t *lo = get<int32_t>(f, total_rows), *hi = get<int32_t>(f, total_rows);
     s5gpu_event_t *ev = h[2] ? get<s5gpu_event_t>(f, total_rows) : nullptr;
-    // the plan
+    // the plan: the work area's parts, each at exactly its size
     const LongWork lw = long_work(n, total_rows);
     if (lw.o_prefix < 4ull * n || lw.o_hist < lw.o_prefix + 8ull * (n + 1ull) || lw.o_order < lw.o_cursor + 4ull * LONG_KEYS ||
         lw.bytes < lw.o_order + 8 * long_order_cap(n, total_rows))
         return 3;
-    uint32_t *verdict = (uint32_t *)malloc(n ? 4ull * n : 1);
-    uint64_t *P = (uint64_t *)malloc(8ull * (n + 1ull));
+    const PileLongArgs A = {n, q, first, qlen, total_rows, ref, R, lo, hi, status, ev, ev_skip, nullptr, nullptr};
+    const uint64_t cap = long_order_cap(n, total_rows);
+    uint32_t hist[LONG_KEYS], cursor[LONG_KEYS], *verdict = (uint32_t *)malloc(n ? 4ull * n : 1);
+    uint64_t *P = (uint64_t *)malloc(8ull * (n + 1ull)), *order = (uint64_t *)malloc(cap ? 8 * cap : 1);   // an ordered list of exactly cap entries
+    const LongPtrs L = {verdict, P, hist, cursor, order, cap};
+    memset(hist, 0, sizeof hist);
     P[0] = 0;
     for (uint32_t k = 0; k < n; k++) {
         verdict[k] = long_verdict(first[k], first[k + 1], qlen[k], status[k], total_rows, ev_skip);
         P[k + 1] = P[k] + (verdict[k] == V_USED ? segs_of(qlen[k], S) : 0u);
     }
-    const uint64_t total = P[n], cap = long_order_cap(n, total_rows);
+    if (!brute(A, verdict, 64u) || !brute(A, verdict, 256u)) return 7;
+    const uint64_t total = P[n];
     // the check, in a shuffled order; seg_find and seg_next agree
     uint64_t *list = (uint64_t *)malloc(total ? 8 * total : 1);
     for (uint64_t g = 0; g < total; g++) list[g] = g;
     shuffle(list, total);
-    uint32_t hist[LONG_KEYS], cursor[LONG_KEYS];
-    memset(hist, 0, sizeof hist);
     const bool sorted = sort && total <= cap;
     uint32_t walk = 0;
     for (uint64_t g = 0; g < total; g++) {
@@ -491,31 +521,26 @@ int main(int argc, char **argv) {
         if (walk != seg_find(P, n, g)) return 4;
     }
     for (uint64_t x = 0; x < total; x++) {
-        const uint64_t g = list[x];
-        const uint32_t k = seg_find(P, n, g), s = (uint32_t)(g - P[k]);
-        if (k >= n || verdict[k] & V_SKIPPED || s >= segs_of(qlen[k], S)) return 4;
-        uint32_t r0, r1;
-        seg_rows(qlen[k], S, s, &r0, &r1);
-        if (r0 >= r1 || r1 > qlen[k] || r1 - r0 > S) return 4;
-        if (!seg_rows_ok(r0, r1, 0, 1, lo + first[k], hi + first[k], R)) verdict[k] |= V_BAD;
-        if (sorted) hist[seg_key(lo[first[k] + r0], R)]++;
+        Seg g = seg_none(n);
+        if (!seg_item(A, S, L, false, list[x], &g) || g.k != seg_find(P, n, list[x]) || verdict[g.k] & V_SKIPPED) return 4;
+        if (g.r0 >= g.r1 || g.r1 > qlen[g.k] || g.r1 - g.r0 > S || g.r0 != g.s * S) return 4;
+        if (!seg_rows_ok(g.r0, g.r1, 0, 1, lo + first[g.k], hi + first[g.k], R)) verdict[g.k] |= V_BAD;
+        if (sorted) hist[seg_key(lo[first[g.k] + g.r0], R)]++;
     }
-    // the sort: an ordered list of exactly cap entries
-    uint64_t *order = (uint64_t *)malloc(cap ? 8 * cap : 1);
-    if (sorted) {
+    if (sorted) {                                                           // the sort
         uint32_t at = 0;
         for (uint32_t b = 0; b < LONG_KEYS; b++) { cursor[b] = at; at += hist[b]; }
         for (uint64_t x = 0; x < total; x++) {
-            const uint64_t g = list[x];
-            const uint32_t k = seg_find(P, n, g), s = (uint32_t)(g - P[k]);
-            const uint64_t pos = cursor[seg_key(lo[first[k] + s * S], R)]++;
+            Seg g = seg_none(n);
+            if (!seg_item(A, S, L, false, list[x], &g)) return 4;
+            const uint64_t pos = cursor[seg_key(lo[first[g.k] + g.r0], R)]++;
             if (pos >= cap) return 5;
-            order[pos] = (uint64_t)k << 32 | s;
+            order[pos] = (uint64_t)g.k << 32 | g.s;
         }
     } else {
         shuffle(list, total);
     }
-    // the cells
+    // the cells: through the ordered list, or in P's order shuffled
     s5gpu_pile_col_t *table = empty_cols(R), *win = empty_cols(cols);
     Window W;
     W.lo = h[6]; W.cols = cols;
@@ -524,18 +549,16 @@ int main(int argc, char **argv) {
     T.R = R;
     uint32_t last_key = 0;
     for (uint64_t x = 0; x < total; x++) {
-        uint32_t k, s;
-        if (sorted) { k = (uint32_t)(order[x] >> 32); s = (uint32_t)order[x]; }
-        else { k = seg_find(P, n, list[x]); s = (uint32_t)(list[x] - P[k]); }
+        Seg g = seg_none(n);
+        if (!seg_item(A, S, L, sorted, sorted ? x : list[x], &g)) return 4;
+        const uint32_t k = g.k;
         if (sorted) {
-            const uint32_t key = seg_key(lo[first[k] + s * S], R);
+            const uint32_t key = seg_key(lo[first[k] + g.r0], R);
             if (key < last_key) return 6;                                   // the list is in the keys' order
             last_key = key;
         }
         if (verdict[k] != V_USED) continue;
-        uint32_t r0, r1;
-        seg_rows(qlen[k], S, s, &r0, &r1);
-        seg_cells<HostOps>(r0, r1, 0, 1, lo + first[k], hi + first[k], q + first[k], ev ? ev + first[k] + ev_skip : nullptr, ref, R, W, win, table, &T.cells,
+        seg_cells<HostOps>(g.r0, g.r1, 0, 1, lo + first[k], hi + first[k], q + first[k], ev ? ev + first[k] + ev_skip : nullptr, ref, R, W, win, table, &T.cells,
                            &T.cost);
     }
     for (uint32_t b = 0; b < cols; b++) {
@@ -595,8 +618,9 @@ def run_long_header_on_the_cpu(tmp_path, extra=(), thorough=True):
 
 
 def test_the_header_code_compiled_for_the_cpu_matches_the_restatement(tmp_path):
-    """long_verdict, segs_of, seg_find / seg_next, seg_rows_ok and seg_cells (row_ok and row_cells with hi_prev from the ragged array), seg_key
-    and the window of pileup_dev.h as g++ compiles them, over the case list, segments in a shuffled order and in the sort's"""
+    """long_verdict, segs_of, seg_find / seg_next, seg_item (against a plain double loop at S 64 and 256, from both start conventions and
+    through an ordered list), seg_rows_ok and seg_cells (row_ok and row_cells with hi_prev from the ragged array), seg_key and the window of
+    ragged_dev.h and pileup_dev.h as g++ compiles them, over the case list, segments in a shuffled order and in the sort's"""
     run_long_header_on_the_cpu(tmp_path)
 
 
