@@ -21,92 +21,41 @@
  * s5gpu_contrast_close: compressed bytes go up; a status per read comes back, and the rows and the two tables once at the end.
  */
 #define _GNU_SOURCE
-#include <inttypes.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+#define S5TOOL "s5contrast"
+#define S5TOOL_DIE 2
+#include "s5tool.h"
 
 enum { EXIT_CORRUPT = 1, EXIT_ERROR = 2 };
 
-static int die(const char *what) {
-    fprintf(stderr, "s5contrast: %s (%s)\n", what, s5gpu_last_error());
-    return EXIT_ERROR;
-}
 /* a status of the decoder's, not one of map's or extend's */
 static int corrupt_status(int32_t s) {
     return s != 0 && s != S5GPU_STATUS_QUERY_SHORT && s != S5GPU_STATUS_PATH_WIDE && s != S5GPU_STATUS_PATH_ROW && s != S5GPU_STATUS_FIT_FLAT &&
            s != S5GPU_STATUS_FIT_RANGE;
 }
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
-
-/* one number per line; NULL (and a message) when the file cannot be read, holds no number or a line is no number */
-static float *read_reference(const char *path, size_t *n_out) {
-    FILE *f = fopen(path, "r");
-    if (!f) { fprintf(stderr, "s5contrast: cannot open %s\n", path); return NULL; }
-    size_t n = 0, cap = 1024, line_cap = 0, line_no = 0;
-    float *v = (float *)malloc(sizeof(float) * cap);
-    char *line = NULL;
-    ssize_t l;
-    while (v && (l = getline(&line, &line_cap, f)) >= 0) {
-        line_no++;
-        while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r' || line[l - 1] == ' ' || line[l - 1] == '\t')) line[--l] = 0;
-        if (l == 0 || line[0] == '#') continue;
-        char *end = NULL;
-        const double x = strtod(line, &end);
-        if (end == line || *end != 0) {
-            fprintf(stderr, "s5contrast: %s line %zu is not a number\n", path, line_no);
-            free(v); free(line); fclose(f);
-            return NULL;
-        }
-        if (n == cap) { cap *= 2; v = (float *)realloc(v, sizeof(float) * cap); }
-        if (v) v[n++] = (float)x;
-    }
-    free(line);
-    fclose(f);
-    if (!v) { fprintf(stderr, "s5contrast: out of memory\n"); return NULL; }
-    if (n == 0 || n > (1u << 22)) { fprintf(stderr, "s5contrast: %s holds %s\n", path, n ? "too many numbers (at most 2^22)" : "no number"); free(v); return NULL; }
-    *n_out = n;
-    return v;
-}
-
 /* the batches of one file into `side` of the handle; 0, EXIT_CORRUPT or EXIT_ERROR */
-static int add_file(void *h, int side, const char *path, long K, void **mem, size_t *len, int32_t *st, uint64_t *n_refused) {
-    slow5_file_t *in = slow5_open(path, "r");
-    if (!in) { fprintf(stderr, "s5contrast: cannot open %s\n", path); return EXIT_ERROR; }
-    if (in->format != SLOW5_FORMAT_BINARY) { fprintf(stderr, "s5contrast: %s is SLOW5 text: convert it to BLOW5 first\n", path); return EXIT_ERROR; }
-    const int rec = rec_code_of(in->compress->record_press->method), sig = sig_code_of(in->compress->signal_press->method);
-    int code = EXIT_SUCCESS, at_end = 0;
-    uint64_t n_done = 0;
-    while (!at_end) {
-        uint32_t n = 0;
-        while (n < (uint32_t)K) {
-            mem[n] = slow5_get_next_mem(&len[n], in);
-            if (!mem[n]) {
-                if (slow5_errno != SLOW5_ERR_EOF) { fprintf(stderr, "s5contrast: cannot read record %" PRIu64 " of %s\n", n_done + n, path); return EXIT_ERROR; }
-                at_end = 1;
-                break;
-            }
-            if (len[n] > 0xFFFFFF00u) { fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is too large\n", n_done + n, path); return EXIT_ERROR; }
-            n++;
-        }
-        if (n == 0) break;
-        const int rc = s5gpu_contrast_add_batch(h, side, n, (const void *const *)mem, len, rec, sig, NULL, NULL, st);
+static int add_file(void *h, int side, const char *path, long K, int32_t *st, uint64_t *n_refused) {
+    slow5_file_t *in = open_blow5(path, NULL);
+    if (!in) return EXIT_ERROR;
+    batch_t bt;
+    if (batch_open(&bt, in, path, K) != 0) return EXIT_ERROR;
+    bt.path_in_messages = 1;
+    int code = EXIT_SUCCESS;
+    int64_t nb;
+    while ((nb = batch_next(&bt)) > 0) {
+        const uint32_t n = (uint32_t)nb;
+        const int rc = s5gpu_contrast_add_batch(h, side, n, (const void *const *)bt.mem, bt.len, bt.rec, bt.sig, NULL, NULL, st);
         if (rc != S5GPU_OK && rc != S5GPU_ERR_DATA) return die("alignment failed");
         for (uint32_t i = 0; i < n; i++) {
             if (corrupt_status(st[i])) {
-                fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is corrupt (status %d)\n", n_done + i, path, st[i]);
+                fprintf(stderr, "s5contrast: record %" PRIu64 " of %s is corrupt (status %d)\n", bt.n_done + i, path, st[i]);
                 code = EXIT_CORRUPT;
             }
             if (st[i] == S5GPU_STATUS_FIT_FLAT || st[i] == S5GPU_STATUS_FIT_RANGE) (*n_refused)++;
-            free(mem[i]);
-            mem[i] = NULL;
         }
-        n_done += n;
+        batch_release(&bt);
     }
+    if (nb < 0) return EXIT_ERROR;
+    batch_close(&bt);
     slow5_close(in);
     return code;
 }
@@ -154,32 +103,28 @@ int main(int argc, char **argv) {
     }
     const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
     size_t R = 0;
-    float *levels = read_reference(ref_path, &R);
+    float *levels = read_reference(ref_path, 1u << 22, "too many numbers (at most 2^22)", &R);
     if (!levels) return EXIT_ERROR;
     int16_t *ref = (int16_t *)malloc(sizeof(int16_t) * R);
     if (!ref) return die("out of memory");
     if (s5gpu_quantise_host(levels, R, M.scale, M.clip, ref) != S5GPU_OK) return die("the reference cannot be quantised");
     free(levels);
     if (s5gpu_init(0) != S5GPU_OK) return die("no GPU");
-    const s5gpu_event_params_t dna = {3, 6, 1.4, 9.0, 0.2}, rnap = {7, 14, 2.5, 9.0, 1.0};
     const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
-    static char obuf[1 << 20];
-    setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+    big_stdout();
 
-    void **mem = (void **)calloc((size_t)K, sizeof(void *));
-    size_t *len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
     int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
     uint8_t *acc[2] = {(uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R)), (uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R))};
     s5gpu_pile_contrast_t *rows = (s5gpu_pile_contrast_t *)malloc(sizeof *rows * R);
-    if (!mem || !len || !st || !acc[0] || !acc[1] || !rows) return die("out of memory");
-    void *h = s5gpu_contrast_open(rna ? &rnap : &dna, &M, &B, 0, ref, (uint32_t)R, (int32_t)q0, (uint32_t)shift);
+    if (!st || !acc[0] || !acc[1] || !rows) return die("out of memory");
+    void *h = s5gpu_contrast_open(event_params(rna), &M, &B, 0, ref, (uint32_t)R, (int32_t)q0, (uint32_t)shift);
     if (!h) return die("the tables cannot be opened");
     const s5gpu_refine_params_t RP = {a_lo, a_hi, 64.0, 127, 16, 16, (uint32_t)iters};
     if (refine && s5gpu_contrast_set_refine(h, &RP) != S5GPU_OK) return die("the rounds cannot be turned on");
     uint64_t n_refused[2] = {0, 0};
     int code = EXIT_SUCCESS;
     for (int side = 0; side < 2; side++) {
-        const int c = add_file(h, side, path[side], K, mem, len, st, &n_refused[side]);
+        const int c = add_file(h, side, path[side], K, st, &n_refused[side]);
         if (c == EXIT_ERROR) return EXIT_ERROR;
         if (c) code = c;
     }
@@ -200,6 +145,6 @@ int main(int argc, char **argv) {
         if (refine) fprintf(stderr, "s5contrast: %s: reads refused by the fit %" PRIu64 " (they count as skipped)\n", path[side], n_refused[side]);
     }
     if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5contrast: write failed\n"); return EXIT_ERROR; }
-    free(mem); free(len); free(st); free(acc[0]); free(acc[1]); free(rows); free(ref);
+    free(st); free(acc[0]); free(acc[1]); free(rows); free(ref);
     return code;
 }

@@ -10,45 +10,17 @@
  *   are printed); 2 on any other error (unreadable or damaged file, a .slow5 argument: text input is not built, convert it first).
  *
  * At most K records (default 4096) go to one s5gpu_signal_events_batch call: compressed bytes go up, 16 bytes per event come back.  The read
- * ids come from the device id path (s5gpu_record_ids_stream) over the same records framed in one buffer; zstd records and ids longer than its
- * pitch are the first column of a skim line (s5gpu_skim_batch).
+ * ids come from the device id path over the same records framed in one buffer; zstd records and ids longer than its pitch are the first
+ * column of a skim line (batch_ids of s5tool.h).
  */
 #define _GNU_SOURCE
-#include <inttypes.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#define S5TOOL "s5events"
+#define S5TOOL_DIE 2
+#include "s5tool.h"
 
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+enum { EXIT_CORRUPT = 1, EXIT_ERROR = 2 };
 
-enum { EXIT_CORRUPT = 1, EXIT_ERROR = 2, PITCH = 128 };
-
-static int die(const char *what) {
-    fprintf(stderr, "s5events: %s (%s)\n", what, s5gpu_last_error());
-    return EXIT_ERROR;
-}
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
-
-/* --rid's layout of s5skim.c: the aux fields' types only, every role "." — a skim line is only needed for its first column */
-static int rid_layout(const char *h, size_t len, s5gpu_skim_layout_t *L) {
-    size_t b = 0;
-    while (b < len) {
-        const char *e = (const char *)memchr(h + b, '\n', len - b);
-        const size_t l = e ? (size_t)(e - h) - b : len - b;
-        if (l >= 6 && memcmp(h + b, "#char*", 6) == 0) {
-            const int k = s5gpu_aux_types_parse(h + b, l, L->type, S5GPU_SKIM_MAX_AUX);
-            if (k < 0) return -1;
-            L->n_aux = (uint32_t)k;
-            for (int a = 0; a < k; a++) L->role[a] = S5GPU_SKIM_DOT;
-            L->n_unhandled = (uint32_t)k;
-            return 0;
-        }
-        b += l + 1;
-    }
-    return -1;
-}
+static int corrupt_status(int32_t s) { return s != 0; }
 
 int main(int argc, char **argv) {
     long K = 4096;
@@ -66,115 +38,46 @@ int main(int argc, char **argv) {
         return EXIT_ERROR;
     }
     if (s5gpu_init(0) != S5GPU_OK) return die("no GPU");
-    slow5_file_t *in = slow5_open(path, "r");
-    if (!in) { fprintf(stderr, "s5events: cannot open %s\n", path); return EXIT_ERROR; }
-    if (in->format != SLOW5_FORMAT_BINARY) { fprintf(stderr, "s5events: %s is SLOW5 text: convert it to BLOW5 first\n", path); return EXIT_ERROR; }
-    const int rec = rec_code_of(in->compress->record_press->method), sig = sig_code_of(in->compress->signal_press->method);
-    const s5gpu_event_params_t dna = {3, 6, 1.4, 9.0, 0.2}, rnap = {7, 14, 2.5, 9.0, 1.0};
-    const s5gpu_event_params_t *P = rna ? &rnap : &dna;
+    slow5_file_t *in = open_blow5(path, NULL);
+    if (!in) return EXIT_ERROR;
+    const s5gpu_event_params_t *P = event_params(rna);
     const int mode = pa ? S5GPU_NORM_PA : S5GPU_NORM_RAW;
-    static char obuf[1 << 20];
-    setvbuf(stdout, obuf, _IOFBF, sizeof obuf);
+    big_stdout();
 
-    void **mem = (void **)calloc((size_t)K, sizeof(void *));
-    size_t *len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
-    uint64_t *first = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)K + 1)), *rec_pos = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)K);
-    uint32_t *rec_len = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)K);
-    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K), *ist = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
-    char *ids = (char *)malloc((size_t)K * PITCH);
-    uint16_t *id_len = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)K);
-    void **line = (void **)calloc((size_t)K, sizeof(void *));
-    size_t *line_len = (size_t *)malloc(sizeof(size_t) * (size_t)K);
-    if (!mem || !len || !first || !rec_pos || !rec_len || !st || !ist || !ids || !id_len || !line || !line_len) return die("out of memory");
-    size_t rows_cap = 1 << 16, chunk_cap = 0;
+    batch_t bt;
+    if (batch_open(&bt, in, path, K) != 0) return EXIT_ERROR;
+    uint64_t *first = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)K + 1));
+    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
+    size_t rows_cap = 1 << 16;
     s5gpu_event_t *rows = (s5gpu_event_t *)malloc(sizeof(s5gpu_event_t) * rows_cap);
-    uint8_t *chunk = NULL;
-    s5gpu_skim_layout_t *L = NULL;
-    if (!rows) return die("out of memory");
-    int code = EXIT_SUCCESS, at_end = 0;
-    uint64_t n_done = 0;
-    while (!at_end) {
-        uint32_t n = 0;
-        size_t bytes = 0;
-        while (n < (uint32_t)K) {
-            mem[n] = slow5_get_next_mem(&len[n], in);
-            if (!mem[n]) {
-                if (slow5_errno != SLOW5_ERR_EOF) { fprintf(stderr, "s5events: cannot read record %" PRIu64 " of %s\n", n_done + n, path); return EXIT_ERROR; }
-                at_end = 1;
-                break;
-            }
-            if (len[n] > 0xFFFFFF00u) { fprintf(stderr, "s5events: record %" PRIu64 " is too large\n", n_done + n); return EXIT_ERROR; }
-            bytes += 8 + len[n];
-            n++;
-        }
-        if (n == 0) break;
-        int rc = s5gpu_signal_events_batch(n, (const void *const *)mem, len, rec, sig, P, mode, rows, rows_cap, first, st);
+    if (!first || !st || !rows) return die("out of memory");
+    int code = EXIT_SUCCESS;
+    int64_t n;
+    while ((n = batch_next(&bt)) > 0) {
+        int rc = s5gpu_signal_events_batch((uint32_t)n, (const void *const *)bt.mem, bt.len, bt.rec, bt.sig, P, mode, rows, rows_cap, first, st);
         if (rc == S5GPU_ERR_NOMEM) {
             rows_cap = (size_t)first[0] + (size_t)first[0] / 4;
             free(rows);
             rows = (s5gpu_event_t *)malloc(sizeof(s5gpu_event_t) * rows_cap);
             if (!rows) return die("out of memory");
-            rc = s5gpu_signal_events_batch(n, (const void *const *)mem, len, rec, sig, P, mode, rows, rows_cap, first, st);
+            rc = s5gpu_signal_events_batch((uint32_t)n, (const void *const *)bt.mem, bt.len, bt.rec, bt.sig, P, mode, rows, rows_cap, first, st);
         }
         if (rc != S5GPU_OK && rc != S5GPU_ERR_DATA) return die("event detection failed");
-        /* the ids: the device id path over the records framed in one buffer; what it leaves (zstd, long ids) is the first column of a skim line */
-        for (uint32_t i = 0; i < n; i++) ist[i] = 5;
-        if (rec != S5GPU_REC_ZSTD) {
-            if (bytes + 64 > chunk_cap) {
-                if (chunk) s5gpu_host_free(chunk);
-                chunk_cap = bytes + bytes / 4 + 64;
-                chunk = (uint8_t *)s5gpu_host_alloc(chunk_cap);
-                if (!chunk) return die("out of memory");
-            }
-            size_t p = 0;
-            for (uint32_t i = 0; i < n; i++) {
-                const uint64_t sz = len[i];
-                memcpy(chunk + p, &sz, 8);
-                memcpy(chunk + p + 8, mem[i], len[i]);
-                rec_pos[i] = p + 8; rec_len[i] = (uint32_t)len[i];
-                p += 8 + len[i];
-            }
-            if (s5gpu_record_ids_stream(n, chunk, p, rec_pos, rec_len, rec, PITCH, ids, id_len, ist) != S5GPU_OK) return die("read ids failed");
+        if (batch_ids(&bt, st, corrupt_status, 0) != 0) return EXIT_ERROR;
+        for (uint32_t i = 0; i < (uint32_t)n; i++) {
+            if (st[i] != 0) { batch_corrupt(&bt, i, st[i]); code = EXIT_CORRUPT; continue; }
+            size_t idl;
+            const char *id = batch_id(&bt, i, &idl);
+            for (uint64_t e = first[i]; e < first[i + 1]; e++)
+                printf("%.*s\t%" PRIu64 "\t%u\t%u\t%.6g\t%.6g\n", (int)idl, id, e - first[i], rows[e].start, rows[e].start + rows[e].length,
+                       (double)rows[e].mean, (double)rows[e].stdv);
         }
-        for (uint32_t i = 0; i < n; i++) {
-            line[i] = NULL;
-            if (ist[i] == 0 || st[i] != 0) continue;              /* (a corrupt record has no skim line either) */
-            if (!L) {
-                L = (s5gpu_skim_layout_t *)calloc(1, sizeof *L);
-                if (!L) return die("out of memory");
-                if (rid_layout(in->header->data, in->header->data_len, L) != 0) return die("the header names no column types");
-            }
-            const void *r1 = mem[i];
-            int32_t s1 = 0;
-            if (s5gpu_skim_batch(1, &r1, &len[i], rec, sig, L, &line[i], &line_len[i], &s1) != S5GPU_OK || !line[i]) return die("read ids failed");
-        }
-        for (uint32_t i = 0; i < n; i++) {
-            const char *id = NULL;
-            size_t idl = 0;
-            if (ist[i] == 0) { id = ids + (size_t)i * PITCH; idl = id_len[i]; }
-            else if (line[i]) {
-                const char *tab = (const char *)memchr(line[i], '\t', line_len[i]);
-                id = (const char *)line[i]; idl = tab ? (size_t)(tab - id) : line_len[i];
-            }
-            if (st[i] != 0) {
-                if (id) fprintf(stderr, "s5events: read %.*s is corrupt (status %d)\n", (int)idl, id, st[i]);
-                else fprintf(stderr, "s5events: record %" PRIu64 " of the file is corrupt (status %d)\n", n_done + i, st[i]);
-                code = EXIT_CORRUPT;
-            } else {
-                for (uint64_t e = first[i]; e < first[i + 1]; e++)
-                    printf("%.*s\t%" PRIu64 "\t%u\t%u\t%.6g\t%.6g\n", (int)idl, id, e - first[i], rows[e].start, rows[e].start + rows[e].length,
-                           (double)rows[e].mean, (double)rows[e].stdv);
-            }
-            free(line[i]);
-            free(mem[i]);
-            mem[i] = NULL;
-        }
-        n_done += n;
+        batch_release(&bt);
     }
+    if (n < 0) return EXIT_ERROR;
     if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5events: write failed\n"); return EXIT_ERROR; }
-    if (chunk) s5gpu_host_free(chunk);
+    batch_close(&bt);
     slow5_close(in);
-    free(mem); free(len); free(first); free(rec_pos); free(rec_len); free(st); free(ist); free(ids); free(id_len); free(line); free(line_len);
-    free(rows); free(L);
+    free(first); free(st); free(rows);
     return code;
 }

@@ -27,8 +27,8 @@
 #include <time.h>
 #include <unistd.h>
 
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+#define S5TOOL "s5get"
+#include "s5tool.h"                  /* rec_code_of, sig_code_of */
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static int g_timing;                 /* S5VIEW_TIMING=1: a timeline of the process on stderr (as s5view's) */
@@ -38,8 +38,6 @@ static int die(const char *what) {
     fprintf(stderr, "s5get: %s (slow5_errno %d; %s)\n", what, slow5_errno, s5gpu_last_error());
     return EXIT_FAILURE;
 }
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
 
 #define GSLOT 8
 enum { ST_EMPTY = 0, ST_FILLED, ST_BUSY, ST_DONE };

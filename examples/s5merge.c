@@ -22,15 +22,13 @@
 #include <string.h>
 #include <unistd.h>
 
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+#define S5TOOL "s5merge"
+#include "s5tool.h"                  /* rec_code_of, sig_code_of */
 
 static int die(const char *what, const char *arg) {
     fprintf(stderr, "s5merge: %s%s%s (slow5_errno %d; %s)\n", what, arg ? " " : "", arg ? arg : "", slow5_errno, s5gpu_last_error());
     return EXIT_FAILURE;
 }
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
 
 /* ---- a header as the merge needs it ---- */
 typedef struct { char *name; char **val; } attr_t;                     /* val[g] = value of read group g (NULL: none) */

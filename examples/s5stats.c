@@ -5,9 +5,9 @@
  *   s5stats file.[b|s]low5
  *       the reference's nine lines (src/stats.c): file path (as given), version, format, the two presses, read groups, auxiliary fields
  *       (count and names; a file without any prints a bare "auxiliary fields" line) and the number of records.  No GPU call is made: the
- *       records of a BLOW5 file are counted by their framing (the reader of s5sum.c / s5skim.c, here over plain memory), those of a SLOW5
- *       file line by line.  Exit 1 with a message on a file that cannot be opened, whose version is above 1.0.0, with a damaged frame or
- *       without the end-of-file marker.
+ *       records of a BLOW5 file are counted by their framing (reader_t of s5tool.h, here over plain memory), those of a SLOW5 file
+ *       line by line (textbatch_t, the same way).  Exit 1 with a message on a file that cannot be opened, whose version is above 1.0.0,
+ *       with a damaged frame or without the end-of-file marker.
  *   s5stats --signal [--hist FILE] [-K batch] file.[b|s]low5
  *       the nine lines, then tab-separated lines from the accumulator:
  *         total samples, sample min, sample max, sample sum, sample sum of squares (modulo 2^64), constant low bits (the trailing zero bits
@@ -21,117 +21,16 @@
  *       A record that does not decode: exit 1, and nothing of the signal section is printed.
  */
 #define _GNU_SOURCE
-#include <inttypes.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <sys/stat.h>
-
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+#define S5TOOL "s5stats"
+#include "s5tool.h"
 
 static int fail(const char *what) {
     fprintf(stderr, "s5stats: %s\n", what);
     return -1;
 }
 static int fail_gpu(const char *what) {
-    fprintf(stderr, "s5stats: %s (%s)\n", what, s5gpu_last_error());
+    complain(what);
     return -1;
-}
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
-
-/* ---- the records of a BLOW5 file, a chunk at a time (s5sum.c, s5skim.c): [u64 size][bytes] framed in place, a record the chunk's end cuts
- * carried over.  pinned: the chunk buffer comes from s5gpu_host_alloc (the signal form); else from malloc (the plain form makes no GPU call) ---- */
-typedef struct {
-    FILE *fp;
-    uint64_t pos, end;           /* file offset of the next unread byte; of the end-of-file marker */
-    uint8_t *buf;
-    size_t cap, have, used;      /* bytes in buf; bytes of buf already handed out */
-    uint64_t *rec_pos;
-    uint32_t *rec_len;
-    uint32_t K;
-    int pinned;
-} reader_t;
-
-static uint8_t *chunk_alloc(const reader_t *R, size_t bytes) { return (uint8_t *)(R->pinned ? s5gpu_host_alloc(bytes) : malloc(bytes)); }
-static void chunk_free(const reader_t *R, uint8_t *p) { if (R->pinned) s5gpu_host_free(p); else free(p); }
-
-static int refill(reader_t *R, size_t need) {
-    const size_t keep = R->have - R->used;
-    if (need > R->cap) {                                   /* a record larger than the chunk: a larger buffer */
-        size_t cap = R->cap;
-        while (cap < need) cap *= 2;
-        uint8_t *b = chunk_alloc(R, cap + 64);
-        if (!b) return -1;
-        memcpy(b, R->buf + R->used, keep);
-        chunk_free(R, R->buf);
-        R->buf = b;
-        R->cap = cap;
-    } else if (keep) {
-        memmove(R->buf, R->buf + R->used, keep);
-    }
-    R->have = keep;
-    R->used = 0;
-    uint64_t want = R->cap - R->have;
-    if (want > R->end - R->pos) want = R->end - R->pos;
-    if (want && fread(R->buf + R->have, 1, (size_t)want, R->fp) != want) return -1;
-    R->pos += want;
-    R->have += (size_t)want;
-    return 0;
-}
-
-/* frames up to K records of the buffer: their count, 0 at the end of the records, -1 on a damaged file */
-static int64_t next_batch(reader_t *R) {
-    uint32_t n = 0;
-    size_t p = R->used;
-    for (;;) {
-        while (n < R->K && p + 8 <= R->have) {
-            uint64_t sz;
-            memcpy(&sz, R->buf + p, 8);
-            if (sz > 0xFFFFFF00ull) return -1;
-            if (p + 8 + sz > R->have) break;
-            R->rec_pos[n] = p + 8;
-            R->rec_len[n] = (uint32_t)sz;
-            n++;
-            p += 8 + sz;
-        }
-        if (n || R->pos == R->end) break;
-        /* nothing framed: the next record is cut by the chunk's end (or the buffer is empty) */
-        size_t need = R->have - R->used;
-        if (need >= 8) { uint64_t sz; memcpy(&sz, R->buf + R->used, 8); if (sz > 0xFFFFFF00ull) return -1; need = 8 + sz; }
-        if (need > R->have - R->used + (R->end - R->pos)) return -1;   /* the record runs past the end-of-file marker */
-        if (refill(R, need < R->cap ? R->cap : need) != 0) return -1;
-        p = R->used;
-    }
-    if (n == 0 && R->have != R->used) return -1;           /* bytes left over that make no record */
-    R->used = p;
-    return n;
-}
-
-static int reader_open(reader_t *R, slow5_file_t *in, const char *path, uint32_t K, size_t chunk, int pinned) {
-    memset(R, 0, sizeof *R);
-    R->pinned = pinned;
-    struct stat st;
-    if (stat(path, &st) != 0 || (uint64_t)st.st_size < in->meta.start_rec_offset + 5) return -1;
-    char eof[5];
-    R->fp = in->fp;
-    if (fseeko(R->fp, (off_t)st.st_size - 5, SEEK_SET) != 0 || fread(eof, 1, 5, R->fp) != 5 || memcmp(eof, "5WOLB", 5) != 0) return -1;
-    if (fseeko(R->fp, (off_t)in->meta.start_rec_offset, SEEK_SET) != 0) return -1;
-    R->pos = in->meta.start_rec_offset;
-    R->end = (uint64_t)st.st_size - 5;
-    if (chunk > R->end - R->pos + 4096) chunk = (size_t)(R->end - R->pos) + 4096;   /* a small file does not need the whole chunk */
-    R->cap = chunk;
-    R->buf = chunk_alloc(R, chunk + 64);
-    R->K = K;
-    R->rec_pos = (uint64_t *)malloc(sizeof(uint64_t) * K);
-    R->rec_len = (uint32_t *)malloc(sizeof(uint32_t) * K);
-    return R->buf && R->rec_pos && R->rec_len ? 0 : -1;
-}
-static void reader_close(reader_t *R) {
-    if (R->buf) chunk_free(R, R->buf);
-    free(R->rec_pos);
-    free(R->rec_len);
 }
 
 static int report_bad_record(const int32_t *status, uint32_t n) {
@@ -167,55 +66,29 @@ done:
 
 /* the record lines of a SLOW5 ASCII file: counted; with h, K lines at a time -> BLOW5 records (none, none) on the device -> back -> the accumulator */
 static int walk_slow5(slow5_file_t *in, uint32_t K, size_t chunk, void *h, int64_t *count) {
-    if (!h) {
-        size_t bytes;
-        char *mem;
-        while ((mem = (char *)slow5_get_next_mem(&bytes, in))) { free(mem); (*count)++; }
-        return slow5_errno == SLOW5_ERR_EOF ? 0 : fail("cannot read a record line");
-    }
     const struct slow5_aux_meta *am = in->header->aux_meta;
-    size_t tcap = chunk, ocap = chunk;
-    uint8_t *txt = (uint8_t *)s5gpu_host_alloc(tcap + 64), *out = (uint8_t *)s5gpu_host_alloc(ocap);
-    uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)K + 1));
-    uint64_t *line_pos = (uint64_t *)malloc(sizeof(uint64_t) * K), *rec_pos = (uint64_t *)malloc(sizeof(uint64_t) * K);
-    uint32_t *line_len = (uint32_t *)malloc(sizeof(uint32_t) * K), *rec_len = (uint32_t *)malloc(sizeof(uint32_t) * K);
-    int32_t *st = (int32_t *)malloc(sizeof(int32_t) * K);
-    char *held = NULL;                                     /* a line read but not yet placed: the chunk was full */
-    size_t held_len = 0;
-    int at_end = 0, rc = -1;
-    if (!txt || !out || !off || !line_pos || !rec_pos || !line_len || !rec_len || !st) { fail_gpu("out of memory"); goto done; }
-    while (!at_end || held) {
-        uint32_t n = 0;
-        size_t have = 0;
-        while (n < K) {
-            if (!held) {
-                held = (char *)slow5_get_next_mem(&held_len, in);
-                if (!held) {
-                    if (slow5_errno != SLOW5_ERR_EOF) { fail("cannot read a record line"); goto done; }
-                    at_end = 1;
-                    break;
-                }
-            }
-            if (held_len > 0xFFFFFF00u) { fail("a record line is too long"); goto done; }
-            if (have + held_len + 32 > tcap) {
-                if (n) break;                              /* this batch is full: the line opens the next one */
-                while (have + held_len + 32 > tcap) tcap *= 2;
-                s5gpu_host_free(txt);
-                txt = (uint8_t *)s5gpu_host_alloc(tcap + 64);
-                if (!txt) { fail_gpu("out of memory"); goto done; }
-            }
-            memcpy(txt + have, held, held_len);
-            line_pos[n] = have;
-            line_len[n] = (uint32_t)held_len;
-            have += held_len;
-            n++;
-            free(held);
-            held = NULL;
-        }
-        if (n == 0) break;
+    textbatch_t T;
+    size_t ocap = chunk;
+    uint8_t *out = NULL;
+    uint64_t *off = NULL, *rec_pos = NULL;
+    uint32_t *rec_len = NULL;
+    int32_t *st = NULL;
+    int rc = -1;
+    if (textbatch_open(&T, K, chunk, h != NULL) != 0) goto done;
+    out = h ? (uint8_t *)s5gpu_host_alloc(ocap) : NULL;
+    off = (uint64_t *)malloc(sizeof(uint64_t) * ((size_t)K + 1));
+    rec_pos = (uint64_t *)malloc(sizeof(uint64_t) * K);
+    rec_len = (uint32_t *)malloc(sizeof(uint32_t) * K);
+    st = (int32_t *)malloc(sizeof(int32_t) * K);
+    if ((h && !out) || !off || !rec_pos || !rec_len || !st) { fail_gpu("out of memory"); goto done; }
+    for (;;) {
+        const int64_t nl = textbatch_next(&T, in);
+        if (nl < 0) goto done;
+        if (nl == 0) break;
+        const uint32_t n = (uint32_t)nl;
         *count += n;
-        memset(txt + have, 0, 32);
-        int arc = s5gpu_ascii_to_blow5_stream(n, txt, have, line_pos, line_len, am ? am->num : 0, am ? am->types : NULL, S5GPU_REC_NONE, S5GPU_SIG_NONE,
+        if (!h) continue;
+        int arc = s5gpu_ascii_to_blow5_stream(n, T.txt, T.have, T.line_pos, T.line_len, am ? am->num : 0, am ? am->types : NULL, S5GPU_REC_NONE, S5GPU_SIG_NONE,
                                               NULL, 0, out, ocap, off, st);
         if (arc == S5GPU_ERR_NOMEM) {
             const size_t need = (size_t)off[0];
@@ -223,7 +96,7 @@ static int walk_slow5(slow5_file_t *in, uint32_t K, size_t chunk, void *h, int64
             ocap = need + need / 4;
             out = (uint8_t *)s5gpu_host_alloc(ocap);
             if (!out) { fail_gpu("out of memory"); goto done; }
-            arc = s5gpu_ascii_to_blow5_stream(n, txt, have, line_pos, line_len, am ? am->num : 0, am ? am->types : NULL, S5GPU_REC_NONE, S5GPU_SIG_NONE,
+            arc = s5gpu_ascii_to_blow5_stream(n, T.txt, T.have, T.line_pos, T.line_len, am ? am->num : 0, am ? am->types : NULL, S5GPU_REC_NONE, S5GPU_SIG_NONE,
                                               NULL, 0, out, ocap, off, st);
         }
         if (arc != S5GPU_OK) { fail_gpu("a record line cannot be parsed"); goto done; }
@@ -234,10 +107,9 @@ static int walk_slow5(slow5_file_t *in, uint32_t K, size_t chunk, void *h, int64
     }
     rc = 0;
 done:
-    if (txt) s5gpu_host_free(txt);
+    textbatch_close(&T);
     if (out) s5gpu_host_free(out);
-    free(held);
-    free(off); free(line_pos); free(rec_pos); free(line_len); free(rec_len); free(st);
+    free(off); free(rec_pos); free(rec_len); free(st);
     return rc;
 }
 

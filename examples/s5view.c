@@ -28,8 +28,8 @@
 #include <time.h>
 #include <unistd.h>
 
-#include "slow5_compat.h"
-#include "slow5gpu.h"
+#define S5TOOL "s5view"
+#include "s5tool.h"                  /* rec_code_of, sig_code_of */
 
 /* S5VIEW_TIMING=1: where the wall time of the whole process goes (stderr, seconds since main() was entered) */
 static double g_t_main;
@@ -173,8 +173,6 @@ typedef struct {
     char why[256];
     uint64_t records;
 } fpipe_t;
-static int rec_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_ZLIB ? S5GPU_REC_ZLIB : m == SLOW5_COMPRESS_ZSTD ? S5GPU_REC_ZSTD : S5GPU_REC_NONE; }
-static int sig_code_of(enum slow5_press_method m) { return m == SLOW5_COMPRESS_SVB_ZD ? S5GPU_SIG_SVB_ZD : m == SLOW5_COMPRESS_EX_ZD ? S5GPU_SIG_EX_ZD : S5GPU_SIG_NONE; }
 static void fpipe_fail(fpipe_t *P, const char *what) {
     pthread_mutex_lock(&P->mu);
     if (!P->failed) { P->failed = 1; snprintf(P->why, sizeof P->why, "%s (%s)", what, s5gpu_last_error()); }

@@ -61,10 +61,11 @@ def build(force=False, verbose=False):
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
     # the view / get / merge / skim / sum / stats / diff / events / map / align / pileup / refine / extend / contrast loop examples = the end-to-end harnesses (plain C against the public headers)
+    tool_h = os.path.join(ROOT, "examples", "s5tool.h")    # what the tools share: each of them includes it
     for name in ("s5view", "s5get", "s5merge", "s5skim", "s5sum", "s5stats", "s5diff", "s5events", "s5map", "s5align", "s5pileup", "s5refine", "s5extend", "s5contrast"):
         ex = os.path.join(ROOT, "examples", name + ".c")
         exe = os.path.join(HERE, name)
-        if os.path.exists(ex) and (force or _newer(exe, [ex, LIB] + deps)):
+        if os.path.exists(ex) and (force or _newer(exe, [ex, tool_h, LIB] + deps)):
             cmd = ["gcc", "-O2", "-g", "-Wall", "-std=c11", "-I", os.path.join(ROOT, "include"), ex, "-o", exe, "-pthread",
                    "-L", HERE, "-lslow5gpu", "-lm", "-Wl,-rpath," + HERE]
             if verbose:
