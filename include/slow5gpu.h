@@ -1200,6 +1200,62 @@ int s5gpu_contrast_add_batch(void *handle, int side, uint32_t n, const void *con
  * ends the handle, whatever it returns.  rows_out NULL: the handle is abandoned. */
 int s5gpu_contrast_close(void *handle, void *acc_a_out, void *acc_b_out, s5gpu_pile_contrast_t *rows_out);
 
+/* ---- sites: per-read levels at chosen reference columns, each held against a control histogram (docs/codecs.md §4.25) ----
+ * sites[0 .. M) are reference columns, strictly increasing, each < R.  Which reads are USED, SKIPPED and BAD is "pileup of whole reads"'
+ * rule with ev_skip = 0.  The cell of read k at site t sums the rows i of a used read with lo[i] <= sites[t] <= hi[i]; the matrix is
+ * site-major, out[t * n + k].  Sums and a minimum only: the bytes do not depend on the order of segments, calls or atomics. */
+typedef struct s5gpu_site_cell {       /* 16 bytes */
+    int64_t sum_q;                     /* the sum of q[i] over the rows that cross the site */
+    uint32_t cells;                    /* how many rows do */
+    uint32_t row0;                     /* the smallest such i; 0xFFFFFFFF in the empty entry {0, 0, 0xFFFFFFFF} */
+} s5gpu_site_cell_t;
+typedef struct s5gpu_site_score {      /* 16 bytes: a cell held against column sites[t] of a control histogram with counts C */
+    int16_t level;                     /* floor((2 sum_q + cells) / (2 cells)): the mean rounded half up */
+    uint16_t flags;                    /* S5GPU_SITE_* */
+    uint32_t below, above, n;          /* with b the bin of level: the sum of C_x over x <= b, over x >= b, over all x; 0xFFFFFFFF: that or more */
+} s5gpu_site_score_t;
+#define S5GPU_SITE_NO_CELL 1u          /* the read has no cell at the site: level = below = above = 0, n is filled */
+#define S5GPU_SITE_EMPTY 2u            /* n = 0 */
+#define S5GPU_SITE_COLUMN 64u          /* sites[t] >= R: no column is read and it counts as empty (S5GPU_SITE_EMPTY is set beside it) */
+#define S5GPU_SITE_HEAD 128u           /* the histogram's head disagrees with R or with 64 bins: set in every row, and nothing else is */
+/* Writes all M n cells to cells_out (DEVICE memory, 16-byte aligned): the empty entries first, then the cells of the n reads of a ragged
+ * batch as s5gpu_pile_hist_accum_long_dev takes it, at the M columns sites_dev (DEVICE memory) lists.  verdict_out (DEVICE memory, [n], or
+ * NULL): 0 used, 1 skipped, 2 bad.  Asynchronous on hip_stream; writes nothing but cells_out, verdict_out and work
+ * (s5gpu_pileup_long_work_bytes(n, total_rows); a work area per call in flight).  A list that is not strictly increasing gives unspecified
+ * counts inside cells_out, never an access outside the arrays; the host-side callers (the handle, the Python module, the tool) validate it.
+ * n = 0: S5GPU_OK and nothing is launched.  S5GPU_ERR_ARG, nothing launched: a NULL or misaligned pointer (first: 8 bytes; work, cells_out:
+ * 16), R outside 1 .. 2^22, total_rows above 2^40, M outside 1 .. 65536, M n above 2^27.  S5GPU_ERR_NOMEM, nothing written: a short work
+ * area.  "pileup_long_seg" and "pileup_long_grid" of s5gpu_set_option count as they do for the table; neither changes the result. */
+int s5gpu_site_cells_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows, uint32_t R,
+                              const int32_t *lo, const int32_t *hi, const int32_t *status, const uint32_t *sites_dev, uint32_t M, void *work,
+                              size_t work_bytes, s5gpu_site_cell_t *cells_out, uint32_t *verdict_out, void *hip_stream);
+/* Writes the M n score rows of cells (as s5gpu_site_cells_long_dev left them) against hist, a histogram of "contrast" with R columns, to out
+ * (DEVICE memory, 16-byte aligned as cells).  The head is read on the device.  All integer; below / n is an empirical share of the control's
+ * cells, not a calibrated probability, and a read that was itself added to the control counts among its own control.  Asynchronous on
+ * hip_stream.  n = 0: S5GPU_OK and nothing is launched.  S5GPU_ERR_ARG: a NULL or misaligned pointer, R outside 1 .. 2^22, M outside
+ * 1 .. 65536, M n above 2^27. */
+int s5gpu_site_score_dev(const s5gpu_site_cell_t *cells, uint32_t n, const uint32_t *sites_dev, uint32_t M, const void *hist, uint32_t R,
+                         s5gpu_site_score_t *out, void *hip_stream);
+/* A per-file handle over the chain of s5gpu_pileup_open_whole: the site list and an empty control histogram on the first device in use.
+ * NULL: the cases of s5gpu_contrast_open, M outside 1 .. 65536, a list that is not strictly increasing, a column >= R. */
+void *s5gpu_sites_open(const s5gpu_event_params_t *event_params, const s5gpu_map_params_t *map_params, const s5gpu_band_params_t *band_params,
+                       size_t scratch_max, const int16_t *ref_host, uint32_t R, const uint32_t *sites_host, uint32_t M, int32_t q0, uint32_t shift);
+/* As s5gpu_contrast_set_refine: the control, the cells and the scores are then fed with the refined queries, paths and statuses. */
+int s5gpu_sites_set_refine(void *handle, const s5gpu_refine_params_t *refine_params);
+/* The chain of s5gpu_pileup_add_batch_whole into the control histogram only.  A corrupt record: S5GPU_ERR_DATA, the rest added. */
+int s5gpu_sites_add_control(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                            int32_t *status_out);
+/* Replaces the control with a histogram made elsewhere (HOST memory, s5gpu_pile_hist_bytes(R)).  S5GPU_ERR_ARG: a head that disagrees with
+ * the handle's R, q0, shift or 64 bins. */
+int s5gpu_sites_set_control(void *handle, const void *hist_host);
+/* The chain into cells_out (HOST memory, [M][n], record k at [t * n + k]) and, where not NULL, scores_out ([M][n], against the control as it
+ * stands).  Records that never reached the device have empty entries (and the scores of one).  The control is not changed.  A corrupt
+ * record: S5GPU_ERR_DATA, the rest of the batch valid, the handle usable.  S5GPU_ERR_ARG: a NULL handle or cells_out, M n above 2^27. */
+int s5gpu_sites_add_batch(void *handle, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method, int sig_method,
+                          s5gpu_ext_row_t *ext_rows_out, s5gpu_site_cell_t *cells_out, s5gpu_site_score_t *scores_out, int32_t *status_out);
+/* Downloads the control histogram to hist_out where not NULL (HOST memory, s5gpu_pile_hist_bytes(R)) and ends the handle, whatever it returns. */
+int s5gpu_sites_close(void *handle, void *hist_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ PileHistHead = np.dtype([("cells", "<u8"), ("reads_used", "<u8"), ("reads_skippe
 PileContrast = np.dtype([("n_a", "<u4"), ("n_b", "<u4"), ("depth_a", "<u4"), ("depth_b", "<u4"), ("ks_num", "<u8"), ("ov_num", "<u8"), ("ks_bin", "<u2"),
                          ("med_a", "<u2"), ("med_b", "<u2"), ("flags", "<u2")])
 assert PileHistHead.itemsize == 64 and PileContrast.itemsize == 40
+# s5gpu_site_cell_t / s5gpu_site_score_t: an entry of the read x site matrix of "sites" and its row against a control (slow5tools_amd/sites.py)
+SiteCell = np.dtype([("sum_q", "<i8"), ("cells", "<u4"), ("row0", "<u4")])
+SiteScore = np.dtype([("level", "<i2"), ("flags", "<u2"), ("below", "<u4"), ("above", "<u4"), ("n", "<u4")])
+assert SiteCell.itemsize == 16 and SiteScore.itemsize == 16
 STATUS_FIT_FLAT, STATUS_FIT_RANGE = 21, 22
 # s5gpu_fit_t: the fit of "refine" (slow5tools_amd/refine.py)
 Fit = np.dtype([("a", "<f8"), ("b", "<f8"), ("n", "<i8"), ("sq", "<i8"), ("sr", "<i8"), ("sqq", "<i8"), ("sqr", "<i8"), ("srr", "<i8")])
@@ -344,6 +348,16 @@ def lib():
                                             C.c_size_t, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.s5gpu_pileup_set_refine.argtypes = [vp, C.POINTER(RefineParams)]
     L.s5gpu_contrast_set_refine.argtypes = [vp, C.POINTER(RefineParams)]
+    # sites: the read x site matrix of a ragged batch, its scores against a control histogram, and the per-file handle
+    L.s5gpu_site_cells_long_dev.argtypes = [u32, vp, vp, vp, u64, u32, vp, vp, vp, vp, u32, vp, C.c_size_t, vp, vp, vp]
+    L.s5gpu_site_score_dev.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp]
+    L.s5gpu_sites_open.restype = vp
+    L.s5gpu_sites_open.argtypes = [C.POINTER(EventParams), C.POINTER(MapParams), C.POINTER(BandParams), C.c_size_t, vp, u32, vp, u32, i32, u32]
+    L.s5gpu_sites_set_refine.argtypes = [vp, C.POINTER(RefineParams)]
+    L.s5gpu_sites_add_control.argtypes = [vp, u32, vp, vp, i32, i32, vp]
+    L.s5gpu_sites_set_control.argtypes = [vp, vp]
+    L.s5gpu_sites_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.s5gpu_sites_close.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -380,4 +394,6 @@ EXPORTS = [
     "s5gpu_contrast_add_batch", "s5gpu_contrast_close",
     "s5gpu_path_fit_long_work_bytes", "s5gpu_path_fit_long_dev", "s5gpu_extend_refine_work_bytes", "s5gpu_extend_refine_dev", "s5gpu_extend_refine_batch",
     "s5gpu_pileup_set_refine", "s5gpu_contrast_set_refine",
+    "s5gpu_site_cells_long_dev", "s5gpu_site_score_dev", "s5gpu_sites_open", "s5gpu_sites_set_refine", "s5gpu_sites_add_control", "s5gpu_sites_set_control",
+    "s5gpu_sites_add_batch", "s5gpu_sites_close",
 ]

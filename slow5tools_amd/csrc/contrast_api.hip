@@ -85,7 +85,7 @@ extern "C" int s5gpu_contrast_add_batch(void *handle, int side, uint32_t n, cons
     if (!h) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
     if (side != 0 && side != 1) { s5gpu_set_error("%s: side %d (0 or 1)", who, side); return S5GPU_ERR_ARG; }
     h->c.started = true;
-    return pilek::add_batch_whole(who, h->c, h->d_acc[side], h->d_hist[side], n, rec, rec_len, rec_method, sig_method, map_rows_out, ext_rows_out, status_out);
+    return pilek::add_batch_whole(who, h->c, h->d_acc[side], h->d_hist[side], nullptr, n, rec, rec_len, rec_method, sig_method, map_rows_out, ext_rows_out, status_out);
 }
 
 extern "C" int s5gpu_contrast_set_refine(void *handle, const s5gpu_refine_params_t *rp) {

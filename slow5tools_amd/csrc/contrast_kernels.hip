@@ -77,14 +77,6 @@ __global__ __launch_bounds__(s5::NT) void k_pile_hist_accum(PileLongArgs A, uint
 
 namespace {
 
-__device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(v, d);
-        if (lane >= (uint32_t)d) v += t;
-    }
-    return v;
-}
 // the smallest lane whose flag is set (one is: lane 63's)
 __device__ __forceinline__ uint32_t first_lane(bool flag) {
     const uint64_t m = __ballot(flag ? 1 : 0);

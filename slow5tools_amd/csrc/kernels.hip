@@ -36,6 +36,7 @@ namespace dfk { int set_option(const char *key, long value); }   // diff_kernels
 namespace dtwk { int path_set_option(const char *key, long value); }   // dtw_path_api.hip: which passes the path call launches
 namespace pilek { int set_option(const char *key, long value); }   // pileup_kernels.hip: the pileup's LDS windows, grids, segments, sort and passes
 namespace pilek { int hist_set_option(const char *key, long value); }   // contrast_kernels.hip: the level histograms' window and grid
+namespace pilek { int site_set_option(const char *key, long value); }   // sites_kernels.hip: which passes the site call launches
 namespace refk { int long_set_option(const char *key, long value); }   // refine_long_kernels.hip: which passes the whole-read refine launches
 namespace bandk { int set_option(const char *key, long value); }   // band_kernels.hip: which passes the band call launches
 extern uint32_t s5host_generation;                    // host_api.hip: bumped by s5gpu_shutdown
@@ -1974,7 +1975,7 @@ extern "C" int s5gpu_set_option(const char *key, long value) {
         if (key && strcmp(key, o.name) == 0 && value >= o.lo && value <= o.hi) { *o.var = (uint32_t)value & o.keep; return S5GPU_OK; }
     if (s5host_set_option(key, value) == S5GPU_OK || fsk::set_option(key, value) == S5GPU_OK || dfk::set_option(key, value) == S5GPU_OK ||
         dtwk::path_set_option(key, value) == S5GPU_OK || pilek::set_option(key, value) == S5GPU_OK || pilek::hist_set_option(key, value) == S5GPU_OK ||
-        refk::long_set_option(key, value) == S5GPU_OK || bandk::set_option(key, value) == S5GPU_OK)
+        pilek::site_set_option(key, value) == S5GPU_OK || refk::long_set_option(key, value) == S5GPU_OK || bandk::set_option(key, value) == S5GPU_OK)
         return S5GPU_OK;
     s5gpu_set_error("s5gpu_set_option: unknown option");
     return S5GPU_ERR_ARG;

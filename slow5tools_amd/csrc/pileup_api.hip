@@ -3,8 +3,8 @@
 // (the front of dtw_host.h -> sDTW with the start -> the paths -> the query's event rows gathered) and adds the batch to the handle's
 // accumulator with k_pileup; the rows and statuses are all that comes back.  s5gpu_pileup_close makes the one download of the table.
 // Whole reads (§4.22): the ragged call, and a handle of a second kind whose add runs the device side of s5gpu_extend_batch (band_host.h)
-// and adds the ragged paths it leaves on the device.  The checks of a ragged call and that add are shared with contrast_api.hip
-// (pileup_host.h), which feeds a level histogram (§4.23) from the same run.
+// and adds the ragged paths it leaves on the device.  The checks of a ragged call and that add are shared with contrast_api.hip and
+// sites_api.hip (pileup_host.h), which feed a level histogram (§4.23) and the site matrix (§4.25) from the same run.
 #include "pileup_host.h"
 
 namespace {
@@ -121,6 +121,13 @@ int pilek::accum_long_checked(const char *who, const PileLongArgs &A, size_t wor
         if (!hist || ((uintptr_t)hist & 15u)) { s5gpu_set_error("%s: NULL or misaligned hist (16 bytes)", who); return S5GPU_ERR_ARG; }
     }
     if (A.acc && !A.ref) { s5gpu_set_error("%s: NULL reference", who); return S5GPU_ERR_ARG; }
+    bool go;
+    const int rc = long_layout_check(who, A, work_bytes, &go);
+    return rc || !go ? rc : launch_pileup_long(A, hist, st);
+}
+
+int pilek::long_layout_check(const char *who, const PileLongArgs &A, size_t work_bytes, bool *go) {
+    *go = false;
     if (A.total_rows > LONG_ROWS_MAX) { s5gpu_set_error("%s: %llu rows in all (at most 2^40)", who, (unsigned long long)A.total_rows); return S5GPU_ERR_ARG; }
     if (A.n == 0) return S5GPU_OK;
     if (!A.first || !A.qlen || !A.status || !A.work || (A.total_rows && (!A.queries || !A.lo || !A.hi))) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
@@ -134,7 +141,8 @@ int pilek::accum_long_checked(const char *who, const PileLongArgs &A, size_t wor
         s5gpu_set_error("%s: a work area of %zu bytes, %llu are needed", who, work_bytes, (unsigned long long)need);
         return S5GPU_ERR_NOMEM;
     }
-    return launch_pileup_long(A, hist, st);
+    *go = true;
+    return S5GPU_OK;
 }
 
 extern "C" int s5gpu_pileup_accum_long_dev(uint32_t n, const int16_t *queries, const uint64_t *first, const uint32_t *qlen, uint64_t total_rows, const int16_t *ref,
@@ -168,7 +176,7 @@ extern "C" void *s5gpu_pileup_open_whole(const s5gpu_event_params_t *ep, const s
     return h;
 }
 
-int pilek::add_batch_whole(const char *who, const WholeChain &W, void *d_acc, void *d_hist, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method,
+int pilek::add_batch_whole(const char *who, const WholeChain &W, void *d_acc, void *d_hist, const SiteSink *sites, uint32_t n, const void *const *rec, const size_t *rec_len, int rec_method,
                            int sig_method, s5gpu_map_row_t *map_rows_out, s5gpu_ext_row_t *ext_rows_out, int32_t *status_out) {
     const uint32_t R = (uint32_t)W.ref.size();
     int rc;
@@ -203,9 +211,11 @@ int pilek::add_batch_whole(const char *who, const WholeChain &W, void *d_acc, vo
         A.R = R; A.lo = (const int32_t *)(dg + E.o_lo); A.hi = (const int32_t *)(dg + E.o_hi); A.status = (const int32_t *)(dg + E.o_st); A.events = F.d_rows;
         A.ev_skip = W.bp.skip; A.work = c->d_scan.p; A.acc = d_acc;
         if (W.refine) { A.queries = (const int16_t *)(dg + E.r_q); A.lo = (const int32_t *)(dg + E.r_lo); A.hi = (const int32_t *)(dg + E.r_hi); }
-        if ((rc = accum_long_checked(who, A, work_bytes, d_hist, false, c->st))) return rc;
+        if ((d_acc || d_hist) && (rc = accum_long_checked(who, A, work_bytes, d_hist, d_acc == nullptr, c->st))) return rc;
+        if (sites && (rc = site_sink_reads(A, work_bytes, *sites, F, n, c->st))) return rc;
     }
-    if ((rc = launch_add_skipped(d_acc, n - m, c->st))) return rc;         // the records that were dropped
+    if (sites && (rc = site_sink_rest(*sites, F, n, R, c->st))) return rc;
+    if (d_acc && (rc = launch_add_skipped(d_acc, n - m, c->st))) return rc;   // the records that were dropped
     if (d_hist && (rc = launch_hist_add_skipped(d_hist, n - m, c->st))) return rc;
     HIP_TRY(hipStreamSynchronize(c->st));                                  // the next holder of this context overwrites the batch
     dtwk::scatter_rows(F, n, hb ? (const s5gpu_map_row_t *)(hb + E.o_map) : nullptr, nullptr, map_rows_out);
@@ -240,5 +250,5 @@ extern "C" int s5gpu_pileup_add_batch_whole(void *handle, uint32_t n, const void
     if (!h || !h->d_acc) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
     if (!h->whole) { s5gpu_set_error("%s: the handle is one of s5gpu_pileup_open", who); return S5GPU_ERR_ARG; }
     h->c.started = true;
-    return pilek::add_batch_whole(who, h->c, h->d_acc, nullptr, n, rec, rec_len, rec_method, sig_method, map_rows_out, ext_rows_out, status_out);
+    return pilek::add_batch_whole(who, h->c, h->d_acc, nullptr, nullptr, n, rec, rec_len, rec_method, sig_method, map_rows_out, ext_rows_out, status_out);
 }

@@ -149,6 +149,15 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
     return v;
 }
+// the inclusive prefix sums of a wave's 64 values (k_pile_contrast, k_site_score: a lane per bin)
+__device__ __forceinline__ uint64_t wave_incl_add64(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up(v, d);
+        if (lane >= (uint32_t)d) v += t;
+    }
+    return v;
+}
 // the reads of a ragged batch, once each, from their verdicts: the grid's threads share them out; in every lane the wave's counts
 struct ReadCounts { uint64_t used, skipped, bad; };
 __device__ __forceinline__ ReadCounts verdict_counts(const uint32_t *verdict, uint32_t n) {

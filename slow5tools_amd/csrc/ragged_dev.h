@@ -1,6 +1,7 @@
 // ragged_dev.h — whole reads (docs/codecs.md §4.22): the ragged layout of s5gpu_sdtw_band_dev, the work area of a call over it, and THE walk
 // over its segments that every whole-read kernel takes: those of the pileup (pileup_kernels.hip), of the level histograms
-// (contrast_kernels.hip, §4.23) and of refine (refine_long_kernels.hip, §4.24).  pileup_dev.h includes this file.
+// (contrast_kernels.hip, §4.23), of refine (refine_long_kernels.hip, §4.24) and of the site matrix (sites_kernels.hip, §4.25).  pileup_dev.h
+// includes this file.
 // With S5_PILEUP_HOST defined only the plain C++ is declared (the switch of dtw_dev.h): tests/test_pileup_long.py, tests/test_contrast.py and
 // tests/test_extend_refine.py compile it for the CPU and resolve their segments through seg_item, the very code a lane runs.
 // Values read from memory form addresses here (first, qlen, P, the ordered list).  The rules, numbered on from 1 - 6 of pileup_kernels.hip;
