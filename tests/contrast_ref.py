@@ -1,13 +1,13 @@
 """The restatements of contrast (docs/codecs.md §4.23) in Python integers and int64 numpy, and the cases the CPU and the GPU tests share:
-hist_ref (the histogram of a test_pileup_long.LongCase), contrast_ref (the rows of two histograms), and the planted case."""
+hist_ref (the histogram of a pileup_ref.LongCase), contrast_ref (the rows of two histograms), and the planted case."""
 import functools
 from fractions import Fraction
 
 import numpy as np
 
-import test_extend as te
-import test_pileup_long as tl
-from test_pileup_long import LONG_QMAX, LongCase, from_paths, path_of
+from dtw_ref import quant_ref
+from extend_ref import band_ref
+from pileup_ref import LONG_QMAX, LongCase, from_paths, long_cases, path_of, pileup_long_ref
 
 HIST_HEAD = np.dtype([("cells", "<u8"), ("reads_used", "<u8"), ("reads_skipped", "<u8"), ("reads_bad", "<u8"), ("R", "<u4"), ("q0", "<i4"), ("shift", "<u4"),
                       ("bins", "<u4"), ("reserved", "<u8", (2,))])
@@ -45,7 +45,7 @@ def hist_ref(case, q0=Q0, shift=SHIFT):
         j = lo[i] + np.arange(w.sum()) - np.repeat(np.cumsum(w) - w, w)
         np.add.at(counts, (j, bin_of(case.q[f0:f0 + Q], q0, shift)[i]), 1)
         cells += len(j)
-    total, cols = tl.pileup_long_ref(case, events=False)
+    total, cols = pileup_long_ref(case, events=False)
     assert counts.sum(axis=1).tolist() == cols["n_events"].tolist() and counts.max(initial=0) < 2 ** 32
     assert (cells, used, skipped, bad) == (total["cells"], total["reads_used"], total["reads_skipped"], total["reads_bad"]) and int(counts.sum()) == cells
     head = np.zeros(1, dtype=HIST_HEAD)
@@ -151,7 +151,7 @@ def hist_cases():
     for R in (1, 65, 300):
         for q0, shift in BIN_PARAMS if R == 300 else BIN_PARAMS[:2]:
             out["edges R=%d q0=%d shift=%d" % (R, q0, shift)] = (with_levels(edge_case(R), q0, shift), q0, shift)
-    for name, c in tl.long_cases().items():
+    for name, c in long_cases().items():
         out[name] = (c, Q0, SHIFT)
     return out
 
@@ -173,7 +173,7 @@ PLANTED_R, PLANTED_READS, PLANTED_EVENTS, PLANTED_COLS, PLANTED_SHIFT = 2048, 12
 
 @functools.lru_cache(maxsize=None)
 def planted(seed=2300):
-    """-> (ref, sides): ref the 2048 levels; sides[s] a list of 12 (q, anchor) pairs, the reads generated as test_extend.planted_read
+    """-> (ref, sides): ref the 2048 levels; sides[s] a list of 12 (q, anchor) pairs, the reads generated as extend_ref.planted_read
     generates them from a start in columns 64 .. 200; side 1 has 48 added to the levels of columns 700 .. 709 before the quantiser"""
     rng = np.random.default_rng(seed)
     ref = np.clip(np.rint(rng.normal(0.0, 40.0, PLANTED_R)), -127, 127).astype(np.int16)
@@ -191,7 +191,7 @@ def planted(seed=2300):
                     truth += [col] * int(rng.integers(1, 3))
                 col += 1
             truth = np.array(truth[:PLANTED_EVENTS])
-            q = te.quant_ref(1.7 * lev[truth] + 30.0 + rng.normal(0.0, 1.5, PLANTED_EVENTS))
+            q = quant_ref(1.7 * lev[truth] + 30.0 + rng.normal(0.0, 1.5, PLANTED_EVENTS))
             reads.append((q, s + (7 if k % 2 else -7)))
         sides.append(reads)
     return ref, sides
@@ -212,7 +212,7 @@ def planted_paths():
     for reads in sides:
         ps = []
         for q, anchor in reads:
-            w = te.band_ref(q, ref, anchor, 64, 128)
+            w = band_ref(q, ref, anchor, 64, 128)
             assert w["row"][6] == 0
             ps.append((np.asarray(w["lo"], np.int32), np.asarray(w["hi"], np.int32)))
         out.append(ps)
@@ -224,3 +224,16 @@ def largest_d(rows, k=5, least=8):
     at = [j for j in range(len(rows)) if rows["n_a"][j] >= least and rows["n_b"][j] >= least]
     d = {j: Fraction(int(rows["ks_num"][j]), int(rows["n_a"][j]) * int(rows["n_b"][j])) for j in at}
     return sorted(at, key=lambda j: (-d[j], j))[:k], d
+
+
+def contrast_lines(ref, rows, ca, cb, min_depth=1, q0=Q0, shift=SHIFT):
+    """the tool's lines, composed from the rows and the two tables"""
+    out = []
+    for j in np.flatnonzero((rows["depth_a"] >= min_depth) & (rows["depth_b"] >= min_depth)):
+        r = rows[j]
+        nn = float(r["n_a"]) * float(r["n_b"])
+        out.append(b"%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%d\t%s\t%d\t%d\n" % (
+            j, ref[j], r["depth_a"], r["depth_b"], ca["n_events"][j], cb["n_events"][j], b"%.6g" % (float(ca["sum_q"][j]) / float(ca["n_events"][j])),
+            b"%.6g" % (float(cb["sum_q"][j]) / float(cb["n_events"][j])), b"%.6g" % (float(r["ks_num"]) / nn), q0 + (int(r["ks_bin"]) << shift),
+            b"%.6g" % (1.0 - float(r["ov_num"]) / nn), q0 + (int(r["med_a"]) << shift), q0 + (int(r["med_b"]) << shift)))
+    return out

@@ -1,24 +1,15 @@
 """The restatement of refine over whole reads (docs/codecs.md §4.24) and the cases the CPU and the GPU tests share.  Nothing of the
-alignment, the fit or the tables is stated again here: band_ref and quant_ref are test_extend's, fit_ref and requant_ref test_refine's,
-LongCase and pileup_long_ref test_pileup_long's.  What is stated here is who is fitted (§4.22's verdict with ev_skip = 0), the layout of
-the outputs, and the rule of the rounds."""
+alignment, the fit or the tables is stated again here: band_ref is extend_ref's, fit_ref and requant_ref refine_ref's, LongCase
+pileup_ref's.  What is stated here is who is fitted (§4.22's verdict with ev_skip = 0), the layout of the outputs, and the rule of the
+rounds."""
 import numpy as np
 
-import test_extend as te
-import test_pileup_long as tl
-import test_refine as tr
-from test_extend import EXT_ROW, NO_COST64, band_ref
-from test_pileup_long import LONG_QMAX, LongCase
-from test_refine import FIT, FIT_FLAT, FIT_NONE, FIT_RANGE, PATH_ROW, fit_ref, requant_ref
+from chain_common import EXT_ROW, FIT, NO_COST64, PATH_ROW
+from extend_ref import band_ref, planted_read, planted_share
+from pileup_ref import LONG_QMAX, LongCase
+from refine_ref import FIT_NONE, fit_ref, requant_ref
 
 V_USED, V_SKIPPED, V_BAD = 0, 1, 2
-DEFAULTS = dict(tr.DEFAULTS)
-
-
-def params(**kw):
-    p = dict(DEFAULTS)
-    p.update(kw)
-    return p
 
 
 def row_none(status):
@@ -156,10 +147,10 @@ def banded_case(qs, ref, anchors, T, band, gap=None, seed=0):
 
 
 def planted_long(seed, n_events, R, a=0.7, b=15.0):
-    """§4.24's planted case: test_extend.planted_read, and once the read's walk is drawn the stretch of the reference it covers,
+    """§4.24's planted case: extend_ref.planted_read, and once the read's walk is drawn the stretch of the reference it covers,
     [s - 100, last column + 100), replaced by rint(a level + b): a region whose levels sit higher and closer together than the target's
     -> (q, ref, anchor, truth)"""
-    q, ref, anchor, truth = te.planted_read(seed, n_events, R)
+    q, ref, anchor, truth = planted_read(seed, n_events, R)
     ref = ref.copy()
     s0, s1 = int(truth[0]) - 100, int(truth[-1]) + 100
     assert 0 <= s0 and s1 <= R
@@ -168,5 +159,5 @@ def planted_long(seed, n_events, R, a=0.7, b=15.0):
 
 
 def share_of(lo, hi, truth):
-    """test_extend.planted_share on arrays"""
-    return te.planted_share(dict(lo=np.asarray(lo).astype(np.int64), hi=np.asarray(hi).astype(np.int64)), truth)[0]
+    """extend_ref.planted_share on arrays"""
+    return planted_share(dict(lo=np.asarray(lo).astype(np.int64), hi=np.asarray(hi).astype(np.int64)), truth)[0]

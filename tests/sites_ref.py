@@ -1,13 +1,12 @@
 """The restatements of sites (docs/codecs.md §4.25) in int64 numpy and Python integers, and the site lists the CPU and the GPU tests share:
-cells_ref (the read x site matrix of a test_pileup_long.LongCase), score_ref (its rows against a control's counts), and the planted case."""
+cells_ref (the read x site matrix of a pileup_ref.LongCase), score_ref (its rows against a control's counts), and the planted case."""
 import functools
 
 import numpy as np
 
 import contrast_ref as cr
-import test_pileup_long as tl
 from contrast_ref import BINS, hist_cases
-from test_pileup_long import LONG_QMAX
+from pileup_ref import LONG_QMAX, pileup_long_ref
 
 SITE_CELL = np.dtype([("sum_q", "<i8"), ("cells", "<u4"), ("row0", "<u4")])
 SITE_SCORE = np.dtype([("level", "<i2"), ("flags", "<u2"), ("below", "<u4"), ("above", "<u4"), ("n", "<u4")])
@@ -37,7 +36,7 @@ def _sums_of(name):
     """per column of a case of hist_cases(): (the cells of its histogram, the table's sum_q), for the invariants"""
     case, q0, shift = hist_cases()[name]
     counts = np.frombuffer(cr.wanted(name), "<u4")[16:].reshape(case.R, BINS).astype(np.int64).sum(axis=1)
-    return counts, tl.pileup_long_ref(case, events=False)[1]["sum_q"].astype(np.int64)
+    return counts, pileup_long_ref(case, events=False)[1]["sum_q"].astype(np.int64)
 
 
 def cells_ref(case, sites, name=None):

@@ -1,7 +1,7 @@
 """align: the whole path of each read's sDTW alignment, event to reference, on the device (docs/codecs.md §4.17;
 slow5tools_amd/csrc/dtw_path_kernels.hip).
 
-The oracle is path_ref in this file: the FULL matrix D of §4.16 in int64 numpy, walked back from (Q - 1, end) with the tie rule.  The device
+The oracle is path_ref of dtw_ref.py: the FULL matrix D of §4.16 in int64 numpy, walked back from (Q - 1, end) with the tie rule.  The device
 runs the recurrence over the columns [start, end] only, so every comparison here also checks §4.17's argument that the window is enough.
 Everything is integer: lo, hi and status are held to the restatement exactly.  The header's lane step, packing and walk (dtw_dev.h) are
 plain C++: they are also compiled for the CPU, 64 lanes in lockstep writing the words the way the kernel lays them out, and held to the
@@ -16,146 +16,9 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
-from blow5_fixture import Blow5, golden
-from test_map import last_lane_batch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DNA = (3, 6, 1.4, 9.0, 0.2)
-MAP_ROW = np.dtype([("cost", "<u4"), ("qlen", "<u4"), ("start", "<i4"), ("end", "<i4")])
-EVENT = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("stdv", "<f4")])
-NO_COST = 0xFFFFFFFF
-EMPTY = (NO_COST, 0, -1, -1)
-QUERY_SHORT, PATH_WIDE, PATH_ROW = 18, 19, 20
-QLENS = [0, 1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 513, 1000, 1024]      # every lane height, both sides of every lane boundary
-KNOWN_SEED = 20261019
-GUARD = 0x5A5A5A5A
-
-
-# ---------------------------------------------------------------------------------------------------------------- the restatement
-
-def quant_ref(m, scale=32.0, clip=127):
-    """quant of §4.16 (copied from test_map.py): float64, sums strictly left to right"""
-    m = np.asarray(m, dtype=np.float32)
-    L = len(m)
-    q = np.zeros(L, dtype=np.int16)
-    if L == 0:
-        return q
-    with np.errstate(all="ignore"):
-        d = m.astype(np.float64)
-        mu = np.cumsum(d)[-1] / np.float64(L)
-        e = d - mu
-        sd = np.sqrt(np.cumsum(e * e)[-1] / np.float64(L))
-        if not (sd > 0.0 and np.isfinite(sd)):
-            return q
-        return np.clip(np.rint((e / sd) * np.float64(scale)), -clip, clip).astype(np.int16)
-
-
-def sdtw_ref(q, r):
-    """(cost, start, end) of §4.16 (copied from test_map.py): D and S filled along anti-diagonals, the predecessor of least D with ties to the
-    diagonal, then (i - 1, j), then (i, j - 1)"""
-    q = np.asarray(q).astype(np.int64)
-    one = q.ndim == 1
-    if one:
-        q = q[None, :]
-    r = np.asarray(r).astype(np.int64)
-    B, Q = q.shape
-    R = len(r)
-    assert Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((B, Q + 1, R + 1), INF, dtype=np.int64)
-    S = np.full((B, Q + 1, R + 1), -1, dtype=np.int64)
-    D[:, 0, :] = 0
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        dg, up, lf = D[:, i, j], D[:, i, j + 1], D[:, i + 1, j]
-        take_dg = (dg <= up) & (dg <= lf)
-        take_up = ~take_dg & (up <= lf)
-        D[:, i + 1, j + 1] = np.abs(q[:, i] - r[j][None, :]) + np.where(take_dg, dg, np.where(take_up, up, lf))
-        s = np.where(take_dg, S[:, i, j], np.where(take_up, S[:, i, j + 1], S[:, i + 1, j]))
-        S[:, i + 1, j + 1] = np.where((i == 0)[None, :], j[None, :], s)
-    last = D[:, Q, 1:]
-    assert last.max() <= 65535 * Q < 2 ** 26
-    end = np.argmin(last, axis=1)
-    b = np.arange(B)
-    cost, start = last[b, end], S[b, Q, end + 1]
-    return (int(cost[0]), int(start[0]), int(end[0])) if one else (cost, start, end)
-
-
-def path_ref(q, r):
-    """(cost, lo, hi) of §4.17 for ONE query: the full D in int64, filled along anti-diagonals; the walk from (Q - 1, end) takes the predecessor
-    of least D, ties to the diagonal, then (i - 1, j), then (i, j - 1), until row 0.  The three invariants and sdtw_ref are asserted."""
-    q = np.asarray(q).astype(np.int64)
-    r = np.asarray(r).astype(np.int64)
-    Q, R = len(q), len(r)
-    assert q.ndim == 1 and Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((Q + 1, R + 1), INF, dtype=np.int64)                       # D[i + 1, j + 1] is D[i][j]; row 0: "a path starts here"
-    D[0, :] = 0
-    c = np.abs(q[:, None] - r[None, :])
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        D[i + 1, j + 1] = c[i, j] + np.minimum(np.minimum(D[i, j], D[i, j + 1]), D[i + 1, j])
-    end = int(np.argmin(D[Q, 1:]))
-    cost = int(D[Q, end + 1])
-    lo, hi = np.full(Q, -1, dtype=np.int64), np.full(Q, -1, dtype=np.int64)
-    i, j, total = Q - 1, end, 0
-    hi[i] = j
-    while True:
-        total += int(c[i, j])
-        if i == 0:
-            lo[0] = j
-            break
-        dg, up, lf = D[i, j], D[i, j + 1], D[i + 1, j]
-        if dg <= up and dg <= lf:
-            lo[i] = j
-            i, j = i - 1, j - 1
-            hi[i] = j
-        elif up <= lf:
-            lo[i] = j
-            i -= 1
-            hi[i] = j
-        else:
-            j -= 1
-    assert total == cost and hi[Q - 1] == end and (lo <= hi).all() and (lo >= 0).all()
-    assert set((lo[1:] - hi[:-1]).tolist()) <= {0, 1}
-    assert sum(int(c[i, lo[i]:hi[i] + 1].sum()) for i in range(Q)) == cost
-    assert sdtw_ref(q, r) == (cost, int(lo[0]), end)
-    return cost, lo.astype(np.int32), hi.astype(np.int32)
-
-
-def known_answer_cases(n_draws=40):
-    """§4.16's known answer (copied from test_map.py, with the repeat counts kept): a reference of 1200 levels, neighbours at least 20 apart;
-    a query that is the slice [a, a + Q) with every level but the first and the last held 1 to 3 times aligns at cost 0 from a to a + Q - 1.
-    -> (ref, [(query, a, Q, rep)])"""
-    rng = np.random.default_rng(KNOWN_SEED)
-    lv = [int(rng.integers(-100, 101))]
-    while len(lv) < 1200:
-        v = int(rng.integers(-100, 101))
-        if abs(v - lv[-1]) >= 20:
-            lv.append(v)
-    ref = np.array(lv, dtype=np.int16)
-    cases = []
-    for _ in range(n_draws):
-        Q = int(rng.integers(2, 131))
-        a = int(rng.integers(0, 1200 - Q + 1))
-        rep = rng.integers(1, 4, Q)
-        rep[0] = rep[-1] = 1
-        piece = ref[a:a + Q]
-        occurrences = sum(np.array_equal(ref[k:k + Q], piece) for k in range(1200 - Q + 1))
-        if occurrences == 1:
-            cases.append((np.repeat(piece, rep).astype(np.int16), a, Q, rep))
-    return ref, cases
-
-
-def levels_signal(n, rng):
-    """a raw signal of random levels of dwell 4 .. 20 with a little noise: an event every dozen samples (copied from test_map.py)"""
-    lv = []
-    while len(lv) < n:
-        lv += [int(rng.integers(300, 700))] * int(rng.integers(4, 21))
-    return np.round(np.array(lv[:n], dtype=np.float64) + rng.normal(0.0, 3.0, n)).astype(np.int16)
-
+from chain_common import DNA, EMPTY, EVENT, GUARD, MAP_ROW, PATH_ROW, PATH_WIDE, QUERY_SHORT, ROOT, host_build, levels_signal, record, synth_file
+from chain_common import gpu  # noqa: F401
+from dtw_ref import QLENS, _g_of, _mixed, known_answer_cases, last_lane_batch, path_ref, quant_ref
 
 # ---------------------------------------------------------------------------------------------------------------- not gpu
 
@@ -351,10 +214,6 @@ int main(int argc, char **argv) {
 '''
 
 
-def _g_of(Q):
-    return next(g for g in (1, 2, 4, 8, 16) if 64 * g >= Q)
-
-
 def _window_case(rng, Q, W, lo, hi):
     """a query and a reference whose window is W wide by construction: W distinct levels far from everything else in the reference, the query
     their sequence with the rows shared out among them (Q >= W), or a query of one level on a flat reference (W = 1)"""
@@ -393,10 +252,7 @@ HAND_MADE = [([1, 2, 3], [7, 7, 1, 2, 3, 7], [2, 3, 4], [2, 3, 4]),
 
 
 def _build_path_host(tmp_path, extra=()):
-    (tmp_path / "path_host.cpp").write_text(PATH_HOST)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           str(tmp_path / "path_host.cpp"), "-o", str(tmp_path / "path_host")])
-    return str(tmp_path / "path_host")
+    return host_build(tmp_path, "path_host", PATH_HOST, ["-O1", "-std=c++17", "-ffp-contract=off"], extra)
 
 
 def test_restatement_on_hand_made_paths():
@@ -488,18 +344,6 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, align, events, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.align = torch, _lib, _lib.lib(), press, events, smap, align
-    return env
-
-
 def _rows_dev(env, qm, qlens, ref, pitch, want_start=True):
     torch = env.torch
     d_q = torch.from_numpy(np.ascontiguousarray(qm)).to("cuda")
@@ -568,13 +412,6 @@ def _check(got, want, what, status=None):
     for name, g, w in (("lo", lo, wl), ("hi", hi, wh)):
         bad = np.argwhere(g != w)
         assert len(bad) == 0, (what, name, bad[0].tolist(), int(g[tuple(bad[0])]), int(w[tuple(bad[0])]))
-
-
-def _mixed(rng, lo, hi):
-    qm = np.full((len(QLENS), 1024), 9999, dtype=np.int16)
-    for i, n in enumerate(QLENS):
-        qm[i, :n] = rng.integers(lo, hi + 1, n)
-    return qm
 
 
 @pytest.fixture(scope="module")
@@ -679,7 +516,7 @@ def test_path_many_waves_and_workgroups(gpu):
 
 @pytest.mark.gpu
 def test_path_dev_finds_the_known_paths(gpu):
-    """the warped slices of test_map.py: cost 0, and event rows lo = hi = the column of their level, each held `rep` times"""
+    """the warped slices of dtw_ref.py: cost 0, and event rows lo = hi = the column of their level, each held `rep` times"""
     torch = gpu.torch
     ref, cases = known_answer_cases()
     assert len(cases) >= 20
@@ -707,23 +544,6 @@ def test_path_dev_finds_the_known_paths(gpu):
         assert np.array_equal(lo2[i], lo[i] if st2[i] == 0 else np.full(pitch, -1)) and np.array_equal(hi2[i], hi[i] if st2[i] == 0 else np.full(pitch, -1))
 
 
-def _record(i, sig):
-    r, keep = ob.make_rec(ob.synth_read_id(i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-    return ob.rec_to_mem(r, ob.REC_ZLIB, ob.SIG_SVB_ZD)[8:]
-
-
-def _synth_file(path, recs):
-    """a BLOW5 file of records without aux fields: the header of a golden zlib + svb-zd file with the aux columns taken off its two '#' lines"""
-    g = Blow5(golden("example_multi_rg_v0.2.0.blow5"))
-    assert (g.rec_method, g.sig_method) == (1, 1)
-    lines = g.header_text.split(b"\n")
-    lines = [b"\t".join(l.split(b"\t")[:8]) if l.startswith(b"#") and b"\t" in l else l for l in lines]
-    ht = b"\n".join(lines)
-    body = b"".join(struct.pack("<Q", len(r)) + r for r in recs)
-    with open(path, "wb") as fh:
-        fh.write(g.raw[:64] + struct.pack("<I", len(ht)) + ht + body + b"5WOLB")
-
-
 @pytest.mark.gpu
 def test_align_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     """read_align, align_dev and file_align (s5align) on level signals, one record corrupt and one read too short: the same rows, lo, hi and
@@ -731,7 +551,7 @@ def test_align_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     torch, al = gpu.torch, gpu.align
     rng = np.random.default_rng(41)
     lengths = [3000, 500, 40, 5000, 1500, 2500]
-    recs = [_record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
+    recs = [record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
     good3 = recs[3]
     bad = bytearray(recs[3])
     bad[-1] ^= 0x5A                                                        # the Adler-32 of the zlib stream
@@ -771,7 +591,7 @@ def test_align_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     keep = [0, 1, 2, 4, 5]
     assert st2[3] == 0 and rows2[3]["qlen"] == qmax and np.array_equal(lo2[keep], wlo[keep]) and rows2[keep].tolist() == wrows[keep].tolist()
     # the tool: exit 1, the corrupt read named, the other reads' lines
-    _synth_file(tmp_path / "reads.blow5", recs)
+    synth_file(tmp_path / "reads.blow5", recs)
     args = ["--skip", str(skip), "--events", str(qmax), "--min-events", str(qmin), str(ref_txt), str(tmp_path / "reads.blow5")]
     p = subprocess.run([al.S5ALIGN, "-K", "4"] + args, capture_output=True, timeout=120)
     assert p.returncode == 1 and ids[3] in p.stderr and b"short" in p.stderr, p.stderr

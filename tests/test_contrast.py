@@ -16,12 +16,13 @@ import numpy as np
 import pytest
 
 import contrast_ref as cr
-import test_pileup as tp
-import test_pileup_long as tl
-from contrast_ref import BINS, CONTRAST_ROW, HIST_HEAD, Q0, SHIFT, contrast_ref, hist_bytes_of, hist_cases, hist_ref, wanted
-from test_pileup import PILE_COL, ROOT
+from chain_common import DEFAULT_COLS, DEFAULT_HIST_COLS, DEFAULT_HIST_GRID, DEFAULT_SEG, DEFAULT_SORT, PILE_COL, ROOT
+from chain_common import host_build, levels_signal, record, synth_file
+from chain_common import gpu  # noqa: F401
+from contrast_ref import BINS, CONTRAST_ROW, HIST_HEAD, Q0, SHIFT, contrast_lines, contrast_ref, hist_bytes_of, hist_cases, hist_ref, wanted
+from dtw_ref import quant_ref
+from pileup_ref import LongCase, _first_lo, mixed_case, relay, table_bytes
 
-DEFAULT_HIST_COLS, DEFAULT_HIST_GRID = 256, 1024                             # the library's defaults (docs/codecs.md §4.23)
 CALLS = ["s5gpu_pile_hist_bytes", "s5gpu_pile_hist_reset_dev", "s5gpu_pile_hist_accum_long_dev", "s5gpu_pile_contrast_dev", "s5gpu_contrast_open",
          "s5gpu_contrast_add_batch", "s5gpu_contrast_close"]
 
@@ -144,7 +145,7 @@ def test_the_options_refuse_bad_values():
             assert L.s5gpu_set_option(key, v) == -1, (key, v)
         for v in good:                                                     # (the defaults last)
             assert L.s5gpu_set_option(key, v) == 0, (key, v)
-    for key, v in ((b"pileup_long_seg", tl.DEFAULT_SEG), (b"pileup_long_cols", tl.DEFAULT_COLS), (b"pileup_lds_cols", tp.DEFAULT_COLS)):   # the old keys keep their meaning
+    for key, v in ((b"pileup_long_seg", DEFAULT_SEG), (b"pileup_long_cols", DEFAULT_COLS), (b"pileup_lds_cols", DEFAULT_COLS)):   # the old keys keep their meaning
         assert L.s5gpu_set_option(key, v) == 0
     assert L.s5gpu_set_option(b"pile_hist_rows", 1) == -1
 
@@ -153,7 +154,7 @@ def test_the_restatements():
     # hand-made: two reads on 4 columns, default bins (bin = (q + 128) >> 2)
     q = np.array([-128, -125, 0, 127, 200], dtype=np.int16)
     lo, hi = np.array([0, 1, 2, 1, 1], dtype=np.int32), np.array([1, 1, 3, 1, 2], dtype=np.int32)
-    head, counts = hist_ref(tl.LongCase(q, [0, 3, 5], [3, 2], [0, 0, 0, 0], lo, hi))
+    head, counts = hist_ref(LongCase(q, [0, 3, 5], [3, 2], [0, 0, 0, 0], lo, hi))
     want = np.zeros((4, 64), np.int64)
     for j, b in ((0, 0), (1, 0), (1, 0), (2, 32), (3, 32), (1, 63), (1, 63), (2, 63)):
         want[j, b] += 1
@@ -309,15 +310,13 @@ def _run_host(exe, tmp_path, case, q0, shift, S=64, cols=0, wlo=0, sort=0, seed=
 
 
 def run_hist_header_on_the_cpu(tmp_path, extra=()):
-    (tmp_path / "hist_host.cpp").write_text(HIST_HOST)
-    exe = str(tmp_path / "hist_host")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"), str(tmp_path / "hist_host.cpp"), "-o", exe])
+    exe = host_build(tmp_path, "hist_host", HIST_HOST, ["-O1", "-g", "-std=c++17", "-Wall"], extra)
     for name, (case, q0, shift) in hist_cases().items():
         if extra and case.total > 100000:
             continue
         want = wanted(name)
         # without a window; a window of 16 columns at the kernel's anchor, at column 0 and hanging over the table's end; shuffled and sorted
-        for cols, wlo, sort, S, seed in ((0, 0, 0, 64, 1), (16, tl._first_lo(case), 1, 64, 2), (16, 0, 0, 256, 3), (16, max(case.R - 10, 0), 1, 1024, 4),
+        for cols, wlo, sort, S, seed in ((0, 0, 0, 64, 1), (16, _first_lo(case), 1, 64, 2), (16, 0, 0, 256, 3), (16, max(case.R - 10, 0), 1, 1024, 4),
                                          (256, max(case.R - 10, 0), 0, 64, 5)):
             got = _run_host(exe, tmp_path, case, q0, shift, S, cols, wlo, sort, seed)
             assert got == want, (name, cols, wlo, sort, S, _explain(got, want))
@@ -352,18 +351,7 @@ def test_the_planted_case_at_the_query_level():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, contrast, events, extend, pileup, press
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.pileup, env.extend, env.contrast = torch, _lib, _lib.lib(), press, events, pileup, extend, contrast
-    return env
-
-
-def _options(env, cols=DEFAULT_HIST_COLS, grid=DEFAULT_HIST_GRID, sort=tl.DEFAULT_SORT, seg=64):
+def _options(env, cols=DEFAULT_HIST_COLS, grid=DEFAULT_HIST_GRID, sort=DEFAULT_SORT, seg=64):
     for key, v in ((b"pile_hist_cols", cols), (b"pile_hist_grid", grid), (b"pileup_long_sort", sort), (b"pileup_long_seg", seg)):
         env.lib.check(env.L.s5gpu_set_option(key, v), key.decode())
 
@@ -419,14 +407,14 @@ def _hist(env, name, **opt):
     try:
         return _accum(env, Hist(env, case.R, q0, shift), case)
     finally:
-        _options(env, seg=tl.DEFAULT_SEG)
+        _options(env, seg=DEFAULT_SEG)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(hist_cases()))
 def test_the_case_list_is_exact(gpu, name):
     want = wanted(name)
-    for opt in (dict(), dict(cols=16, sort=0), dict(seg=tl.DEFAULT_SEG)):
+    for opt in (dict(), dict(cols=16, sort=0), dict(seg=DEFAULT_SEG)):
         got = _hist(gpu, name, **opt)
         assert got == want, (opt, _explain(got, want))
 
@@ -446,10 +434,10 @@ def test_the_options_do_not_change_a_byte(gpu, name):
 @pytest.mark.gpu
 def test_two_calls_on_two_streams_and_a_short_work_area(gpu):
     torch = gpu.torch
-    case = tp.mixed_case(129, 200)
-    whole = tl.relay(case)
+    case = mixed_case(129, 200)
+    whole = relay(case)
     want = hist_bytes_of(hist_ref(whole))
-    a, b = tl.relay(case.part(0, 90)), tl.relay(case.part(90, 200))
+    a, b = relay(case.part(0, 90)), relay(case.part(90, 200))
     hist = Hist(gpu, case.R)
     _options(gpu)
     try:
@@ -461,14 +449,14 @@ def test_two_calls_on_two_streams_and_a_short_work_area(gpu):
         # a work area one byte short: S5GPU_ERR_NOMEM, and neither the histogram nor the work area is touched
         assert _accum(gpu, hist, a, short=1, want_rc=-3) == want
     finally:
-        _options(gpu, seg=tl.DEFAULT_SEG)
+        _options(gpu, seg=DEFAULT_SEG)
 
 
 @pytest.mark.gpu
 def test_a_fixed_pitch_batch_equals_the_ragged_call(gpu):
     torch, ct = gpu.torch, gpu.contrast
-    case = tp.mixed_case(129, 200)
-    want = hist_bytes_of(hist_ref(tl.relay(case, seed=3)))
+    case = mixed_case(129, 200)
+    want = hist_bytes_of(hist_ref(relay(case, seed=3)))
 
     def dev(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
@@ -476,7 +464,7 @@ def test_a_fixed_pitch_batch_equals_the_ragged_call(gpu):
     head, counts = ct.hist_to_host(hist)
     got = hist_bytes_of((head, counts))
     assert got == want, _explain(got, want)
-    assert _accum(gpu, Hist(gpu, case.R), tl.relay(case)) == want
+    assert _accum(gpu, Hist(gpu, case.R), relay(case)) == want
 
 
 def _upload_hist(env, counts, q0=Q0, shift=SHIFT, R=None):
@@ -590,8 +578,8 @@ def files(gpu):
     contrast_whole_dev makes of them"""
     rng = np.random.default_rng(4023)
     levels = rng.normal(500.0, 110.0, 3500).astype(np.float32)
-    ref = tp.quant_ref(levels)
-    recs = [[tl._record(10 * s + i, tp.levels_signal(n, rng)) for i, n in enumerate(lengths)] for s, lengths in enumerate(([30000, 100, 26000, 28000], [27000, 31000, 100]))]
+    ref = quant_ref(levels)
+    recs = [[record(10 * s + i, levels_signal(n, rng)) for i, n in enumerate(lengths)] for s, lengths in enumerate(([30000, 100, 26000, 28000], [27000, 31000, 100]))]
     kw = dict(skip=2, qmax=100, qmin=20, tile_rows=64, band=128)
     env = type("Files", (), {})()
     env.recs, env.levels, env.ref, env.kw = recs, levels, ref, kw
@@ -600,19 +588,6 @@ def files(gpu):
     env.accs = [gpu.pileup.to_host(a) for a in accs]
     env.hists = [gpu.contrast.hist_to_host(h) for h in hists]
     return env
-
-
-def _lines(ref, rows, ca, cb, min_depth=1, q0=Q0, shift=SHIFT):
-    """the tool's lines, composed from the rows and the two tables"""
-    out = []
-    for j in np.flatnonzero((rows["depth_a"] >= min_depth) & (rows["depth_b"] >= min_depth)):
-        r = rows[j]
-        nn = float(r["n_a"]) * float(r["n_b"])
-        out.append(b"%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%d\t%s\t%d\t%d\n" % (
-            j, ref[j], r["depth_a"], r["depth_b"], ca["n_events"][j], cb["n_events"][j], b"%.6g" % (float(ca["sum_q"][j]) / float(ca["n_events"][j])),
-            b"%.6g" % (float(cb["sum_q"][j]) / float(cb["n_events"][j])), b"%.6g" % (float(r["ks_num"]) / nn), q0 + (int(r["ks_bin"]) << shift),
-            b"%.6g" % (1.0 - float(r["ov_num"]) / nn), q0 + (int(r["med_a"]) << shift), q0 + (int(r["med_b"]) << shift)))
-    return out
 
 
 @pytest.mark.gpu
@@ -627,7 +602,7 @@ def test_the_chain_and_the_handle(gpu, files):
         total, cols = files.accs[s]
         assert counts.sum(axis=1).tolist() == cols["n_events"].tolist() and head["cells"] == total["cells"]
         assert (head["reads_used"], head["reads_skipped"], head["reads_bad"]) == (total["reads_used"], total["reads_skipped"], total["reads_bad"]) == ((3, 1, 0), (2, 1, 0))[s]
-    tables = [tp.table_bytes(a) for a in files.accs]
+    tables = [table_bytes(a) for a in files.accs]
     # the handle: a batch a side, and two
     for split in (None, 2):
         with ct.Contrast(files.ref, **files.kw) as h:
@@ -638,12 +613,12 @@ def test_the_chain_and_the_handle(gpu, files):
                     assert rc == 0 and len(ext_rows) == len(part)
             rows, a, b = h.close()
         _same_rows(rows, files.rows)
-        assert [tp.table_bytes(a), tp.table_bytes(b)] == tables
+        assert [table_bytes(a), table_bytes(b)] == tables
     # ... whose tables are PileupWhole's of the same files
     for s in (0, 1):
         with pl.PileupWhole(files.ref, **files.kw) as h:
             h.add(files.recs[s])
-            assert tp.table_bytes(h.close()) == tables[s]
+            assert table_bytes(h.close()) == tables[s]
     # a corrupt record: -5, the rest accumulated, the handle usable
     recs = list(files.recs[0])
     bad = bytearray(recs[2])
@@ -660,10 +635,10 @@ def test_the_chain_and_the_handle(gpu, files):
     rc, _, _, _ = h.add(1, files.recs[1])
     assert rc == 0
     rows, (ta, ca), (tb, cb) = h.close()
-    assert (ta["reads_used"], ta["reads_skipped"]) == (2, 2) and tp.table_bytes((tb, cb)) == tables[1]
+    assert (ta["reads_used"], ta["reads_skipped"]) == (2, 2) and table_bytes((tb, cb)) == tables[1]
     with pl.PileupWhole(files.ref, **files.kw) as p:
         p.add(recs, raise_on_error=False)
-        assert tp.table_bytes(p.close()) == tp.table_bytes((ta, ca))
+        assert table_bytes(p.close()) == table_bytes((ta, ca))
     assert rows["n_a"].tolist() == ca["n_events"].tolist() and rows["n_b"].tolist() == files.rows["n_b"].tolist() and not (rows["flags"] & 48).any()
 
 
@@ -673,16 +648,16 @@ def test_the_tool_and_file_contrast(gpu, files, tmp_path):
     ref_txt = tmp_path / "ref.txt"
     ref_txt.write_text("".join("%.9g\n" % v for v in files.levels))
     for s, name in enumerate(("a.blow5", "b.blow5")):
-        tp._synth_file(tmp_path / name, files.recs[s])
+        synth_file(tmp_path / name, files.recs[s])
     kw = files.kw
     paths = [str(ref_txt), str(tmp_path / "a.blow5"), str(tmp_path / "b.blow5")]
     args = ["--skip", str(kw["skip"]), "--events", str(kw["qmax"]), "--min-events", str(kw["qmin"]), "--tile", str(kw["tile_rows"]), "--band", str(kw["band"])]
     p = subprocess.run([ct.S5CONTRAST, "-K", "3"] + args + paths, capture_output=True, timeout=120)
     assert p.returncode == 0 and b"a.blow5: reads used 3, skipped 1, bad 0" in p.stderr and b"b.blow5: reads used 2, skipped 1, bad 0" in p.stderr, p.stderr
-    want = _lines(files.ref, files.rows, files.accs[0][1], files.accs[1][1])
+    want = contrast_lines(files.ref, files.rows, files.accs[0][1], files.accs[1][1])
     assert p.stdout == b"".join(want) and len(want) > 100
     p = subprocess.run([ct.S5CONTRAST, "-K", "3", "--min-depth", "2"] + args + paths, capture_output=True, timeout=120)
-    assert p.returncode == 0 and p.stdout == b"".join(_lines(files.ref, files.rows, files.accs[0][1], files.accs[1][1], 2)) and len(p.stdout) < len(b"".join(want))
+    assert p.returncode == 0 and p.stdout == b"".join(contrast_lines(files.ref, files.rows, files.accs[0][1], files.accs[1][1], 2)) and len(p.stdout) < len(b"".join(want))
     t = ct.file_contrast(paths[1], paths[2], paths[0], batch=3, tile_rows=kw["tile_rows"], band=kw["band"], skip=kw["skip"], qmax=kw["qmax"], qmin=kw["qmin"])
     at = np.flatnonzero((files.rows["depth_a"] >= 1) & (files.rows["depth_b"] >= 1))
     assert t["ref_pos"].tolist() == at.tolist() and t["events_a"].tolist() == files.rows["n_a"][at].tolist() and t["depth_b"].tolist() == files.rows["depth_b"][at].tolist()

@@ -1,6 +1,6 @@
-"""extend: whole-read banded alignment in tiles from map's anchor (docs/codecs.md §4.21).  The oracle is band_ref below: §4.21 written in
-int64 numpy, with every tile's full D kept for the walk.  The CPU tests compile band_dev.h and dtw_dev.h's lane code for the host and run 64
-lanes in lockstep against it; the GPU tests hold s5gpu_event_queries_long_dev and s5gpu_sdtw_band_dev to it bit for bit."""
+"""extend: whole-read banded alignment in tiles from map's anchor (docs/codecs.md §4.21).  The oracle is band_ref of extend_ref.py: §4.21
+written in int64 numpy, with every tile's full D kept for the walk.  The CPU tests compile band_dev.h and dtw_dev.h's lane code for the host
+and run 64 lanes in lockstep against it; the GPU tests hold s5gpu_event_queries_long_dev and s5gpu_sdtw_band_dev to it bit for bit."""
 import ctypes as C
 import os
 import struct
@@ -10,21 +10,11 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
-from blow5_fixture import Blow5, golden
+from chain_common import DNA, EVENT, EXT_ROW, NO_COST64, PATH_ROW, PATH_WIDE, QUERY_SHORT, ROOT, host_build, levels_signal, record, synth_file, to_dev
+from chain_common import gpu  # noqa: F401
+from dtw_ref import path_ref, quant_ref, sdtw_ref
+from extend_ref import MIXED_Q, QLENS, RLENS, SHAPES, band_ref, bparams, planted_read, planted_share, tracking_read
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EVENT = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("stdv", "<f4")])
-EXT_ROW = np.dtype([("cost", "<u8"), ("qlen", "<u4"), ("tiles", "<u4"), ("start", "<i4"), ("end", "<i4"), ("a_last", "<i4"), ("status", "<i4")])
-MAP_ROW = np.dtype([("cost", "<u4"), ("qlen", "<u4"), ("start", "<i4"), ("end", "<i4")])
-DNA = (3, 6, 1.4, 9.0, 0.2)
-QUERY_SHORT, PATH_WIDE, PATH_ROW = 18, 19, 20
-FAR = 1 << 30
-NO_COST64 = (1 << 64) - 1
-GUARD = 0x5A5A5A5A
-
-QLENS = [1, 63, 64, 65, 127, 128, 129, 200, 321]                           # one tile, exact multiples, one row into the next tile
-RLENS = [1, 40, 64, 65, 300]                                               # R < band, windows clipped at 0 and at R - 1
-SHAPES = [(64, 64), (64, 128), (128, 128)]                                 # (tile_rows, band)
 # the planted case: every seed that was tried is here, none was dropped
 PLANTED_SEEDS = [1, 2, 3, 4, 5, 6, 7, 8]
 # what band_ref gives on them, at both shapes alike: a share of events within 2 columns of the truth of 0.9980 (seed 5) to 1.0, the worst
@@ -33,206 +23,6 @@ PLANTED_SHARE, PLANTED_WORST = 0.998, 4
 
 
 # ---------------------------------------------------------------------------------------------------------------- restatement
-
-def quant_ref(m, scale=32.0, clip=127):
-    """quant of §4.16 (copied from test_refine.py): float64, sums strictly left to right"""
-    m = np.asarray(m, dtype=np.float32)
-    L = len(m)
-    q = np.zeros(L, dtype=np.int16)
-    if L == 0:
-        return q
-    with np.errstate(all="ignore"):
-        d = m.astype(np.float64)
-        mu = np.cumsum(d)[-1] / np.float64(L)
-        e = d - mu
-        sd = np.sqrt(np.cumsum(e * e)[-1] / np.float64(L))
-        if not (sd > 0.0 and np.isfinite(sd)):
-            return q
-        return np.clip(np.rint((e / sd) * np.float64(scale)), -clip, clip).astype(np.int16)
-
-
-def sdtw_ref(q, r):
-    """(cost, start, end) of §4.16 (copied from test_refine.py): D and S filled along anti-diagonals, the predecessor of least D with ties to
-    the diagonal, then (i - 1, j), then (i, j - 1)"""
-    q = np.asarray(q).astype(np.int64)
-    one = q.ndim == 1
-    if one:
-        q = q[None, :]
-    r = np.asarray(r).astype(np.int64)
-    B, Q = q.shape
-    R = len(r)
-    assert Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((B, Q + 1, R + 1), INF, dtype=np.int64)
-    S = np.full((B, Q + 1, R + 1), -1, dtype=np.int64)
-    D[:, 0, :] = 0
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        dg, up, lf = D[:, i, j], D[:, i, j + 1], D[:, i + 1, j]
-        take_dg = (dg <= up) & (dg <= lf)
-        take_up = ~take_dg & (up <= lf)
-        D[:, i + 1, j + 1] = np.abs(q[:, i] - r[j][None, :]) + np.where(take_dg, dg, np.where(take_up, up, lf))
-        s = np.where(take_dg, S[:, i, j], np.where(take_up, S[:, i, j + 1], S[:, i + 1, j]))
-        S[:, i + 1, j + 1] = np.where((i == 0)[None, :], j[None, :], s)
-    last = D[:, Q, 1:]
-    assert last.max() <= 65535 * Q < 2 ** 26
-    end = np.argmin(last, axis=1)
-    b = np.arange(B)
-    cost, start = last[b, end], S[b, Q, end + 1]
-    return (int(cost[0]), int(start[0]), int(end[0])) if one else (cost, start, end)
-
-
-def path_ref(q, r, cross_check=True):
-    """(cost, lo, hi) of §4.17 for ONE query (copied from test_refine.py): the full D in int64, filled along anti-diagonals; the walk from
-    (Q - 1, end) takes the predecessor of least D, ties to the diagonal, then (i - 1, j), then (i, j - 1), until row 0.  The three invariants
-    are asserted, and sdtw_ref with cross_check."""
-    q = np.asarray(q).astype(np.int64)
-    r = np.asarray(r).astype(np.int64)
-    Q, R = len(q), len(r)
-    assert q.ndim == 1 and Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((Q + 1, R + 1), INF, dtype=np.int64)                       # D[i + 1, j + 1] is D[i][j]; row 0: "a path starts here"
-    D[0, :] = 0
-    c = np.abs(q[:, None] - r[None, :])
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        D[i + 1, j + 1] = c[i, j] + np.minimum(np.minimum(D[i, j], D[i, j + 1]), D[i + 1, j])
-    end = int(np.argmin(D[Q, 1:]))
-    cost = int(D[Q, end + 1])
-    lo, hi = np.full(Q, -1, dtype=np.int64), np.full(Q, -1, dtype=np.int64)
-    i, j, total = Q - 1, end, 0
-    hi[i] = j
-    while True:
-        total += int(c[i, j])
-        if i == 0:
-            lo[0] = j
-            break
-        dg, up, lf = D[i, j], D[i, j + 1], D[i + 1, j]
-        if dg <= up and dg <= lf:
-            lo[i] = j
-            i, j = i - 1, j - 1
-            hi[i] = j
-        elif up <= lf:
-            lo[i] = j
-            i -= 1
-            hi[i] = j
-        else:
-            j -= 1
-    assert total == cost and hi[Q - 1] == end and (lo <= hi).all() and (lo >= 0).all()
-    assert set((lo[1:] - hi[:-1]).tolist()) <= {0, 1}
-    assert sum(int(c[i, lo[i]:hi[i] + 1].sum()) for i in range(Q)) == cost
-    if cross_check:
-        assert sdtw_ref(q, r) == (cost, int(lo[0]), end)
-    return cost, lo.astype(np.int32), hi.astype(np.int32)
-
-
-def band_none(status):
-    return dict(row=(NO_COST64, 0, 0, -1, -1, -1, status), a=[], lo=None, hi=None, clamped=0)
-
-
-def band_ref(q, r, anchor, T=256, band=512, status_in=0, walk=True):
-    """§4.21 for ONE query: -> dict(row=(cost, qlen, tiles, start, end, a_last, status), a=[a_k], lo, hi, clamped=carried cells the 2^29 rule
-    turned into "no cell").  Every tile's D is kept in int64 (D[i + 1, x + 1] is cell (i, x) of the window; row 0 is the carried row, column
-    0 "no cell" left of the window); the walk takes the predecessor of least D, ties to the diagonal, then (i - 1, j), then (i, j - 1), and
-    asserts that every cell it visits is real and that the cells' costs sum to `cost`."""
-    q = np.asarray(q).astype(np.int64)
-    r = np.asarray(r).astype(np.int64)
-    Q, R = len(q), len(r)
-    assert T in (64, 128, 256, 512, 1024) and band % 64 == 0 and 64 <= band <= 4096 and R >= 1
-    if status_in != 0:
-        return band_none(status_in)
-    if Q == 0:
-        return band_none(0)
-    if not 0 <= anchor < R:
-        return band_none(PATH_ROW)
-    INF = np.int64(1) << 40
-    amax = max(R - band, 0)
-    a = min(max(anchor - band // 4, 0), amax)
-    K = (Q + T - 1) // T
-    tiles, base, clamped = [], 0, 0
-    prev = None                                                            # (a, W, bottom row, min) of the tile before
-    for k in range(K):
-        qk = q[k * T:(k + 1) * T]
-        Qk, W = len(qk), min(band, R - a)
-        D = np.full((Qk + 1, W + 1), INF, dtype=np.int64)
-        if prev is None:
-            D[0, :] = 0
-        else:
-            pa, pW, pB, pmin = prev
-            for x in range(W + 1):                                         # column a + x - 1
-                jp = a + x - 1 - pa
-                if 0 <= jp < pW and pB[jp] < FAR:
-                    if pB[jp] - pmin >= (1 << 29):
-                        clamped += 1
-                    else:
-                        D[0, x] = pB[jp] - pmin
-        c = np.abs(qk[:, None] - r[None, a:a + W])
-        for d in range(Qk + W - 1):
-            i = np.arange(max(0, d - W + 1), min(Qk - 1, d) + 1)
-            j = d - i
-            D[i + 1, j + 1] = c[i, j] + np.minimum(np.minimum(D[i, j], D[i, j + 1]), D[i + 1, j])
-        B = D[Qk, 1:]
-        m = int(np.argmin(B))
-        mn = int(B[m])
-        assert mn < FAR and mn <= 65535 * T and int(B[B < FAR].max()) < FAR
-        base += mn
-        tiles.append((a, W, D, c))
-        prev = (a, W, B, mn)
-        end = a + m
-        if k + 1 < K:
-            a = min(max(end - band // 4, a), amax)
-            assert a <= end < a + min(band, R - a)                         # the next window holds m_k
-    cost = base
-    out = dict(row=(cost, Q, K, -1, end, tiles[-1][0], 0), a=[t[0] for t in tiles], lo=None, hi=None, clamped=clamped)
-    if not walk:
-        return out
-    lo, hi = np.full(Q, -1, dtype=np.int64), np.full(Q, -1, dtype=np.int64)
-    k, col, total = K - 1, end, 0
-    i = len(tiles[k][2]) - 2
-    hi[Q - 1] = end
-    while True:
-        a, W, D, c = tiles[k]
-        x = col - a
-        assert 0 <= x < W and D[i + 1, x + 1] < FAR                        # a path cell is real
-        total += int(c[i, x])
-        gi = k * T + i
-        if gi == 0:
-            lo[0] = col
-            break
-        dg, up, lf = D[i, x], D[i, x + 1], D[i + 1, x]
-        if dg <= up and dg <= lf:
-            lo[gi] = col
-            col -= 1
-            hi[gi - 1] = col
-            i -= 1
-        elif up <= lf:
-            lo[gi] = col
-            hi[gi - 1] = col
-            i -= 1
-        else:
-            col -= 1
-        if i < 0:
-            k -= 1
-            i = len(tiles[k][2]) - 2
-    assert total == cost and (lo <= hi).all() and (lo >= 0).all() and set((lo[1:] - hi[:-1]).tolist()) <= {0, 1}
-    assert sum(int(np.abs(q[i] - r[lo[i]:hi[i] + 1]).sum()) for i in range(Q)) == cost
-    out["row"] = (cost, Q, K, int(lo[0]), end, tiles[-1][0], 0)
-    out["lo"], out["hi"] = lo.astype(np.int32), hi.astype(np.int32)
-    return out
-
-
-def tracking_read(rng, Q, R, noise=2.0):
-    """a reference of R levels, a query of Q rows that follows it from a random column (each level held 1 or 2 times, the last one to the
-    end), and an anchor a few columns off the start"""
-    ref = np.clip(np.rint(rng.normal(0.0, 40.0, R)), -127, 127).astype(np.int16)
-    s = int(rng.integers(0, R))
-    cols = np.minimum(s + np.cumsum(rng.integers(0, 2, Q)), R - 1)
-    q = np.clip(np.rint(ref[cols] + rng.normal(0.0, noise, Q)), -127, 127).astype(np.int16)
-    anchor = int(np.clip(s + rng.integers(-5, 6), 0, R - 1))
-    return q, ref, anchor
-
 
 def test_restatement_known_answers():
     """band_ref on cases small enough to do by hand, and its uint64 cost with the per-tile renormalisation"""
@@ -443,10 +233,7 @@ def host_cases():
 
 
 def _build_band_host(tmp_path, extra=()):
-    (tmp_path / "band_host.cpp").write_text(BAND_HOST)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           str(tmp_path / "band_host.cpp"), "-o", str(tmp_path / "band_host")])
-    return str(tmp_path / "band_host")
+    return host_build(tmp_path, "band_host", BAND_HOST, ["-O1", "-std=c++17", "-ffp-contract=off"], extra)
 
 
 def write_host_cases(path, cases):
@@ -517,29 +304,6 @@ def test_a_band_as_wide_as_the_reference_is_the_full_matrix():
     assert n >= 40
 
 
-def planted_read(seed, n_events=3000, R=4096):
-    """§4.21's planted case: 4096 levels; a read that walks them from a random column with 5 % of the levels skipped and 1 or 2 events a
-    level otherwise (1.5 on average); the event means are the levels through the level change 1.7 x + 30 with a little noise, and the query is
-    §4.16's quant of them, as in the chain; the anchor is 7 columns off.  -> (q, ref, anchor, truth): truth[i] is the column of event i"""
-    rng = np.random.default_rng(seed)
-    ref = np.clip(np.rint(rng.normal(0.0, 40.0, R)), -127, 127).astype(np.int16)
-    s = int(rng.integers(64, R - 2200 - 64))
-    truth, col = [], s
-    while len(truth) < n_events:
-        if rng.random() >= 0.05:
-            truth += [col] * int(rng.integers(1, 3))
-        col += 1
-    truth = np.array(truth[:n_events])
-    q = quant_ref(1.7 * ref[truth] + 30.0 + rng.normal(0.0, 1.5, n_events))
-    return q, ref, s + (7 if seed % 2 else -7), truth
-
-
-def planted_share(w, truth):
-    """the share of events whose span [lo, hi] comes within 2 columns of the truth, and the worst distance"""
-    d = np.maximum(np.maximum(w["lo"] - truth, truth - w["hi"]), 0)
-    return float((d <= 2).mean()), int(d.max())
-
-
 @pytest.mark.parametrize("T,band", [(64, 128), (256, 512)])
 def test_the_planted_case(T, band):
     """§4.21's planted case in the restatement, on every seed of PLANTED_SEEDS: the share of events within 2 columns of the truth is at least
@@ -552,12 +316,6 @@ def test_the_planted_case(T, band):
         assert share >= PLANTED_SHARE and worst <= PLANTED_WORST, (seed, share, worst)
         assert abs(w["row"][3] - truth[0]) <= PLANTED_WORST and abs(w["row"][4] - truth[-1]) <= PLANTED_WORST, (seed, w["row"], truth[0], truth[-1])
         assert w["clamped"] == 0
-
-
-def bparams(skip=0, emin=1, emax=1 << 20, tile_rows=256, band=512, clip=127, scale=32.0):
-    from slow5tools_amd import _lib
-
-    return _lib.BandParams(skip, emin, emax, tile_rows, band, clip, scale)
 
 
 def test_refused_arguments_are_refused_before_a_device_is_needed():
@@ -645,22 +403,6 @@ def test_library_exports_the_extend_calls():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, events, extend, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.extend = torch, _lib, _lib.lib(), press, events, smap, extend
-    return env
-
-
-def _dev(env, a, dtype=None):
-    return env.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
 class Reads:
     """event rows of n reads, ragged, whose means follow a reference from an anchor; what quant_ref makes of them is the host's query"""
 
@@ -694,9 +436,9 @@ class Reads:
 def _run_band(env, rd, T, band, emin=1, anchor=None, scratch_bytes_=None):
     ex, t = env.extend, env.torch
     p = ex.BandParams(rd.skip, emin, 1 << 20, T, band)
-    d_rows, d_first = _dev(env, rd.rows.view(np.int32).reshape(-1, 4)), _dev(env, np.array(rd.first, dtype=np.int64))
-    q, ql, st = ex.queries_long_dev(d_rows, d_first, _dev(env, np.array(rd.ev_status, dtype=np.int32)), p)
-    rows, lo, hi = ex.band_dev(q, d_first, ql, _dev(env, rd.ref), _dev(env, np.array(rd.anchor if anchor is None else anchor, dtype=np.int32)), st, p, scratch_bytes_)
+    d_rows, d_first = to_dev(env, rd.rows.view(np.int32).reshape(-1, 4)), to_dev(env, np.array(rd.first, dtype=np.int64))
+    q, ql, st = ex.queries_long_dev(d_rows, d_first, to_dev(env, np.array(rd.ev_status, dtype=np.int32)), p)
+    rows, lo, hi = ex.band_dev(q, d_first, ql, to_dev(env, rd.ref), to_dev(env, np.array(rd.anchor if anchor is None else anchor, dtype=np.int32)), st, p, scratch_bytes_)
     t.cuda.synchronize()
     return q.cpu().numpy(), ql.cpu().numpy(), st.cpu().numpy(), rows.cpu().numpy().view(EXT_ROW).reshape(-1), lo.cpu().numpy(), hi.cpu().numpy()
 
@@ -718,9 +460,6 @@ def _check_band(rd, got, T, band, emin=1, anchor=None, wants=None):
         _same_result((i, Q, T, band), wants[key], rows[i], None, lo[f0:f0 + Q], hi[f0:f0 + Q])
         assert (lo[f0 + Q:f1] == -1).all() and (hi[f0 + Q:f1] == -1).all(), i
     return wants
-
-
-MIXED_Q = QLENS * 4 + [0, 0, 5, 70]
 
 
 @pytest.mark.gpu
@@ -783,7 +522,7 @@ def test_a_scratch_one_slot_too_small_is_refused_and_nothing_is_written(gpu):
     ex, t = gpu.extend, gpu.torch
     rd = Reads(300, [200, 129, 64], skip=0, seed=3)
     p = ex.BandParams(0, 1, 1 << 20, 64, 128)
-    d_rows, d_first = _dev(gpu, rd.rows.view(np.int32).reshape(-1, 4)), _dev(gpu, np.array(rd.first, dtype=np.int64))
+    d_rows, d_first = to_dev(gpu, rd.rows.view(np.int32).reshape(-1, 4)), to_dev(gpu, np.array(rd.first, dtype=np.int64))
     q, ql, st = ex.queries_long_dev(d_rows, d_first, None, p)
     need = ex.scratch_bytes(rd.n, rd.total, 64, 128)
     slot = gpu.L.s5gpu_sdtw_path_slot_bytes(64, 128)
@@ -792,7 +531,7 @@ def test_a_scratch_one_slot_too_small_is_refused_and_nothing_is_written(gpu):
     rows = t.full((rd.n, 4), -3, dtype=t.int64, device="cuda")
     lo, hi = t.full((rd.total,), -3, dtype=t.int32, device="cuda"), t.full((rd.total,), -3, dtype=t.int32, device="cuda")
     scratch = t.full((need // 4,), -3, dtype=t.int32, device="cuda")
-    ref, an, zero = _dev(gpu, rd.ref), _dev(gpu, np.array(rd.anchor, dtype=np.int32)), t.zeros(rd.n, dtype=t.int32, device="cuda")
+    ref, an, zero = to_dev(gpu, rd.ref), to_dev(gpu, np.array(rd.anchor, dtype=np.int32)), t.zeros(rd.n, dtype=t.int32, device="cuda")
     rc = gpu.L.s5gpu_sdtw_band_dev(rd.n, q.data_ptr(), d_first.data_ptr(), ql.data_ptr(), rd.total, ref.data_ptr(), rd.R, an.data_ptr(), zero.data_ptr(),
                                    C.byref(p), scratch.data_ptr(), need - slot, rows.data_ptr(), lo.data_ptr(), hi.data_ptr(), None)
     t.cuda.synchronize()
@@ -800,32 +539,6 @@ def test_a_scratch_one_slot_too_small_is_refused_and_nothing_is_written(gpu):
     assert (rows == -3).all() and (lo == -3).all() and (hi == -3).all() and (scratch == -3).all()
     with pytest.raises(gpu.lib.S5GpuError, match="rc=-3"):
         ex.band_dev(q, d_first, ql, ref, an, None, p, scratch_bytes_=need - 1)
-
-
-def levels_signal(n, rng):
-    """a raw signal of random levels of dwell 4 .. 20 with a little noise: an event every dozen samples (copied from test_refine.py)"""
-    lv = []
-    while len(lv) < n:
-        lv += [int(rng.integers(300, 700))] * int(rng.integers(4, 21))
-    return np.round(np.array(lv[:n], dtype=np.float64) + rng.normal(0.0, 3.0, n)).astype(np.int16)
-
-
-def _record(i, sig):
-    r, keep = ob.make_rec(ob.synth_read_id(i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-    return ob.rec_to_mem(r, ob.REC_ZLIB, ob.SIG_SVB_ZD)[8:]
-
-
-def _synth_file(path, recs):
-    """a BLOW5 file of records without aux fields (as test_refine.py makes its own): the header of a golden zlib + svb-zd file with the aux
-    columns taken off its two '#' lines"""
-    g = Blow5(golden("example_multi_rg_v0.2.0.blow5"))
-    assert (g.rec_method, g.sig_method) == (1, 1)
-    lines = g.header_text.split(b"\n")
-    lines = [b"\t".join(l.split(b"\t")[:8]) if l.startswith(b"#") and b"\t" in l else l for l in lines]
-    ht = b"\n".join(lines)
-    body = b"".join(struct.pack("<Q", len(r)) + r for r in recs)
-    with open(path, "wb") as fh:
-        fh.write(g.raw[:64] + struct.pack("<I", len(ht)) + ht + body + b"5WOLB")
 
 
 @pytest.mark.gpu
@@ -836,7 +549,7 @@ def test_extend_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     ex = gpu.extend
     rng = np.random.default_rng(47)
     lengths = [24000, 20000, 40, 5000, 22000]
-    recs = [_record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
+    recs = [record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
     bad = bytearray(recs[3])
     bad[-1] ^= 0x5A                                                        # the Adler-32 of the zlib stream
     recs[3] = bytes(bad)
@@ -895,7 +608,7 @@ def test_extend_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     same(1, b_rows[1], b_lo, b_hi)
     assert b_first.tolist() == [0, 0, E[1] - skip, E[1] - skip, E[1] - skip, E[1] - skip]
     # the tool: exit 1, the corrupt read named, the other reads' lines
-    _synth_file(tmp_path / "reads.blow5", recs)
+    synth_file(tmp_path / "reads.blow5", recs)
     args = ["--skip", str(skip), "--events", str(qmax), "--min-events", str(qmin), "--tile", str(T), "--band", str(band), str(ref_txt), str(tmp_path / "reads.blow5")]
     p = subprocess.run([ex.S5EXTEND, "-K", "2"] + args, capture_output=True, timeout=120)
     assert p.returncode == 1 and ids[3] in p.stderr and b"short" in p.stderr, p.stderr

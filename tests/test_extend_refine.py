@@ -12,16 +12,16 @@ import pytest
 
 import contrast_ref as cr
 import extend_refine_ref as er
-import test_extend as te
-import test_pileup_long as tl
-import test_refine as tr
-from extend_refine_ref import FIT_FLAT, FIT_RANGE, PATH_ROW, fit_long_ref, params, refine_long_ref
-from test_extend import EXT_ROW, NO_COST64, QLENS, RLENS, SHAPES, band_ref, tracking_read
-from test_pileup_long import LongCase
-from test_refine import FIT, FIT_NONE, params_bytes
+import oracle_bind as ob
+from chain_common import DEFAULT_GRID, DEFAULT_SEG, DEFAULT_SORT, DNA, EVENT, EXT_ROW, FIT, FIT_FLAT, FIT_RANGE, PATH_ROW, QUERY_SHORT, ROOT
+from chain_common import host_build, levels_signal, pile_lines, record, synth_file, to_dev
+from chain_common import gpu  # noqa: F401
+from dtw_ref import quant_ref
+from extend_ref import MIXED_Q, QLENS, RLENS, SHAPES, band_ref, bparams, tracking_read
+from extend_refine_ref import fit_long_ref, refine_long_ref
+from pileup_ref import LongCase, pileup_long_ref, table_bytes
+from refine_ref import FIT_NONE, c_params, params, params_bytes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 0x5A5A5A5A
 NEW_CALLS = ["s5gpu_path_fit_long_work_bytes", "s5gpu_path_fit_long_dev", "s5gpu_extend_refine_work_bytes", "s5gpu_extend_refine_dev",
              "s5gpu_extend_refine_batch", "s5gpu_pileup_set_refine", "s5gpu_contrast_set_refine"]
 PLANTED_SEEDS = [1, 2, 3, 4, 5, 6, 7, 8]
@@ -378,11 +378,8 @@ def write_host_batches(path, batches, shuffle=12345):
 
 
 def _build_host(tmp_path, extra=()):
-    (tmp_path / "refine_long_host.cpp").write_text(REFINE_LONG_HOST)
-    exe = str(tmp_path / ("refine_long_host" + ("_san" if extra else "")))
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           "-I", os.path.join(ROOT, "include"), str(tmp_path / "refine_long_host.cpp"), "-o", exe])
-    return exe
+    return host_build(tmp_path, "refine_long_host", REFINE_LONG_HOST, ["-O1", "-g", "-std=c++17", "-ffp-contract=off"], extra, api=True,
+                      exe="refine_long_host" + ("_san" if extra else ""))
 
 
 def _take(raw, at, dtype, count):
@@ -499,7 +496,7 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
     assert wr(4, (1 << 40) + 1) == 0 and wr(4, 1000) == wb(4, 1000) + 4 * (32 + 64) + 3 * 16 + 2 * 4000 + 2000
 
     def fl(n=4, q=A, first=A, qlen=A, total=1000, ref=A, R=100, lo=A, hi=A, si=A, P=None, pnull=False, work=A, wbytes=1 << 30, fit=A, qo=A + 4096, so=A + 8192):
-        p = tr.c_params(P or params())
+        p = c_params(P or params())
         return L.s5gpu_path_fit_long_dev(n, q, first, qlen, total, ref, R, lo, hi, si, None if pnull else C.byref(p), work, wbytes, fit, qo, so, None)
     assert fl(pnull=True) == -1 and fl(R=0) == -1 and fl(R=1 << 31) == -1 and fl(ref=None) == -1 and fl(total=(1 << 40) + 1) == -1
     for kw in bad_refine:
@@ -517,14 +514,14 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
 
     def rf(n=4, q=A, first=A, qlen=A, total=1000, ref=A, R=100, ri=A, li=A, hi_=A, BP=None, bnull=False, P=None, pnull=False, scratch=A, sbytes=1 << 30, work=A,
            wbytes=1 << 30, qo=A + 4096, ro=A + 4096, lo=A + 4096, ho=A + 4096, fit=A, rnd=A):
-        p, bp = tr.c_params(P or params()), BP or te.bparams()
+        p, bp = c_params(P or params()), BP or bparams()
         return L.s5gpu_extend_refine_dev(n, q, first, qlen, total, ref, R, ri, li, hi_, None if bnull else C.byref(bp), None if pnull else C.byref(p), scratch,
                                          sbytes, work, wbytes, qo, ro, lo, ho, fit, rnd, None)
     assert rf(pnull=True) == -1 and rf(bnull=True) == -1 and rf(R=0) == -1 and rf(R=1 << 31) == -1 and rf(ref=None) == -1 and rf(total=(1 << 40) + 1) == -1
     for kw in bad_refine:
         assert rf(P=params(**kw)) == -1, kw
     for kw in bad_band:
-        assert rf(BP=te.bparams(**kw)) == -1, kw
+        assert rf(BP=bparams(**kw)) == -1, kw
     for name in ("q", "first", "qlen", "ri", "li", "hi_", "scratch", "work", "qo", "ro", "lo", "ho", "fit", "rnd"):
         assert rf(**{name: None}) == -1, name
     for name, off in (("q", 1), ("first", 4), ("qlen", 2), ("ref", 1), ("ri", 8), ("li", 2), ("hi_", 2), ("scratch", 8), ("work", 8), ("qo", 1), ("ro", 8),
@@ -545,7 +542,7 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
     before = {k: v.copy() for k, v in bufs.items()}
 
     def batch(pr=(0, 64, 10, 32.0, 127, 1), BP=None, bnull=False, P=None, pnull=False, R=100, ref=True, methods=(1, 1), **off):
-        e, p, bp, rp = _lib.EventParams(*te.DNA), _lib.MapParams(*pr), BP or te.bparams(emin=10), tr.c_params(P or params())
+        e, p, bp, rp = _lib.EventParams(*DNA), _lib.MapParams(*pr), BP or bparams(emin=10), c_params(P or params())
         a = {k: (None if off.get(k) is False else v.ctypes.data_as(vp)) for k, v in bufs.items()}
         return L.s5gpu_extend_refine_batch(1, rec_p, rl, methods[0], methods[1], C.byref(e), C.byref(p), None if bnull else C.byref(bp),
                                            None if pnull else C.byref(rp), 0, h_ref.ctypes.data_as(vp) if ref else None, R, a["map"], a["rows1"], a["rows"],
@@ -557,11 +554,11 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
     for kw in bad_refine:
         assert batch(P=params(**kw)) == -1, kw
     for kw in bad_band:
-        assert batch(BP=te.bparams(**dict(dict(emin=10), **kw))) == -1, kw
-    assert batch(BP=te.bparams(emin=10, skip=1)) == -1
+        assert batch(BP=bparams(**dict(dict(emin=10), **kw))) == -1, kw
+    assert batch(BP=bparams(emin=10, skip=1)) == -1
     assert all((bufs[k] == before[k]).all() for k in bufs)
     # the switches of the handles: a NULL handle
-    p = tr.c_params(params())
+    p = c_params(params())
     assert L.s5gpu_pileup_set_refine(None, C.byref(p)) == -1 and L.s5gpu_contrast_set_refine(None, C.byref(p)) == -1
 
 
@@ -589,34 +586,18 @@ def test_library_exports_the_whole_read_refine_calls_and_the_tools_take_the_flag
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, contrast, events, extend, pileup, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.extend, env.pileup, env.contrast = torch, _lib, _lib.lib(), press, events, smap, extend, pileup, contrast
-    return env
-
-
-def _dev(env, a, dtype=None):
-    return env.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
-def _options(env, seg=tl.DEFAULT_SEG, sort=tl.DEFAULT_SORT, grid=tl.DEFAULT_GRID):
+def _options(env, seg=DEFAULT_SEG, sort=DEFAULT_SORT, grid=DEFAULT_GRID):
     for key, v in ((b"pileup_long_seg", seg), (b"pileup_long_sort", sort), (b"pileup_long_grid", grid)):
         env.lib.check(env.L.s5gpu_set_option(key, v), key.decode())
 
 
 def _upload(env, case):
-    return dict(q=_dev(env, case.q), first=_dev(env, case.first.view(np.int64)), qlen=_dev(env, case.qlen.view(np.int32)), ref=_dev(env, case.ref),
-                lo=_dev(env, case.lo), hi=_dev(env, case.hi), status=_dev(env, case.status))
+    return dict(q=to_dev(env, case.q), first=to_dev(env, case.first.view(np.int64)), qlen=to_dev(env, case.qlen.view(np.int32)), ref=to_dev(env, case.ref),
+                lo=to_dev(env, case.lo), hi=to_dev(env, case.hi), status=to_dev(env, case.status))
 
 
 def _fit(env, d, P, want_queries=True):
-    fit, q1, st = env.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], tr.c_params(P), want_queries)
+    fit, q1, st = env.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], c_params(P), want_queries)
     env.torch.cuda.synchronize()
     return fit.cpu().numpy().view(FIT).reshape(-1), (q1.cpu().numpy() if want_queries else None), st.cpu().numpy()
 
@@ -638,8 +619,8 @@ def _band_on_device(env, qs, ref, anchors, T, band, gap=None, seed=0):
     for k, x in enumerate(qs):
         q[int(first[k]):int(first[k]) + len(x)] = x
     p = ex.BandParams(0, 1, 1 << 20, T, band)
-    rows, lo, hi = ex.band_dev(_dev(env, q), _dev(env, first.view(np.int64)), _dev(env, np.array([len(x) for x in qs], np.int32)), _dev(env, ref),
-                               _dev(env, np.array(anchors, np.int32)), None, p)
+    rows, lo, hi = ex.band_dev(to_dev(env, q), to_dev(env, first.view(np.int64)), to_dev(env, np.array([len(x) for x in qs], np.int32)), to_dev(env, ref),
+                               to_dev(env, np.array(anchors, np.int32)), None, p)
     env.torch.cuda.synchronize()
     rows = rows.cpu().numpy().view(EXT_ROW).reshape(-1).copy()
     return LongCase(q, first, [len(x) for x in qs], ref, lo.cpu().numpy(), hi.cpu().numpy(), rows["status"].astype(np.int32)), rows
@@ -672,7 +653,7 @@ def test_fit_long_is_exact_on_a_mixed_batch(gpu, R):
     rng = np.random.default_rng(4240 + R)
     ref = np.clip(np.rint(rng.normal(0.0, 40.0, R)), -127, 127).astype(np.int16)
     qs, anchors = [], []
-    for i, Q in enumerate(te.MIXED_Q):
+    for i, Q in enumerate(MIXED_Q):
         s = int(rng.integers(0, R))
         cols = np.minimum(s + np.cumsum(rng.integers(0, 2, Q)), R - 1)
         qs.append(rng.integers(-1, 2, Q).astype(np.int16) if i % 5 == 4 else
@@ -700,9 +681,9 @@ def test_fit_long_is_exact_on_a_mixed_batch(gpu, R):
     P2 = params(min_cells=2, a_max=1.5)
     want2 = fit_long_ref(case, P2)
     with t.cuda.stream(s1):
-        a = gpu.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], tr.c_params(P))
+        a = gpu.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], c_params(P))
     with t.cuda.stream(s2):
-        b = gpu.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], tr.c_params(P2))
+        b = gpu.extend.fit_long_dev(d["q"], d["first"], d["qlen"], d["ref"], d["lo"], d["hi"], d["status"], c_params(P2))
     t.cuda.synchronize()
     for got, w in ((a, want), (b, want2)):
         _same_fit((R, "streams"), (got[0].cpu().numpy().view(FIT).reshape(-1), got[1].cpu().numpy(), got[2].cpu().numpy()), w)
@@ -738,8 +719,8 @@ def test_fit_long_over_many_workgroups_and_a_long_read(gpu):
 
 def _refine(env, case, rows, T, band, P, scratch_bytes_=None):
     d = _upload(env, case)
-    x = env.extend.refine_long_dev(d["q"], d["first"], d["qlen"], d["ref"], _dev(env, rows.view(np.int64).reshape(-1, 4)), d["lo"], d["hi"],
-                                   env.extend.BandParams(0, 1, 1 << 20, T, band), tr.c_params(P), scratch_bytes_)
+    x = env.extend.refine_long_dev(d["q"], d["first"], d["qlen"], d["ref"], to_dev(env, rows.view(np.int64).reshape(-1, 4)), d["lo"], d["hi"],
+                                   env.extend.BandParams(0, 1, 1 << 20, T, band), c_params(P), scratch_bytes_)
     env.torch.cuda.synchronize()
     return dict(q=x.queries.cpu().numpy(), rows=x.rows.cpu().numpy().view(EXT_ROW).reshape(-1), lo=x.lo.cpu().numpy(), hi=x.hi.cpu().numpy(),
                 fit=x.fit.cpu().numpy().view(FIT).reshape(-1), rounds=x.rounds.cpu().numpy().view(np.uint32))
@@ -778,7 +759,7 @@ def test_the_rounds_on_a_mixed_batch_where_reads_drop_out(gpu):
     everything equals refine_long_ref, also at segments of 64 without the sort, and there with one workgroup and with three (see
     test_fit_long_is_exact_on_a_mixed_batch); and a scratch one slot too small is refused with nothing written"""
     t = gpu.torch
-    case, rows = mixed_case(64, 128, 300, te.MIXED_Q, 4241)
+    case, rows = mixed_case(64, 128, 300, MIXED_Q, 4241)
     case, rows = _flawed(case, rows)
     P = params(iters=4, min_cells=16, a_max=1.6)
     want = refine_long_ref(case, rows, 64, 128, P)
@@ -802,8 +783,8 @@ def test_the_rounds_on_a_mixed_batch_where_reads_drop_out(gpu):
     g = lambda count, dt: t.full((count,), -3, dtype=dt, device="cuda")
     scratch, work = g(need // 4, t.int32), g(wb // 4 + 4, t.int32)
     out = [g(case.total, t.int16), g(case.n * 4, t.int64), g(case.total, t.int32), g(case.total, t.int32), g(case.n * 8, t.int64), g(case.n, t.int32)]
-    d_rows = _dev(gpu, rows.view(np.int64).reshape(-1, 4))
-    bp, rp = ex.BandParams(0, 1, 1 << 20, 64, 128), tr.c_params(P)
+    d_rows = to_dev(gpu, rows.view(np.int64).reshape(-1, 4))
+    bp, rp = ex.BandParams(0, 1, 1 << 20, 64, 128), c_params(P)
     rc = gpu.L.s5gpu_extend_refine_dev(case.n, d["q"].data_ptr(), d["first"].data_ptr(), d["qlen"].data_ptr(), case.total, d["ref"].data_ptr(), case.R,
                                        d_rows.data_ptr(), d["lo"].data_ptr(), d["hi"].data_ptr(), C.byref(bp), C.byref(rp), scratch.data_ptr(), need - slot,
                                        work.data_ptr(), wb, *[o.data_ptr() for o in out], None)
@@ -820,29 +801,29 @@ def chain(gpu):
     three of the reads, squeezed to 0.7 x + 180 so that they sit higher and closer together than the reads have them; and what the
     unrefined device chain leaves for each side as a LongCase"""
     rng = np.random.default_rng(4024)
-    sigs = [[te.levels_signal(n, rng) for n in lengths] for lengths in ([30000, 100, 26000, 28000], [27000, 31000, 100])]
+    sigs = [[levels_signal(n, rng) for n in lengths] for lengths in ([30000, 100, 26000, 28000], [27000, 31000, 100])]
     sigs[1][0] = sigs[0][0]                                                # a read both sides hold: their columns overlap
-    recs = [[tl._record(10 * s + i, sig) for i, sig in enumerate(side)] for s, side in enumerate(sigs)]
+    recs = [[record(10 * s + i, sig) for i, sig in enumerate(side)] for s, side in enumerate(sigs)]
     kw = dict(skip=2, qmax=100, qmin=20, tile_rows=64, band=128)
     env = type("Chain", (), {})()
     env.decs = [gpu.press.decode_to_device(r) for r in recs]
     means = []
     for dec in env.decs:
-        ev, first = gpu.events.events_dev(dec, te.DNA, "raw")
-        h_ev, h_first = ev.cpu().numpy().view(tl.EVENT).reshape(-1), first.cpu().numpy()
+        ev, first = gpu.events.events_dev(dec, DNA, "raw")
+        h_ev, h_first = ev.cpu().numpy().view(EVENT).reshape(-1), first.cpu().numpy()
         means.append([h_ev["mean"][h_first[i]:h_first[i + 1]] for i in range(len(h_first) - 1)])
     squeeze = lambda m: (0.7 * m.astype(np.float64) + 180.0).astype(np.float32)
     levels = np.concatenate([rng.normal(500.0, 110.0, 300), squeeze(means[0][0]), rng.normal(500.0, 110.0, 200), squeeze(means[0][3]),
                              rng.normal(500.0, 110.0, 100), squeeze(means[1][1]), rng.normal(500.0, 110.0, 100)]).astype(np.float32)
-    ref = te.quant_ref(levels)
+    ref = quant_ref(levels)
     env.recs, env.levels, env.ref, env.kw, env.P = recs, levels, ref, kw, params(min_cells=16, iters=2)
     env.cases, env.rows, env.maps, env.wants = [], [], [], []
     for dec in env.decs:
-        ev, first = gpu.events.events_dev(dec, te.DNA, "raw")
+        ev, first = gpu.events.events_dev(dec, DNA, "raw")
         out, x = gpu.extend.extend_dev(dec, ref, host=False, **kw)
         rows = x.rows.cpu().numpy().view(EXT_ROW).reshape(-1).copy()
         case = LongCase(x.queries.cpu().numpy(), x.first.cpu().numpy().astype(np.uint64), x.qlen.cpu().numpy(), ref, x.lo.cpu().numpy(), x.hi.cpu().numpy(),
-                        rows["status"], ev.cpu().numpy().view(tl.EVENT).reshape(-1), kw["skip"])
+                        rows["status"], ev.cpu().numpy().view(EVENT).reshape(-1), kw["skip"])
         env.cases.append(case)
         env.rows.append(rows)
         env.maps.append(out.cpu().numpy())
@@ -860,10 +841,10 @@ def test_the_chain_with_refine(gpu, chain, tmp_path):
     scratch_max that forces several groups; s5extend --refine prints those rows; and refine=None is what it was"""
     ex = gpu.extend
     kw, P = chain.kw, chain.P
-    rp = tr.c_params(P)
+    rp = c_params(P)
     case, rows, want = chain.cases[0], chain.rows[0], chain.wants[0]
     print("chain: statuses", want["rows"]["status"].tolist(), "rounds", want["rounds"].tolist(), "fits", want["fit"]["a"].tolist(), want["fit"]["b"].tolist())
-    assert rows["status"].tolist() == [0, te.QUERY_SHORT, 0, 0] and want["rows"]["status"][[0, 3]].tolist() == [0, 0] and want["rounds"][[0, 1, 3]].tolist() == [2, 0, 2]
+    assert rows["status"].tolist() == [0, QUERY_SHORT, 0, 0] and want["rows"]["status"][[0, 3]].tolist() == [0, 0] and want["rounds"][[0, 1, 3]].tolist() == [2, 0, 2]
     mrows, X = ex.extend_dev(chain.decs[0], chain.ref, refine=rp, **kw)
     got = dict(q=X.queries, rows=X.rows, lo=X.lo, hi=X.hi, fit=X.fit, rounds=X.rounds.view(np.uint32))
     _same_out("extend_dev", got, want)
@@ -887,7 +868,7 @@ def test_the_chain_with_refine(gpu, chain, tmp_path):
     # the tool
     ref_txt = tmp_path / "ref.txt"
     ref_txt.write_text("".join("%.9g\n" % v for v in chain.levels))
-    te._synth_file(tmp_path / "reads.blow5", chain.recs[0])
+    synth_file(tmp_path / "reads.blow5", chain.recs[0])
     ids = [ob_id(10 * 0 + i) for i in range(4)]
     args = ["--skip", str(kw["skip"]), "--events", str(kw["qmax"]), "--min-events", str(kw["qmin"]), "--tile", str(kw["tile_rows"]), "--band", str(kw["band"]),
             str(ref_txt), str(tmp_path / "reads.blow5")]
@@ -915,7 +896,7 @@ def test_the_chain_with_refine(gpu, chain, tmp_path):
 
 
 def ob_id(i):
-    x = te.ob.synth_read_id(i)
+    x = ob.synth_read_id(i)
     return x if isinstance(x, bytes) else x.encode()
 
 
@@ -926,69 +907,68 @@ def test_pileup_and_contrast_with_refine(gpu, chain, tmp_path):
     of the same; without refine everything is what it was; set_refine is refused once a batch has been added"""
     pl, ct = gpu.pileup, gpu.contrast
     kw, P = chain.kw, chain.P
-    rp = tr.c_params(P)
+    rp = c_params(P)
     R = len(chain.ref)
     fed = [er.refined_case(c, w) for c, w in zip(chain.cases, chain.wants)]
-    tables = [tl.table_bytes(tl.pileup_long_ref(c)) for c in fed]
-    plain = [tl.table_bytes(tl.pileup_long_ref(c)) for c in chain.cases]
+    tables = [table_bytes(pileup_long_ref(c)) for c in fed]
+    plain = [table_bytes(pileup_long_ref(c)) for c in chain.cases]
     assert tables[0] != plain[0] and tables[1] != plain[1]
     hists = [cr.hist_ref(c) for c in fed]
     for s in (0, 1):
         acc, st, ext = pl.pileup_whole_dev(chain.decs[s], chain.ref, pl.new_acc(R), refine=rp, **kw)
-        assert tl.table_bytes(pl.to_host(acc)) == tables[s] and st.cpu().numpy().tolist() == chain.wants[s]["rows"]["status"].tolist()
+        assert table_bytes(pl.to_host(acc)) == tables[s] and st.cpu().numpy().tolist() == chain.wants[s]["rows"]["status"].tolist()
         assert ext.cpu().numpy().view(EXT_ROW).reshape(-1).tolist() == chain.wants[s]["rows"].tolist()
         acc, st, ext = pl.pileup_whole_dev(chain.decs[s], chain.ref, pl.new_acc(R), refine=None, **kw)
-        assert tl.table_bytes(pl.to_host(acc)) == plain[s]
+        assert table_bytes(pl.to_host(acc)) == plain[s]
         with pl.PileupWhole(chain.ref, refine=rp, **kw) as h:
             rc, map_rows, rows, status = h.add(chain.recs[s][:2])
             assert gpu.L.s5gpu_pileup_set_refine(h._h, None) == -1          # a batch has been added
             h.add(chain.recs[s][2:])
             assert rc == 0 and rows.tolist() == chain.wants[s]["rows"][:2].tolist()
-            assert tl.table_bytes(h.close()) == tables[s]
+            assert table_bytes(h.close()) == tables[s]
         with pl.PileupWhole(chain.ref, refine=None, **kw) as h:
             h.add(chain.recs[s])
-            assert tl.table_bytes(h.close()) == plain[s]
+            assert table_bytes(h.close()) == plain[s]
     f = pl.Pileup(chain.ref, skip=2, qmax=100, qmin=20)
     assert gpu.L.s5gpu_pileup_set_refine(f._h, C.byref(rp)) == -1          # not a whole-read handle
     f.abandon()
     # contrast
-    want_rows = cr.contrast_ref(hists[0][1], hists[1][1], tl.pileup_long_ref(fed[0])[1], tl.pileup_long_ref(fed[1])[1])
+    want_rows = cr.contrast_ref(hists[0][1], hists[1][1], pileup_long_ref(fed[0])[1], pileup_long_ref(fed[1])[1])
     rows, accs, hs = ct.contrast_whole_dev(chain.decs[0], chain.decs[1], chain.ref, refine=rp, **kw)
     rows = ct.rows_to_host(rows)
     assert rows.tobytes() == np.ascontiguousarray(want_rows).tobytes()
     for s in (0, 1):
         head, counts = ct.hist_to_host(hs[s])
-        assert cr.hist_bytes_of((head, counts)) == cr.hist_bytes_of(hists[s]) and tl.table_bytes(pl.to_host(accs[s])) == tables[s]
+        assert cr.hist_bytes_of((head, counts)) == cr.hist_bytes_of(hists[s]) and table_bytes(pl.to_host(accs[s])) == tables[s]
     with ct.Contrast(chain.ref, refine=rp, **kw) as h:
         for s in (1, 0):
             h.add(s, chain.recs[s])
         assert gpu.L.s5gpu_contrast_set_refine(h._h, None) == -1
         hrows, a, b = h.close()
-    assert hrows.tobytes() == rows.tobytes() and [tl.table_bytes(a), tl.table_bytes(b)] == tables
+    assert hrows.tobytes() == rows.tobytes() and [table_bytes(a), table_bytes(b)] == tables
     rows0, _, _ = ct.contrast_whole_dev(chain.decs[0], chain.decs[1], chain.ref, **kw)
     with ct.Contrast(chain.ref, refine=None, **kw) as h:
         for s in (0, 1):
             h.add(s, chain.recs[s])
         hrows0, a, b = h.close()
-    assert hrows0.tobytes() == ct.rows_to_host(rows0).tobytes() and [tl.table_bytes(a), tl.table_bytes(b)] == plain
+    assert hrows0.tobytes() == ct.rows_to_host(rows0).tobytes() and [table_bytes(a), table_bytes(b)] == plain
     # the tools
     ref_txt = tmp_path / "ref.txt"
     ref_txt.write_text("".join("%.9g\n" % v for v in chain.levels))
     for s, name in enumerate(("a.blow5", "b.blow5")):
-        te._synth_file(tmp_path / name, chain.recs[s])
+        synth_file(tmp_path / name, chain.recs[s])
     args = ["--skip", str(kw["skip"]), "--events", str(kw["qmax"]), "--min-events", str(kw["qmin"]), "--tile", str(kw["tile_rows"]), "--band", str(kw["band"])]
     paths = [str(ref_txt), str(tmp_path / "a.blow5"), str(tmp_path / "b.blow5")]
     p = subprocess.run([pl.S5PILEUP, "-K", "3", "--whole", "--refine"] + args + paths[:2], capture_output=True, timeout=120)
-    cols = tl.pileup_long_ref(fed[0])[1]
+    cols = pileup_long_ref(fed[0])[1]
     refused = [int(np.isin(w["rows"]["status"], (FIT_FLAT, FIT_RANGE)).sum()) for w in chain.wants]
-    assert p.returncode == 0 and b"reads refused by the fit %d" % refused[0] in p.stderr and p.stdout == b"".join(tl.tp._lines(chain.ref, cols)), p.stderr
+    assert p.returncode == 0 and b"reads refused by the fit %d" % refused[0] in p.stderr and p.stdout == b"".join(pile_lines(chain.ref, cols)), p.stderr
     p = subprocess.run([pl.S5PILEUP, "-K", "3", "--whole"] + args + paths[:2], capture_output=True, timeout=120)
-    assert p.returncode == 0 and b"refused" not in p.stderr and p.stdout == b"".join(tl.tp._lines(chain.ref, tl.pileup_long_ref(chain.cases[0])[1]))
+    assert p.returncode == 0 and b"refused" not in p.stderr and p.stdout == b"".join(pile_lines(chain.ref, pileup_long_ref(chain.cases[0])[1]))
     p = subprocess.run([pl.S5PILEUP, "--refine"] + args + paths[:2], capture_output=True, timeout=120)
     assert p.returncode == 2                                                # --refine belongs to --whole
-    import test_contrast as tc
     p = subprocess.run([ct.S5CONTRAST, "-K", "3", "--refine"] + args + paths, capture_output=True, timeout=120)
-    lines = tc._lines(chain.ref, want_rows, tl.pileup_long_ref(fed[0])[1], tl.pileup_long_ref(fed[1])[1])
+    lines = cr.contrast_lines(chain.ref, want_rows, pileup_long_ref(fed[0])[1], pileup_long_ref(fed[1])[1])
     assert p.returncode == 0 and b"a.blow5: reads refused by the fit %d" % refused[0] in p.stderr and p.stdout == b"".join(lines) and len(lines) > 100, p.stderr
     t = ct.file_contrast(paths[1], paths[2], paths[0], batch=3, tile_rows=kw["tile_rows"], band=kw["band"], skip=kw["skip"], qmax=kw["qmax"], qmin=kw["qmin"], refine=True)
     assert len(t) == len(lines)

@@ -1,7 +1,7 @@
 """map: subsequence DTW of each read's events against a reference squiggle on the device (docs/codecs.md §4.16;
 slow5tools_amd/csrc/dtw_kernels.hip).
 
-The oracle is a numpy restatement of §4.16 kept in this file: the quantiser in float64 summed strictly left to right, and sDTW with the
+The oracle is the numpy restatement of §4.16 in dtw_ref.py: the quantiser in float64 summed strictly left to right, and sDTW with the
 matrices D and S and the tie rule, vectorised over anti-diagonals (and over a batch of queries of one length).  The definition is integer
 from the quantiser onward, so the device is held to it exactly on all four columns of a row.  The code a lane of k_sdtw runs (dtw_dev.h) is
 plain C++: it is also compiled for the CPU, 64 lanes in a loop with the lane exchange passed in as a function, and held to the same oracle.
@@ -14,115 +14,11 @@ import subprocess
 import numpy as np
 import pytest
 
-import oracle_bind as ob
 from blow5_fixture import Blow5, golden
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DNA = (3, 6, 1.4, 9.0, 0.2)
-MAP_ROW = np.dtype([("cost", "<u4"), ("qlen", "<u4"), ("start", "<i4"), ("end", "<i4")])
-EVENT = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("stdv", "<f4")])
-NO_COST = 0xFFFFFFFF
-EMPTY = (NO_COST, 0, -1, -1)
-QUERY_SHORT = 18
-QLENS = [0, 1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 513, 1000, 1024]      # every lane height, both sides of every lane boundary
-RS = [1, 2, 63, 64, 65, 129, 500]                                                     # R < 64, R < Q, R no multiple of the reference block
-KNOWN_SEED = 20261019
-
-
-# ---------------------------------------------------------------------------------------------------------------- the restatement
-
-def quant_ref(m, scale=32.0, clip=127):
-    """quant of §4.16: float64, sums strictly left to right (cumsum accumulates in order; np.sum would add pairwise)"""
-    m = np.asarray(m, dtype=np.float32)
-    L = len(m)
-    q = np.zeros(L, dtype=np.int16)
-    if L == 0:
-        return q
-    with np.errstate(all="ignore"):
-        d = m.astype(np.float64)
-        mu = np.cumsum(d)[-1] / np.float64(L)
-        e = d - mu
-        sd = np.sqrt(np.cumsum(e * e)[-1] / np.float64(L))
-        if not (sd > 0.0 and np.isfinite(sd)):
-            return q
-        return np.clip(np.rint((e / sd) * np.float64(scale)), -clip, clip).astype(np.int16)
-
-
-def sdtw_ref(q, r):
-    """(cost, start, end) of §4.16 for a batch q[B, Q] of queries of one length (or one query q[Q]) against r[R]: int64 matrices D and S
-    filled along anti-diagonals, the predecessor of least D with ties to the diagonal, then (i - 1, j), then (i, j - 1)"""
-    q = np.asarray(q).astype(np.int64)
-    one = q.ndim == 1
-    if one:
-        q = q[None, :]
-    r = np.asarray(r).astype(np.int64)
-    B, Q = q.shape
-    R = len(r)
-    assert Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((B, Q + 1, R + 1), INF, dtype=np.int64)                    # D[:, i + 1, j + 1] is D[i][j]; row 0: "a path starts here"
-    S = np.full((B, Q + 1, R + 1), -1, dtype=np.int64)
-    D[:, 0, :] = 0
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        dg, up, lf = D[:, i, j], D[:, i, j + 1], D[:, i + 1, j]
-        take_dg = (dg <= up) & (dg <= lf)
-        take_up = ~take_dg & (up <= lf)
-        D[:, i + 1, j + 1] = np.abs(q[:, i] - r[j][None, :]) + np.where(take_dg, dg, np.where(take_up, up, lf))
-        s = np.where(take_dg, S[:, i, j], np.where(take_up, S[:, i, j + 1], S[:, i + 1, j]))
-        S[:, i + 1, j + 1] = np.where((i == 0)[None, :], j[None, :], s)
-    last = D[:, Q, 1:]
-    assert last.max() <= 65535 * Q < 2 ** 26
-    end = np.argmin(last, axis=1)                                          # the first of equal minima: the smallest j
-    b = np.arange(B)
-    cost, start = last[b, end], S[b, Q, end + 1]
-    return (int(cost[0]), int(start[0]), int(end[0])) if one else (cost, start, end)
-
-
-def rows_ref(queries, qlens, r, want_start):
-    """the MAP_ROW rows of a batch: queries a list of int16 arrays (or a matrix), qlens what of each is the query"""
-    out = np.zeros(len(qlens), dtype=MAP_ROW)
-    for i, n in enumerate(qlens):
-        if n == 0:
-            out[i] = EMPTY
-        else:
-            c, s, e = sdtw_ref(np.asarray(queries[i])[:n], r)
-            out[i] = (c, n, s if want_start else -1, e)
-    return out
-
-
-def known_answer_cases(n_draws=40):
-    """§4.16's known answer: a reference of 1200 levels from -100 .. 100, neighbours at least 20 apart; a query that is the slice [a, a + Q)
-    with every level but the first and the last held 1 to 3 times (time warping) aligns at cost 0 from a to a + Q - 1.  Draws whose level
-    sequence stands in the reference twice are dropped.  -> (ref, [(query, a, Q)])"""
-    rng = np.random.default_rng(KNOWN_SEED)
-    lv = [int(rng.integers(-100, 101))]
-    while len(lv) < 1200:
-        v = int(rng.integers(-100, 101))
-        if abs(v - lv[-1]) >= 20:
-            lv.append(v)
-    ref = np.array(lv, dtype=np.int16)
-    cases = []
-    for _ in range(n_draws):
-        Q = int(rng.integers(2, 131))
-        a = int(rng.integers(0, 1200 - Q + 1))
-        rep = rng.integers(1, 4, Q)
-        rep[0] = rep[-1] = 1
-        piece = ref[a:a + Q]
-        occurrences = sum(np.array_equal(ref[k:k + Q], piece) for k in range(1200 - Q + 1))
-        if occurrences == 1:
-            cases.append((np.repeat(piece, rep).astype(np.int16), a, Q))
-    return ref, cases
-
-
-def levels_signal(n, rng):
-    """a raw signal of random levels of dwell 4 .. 20 with a little noise: an event every dozen samples"""
-    lv = []
-    while len(lv) < n:
-        lv += [int(rng.integers(300, 700))] * int(rng.integers(4, 21))
-    return np.round(np.array(lv[:n], dtype=np.float64) + rng.normal(0.0, 3.0, n)).astype(np.int16)
-
+from chain_common import DNA, EMPTY, EVENT, MAP_ROW, NO_COST, QUERY_SHORT, ROOT, host_build, levels_signal, record
+from chain_common import gpu  # noqa: F401
+from dtw_ref import QLENS, RS, _g_of, known_answer_cases, last_lane_batch, map_lines, quant_ref, rows_ref, sdtw_ref
+from dtw_ref import map_ref, mixed_batches  # noqa: F401
 
 # ---------------------------------------------------------------------------------------------------------------- not gpu
 
@@ -293,10 +189,6 @@ int main(int argc, char **argv) {
 '''
 
 
-def _g_of(Q):
-    return next(g for g in (1, 2, 4, 8, 16) if 64 * g >= Q)
-
-
 def test_the_lane_code_compiled_for_the_cpu_matches_the_restatement(tmp_path):
     """lane_init, lane_step, lane_best and the quantiser of dtw_dev.h as g++ compiles them, contraction off: Q on both sides of the lane
     boundaries, R below, at and above the 64 lanes; the lane height the kernel would take and a larger one; values of +-127, of {-1, 0, 1}
@@ -325,10 +217,8 @@ def test_the_lane_code_compiled_for_the_cpu_matches_the_restatement(tmp_path):
             wide = np.full((len(m), stride), 1e30, dtype=np.float32)       # what stands between the means must not matter
             wide[:, 0] = m
             fh.write(struct.pack("<IIIdi", 2, len(m), stride, scale, clip) + wide.tobytes())
-    (tmp_path / "lanes_host.cpp").write_text(LANES_HOST)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           str(tmp_path / "lanes_host.cpp"), "-o", str(tmp_path / "lanes_host")])
-    subprocess.check_call([str(tmp_path / "lanes_host"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    exe = host_build(tmp_path, "lanes_host", LANES_HOST, ["-O1", "-std=c++17", "-ffp-contract=off"])
+    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
     raw, at = (tmp_path / "out.bin").read_bytes(), 0
     for q, r, g in dtw:
         got = np.frombuffer(raw, MAP_ROW, 2, at)
@@ -367,24 +257,12 @@ def test_restatement_finds_the_known_span():
     the reference twice are dropped: at least 20 remain)"""
     ref, cases = known_answer_cases()
     assert len(cases) >= 20 and np.abs(np.diff(ref.astype(np.int64))).min() >= 20
-    assert any(len(q) > Q for q, a, Q in cases)
-    for q, a, Q in cases:
+    assert any(len(q) > Q for q, a, Q, _ in cases)
+    for q, a, Q, _ in cases:
         assert sdtw_ref(q, ref) == (0, a, a + Q - 1), (a, Q)
 
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, events, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map = torch, _lib, _lib.lib(), press, events, smap
-    return env
-
 
 def _run_sdtw(env, qm, qlens, ref, want_start, pitch=None):
     """s5gpu_sdtw_dev on a query matrix (numpy [n, pitch] int16) with guard rows around out_rows -> MAP_ROW array.  Guards and inputs are
@@ -402,35 +280,6 @@ def _run_sdtw(env, qm, qlens, ref, want_start, pitch=None):
     assert (out[:4] == 0x5A5A5A5A).all() and (out[-4:] == 0x5A5A5A5A).all(), "a guard row around out_rows was written"
     assert np.array_equal(d_q.cpu().numpy(), qm) and np.array_equal(d_r.cpu().numpy(), np.asarray(ref, dtype=np.int16))
     return out[4:-4].view(MAP_ROW).copy()
-
-
-def _mixed(rng, lo, hi):
-    """the mixed batch: a [16, 1024] matrix with row i random in [lo, hi] up to QLENS[i]; behind the query stands what a kernel must not read
-    as part of it"""
-    qm = np.full((len(QLENS), 1024), 9999, dtype=np.int16)
-    for i, n in enumerate(QLENS):
-        qm[i, :n] = rng.integers(lo, hi + 1, n)
-    return qm
-
-
-@pytest.fixture(scope="module")
-def mixed_batches():
-    rng = np.random.default_rng(4)
-    return {"pm127": _mixed(rng, -127, 127), "ties": _mixed(rng, -1, 1)}
-
-
-def last_lane_batch(seed=41):
-    """Every row of the last lane: for each lane height G the queries of Q = 64 G - k rows, k < G, whose last row is row (Q - 1) % G of the
-    lane that holds it (the walks are compiled per such row), and for G > 1 the smallest query of the class, 32 G + 1.  -> (the [35, 1024]
-    matrix of +-127, 9999 behind each query; the 35 lengths).  That every row of every lane height occurs is asserted here."""
-    ql = [64 * g - k for g in (1, 2, 4, 8, 16) for k in range(g)] + [32 * g + 1 for g in (2, 4, 8, 16)]
-    for g in (1, 2, 4, 8, 16):
-        assert {(Q - 1) % g for Q in ql if _g_of(Q) == g} == set(range(g)), g
-    rng = np.random.default_rng(seed)
-    qm = np.full((len(ql), 1024), 9999, dtype=np.int16)
-    for i, n in enumerate(ql):
-        qm[i, :n] = rng.integers(-127, 128, n)
-    return qm, ql
 
 
 def _check_rows(got, want, what):
@@ -509,22 +358,17 @@ def test_sdtw_many_waves_and_workgroups(gpu):
 def test_sdtw_dev_finds_the_known_span(gpu):
     torch = gpu.torch
     ref, cases = known_answer_cases()
-    pitch = max(len(q) for q, a, Q in cases)
+    pitch = max(len(q) for q, a, Q, _ in cases)
     qm = np.zeros((len(cases), pitch), dtype=np.int16)
-    for i, (q, a, Q) in enumerate(cases):
+    for i, (q, a, Q, _) in enumerate(cases):
         qm[i, :len(q)] = q
-    ql = [len(q) for q, a, Q in cases]
+    ql = [len(q) for q, a, Q, _ in cases]
     out = gpu.map.sdtw_dev(torch.from_numpy(qm).to("cuda"), torch.from_numpy(np.array(ql, dtype=np.int32)).to("cuda"), torch.from_numpy(ref).to("cuda"),
                            want_start=True)
     assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (len(cases), 4)
     got = out.cpu().numpy().view(MAP_ROW).reshape(-1)
     assert len(cases) >= 20
-    assert got.tolist() == [(0, len(q), a, a + Q - 1) for q, a, Q in cases]
-
-
-def _record(i, sig):
-    r, keep = ob.make_rec(ob.synth_read_id(i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-    return ob.rec_to_mem(r, ob.REC_ZLIB, ob.SIG_SVB_ZD)[8:]
+    assert got.tolist() == [(0, len(q), a, a + Q - 1) for q, a, Q, _ in cases]
 
 
 @pytest.fixture(scope="module")
@@ -532,7 +376,7 @@ def decoded(gpu):
     """a decoded mixed batch with one record that fails to decode, and its event rows as the library makes them"""
     rng = np.random.default_rng(12)
     lengths = [0, 5, 70, 400, 4000, 20000, 400]
-    recs = [_record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
+    recs = [record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
     bad = bytearray(recs[6])
     bad[-1] ^= 0x5A                                                        # the Adler-32 of the zlib stream
     recs[6] = bytes(bad)
@@ -577,12 +421,6 @@ def test_event_queries_are_the_quantised_means(gpu, decoded, skip, qmax, qmin):
         assert (ws[:6] == QUERY_SHORT).sum() >= 2 and (ws[:6] == 0).sum() >= 2
     if qmax > 1:
         assert np.abs(wq[5].astype(np.int64)).max() > 20 and abs(int(wq[5].astype(np.int64).sum())) < 16 * qmax
-
-
-@pytest.fixture(scope="module")
-def map_ref():
-    rng = np.random.default_rng(21)
-    return quant_ref(rng.normal(90.0, 12.0, 800).astype(np.float32))
 
 
 def _map_want(gpu, dec, n, ref, skip, qmax, qmin, want_start):
@@ -637,17 +475,6 @@ def test_map_batch_with_a_corrupt_record(gpu, map_ref):
     assert got[1].tolist() == EMPTY and got[0] == good[0] and np.array_equal(got[2:], good[2:])
 
 
-def _lines(ids, rows, want_start):
-    out = []
-    for rid, r in zip(ids, rows):
-        if r["qlen"] == 0:
-            out.append(rid + b"\t*\t*\t*\t*\t*\n")
-        else:
-            out.append(b"%s\t%d\t%d\t%s\t%s\t%d\n" % (rid, r["qlen"], r["cost"], b"%.6g" % (float(r["cost"]) / float(r["qlen"])),
-                                                     b"%d" % r["start"] if want_start else b"*", r["end"]))
-    return b"".join(out)
-
-
 @pytest.mark.gpu
 def test_s5map_prints_the_restatements_lines(gpu, tmp_path):
     rng = np.random.default_rng(31)
@@ -666,7 +493,7 @@ def test_s5map_prints_the_restatements_lines(gpu, tmp_path):
         want, wst = _map_want(gpu, dec, n, ref, skip, qmax, qmin, ws)
         p = subprocess.run([gpu.map.S5MAP] + args + [str(ref_txt), golden("example_multi_rg_v0.2.0.blow5")], capture_output=True, timeout=120)
         assert p.returncode == 0, p.stderr
-        assert p.stdout == _lines(ids, want, ws), args
+        assert p.stdout == map_lines(ids, want, ws), args
     assert 0 < (want["qlen"] == 0).sum() < n                               # the last run printed both kinds of line
     got_ids, got = gpu.map.file_map(golden("example_multi_rg_v0.2.0.blow5"), ref_txt, qmax=some, qmin=some, want_start=True)
     assert got_ids == ids and got.tolist() == want.tolist()
@@ -678,7 +505,7 @@ def test_s5map_prints_the_restatements_lines(gpu, tmp_path):
     p = subprocess.run([gpu.map.S5MAP, "--events", "64", "--min-events", "20", str(ref_txt), str(tmp_path / "bad.blow5")], capture_output=True, timeout=120)
     assert p.returncode == 1 and ids[1] in p.stderr
     keep = [i for i in range(n) if i != 1]
-    assert p.stdout == _lines([ids[i] for i in keep], want[keep], False)
+    assert p.stdout == map_lines([ids[i] for i in keep], want[keep], False)
     # an empty reference, an unparsable one, no arguments: exit 2
     (tmp_path / "empty.txt").write_text("# nothing\n\n")
     (tmp_path / "words.txt").write_text("1.5\nabc\n")

@@ -3,7 +3,7 @@ slow5tools_amd/csrc/dtw_dev.h `lane_second`, dtw_kernels.hip `k_sdtw2`, refseq.c
 
 The oracle is numpy, kept in this file: the last row of §4.16's matrix by its recurrence, the direct definition of cost2 / end2 / mapq over
 that row, and the level, segment and wall rules of a reference.  Everything is integer from the quantiser onward, so the library is held
-to it exactly.  The restatement of the best hit (cost, start, end) and of the quantiser is that of tests/test_map.py.
+to it exactly.  The restatement of the best hit (cost, start, end) and of the quantiser is that of tests/dtw_ref.py.
 """
 import ctypes as C
 import os
@@ -14,9 +14,11 @@ import numpy as np
 import pytest
 
 from blow5_fixture import Blow5, golden
-from test_map import DNA, EVENT, MAP_ROW, NO_COST, QLENS, QUERY_SHORT, RS, _lines, _mixed, last_lane_batch, quant_ref, sdtw_ref
+from chain_common import DNA, EVENT, GUARD, MAP_ROW, NO_COST, QUERY_SHORT, ROOT, host_build
+from chain_common import gpu  # noqa: F401
+from dtw_ref import QLENS, RS, _g_of, last_lane_batch, map_lines, quant_ref, sdtw_ref
+from dtw_ref import map_ref, mixed_batches  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAP_SECOND = np.dtype([("cost2", "<u4"), ("end2", "<i4"), ("mapq", "<u4"), ("zero", "<u4")])
 NONE2 = (NO_COST, -1, 0, 0)
 RNA = (7, 14, 2.5, 9.0, 1.0)                                               # s5map --rna's event parameters
@@ -276,10 +278,6 @@ int main(int argc, char **argv) {
 '''
 
 
-def _g_of(Q):
-    return next(g for g in (1, 2, 4, 8, 16) if 64 * g >= Q)
-
-
 def test_lane_second_compiled_for_the_cpu_matches_the_restatement(tmp_path):
     """lane_second, second_flush and second_row of dtw_dev.h as g++ compiles them, in 64-lane lockstep: every Q and R of the issue at block
     shifts 6 and 7, values of +-127 and of {-1, 0, 1} (ties); references within three blocks (no runner-up unless the best hit is in an outer
@@ -306,10 +304,8 @@ def test_lane_second_compiled_for_the_cpu_matches_the_restatement(tmp_path):
     with open(tmp_path / "in.bin", "wb") as fh:
         for q, r, g, b in cases:
             fh.write(struct.pack("<IIII", len(q), len(r), g, b) + q.tobytes() + r.tobytes())
-    (tmp_path / "second_host.cpp").write_text(SECOND_HOST)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           str(tmp_path / "second_host.cpp"), "-o", str(tmp_path / "second_host")])
-    subprocess.check_call([str(tmp_path / "second_host"), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    exe = host_build(tmp_path, "second_host", SECOND_HOST, ["-O1", "-std=c++17", "-ffp-contract=off"])
+    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
     raw = (tmp_path / "out.bin").read_bytes()
     assert len(raw) == 64 * len(cases)
     none = some = 0
@@ -481,21 +477,6 @@ def test_the_wall_property_on_the_restatement():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, align, events, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.align = torch, _lib, _lib.lib(), press, events, smap, align
-    return env
-
-
-GUARD = 0x5A5A5A5A
-
-
 def _run_sdtw2(env, qm, qlens, ref, want_start, bshift=6, compare=True):
     """s5gpu_sdtw2_dev on a query matrix with guard rows around both outputs -> (MAP_ROW array, MAP_SECOND array); out_rows is held to what
     s5gpu_sdtw_dev writes for the same arguments, bit for bit"""
@@ -525,12 +506,6 @@ def _check_second(got, want, what):
     for col in ("cost2", "end2", "mapq", "zero"):
         bad = np.nonzero(got[col] != want[col])[0]
         assert len(bad) == 0, (what, col, int(bad[0]), got[bad[0]].tolist(), want[bad[0]].tolist())
-
-
-@pytest.fixture(scope="module")
-def mixed_batches():
-    rng = np.random.default_rng(4)
-    return {"pm127": _mixed(rng, -127, 127), "ties": _mixed(rng, -1, 1)}
 
 
 @pytest.mark.gpu
@@ -698,12 +673,6 @@ def _map2_want(gpu, dec, n, ref, skip, qmax, qmin, want_start, bshift, event_par
     return want, want2, st
 
 
-@pytest.fixture(scope="module")
-def map_ref():
-    rng = np.random.default_rng(21)
-    return quant_ref(rng.normal(90.0, 12.0, 800).astype(np.float32))
-
-
 @pytest.mark.gpu
 def test_read_map2_and_map2_dev_on_a_golden_file(gpu, map_ref):
     f = Blow5(golden("exp_1_lossless.blow5"))
@@ -742,7 +711,7 @@ def test_map2_batch_with_a_corrupt_record(gpu, map_ref):
 
 def _lines2(ids, rows, sec, want_start):
     out = []
-    for line, r, s in zip(_lines(ids, rows, want_start).split(b"\n"), rows, sec):
+    for line, r, s in zip(map_lines(ids, rows, want_start).split(b"\n"), rows, sec):
         tail = b"\t*\t*\t*" if r["qlen"] == 0 else b"\t*\t*\t%d" % s["mapq"] if s["end2"] < 0 else b"\t%d\t%d\t%d" % (s["cost2"], s["end2"], s["mapq"])
         out.append(line + tail + b"\n")
     return b"".join(out)
@@ -772,7 +741,7 @@ def test_s5map_second_and_the_plain_lines(gpu, tmp_path):
         assert p.stdout == _lines2(ids, want, want2, ws), new + plain
         # without the new options: byte for byte the lines of the tool as it was
         p = subprocess.run([gpu.map.S5MAP] + plain + [str(ref_txt), path], capture_output=True, timeout=120)
-        assert p.returncode == 0 and p.stdout == _lines(ids, want, ws), plain
+        assert p.returncode == 0 and p.stdout == map_lines(ids, want, ws), plain
     assert 0 < (want["qlen"] == 0).sum() < n
     got_ids, got = gpu.map.file_map(path, ref_txt, qmax=some, qmin=some, want_start=True)
     assert got_ids == ids and got.tolist() == want.tolist()

@@ -1,15 +1,14 @@
 """pileup of whole reads: the ragged paths of extend added to the table (docs/codecs.md §4.22; slow5tools_amd/csrc/pileup_kernels.hip, the
 layout and the walk over its segments in ragged_dev.h).
 
-The oracle is pileup_long_ref in this file: the definition of §4.22 in int64 numpy for the ragged layout, read by read, with the invariants
-asserted.  It is tied to §4.18's restatement (test_pileup.pileup_ref) on every case of that file re-laid as ragged.  Every member of the
+The oracle is pileup_long_ref of pileup_ref.py: the definition of §4.22 in int64 numpy for the ragged layout, read by read, with the invariants
+asserted.  It is tied to §4.18's restatement (pileup_ref, in the same file) on every case of that file re-laid as ragged.  Every member of the
 table is an integer sum, minimum or maximum, so the device is held to it byte for byte, whatever the segment length, the window, the sort,
 the grid, the calls and the streams.  The headers' plain C++ (ragged_dev.h, pileup_dev.h) is also compiled for the CPU, once more under the
 address and undefined-behaviour sanitizers, and held to the same oracle with the segments visited in a shuffled order, each resolved by
 seg_item, the one resolver the kernels walk with; seg_item itself is held to a plain double loop over reads and segments.
 """
 import ctypes as C
-import functools
 import os
 import struct
 import subprocess
@@ -17,260 +16,12 @@ import subprocess
 import numpy as np
 import pytest
 
-import test_pileup as tp
-from test_pileup import BEHIND, EVENT, PATH_ROW, PATH_WIDE, PILE_COL, PILE_TOTAL, QUERY_SHORT, ROOT, _explain, table_bytes
-
-EXT_ROW = np.dtype([("cost", "<u8"), ("qlen", "<u4"), ("tiles", "<u4"), ("start", "<i4"), ("end", "<i4"), ("a_last", "<i4"), ("status", "<i4")])
-LONG_QMAX = 1 << 20
-DEFAULT_SEG, DEFAULT_COLS, DEFAULT_SORT, DEFAULT_GRID = 256, 1024, 1, 1024   # the library's defaults (docs/codecs.md §4.22)
-
-
-# ---------------------------------------------------------------------------------------------------------------- the restatement
-
-class LongCase:
-    """the inputs of s5gpu_pileup_accum_long_dev on the host: q, lo, hi [total_rows], first [n + 1] uint64, qlen [n], status [n], ref [R],
-    ev [total_rows] EVENT and ev_skip.  total_rows is the arrays' length whatever `first` claims."""
-
-    def __init__(self, q, first, qlen, ref, lo, hi, status=None, ev=None, ev_skip=0):
-        self.q = np.ascontiguousarray(q, dtype=np.int16)
-        self.total = len(self.q)
-        self.first = np.asarray(first, dtype=np.uint64).copy()
-        self.n = len(self.first) - 1
-        self.qlen = np.asarray(qlen, dtype=np.uint32).copy()
-        self.ref = np.ascontiguousarray(ref, dtype=np.int16)
-        self.R = len(self.ref)
-        self.lo, self.hi = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
-        self.status = np.zeros(self.n, dtype=np.int32) if status is None else np.asarray(status, dtype=np.int32).copy()
-        if ev is None:
-            ev = np.zeros(self.total, dtype=EVENT)
-            ev["length"] = np.random.default_rng(self.n * 31 + self.R).integers(1, 5000, self.total)
-            ev["start"], ev["mean"], ev["stdv"] = 7, 1.5, 0.25
-        self.ev = np.ascontiguousarray(ev, dtype=EVENT)
-        self.ev_skip = int(ev_skip)
-        assert self.n >= 0 and len(self.qlen) == len(self.status) == self.n and len(self.lo) == len(self.hi) == len(self.ev) == self.total
-
-    def copy(self):
-        return LongCase(self.q.copy(), self.first, self.qlen, self.ref.copy(), self.lo.copy(), self.hi.copy(), self.status, self.ev.copy(), self.ev_skip)
-
-
-def pileup_long_ref(case, events=True):
-    """(total, cols) of §4.22 for a LongCase.  int64 numpy, a read at a time; the invariants asserted."""
-    R = case.R
-    r = case.ref.astype(np.int64)
-    depth, n_events, n_samples = np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
-    sum_q, sumsq_q, sum_cost = np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
-    min_q, max_q = np.full(R, 32767, np.int64), np.full(R, -32768, np.int64)
-    used = skipped = bad = cells = cost = spans = 0
-    skip = case.ev_skip if events else 0
-    for k in range(case.n):
-        Q, f0, f1 = int(case.qlen[k]), int(case.first[k]), int(case.first[k + 1])
-        if case.status[k] != 0 or Q == 0:
-            skipped += 1
-            continue
-        if Q > LONG_QMAX or f0 > f1 or f1 > case.total or Q + skip > f1 - f0:
-            bad += 1
-            continue
-        lo, hi = case.lo[f0:f0 + Q].astype(np.int64), case.hi[f0:f0 + Q].astype(np.int64)
-        ok = ((0 <= lo) & (lo <= hi) & (hi < R)).all()
-        ok = ok and bool(np.isin(lo[1:] - hi[:-1], (0, 1)).all())
-        if not ok:
-            bad += 1
-            continue
-        used += 1
-        w = hi - lo + 1
-        i = np.repeat(np.arange(Q), w)                                     # the cells (i, j), row by row
-        j = lo[i] + np.arange(w.sum()) - np.repeat(np.cumsum(w) - w, w)
-        assert (j >= lo[i]).all() and (j <= hi[i]).all() and len(j) <= Q + R
-        first = (i == 0) | (j > hi[np.maximum(i - 1, 0)])
-        q = case.q[f0:f0 + Q].astype(np.int64)[i]
-        c = np.abs(q - r[j])
-        np.add.at(depth, j, first.astype(np.int64))
-        np.add.at(n_events, j, 1)
-        if events:
-            np.add.at(n_samples, j, case.ev["length"][f0 + skip:f0 + skip + Q].astype(np.int64)[i])
-        np.add.at(sum_q, j, q)
-        np.add.at(sumsq_q, j, q * q)
-        np.add.at(sum_cost, j, c)
-        np.minimum.at(min_q, j, q)
-        np.maximum.at(max_q, j, q)
-        cells += len(j)
-        cost += int(c.sum())
-        spans += int(hi[Q - 1] - lo[0] + 1)
-        assert int(first.sum()) == int(hi[Q - 1] - lo[0] + 1)              # a read is first once in every column it covers, seams or not
-    assert int(n_events.sum()) == cells and int(sum_cost.sum()) == cost and int(depth.sum()) == spans
-    assert used + skipped + bad == case.n and (depth <= n_events).all() and n_events.max(initial=0) < 2 ** 32 and sumsq_q.min(initial=0) >= 0
-    cols = np.zeros(R, dtype=PILE_COL)
-    for name, a in (("depth", depth), ("n_events", n_events), ("n_samples", n_samples), ("sum_q", sum_q), ("sumsq_q", sumsq_q), ("sum_cost", sum_cost),
-                    ("min_q", min_q), ("max_q", max_q)):
-        cols[name] = a
-    total = np.zeros(1, dtype=PILE_TOTAL)
-    total[0] = (used, skipped, bad, cells, cost, R, (0, 0, 0, 0, 0))
-    return total[0], cols
-
-
-def relay(case, ev_skip=0, seed=1):
-    """a test_pileup.Case re-laid as ragged: read k's Q = min(qlen, pitch) rows at first[k], its event rows ev_skip further on, and 0 to 2
-    rows that belong to nobody behind them"""
-    rng = np.random.default_rng(seed)
-    Q = np.minimum(case.qlen.astype(np.int64), case.pitch)
-    rows = Q + ev_skip + rng.integers(0, 3, case.n)
-    first = np.concatenate(([0], np.cumsum(rows))).astype(np.uint64)
-    total = int(first[-1])
-    q, lo, hi = np.zeros(total, np.int16), np.full(total, BEHIND, np.int32), np.full(total, BEHIND, np.int32)
-    ev = np.zeros(total, dtype=EVENT)
-    ev["length"] = 99999                                                    # (never a row's own: a wrong index shows)
-    for k in range(case.n):
-        f, n = int(first[k]), int(Q[k])
-        q[f:f + n], lo[f:f + n], hi[f:f + n] = case.qm[k, :n], case.lo[k, :n], case.hi[k, :n]
-        ev[f + ev_skip:f + ev_skip + n] = case.ev[k, :n]
-    return LongCase(q, first, Q, case.ref, lo, hi, case.status, ev, ev_skip)
-
-
-def path_of(start, steps, spans):
-    """lo, hi of the path that starts at column `start`: row i begins steps[i] (0 or 1) right of where row i - 1 ended and covers spans[i]"""
-    lo, hi = np.zeros(len(spans), np.int64), np.zeros(len(spans), np.int64)
-    at = start
-    for i, (st, sp) in enumerate(zip(steps, spans)):
-        lo[i] = at if i == 0 else at + st
-        at = hi[i] = lo[i] + sp - 1
-    return lo, hi
-
-
-def from_paths(seed, paths, R, ev_skip=0, lohi=127):
-    """a LongCase of the reads whose (lo, hi) are given, random queries and reference"""
-    rng = np.random.default_rng(seed)
-    Q = np.array([len(p[0]) for p in paths], dtype=np.int64)
-    first = np.concatenate(([0], np.cumsum(Q + ev_skip))).astype(np.uint64)
-    total = int(first[-1])
-    lo, hi = np.full(total, BEHIND, np.int32), np.full(total, BEHIND, np.int32)
-    for k, (l, h) in enumerate(paths):
-        f = int(first[k])
-        lo[f:f + len(l)], hi[f:f + len(h)] = l, h
-    return LongCase(rng.integers(-lohi, lohi + 1, total), first, Q, rng.integers(-lohi, lohi + 1, R), lo, hi, ev_skip=ev_skip)
-
-
-def mixed_long(R, ev_skip=0):
-    qlens = [1, 63, 64, 65, 128, 129, 1025, 3000]
-    rng = np.random.default_rng(500 + R)
-    lo, hi = tp.random_paths(rng, qlens, R, 3000)
-    return from_paths(600 + R, [(lo[k, :Q], hi[k, :Q]) for k, Q in enumerate(qlens)], R, ev_skip)
-
-
-def seams_case():
-    """at segments of 64 rows: read 0 has a row of 300 columns that ends segment 0 (row 63) and another that starts segment 1 (row 64); read 1
-    stays at rows 64 and 128 (lo == hi of the row before), read 2 steps there; every read covers its columns once"""
-    R, Q = 1000, 200
-    ones, zeros = np.ones(Q, np.int64), np.zeros(Q, np.int64)
-    sp = ones.copy()
-    sp[63] = sp[64] = 300
-    st = zeros.copy()
-    st[64] = 1
-    wide = path_of(10, st, sp)
-    rng = np.random.default_rng(64)
-    st1, st2, sp12 = rng.integers(0, 2, Q), rng.integers(0, 2, Q), rng.integers(1, 4, Q)
-    st1[[64, 128]], st2[[64, 128]] = 0, 1
-    stay, step = path_of(100, st1, sp12), path_of(120, st2, sp12)
-    assert wide[1][63] - wide[0][63] + 1 == 300 and wide[0][64] == wide[1][63] + 1 and wide[1][64] - wide[0][64] + 1 == 300
-    assert stay[0][64] == stay[1][63] and stay[0][128] == stay[1][127] and step[0][64] == step[1][63] + 1 and step[0][128] == step[1][127] + 1
-    assert max(wide[1][-1], stay[1][-1], step[1][-1]) < R
-    return from_paths(65, [wide, stay, step], R)
-
-
-def flawed_long_cases():
-    """{name: (LongCase, skipped, bad)}: two reads of 200 rows around a 3000-row read that is valid but for one flaw (a segment of 64 rows
-    never sees a flaw in another), or that is skipped"""
-    R, Q, at = 4000, 3000, 1
-    rng = np.random.default_rng(3000)
-    lo, hi = tp.random_paths(rng, [200, Q, 200], R - 4, 3000, start=[5, 20, 900])
-    assert hi[at, Q - 1] < R - 4
-    base = from_paths(3001, [(lo[k, :n], hi[k, :n]) for k, n in enumerate([200, Q, 200])], R)
-    f = int(base.first[at])
-    out = {}
-
-    def put(name, skipped, bad, fn):
-        c = base.copy()
-        fn(c)
-        out[name] = (c, skipped, bad)
-    put("valid", 0, 0, lambda c: None)
-    put("lo -1 at row 2999", 0, 1, lambda c: c.lo.__setitem__(f + 2999, -1))
-    put("hi R at row 0", 0, 1, lambda c: c.hi.__setitem__(f, R))
-
-    def gap2(c):                                                            # rows 128 .. move right by 2: only the gap rule fails, at row 128
-        c.lo[f + 128:f + Q] += 2
-        c.hi[f + 128:f + Q] += 2
-    put("gap 2 between rows 127 and 128", 0, 1, gap2)
-    for s in (QUERY_SHORT, PATH_WIDE, PATH_ROW, 5):
-        put("status %d" % s, 1, 0, lambda c, s=s: c.status.__setitem__(at, s))
-    put("qlen 0", 1, 0, lambda c: c.qlen.__setitem__(at, 0))
-    return out
-
-
-def layout_cases():
-    """{name: (LongCase, bad read)}: four reads of 150 rows, one of which fails ONE layout check; its own path is valid, so a missing check
-    would show in the table"""
-    out = {}
-    R, Q = 700, 150
-
-    def base(ev_skip=0, pad=0, qs=(Q, Q, Q, Q)):
-        rng = np.random.default_rng(150)
-        lo, hi = tp.random_paths(rng, list(qs), R, max(qs))
-        c = from_paths(151, [(lo[k, :n], hi[k, :n]) for k, n in enumerate(qs)], R, ev_skip)
-        if pad:                                                             # rows behind the last read that belong to nobody
-            c = LongCase(np.concatenate((c.q, np.zeros(pad, np.int16))), c.first, c.qlen, c.ref, np.concatenate((c.lo, np.full(pad, BEHIND, np.int32))),
-                         np.concatenate((c.hi, np.full(pad, BEHIND, np.int32))), c.status, np.concatenate((c.ev, np.zeros(pad, EVENT))), ev_skip)
-        return c
-    # first[1] > first[2]: read 1 claims rows [200, 150); read 0 keeps its 150 rows, read 2 starts at 150 as if read 1 were empty
-    c = base(qs=(Q, 0, Q, Q))
-    c.first[1] = 200
-    c.qlen[1] = 1                                                           # (row 200 is a row of read 2's: valid as a row 0)
-    out["first[k] > first[k + 1]"] = (c, 1)
-    c = base()
-    c.first[4] = c.total + 1
-    out["first[k + 1] > total_rows"] = (c, 3)
-    c = base(ev_skip=3, pad=8)
-    c.qlen[2] += 1                                                          # Q + ev_skip one above the read's rows; the row behind is made valid
-    f = int(c.first[2])
-    c.lo[f + Q] = c.hi[f + Q] = c.hi[f + Q - 1]
-    out["Q + ev_skip one above the rows"] = (c, 2)
-    # Q = 2^20 + 1 with the rows to match: a read that stays at column 3 all the way
-    big = LONG_QMAX + 1
-    lo, hi = tp.random_paths(np.random.default_rng(7), [Q, Q], R, Q)
-    stay = (np.full(big, 3, np.int64), np.full(big, 3, np.int64))
-    c = from_paths(152, [(lo[0], hi[0]), stay, (lo[1], hi[1])], R)
-    out["Q = 2^20 + 1"] = (c, 1)
-    return out
-
-
-def sums_long():
-    """one read of 65 536 rows, every q = 32767, on a reference of one level -32768"""
-    Q = 65536
-    return LongCase(np.full(Q, 32767, np.int16), [0, Q], [Q], [-32768], np.zeros(Q, np.int32), np.zeros(Q, np.int32))
-
-
-def piling_case():
-    """48 reads of 700 rows piling on the same 300 columns"""
-    rng = np.random.default_rng(48)
-    n, Q = 48, 700
-    lo, hi = tp.random_paths(rng, [Q] * n, 1000, Q, start=rng.integers(100, 104, n), cap=399)
-    return from_paths(49, [(lo[k], hi[k]) for k in range(n)], 1000)
-
-
-@functools.lru_cache(maxsize=None)
-def long_cases():
-    """the case list of the CPU and the GPU tests: {name: LongCase}, at segments of 64 rows unless a test says otherwise"""
-    cases = {}
-    for R in (1, 65, 5000):
-        cases["mixed R=%d" % R] = mixed_long(R)
-    cases["mixed R=5000 ev_skip 3"] = mixed_long(5000, 3)
-    cases["seams"] = seams_case()
-    cases.update({"flawed: " + k: v[0] for k, v in flawed_long_cases().items()})
-    cases.update({"layout: " + k: v[0] for k, v in layout_cases().items()})
-    cases["64-bit sums"] = sums_long()
-    cases["piling"] = piling_case()
-    cases["empty batch"] = LongCase(np.zeros(0, np.int16), [0], [], [1, 2, 3], np.zeros(0, np.int32), np.zeros(0, np.int32))
-    cases["n = 1"] = from_paths(1, [path_of(2, np.ones(70, np.int64), np.full(70, 2, np.int64))], 200)
-    return cases
-
+from chain_common import BEHIND, DEFAULT_COLS, DEFAULT_GRID, DEFAULT_SEG, DEFAULT_SORT, DNA, EVENT, EXT_ROW, PATH_ROW, PATH_WIDE, PILE_COL, PILE_TOTAL, QUERY_SHORT, ROOT
+from chain_common import Acc, host_build, levels_signal, pile_accum, pile_lines, record, synth_file
+from chain_common import gpu  # noqa: F401
+from dtw_ref import quant_ref
+from pileup_ref import LongCase, _explain, _first_lo, flawed_long_cases, kernel_cases, layout_cases, long_cases, mixed_case, pileup_long_ref, pileup_ref, piling_case
+from pileup_ref import relay, sums_long, table_bytes
 
 _WANT = {}
 
@@ -381,7 +132,7 @@ def test_the_options_refuse_bad_values():
             assert L.s5gpu_set_option(key, v) == -1, (key, v)
         for v in good:                                                     # (the defaults last)
             assert L.s5gpu_set_option(key, v) == 0, (key, v)
-    for key, v in ((b"pileup_lds_cols", tp.DEFAULT_COLS), (b"pileup_grid", tp.DEFAULT_GRID)):     # the old keys keep their meaning
+    for key, v in ((b"pileup_lds_cols", DEFAULT_COLS), (b"pileup_grid", DEFAULT_GRID)):     # the old keys keep their meaning
         assert L.s5gpu_set_option(key, v) == 0
 
 
@@ -396,9 +147,9 @@ def test_restatement_on_hand_made_paths_and_against_the_fixed_pitch_one():
     assert cols["n_samples"].tolist() == [4, 4 + 5 + 7, 6 + 8, 6, 6, 0] and cols["sum_cost"].tolist() == [9, 8 + 18 + 3, 27 + 8, 26, 25, 0]
     assert tuple(total)[:6] == (2, 0, 0, 8, 124, 6)
     # every case of the fixed-pitch list, re-laid: the two definitions agree
-    for name, case in tp.kernel_cases().items():
+    for name, case in kernel_cases().items():
         for events in (True, False):
-            want = table_bytes(tp.pileup_ref(case, events))
+            want = table_bytes(pileup_ref(case, events))
             for ev_skip in (0, 3):
                 got = table_bytes(pileup_long_ref(relay(case, ev_skip), events))
                 assert got == want, (name, events, ev_skip, _explain(got, want))
@@ -582,10 +333,7 @@ int main(int argc, char **argv) {
 
 
 def _build_host(tmp_path, extra=()):
-    (tmp_path / "pile_long_host.cpp").write_text(PILE_LONG_HOST)
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"), str(tmp_path / "pile_long_host.cpp"),
-                           "-o", str(tmp_path / "pile_long_host")])
-    return str(tmp_path / "pile_long_host")
+    return host_build(tmp_path, "pile_long_host", PILE_LONG_HOST, ["-O1", "-g", "-std=c++17", "-Wall"], extra)
 
 
 def _run_host(exe, tmp_path, case, events=True, S=64, cols=0, wlo=0, sort=0, seed=1):
@@ -595,12 +343,6 @@ def _run_host(exe, tmp_path, case, events=True, S=64, cols=0, wlo=0, sort=0, see
             fh.write(a.tobytes())
     subprocess.check_call([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
     return (tmp_path / "out.bin").read_bytes()
-
-
-def _first_lo(case):
-    at = [int(case.lo[int(case.first[k])]) for k in range(case.n) if case.status[k] == 0 and case.qlen[k] and int(case.first[k]) < case.total]
-    at = [a for a in at if 0 <= a < case.R]
-    return min(at) if at else 0
 
 
 def run_long_header_on_the_cpu(tmp_path, extra=(), thorough=True):
@@ -630,18 +372,6 @@ def test_the_header_code_runs_clean_under_the_sanitizers(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, align, events, extend, pileup, press
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.align, env.pileup, env.extend = torch, _lib, _lib.lib(), press, events, smap, align, pileup, extend
-    return env
-
 
 def _options(env, seg=64, cols=DEFAULT_COLS, sort=DEFAULT_SORT, grid=DEFAULT_GRID):
     for key, v in ((b"pileup_long_seg", seg), (b"pileup_long_cols", cols), (b"pileup_long_sort", sort), (b"pileup_long_grid", grid)):
@@ -681,7 +411,7 @@ def _accum_long(env, acc, case, events=True, stream=None, sync=True, short=0, wa
 def _table(env, case, events=True, **opt):
     _options(env, **opt)
     try:
-        return _accum_long(env, tp.Acc(env, case.R), case, events)
+        return _accum_long(env, Acc(env, case.R), case, events)
     finally:
         _options(env, seg=DEFAULT_SEG)
 
@@ -719,8 +449,8 @@ def test_the_options_do_not_change_the_table(gpu, name):
 
 @pytest.mark.gpu
 def test_short_reads_give_the_table_of_the_fixed_pitch_kernel(gpu):
-    case = tp.mixed_case(129, 200)
-    fixed = tp._accum(gpu, tp.Acc(gpu, case.R), case)
+    case = mixed_case(129, 200)
+    fixed = pile_accum(gpu, Acc(gpu, case.R), case)
     for ev_skip in (0, 3):
         for sort in (0, 1):
             got = _table(gpu, relay(case, ev_skip), True, sort=sort)
@@ -730,14 +460,14 @@ def test_short_reads_give_the_table_of_the_fixed_pitch_kernel(gpu):
 @pytest.mark.gpu
 def test_ragged_and_fixed_pitch_calls_share_an_accumulator(gpu):
     torch = gpu.torch
-    case = tp.mixed_case(129, 200)
-    want = table_bytes(tp.pileup_ref(case))
+    case = mixed_case(129, 200)
+    want = table_bytes(pileup_ref(case))
     a, b, c = relay(case.part(0, 60)), relay(case.part(60, 130), 3), case.part(130, 200)
-    acc = tp.Acc(gpu, case.R)
+    acc = Acc(gpu, case.R)
     _options(gpu)
     try:
         s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-        checks = [_accum_long(gpu, acc, a, stream=s1, sync=False), _accum_long(gpu, acc, b, stream=s2, sync=False), tp._accum(gpu, acc, c, sync=False)]
+        checks = [_accum_long(gpu, acc, a, stream=s1, sync=False), _accum_long(gpu, acc, b, stream=s2, sync=False), pile_accum(gpu, acc, c, sync=False)]
         torch.cuda.synchronize()
         got = [f() for f in checks][-1]
         assert got == want, _explain(got, want)
@@ -747,10 +477,6 @@ def test_ragged_and_fixed_pitch_calls_share_an_accumulator(gpu):
         _options(gpu, seg=DEFAULT_SEG)
 
 
-def _record(i, sig):
-    return tp._record(i, sig)
-
-
 @pytest.fixture(scope="module")
 def chain(gpu):
     """five synthetic reads of about 3000 events, one of them too short for a query: the records, the reference, and the restatement fed with
@@ -758,12 +484,12 @@ def chain(gpu):
     torch = gpu.torch
     rng = np.random.default_rng(4022)
     lengths = [36000, 30000, 100, 40000, 33000]
-    recs = [_record(i, tp.levels_signal(n, rng)) for i, n in enumerate(lengths)]
+    recs = [record(i, levels_signal(n, rng)) for i, n in enumerate(lengths)]
     levels = rng.normal(500.0, 110.0, 3500).astype(np.float32)
-    ref = tp.quant_ref(levels)
+    ref = quant_ref(levels)
     kw = dict(skip=2, qmax=100, qmin=20, tile_rows=64, band=128)
     dec = gpu.press.decode_to_device(recs)
-    ev, first = gpu.events.events_dev(dec, tp.DNA, "raw")
+    ev, first = gpu.events.events_dev(dec, DNA, "raw")
     out, x = gpu.extend.extend_dev(dec, ref, host=False, **kw)
     rows = x.rows.cpu().numpy().view(EXT_ROW).reshape(-1)
     case = LongCase(x.queries.cpu().numpy(), x.first.cpu().numpy().astype(np.uint64), x.qlen.cpu().numpy(), ref, x.lo.cpu().numpy(), x.hi.cpu().numpy(),
@@ -834,14 +560,14 @@ def test_the_tool_with_and_without_whole(gpu, chain, tmp_path):
     pl = gpu.pileup
     ref_txt = tmp_path / "ref.txt"
     ref_txt.write_text("".join("%.9g\n" % v for v in chain.levels))
-    tp._synth_file(tmp_path / "reads.blow5", chain.recs)
+    synth_file(tmp_path / "reads.blow5", chain.recs)
     kw = chain.kw
     args = ["--skip", str(kw["skip"]), "--events", str(kw["qmax"]), "--min-events", str(kw["qmin"])]
     files = [str(ref_txt), str(tmp_path / "reads.blow5")]
     total, cols = chain.want
     p = subprocess.run([pl.S5PILEUP, "-K", "3", "--whole", "--tile", str(kw["tile_rows"]), "--band", str(kw["band"])] + args + files, capture_output=True, timeout=120)
     assert p.returncode == 0 and b"short" in p.stderr and b"reads used 4, skipped 1, bad 0" in p.stderr, p.stderr
-    assert p.stdout == b"".join(tp._lines(chain.ref, cols)) and len(p.stdout.splitlines()) == int((cols["depth"] >= 1).sum()) > 100
+    assert p.stdout == b"".join(pile_lines(chain.ref, cols)) and len(p.stdout.splitlines()) == int((cols["depth"] >= 1).sum()) > 100
     t = pl.file_pileup(files[1], files[0], batch=3, whole=True, tile_rows=kw["tile_rows"], band=kw["band"], skip=kw["skip"], qmax=kw["qmax"], qmin=kw["qmin"])
     at = np.flatnonzero(cols["depth"] >= 1)
     assert t["ref_pos"].tolist() == at.tolist() and t["events"].tolist() == cols["n_events"][at].tolist() and t["samples"].tolist() == cols["n_samples"][at].tolist()
@@ -850,5 +576,5 @@ def test_the_tool_with_and_without_whole(gpu, chain, tmp_path):
     h.add(chain.recs)
     _, head_cols = h.close()
     p = subprocess.run([pl.S5PILEUP, "-K", "3"] + args + files, capture_output=True, timeout=120)
-    assert p.returncode == 0 and p.stdout == b"".join(tp._lines(chain.ref, head_cols)) and b"reads used 4, skipped 1, bad 0" in p.stderr, p.stderr
+    assert p.returncode == 0 and p.stdout == b"".join(pile_lines(chain.ref, head_cols)) and b"reads used 4, skipped 1, bad 0" in p.stderr, p.stderr
     assert head_cols["n_events"].sum() < cols["n_events"].sum() // 10

@@ -1,9 +1,9 @@
 """refine: per-read level rescaling from the path, and a windowed realign, on the device (docs/codecs.md §4.20;
 slow5tools_amd/csrc/refine_kernels.hip).
 
-The oracle is in this file: the fit in Python integers and np.float64 in the order §4.20 states (fit_ref), the requantiser (requant_ref),
-and the realign as path_ref, the FULL matrix of §4.16 / §4.17, on the slice of the reference that is the window (window_ref); refine_ref
-iterates them.  Sums, a, b, q', rows, lo, hi, statuses and rounds are held to it exactly.  refine_dev.h and the new walk of dtw_dev.h are
+The oracle is in refine_ref.py: the fit in Python integers and np.float64 in the order §4.20 states (fit_ref), the requantiser (requant_ref),
+and the realign as dtw_ref.path_ref, the FULL matrix of §4.16 / §4.17, on the slice of the reference that is the window (window_ref);
+refine_ref iterates them.  Sums, a, b, q', rows, lo, hi, statuses and rounds are held to it exactly.  refine_dev.h and the new walk of dtw_dev.h are
 plain C++: they are also compiled for the CPU, 64 lanes in lockstep over the window, and held to the same oracle.
 """
 import ctypes as C
@@ -15,249 +15,15 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
-from blow5_fixture import Blow5, golden
-from test_map import last_lane_batch
+from chain_common import DNA, EMPTY, EVENT, FIT, FIT_FLAT, FIT_RANGE, GUARD, MAP_ROW, PATH_ROW, PATH_WIDE, QUERY_SHORT, ROOT
+from chain_common import host_build, levels_signal, record, synth_file, to_dev
+from chain_common import gpu  # noqa: F401
+from dtw_ref import _g_of, last_lane_batch, path_ref, quant_ref
+from refine_ref import FIT_NONE, c_params, fit_ref, params, params_bytes, path_status_ref, planted, planted_refined, refine_ref, requant_ref, round_ref, window_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DNA = (3, 6, 1.4, 9.0, 0.2)
-MAP_ROW = np.dtype([("cost", "<u4"), ("qlen", "<u4"), ("start", "<i4"), ("end", "<i4")])
-EVENT = np.dtype([("start", "<u4"), ("length", "<u4"), ("mean", "<f4"), ("stdv", "<f4")])
-FIT = np.dtype([("a", "<f8"), ("b", "<f8"), ("n", "<i8"), ("sq", "<i8"), ("sr", "<i8"), ("sqq", "<i8"), ("sqr", "<i8"), ("srr", "<i8")])
-NO_COST = 0xFFFFFFFF
-EMPTY = (NO_COST, 0, -1, -1)
-QUERY_SHORT, PATH_WIDE, PATH_ROW, FIT_FLAT, FIT_RANGE = 18, 19, 20, 21, 22
 QLENS = [1, 63, 64, 65, 128, 129, 256, 257, 513, 1024]                     # every lane height and its seams
 PADS = [0, 1, 64]
-GUARD = 0x5A5A5A5A
 PLANTED_SEED = 276                                                         # the conditions of test_the_planted_case hold for it
-# a_min, a_max, b_max, clip, pad, min_cells, iters
-DEFAULTS = dict(a_min=0.5, a_max=2.0, b_max=64.0, clip=127, pad=16, min_cells=16, iters=2)
-
-
-def params(**kw):
-    p = dict(DEFAULTS)
-    p.update(kw)
-    return p
-
-
-def params_bytes(p):
-    return struct.pack("<dddiIII", p["a_min"], p["a_max"], p["b_max"], p["clip"], p["pad"], p["min_cells"], p["iters"])
-
-
-def c_params(p):
-    from slow5tools_amd import _lib
-
-    return _lib.RefineParams(p["a_min"], p["a_max"], p["b_max"], p["clip"], p["pad"], p["min_cells"], p["iters"])
-
-
-# ---------------------------------------------------------------------------------------------------------------- the restatement
-
-def quant_ref(m, scale=32.0, clip=127):
-    """quant of §4.16 (copied from test_map.py): float64, sums strictly left to right"""
-    m = np.asarray(m, dtype=np.float32)
-    L = len(m)
-    q = np.zeros(L, dtype=np.int16)
-    if L == 0:
-        return q
-    with np.errstate(all="ignore"):
-        d = m.astype(np.float64)
-        mu = np.cumsum(d)[-1] / np.float64(L)
-        e = d - mu
-        sd = np.sqrt(np.cumsum(e * e)[-1] / np.float64(L))
-        if not (sd > 0.0 and np.isfinite(sd)):
-            return q
-        return np.clip(np.rint((e / sd) * np.float64(scale)), -clip, clip).astype(np.int16)
-
-
-def sdtw_ref(q, r):
-    """(cost, start, end) of §4.16 (copied from test_map.py): D and S filled along anti-diagonals, the predecessor of least D with ties to the
-    diagonal, then (i - 1, j), then (i, j - 1)"""
-    q = np.asarray(q).astype(np.int64)
-    one = q.ndim == 1
-    if one:
-        q = q[None, :]
-    r = np.asarray(r).astype(np.int64)
-    B, Q = q.shape
-    R = len(r)
-    assert Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((B, Q + 1, R + 1), INF, dtype=np.int64)
-    S = np.full((B, Q + 1, R + 1), -1, dtype=np.int64)
-    D[:, 0, :] = 0
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        dg, up, lf = D[:, i, j], D[:, i, j + 1], D[:, i + 1, j]
-        take_dg = (dg <= up) & (dg <= lf)
-        take_up = ~take_dg & (up <= lf)
-        D[:, i + 1, j + 1] = np.abs(q[:, i] - r[j][None, :]) + np.where(take_dg, dg, np.where(take_up, up, lf))
-        s = np.where(take_dg, S[:, i, j], np.where(take_up, S[:, i, j + 1], S[:, i + 1, j]))
-        S[:, i + 1, j + 1] = np.where((i == 0)[None, :], j[None, :], s)
-    last = D[:, Q, 1:]
-    assert last.max() <= 65535 * Q < 2 ** 26
-    end = np.argmin(last, axis=1)
-    b = np.arange(B)
-    cost, start = last[b, end], S[b, Q, end + 1]
-    return (int(cost[0]), int(start[0]), int(end[0])) if one else (cost, start, end)
-
-
-def path_ref(q, r, cross_check=True):
-    """(cost, lo, hi) of §4.17 for ONE query (copied from test_align.py): the full D in int64, filled along anti-diagonals; the walk from
-    (Q - 1, end) takes the predecessor of least D, ties to the diagonal, then (i - 1, j), then (i, j - 1), until row 0.  The three invariants
-    are asserted, and sdtw_ref with cross_check."""
-    q = np.asarray(q).astype(np.int64)
-    r = np.asarray(r).astype(np.int64)
-    Q, R = len(q), len(r)
-    assert q.ndim == 1 and Q >= 1 and R >= 1
-    INF = np.int64(1) << 40
-    D = np.full((Q + 1, R + 1), INF, dtype=np.int64)                       # D[i + 1, j + 1] is D[i][j]; row 0: "a path starts here"
-    D[0, :] = 0
-    c = np.abs(q[:, None] - r[None, :])
-    for k in range(Q + R - 1):
-        i = np.arange(max(0, k - R + 1), min(Q - 1, k) + 1)
-        j = k - i
-        D[i + 1, j + 1] = c[i, j] + np.minimum(np.minimum(D[i, j], D[i, j + 1]), D[i + 1, j])
-    end = int(np.argmin(D[Q, 1:]))
-    cost = int(D[Q, end + 1])
-    lo, hi = np.full(Q, -1, dtype=np.int64), np.full(Q, -1, dtype=np.int64)
-    i, j, total = Q - 1, end, 0
-    hi[i] = j
-    while True:
-        total += int(c[i, j])
-        if i == 0:
-            lo[0] = j
-            break
-        dg, up, lf = D[i, j], D[i, j + 1], D[i + 1, j]
-        if dg <= up and dg <= lf:
-            lo[i] = j
-            i, j = i - 1, j - 1
-            hi[i] = j
-        elif up <= lf:
-            lo[i] = j
-            i -= 1
-            hi[i] = j
-        else:
-            j -= 1
-    assert total == cost and hi[Q - 1] == end and (lo <= hi).all() and (lo >= 0).all()
-    assert set((lo[1:] - hi[:-1]).tolist()) <= {0, 1}
-    assert sum(int(c[i, lo[i]:hi[i] + 1].sum()) for i in range(Q)) == cost
-    if cross_check:
-        assert sdtw_ref(q, r) == (cost, int(lo[0]), end)
-    return cost, lo.astype(np.int32), hi.astype(np.int32)
-
-
-FIT_NONE = (1.0, 0.0, 0, 0, 0, 0, 0, 0)
-
-
-def path_status_ref(lo, hi, R, wmax):
-    """the row rules of §4.18 and the span of §4.20 for a path of Q >= 1 rows -> 0, PATH_ROW or PATH_WIDE"""
-    lo, hi = [int(x) for x in lo], [int(x) for x in hi]
-    for i in range(len(lo)):
-        if lo[i] < 0 or lo[i] > hi[i] or hi[i] >= R or (i and lo[i] - hi[i - 1] not in (0, 1)):
-            return PATH_ROW
-    return PATH_WIDE if hi[-1] - lo[0] + 1 > wmax else 0
-
-
-def fit_ref(q, r, lo, hi, P):
-    """the six sums in Python integers over the cells of a valid path, and the solve in np.float64: every operation on its own, the products
-    before the subtraction -> (status, (a, b, n, Sq, Sr, Sqq, Sqr, Srr))"""
-    n = Sq = Sr = Sqq = Sqr = Srr = 0
-    for i in range(len(q)):
-        qi = int(q[i])
-        seg = [int(x) for x in r[int(lo[i]):int(hi[i]) + 1]]
-        n += len(seg); Sq += len(seg) * qi; Sqq += len(seg) * qi * qi
-        Sr += sum(seg); Sqr += qi * sum(seg); Srr += sum(x * x for x in seg)
-    sums = (n, Sq, Sr, Sqq, Sqr, Srr)
-    f = np.float64
-    with np.errstate(all="ignore"):
-        den = f(n) * f(Sqq) - f(Sq) * f(Sq)
-        if n < P["min_cells"] or not den > 0.0:
-            return FIT_FLAT, (1.0, 0.0) + sums
-        a = (f(n) * f(Sqr) - f(Sq) * f(Sr)) / den
-        b = (f(Sr) - a * f(Sq)) / f(n)
-    if not (np.isfinite(a) and P["a_min"] <= a <= P["a_max"] and abs(b) <= P["b_max"]):
-        return FIT_RANGE, (1.0, 0.0) + sums
-    return 0, (float(a), float(b)) + sums
-
-
-def requant_ref(q0, a, b, clip):
-    p = np.float64(a) * np.asarray(q0).astype(np.float64)
-    s = p + np.float64(b)
-    return np.clip(np.rint(s), -clip, clip).astype(np.int16)
-
-
-def window_ref(q, r, row, pad, wmax):
-    """§4.20's window: -> (status, row', lo, hi) of a query of Q >= 1 rows; the alignment is path_ref on the slice"""
-    Q, R = len(q), len(r)
-    cost, qlen, start, end = (int(x) for x in row)
-    none = (EMPTY, np.full(Q, -1, dtype=np.int32), np.full(Q, -1, dtype=np.int32))
-    if qlen != Q or start < 0 or start > end or end >= R:
-        return (PATH_ROW,) + none
-    ws, we = max(0, start - pad), min(R - 1, end + pad)
-    if we - ws + 1 > wmax:
-        return (PATH_WIDE,) + none
-    c, lo, hi = path_ref(q, np.asarray(r)[ws:we + 1], cross_check=False)
-    return 0, (c, Q, int(lo[0]) + ws, int(hi[-1]) + ws), lo + ws, hi + ws
-
-
-def round_ref(q0, r, row, lo, hi, wmax, P):
-    """one round for a read with a query and status 0 -> (st_fit, fit, q', st_win, row', lo', hi')"""
-    Q = len(q0)
-    none = (EMPTY, np.full(Q, -1, dtype=np.int32), np.full(Q, -1, dtype=np.int32))
-    st = path_status_ref(lo, hi, len(r), wmax)
-    if st:
-        return (st, FIT_NONE, np.zeros(Q, dtype=np.int16), st) + none
-    st, fit = fit_ref(q0, r, lo, hi, P)
-    q1 = requant_ref(q0, fit[0], fit[1], P["clip"]) if st == 0 else np.asarray(q0, dtype=np.int16).copy()
-    return (st, fit, q1) + window_ref(q1, r, row, P["pad"], wmax)
-
-
-def refine_ref(q0, r, row, lo, hi, status_in, wmax, P):
-    """§4.20's rounds for one read (q0: its Q rows) -> dict(q, row, lo, hi, fit, status, rounds)"""
-    Q = len(q0)
-
-    def none(st):
-        return dict(q=np.zeros(Q, dtype=np.int16), row=EMPTY, lo=np.full(Q, -1, dtype=np.int32), hi=np.full(Q, -1, dtype=np.int32), fit=FIT_NONE, status=st, rounds=0)
-    if status_in != 0 or Q == 0:
-        return none(status_in)
-    cur = dict(q=np.asarray(q0, dtype=np.int16).copy(), row=tuple(int(x) for x in row), lo=np.asarray(lo, dtype=np.int32).copy(),
-               hi=np.asarray(hi, dtype=np.int32).copy(), fit=FIT_NONE, status=0, rounds=0)
-    for k in range(1, P["iters"] + 1):
-        sf, fit, q1, sw, row1, lo1, hi1 = round_ref(q0, r, cur["row"], cur["lo"], cur["hi"], wmax, P)
-        if sf in (PATH_ROW, PATH_WIDE):
-            return none(sf)
-        if sf or sw:
-            cur["status"] = sf or sw
-            break
-        cur = dict(q=q1, row=row1, lo=lo1, hi=hi1, fit=fit, status=0, rounds=k)
-    return cur
-
-
-def planted(seed, n_reads=24):
-    """the case of §4.20: a reference of 600 levels whose halves are drawn from N(90, 12) and N(108, 20), quantised as a whole; queries of
-    40 .. 129 events cut from it, put through 1.7 x + 30 plus N(0, 1) and quantised each on its own -> (ref, [(query, true_start, true_end)])"""
-    rng = np.random.default_rng(seed)
-    levels = np.concatenate([rng.normal(90.0, 12.0, 300), rng.normal(108.0, 20.0, 300)]).astype(np.float32)
-    ref = quant_ref(levels)
-    reads = []
-    for _ in range(n_reads):
-        Q = int(rng.integers(40, 130))
-        s = int(rng.integers(0, 600 - Q + 1))
-        x = 1.7 * levels[s:s + Q].astype(np.float64) + 30.0 + rng.normal(0.0, 1.0, Q)
-        reads.append((quant_ref(x.astype(np.float32)), s, s + Q - 1))
-    return ref, reads
-
-
-def planted_refined(seed, P=None, wmax=1 << 20):
-    """-> (ref, [(query, true span, first (cost, lo, hi), refine_ref's dict)])"""
-    P = P or params()
-    ref, reads = planted(seed)
-    out = []
-    for q, s, e in reads:
-        c, lo, hi = path_ref(q, ref, cross_check=False)
-        out.append((q, (s, e), (c, lo, hi), refine_ref(q, ref, (c, len(q), int(lo[0]), int(hi[-1])), lo, hi, 0, wmax, P)))
-    return ref, out
-
 
 # ---------------------------------------------------------------------------------------------------------------- not gpu
 
@@ -472,10 +238,6 @@ int main(int argc, char **argv) {
 '''
 
 
-def _g_of(Q):
-    return next(g for g in (1, 2, 4, 8, 16) if 64 * g >= Q)
-
-
 def scaled_read(rng, Q, R, where="mid", a=1.7, b=30.0):
     """a reference of R levels and a query of Q rows that is a piece of it seen through another scale: the piece's levels, each held 1 to 3
     times, put through (x - b) / a plus a little noise.  where: the piece starts at column 0, ends at column R - 1, or lies inside."""
@@ -525,10 +287,7 @@ def _want_case(case):
 
 
 def _build_refine_host(tmp_path, extra=()):
-    (tmp_path / "refine_host.cpp").write_text(REFINE_HOST)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"),
-                           str(tmp_path / "refine_host.cpp"), "-o", str(tmp_path / "refine_host")])
-    return str(tmp_path / "refine_host")
+    return host_build(tmp_path, "refine_host", REFINE_HOST, ["-O1", "-std=c++17", "-ffp-contract=off"], extra)
 
 
 def write_host_cases(path, cases):
@@ -661,29 +420,13 @@ def test_refused_arguments_are_refused_before_a_device_is_needed():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, align, events, pileup, press, refine
-    from slow5tools_amd import map as smap
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.map, env.align, env.refine, env.pileup = torch, _lib, _lib.lib(), press, events, smap, align, refine, pileup
-    return env
-
-
-def _dev(env, a, dtype=None):
-    return env.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to("cuda")
-
-
 class Batch:
     """queries [n, pitch], qlen and a reference, and what the device makes of them with s5gpu_sdtw_dev and s5gpu_sdtw_path_dev, on both sides"""
 
     def __init__(self, env, qm, qlens, ref):
         self.qm, self.ql, self.ref = np.ascontiguousarray(qm, dtype=np.int16), np.asarray(qlens, dtype=np.int32), np.ascontiguousarray(ref, dtype=np.int16)
         self.n, self.pitch, self.R = len(self.ql), self.qm.shape[1], len(self.ref)
-        self.d_q, self.d_ql, self.d_r = _dev(env, self.qm), _dev(env, self.ql), _dev(env, self.ref)
+        self.d_q, self.d_ql, self.d_r = to_dev(env, self.qm), to_dev(env, self.ql), to_dev(env, self.ref)
         self.d_rows = env.map.sdtw_dev(self.d_q, self.d_ql, self.d_r, want_start=True)
         self.d_lo, self.d_hi, self.d_st = env.align.path_dev(self.d_q, self.d_ql, self.d_r, self.d_rows, wmax=self.R)
         env.torch.cuda.synchronize()
@@ -719,7 +462,7 @@ def _run_fit(env, B, lo, hi, st_in, wmax, P, want_queries=True):
     """s5gpu_path_fit_dev with guard words around every output -> (fit [n] FIT, q' [n, pitch], status)"""
     torch, L = env.torch, env.L
     n, pitch = B.n, B.pitch
-    d_lo, d_hi, d_si = _dev(env, lo, np.int32), _dev(env, hi, np.int32), _dev(env, st_in, np.int32)
+    d_lo, d_hi, d_si = to_dev(env, lo, np.int32), to_dev(env, hi, np.int32), to_dev(env, st_in, np.int32)
     d_fit = torch.full(((n + 2) * 16,), GUARD, dtype=torch.int32, device="cuda")
     d_qo = torch.full(((n + 2) * pitch,), 0x5A5A, dtype=torch.int16, device="cuda")
     d_so = torch.full((n + 2,), GUARD, dtype=torch.int32, device="cuda")
@@ -791,7 +534,7 @@ def _run_window(env, B, rows, pad, wmax, scratch_bytes=None, expect=0):
     """s5gpu_sdtw_window_dev with guards around rows_out, lo, hi and status and behind the scratch -> (rows', lo, hi, status)"""
     torch, L = env.torch, env.L
     n, pitch = B.n, B.pitch
-    d_rows = _dev(env, np.ascontiguousarray(rows).view(np.int32).reshape(n, 4))
+    d_rows = to_dev(env, np.ascontiguousarray(rows).view(np.int32).reshape(n, 4))
     slot = L.s5gpu_sdtw_path_slot_bytes(pitch, wmax)
     sb = slot * n if scratch_bytes is None else scratch_bytes
     d_scr = torch.full((sb // 4 + 64,), GUARD, dtype=torch.int32, device="cuda")
@@ -902,7 +645,7 @@ def _want_refine(B, st_in, wmax, P):
 
 
 def _got_refine(env, B, st_in, wmax, P, scratch_bytes=None):
-    R = env.refine.refine_dev(B.d_q, B.d_ql, B.d_r, B.d_rows, B.d_lo, B.d_hi, _dev(env, st_in, np.int32), wmax, c_params(P), scratch_bytes)
+    R = env.refine.refine_dev(B.d_q, B.d_ql, B.d_r, B.d_rows, B.d_lo, B.d_hi, to_dev(env, st_in, np.int32), wmax, c_params(P), scratch_bytes)
     env.torch.cuda.synchronize()
     return (R.queries.cpu().numpy(), R.rows.cpu().numpy().view(MAP_ROW).reshape(-1), R.lo.cpu().numpy(), R.hi.cpu().numpy(), R.fit.cpu().numpy().view(FIT).reshape(-1),
             R.status.cpu().numpy(), R.rounds.cpu().numpy())
@@ -967,32 +710,6 @@ def test_refined_outputs_feed_the_pileup(gpu):
     assert (cols["min_q"][empty] == 32767).all() and (cols["max_q"][empty] == -32768).all() and (cols["min_q"][~empty] <= cols["max_q"][~empty]).all()
 
 
-def levels_signal(n, rng):
-    """a raw signal of random levels of dwell 4 .. 20 with a little noise: an event every dozen samples (copied from test_map.py)"""
-    lv = []
-    while len(lv) < n:
-        lv += [int(rng.integers(300, 700))] * int(rng.integers(4, 21))
-    return np.round(np.array(lv[:n], dtype=np.float64) + rng.normal(0.0, 3.0, n)).astype(np.int16)
-
-
-def _record(i, sig):
-    r, keep = ob.make_rec(ob.synth_read_id(i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-    return ob.rec_to_mem(r, ob.REC_ZLIB, ob.SIG_SVB_ZD)[8:]
-
-
-def _synth_file(path, recs):
-    """a BLOW5 file of records without aux fields (as in test_align.py): the header of a golden zlib + svb-zd file with the aux columns taken
-    off its two '#' lines"""
-    g = Blow5(golden("example_multi_rg_v0.2.0.blow5"))
-    assert (g.rec_method, g.sig_method) == (1, 1)
-    lines = g.header_text.split(b"\n")
-    lines = [b"\t".join(l.split(b"\t")[:8]) if l.startswith(b"#") and b"\t" in l else l for l in lines]
-    ht = b"\n".join(lines)
-    body = b"".join(struct.pack("<Q", len(r)) + r for r in recs)
-    with open(path, "wb") as fh:
-        fh.write(g.raw[:64] + struct.pack("<I", len(ht)) + ht + body + b"5WOLB")
-
-
 @pytest.mark.gpu
 def test_refine_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     """read_refine (s5gpu_refine_batch) and file_refine (s5refine) agree with refine_on on level signals, one record corrupt and one read too
@@ -1001,7 +718,7 @@ def test_refine_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     rng = np.random.default_rng(43)
     lengths = [3000, 500, 40, 5000, 1500, 2500]
     sigs = [levels_signal(n, rng) for n in lengths]
-    recs = [_record(i, s) for i, s in enumerate(sigs)]
+    recs = [record(i, s) for i, s in enumerate(sigs)]
     bad = bytearray(recs[3])
     bad[-1] ^= 0x5A                                                        # the Adler-32 of the zlib stream
     recs[3] = bytes(bad)
@@ -1045,7 +762,7 @@ def test_refine_end_to_end_on_a_synthetic_file(gpu, tmp_path):
     assert o1[1].tolist() == w1.rows.tolist() and o1[6].tolist() == w1.status.tolist() and set(w1.status[[0, 1, 4, 5]].tolist()) <= {FIT_RANGE, FIT_FLAT}
     assert o1[1][[0, 1, 4, 5]].tolist() == rows[[0, 1, 4, 5]].tolist() and not o1[7].any()
     # the tool: exit 1, the corrupt read named, the other reads' lines
-    _synth_file(tmp_path / "reads.blow5", recs)
+    synth_file(tmp_path / "reads.blow5", recs)
     args = ["--skip", str(skip), "--events", str(qmax), "--min-events", str(qmin), str(ref_txt), str(tmp_path / "reads.blow5")]
     p = subprocess.run([rf.S5REFINE, "-K", "4"] + args, capture_output=True, timeout=120)
     assert p.returncode == 1 and ids[3] in p.stderr and b"short" in p.stderr, p.stderr

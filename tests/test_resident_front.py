@@ -12,25 +12,14 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
+from chain_common import levels_signal, record
+from chain_common import gpu  # noqa: F401
 
 ZS = (ob.REC_ZLIB, ob.SIG_SVB_ZD)
 BAD, BIG = 2, 3                       # the truncated record and the one that outgrows its slot
 GOOD = [0, 1, 3, 4, 5]
 KW = dict(skip=1, qmax=64, qmin=10)
 ERR_DATA = -5
-
-
-def levels_signal(n, rng):
-    """a raw signal of random levels of dwell 4 .. 20 with a little noise: an event every dozen samples (as in test_align.py)"""
-    lv = []
-    while len(lv) < n:
-        lv += [int(rng.integers(300, 700))] * int(rng.integers(4, 21))
-    return np.round(np.array(lv[:n], dtype=np.float64) + rng.normal(0.0, 3.0, n)).astype(np.int16)
-
-
-def _record(i, sig, methods):
-    r, keep = ob.make_rec(ob.synth_read_id(i), 0, 8192.0, 23.0, 1467.61, 4000.0, sig)
-    return ob.rec_to_mem(r, methods[0], methods[1])[8:]
 
 
 class Batch:
@@ -41,10 +30,10 @@ class Batch:
         rng = np.random.default_rng(1906)
         sigs = [levels_signal(n, rng) for n in (300, 451, 500, 0, 257, 600)]
         sigs[BIG] = np.tile(np.repeat(np.array([400, 600], dtype=np.int16), 10), 2000)
-        self.intact = [_record(i, s, ZS) for i, s in enumerate(sigs)]
+        self.intact = [record(i, s, ZS) for i, s in enumerate(sigs)]
         self.recs = list(self.intact)
         self.recs[BAD] = self.recs[BAD][: len(self.recs[BAD]) // 2]
-        self.plain_intact = [_record(i, s, (ob.REC_NONE, ob.SIG_NONE)) for i, s in enumerate(sigs)]
+        self.plain_intact = [record(i, s, (ob.REC_NONE, ob.SIG_NONE)) for i, s in enumerate(sigs)]
         self.plain = list(self.plain_intact)
         self.plain[BAD] = self.plain[BAD][: len(self.plain[BAD]) // 2]
         self.ref = np.clip(np.round(rng.normal(0.0, 32.0, 300)), -127, 127).astype(np.int16)
@@ -67,18 +56,6 @@ def test_the_batch_holds_what_the_test_is_about(batch):
     with pytest.raises(zlib.error):
         zlib.decompress(batch.recs[BAD])
     assert len(batch.recs) == 6 and len(batch.ref) == 300
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    from slow5tools_amd import _lib, align, diff, digest, events, fstats, pileup, signals
-    from slow5tools_amd import map as map_
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.lib, env.L = _lib, _lib.lib()
-    env.align, env.diff, env.digest, env.events, env.fstats, env.pileup, env.signals, env.map = align, diff, digest, events, fstats, pileup, signals, map_
-    return env
 
 
 def _same(a, b):

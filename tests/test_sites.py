@@ -16,16 +16,18 @@ import numpy as np
 import pytest
 
 import contrast_ref as cr
+import oracle_bind as ob
 import sites_ref as sr
-import test_pileup as tp
-import test_pileup_long as tl
+from chain_common import DEFAULT_GRID, DEFAULT_SEG, EXT_ROW, ROOT, host_build, levels_signal, record, synth_file
+from chain_common import gpu  # noqa: F401
 from contrast_ref import BINS, HIST_HEAD, Q0, SHIFT, hist_bytes_of, hist_cases, hist_ref
+from dtw_ref import quant_ref
+from pileup_ref import LongCase, long_cases, mixed_case, relay
 from sites_ref import ROW_NONE, SITE_CELL, SITE_SCORE, cells_ref, score_ref, site_lists, verdicts_ref, wanted
-from test_pileup import ROOT
 
 CALLS = ["s5gpu_site_cells_long_dev", "s5gpu_site_score_dev", "s5gpu_sites_open", "s5gpu_sites_set_refine", "s5gpu_sites_add_control", "s5gpu_sites_set_control",
          "s5gpu_sites_add_batch", "s5gpu_sites_close"]
-SETTINGS = ((64, 1), (64, tl.DEFAULT_GRID), (256, 7), (1024, tl.DEFAULT_GRID))   # pileup_long_seg, pileup_long_grid
+SETTINGS = ((64, 1), (64, DEFAULT_GRID), (256, 7), (1024, DEFAULT_GRID))   # pileup_long_seg, pileup_long_grid
 
 
 def _explain(got, want):
@@ -157,7 +159,7 @@ def test_the_restatements():
     # hand-made: two reads on 4 columns; read 0 rows (0..1), (1..1), (2..3); read 1 rows (1..1), (1..2)
     q = np.array([-128, -125, 0, 127, 200], dtype=np.int16)
     lo, hi = np.array([0, 1, 2, 1, 1], dtype=np.int32), np.array([1, 1, 3, 1, 2], dtype=np.int32)
-    case = tl.LongCase(q, [0, 3, 5], [3, 2], [0, 0, 0, 0], lo, hi)
+    case = LongCase(q, [0, 3, 5], [3, 2], [0, 0, 0, 0], lo, hi)
     got = cells_ref(case, [0, 1, 2, 3])
     assert got.tolist() == [[(-128, 1, 0), (0, 0, ROW_NONE)], [(-253, 2, 0), (327, 2, 0)], [(0, 1, 2), (200, 1, 1)], [(0, 1, 2), (0, 0, ROW_NONE)]]
     assert verdicts_ref(case).tolist() == [0, 0]
@@ -334,10 +336,7 @@ def _run_score_host(exe, tmp_path, cells, sites, counts, q0, shift, R, bins):
 
 
 def run_sites_header_on_the_cpu(tmp_path, extra=()):
-    (tmp_path / "sites_host.cpp").write_text(SITES_HOST)
-    exe = str(tmp_path / "sites_host")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-I", os.path.join(ROOT, "slow5tools_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           str(tmp_path / "sites_host.cpp"), "-o", exe])
+    exe = host_build(tmp_path, "sites_host", SITES_HOST, ["-O1", "-g", "-std=c++17", "-Wall"], extra, api=True)
     for name, (case, q0, shift) in hist_cases().items():
         v = verdicts_ref(case)
         for label, s in site_lists(name).items():
@@ -371,18 +370,7 @@ def test_the_planted_case_at_the_query_level():
 
 # ---------------------------------------------------------------------------------------------------------------- gpu
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    from slow5tools_amd import _lib, contrast, events, extend, pileup, press, sites
-
-    _lib.check(_lib.lib().s5gpu_init(0), "s5gpu_init")
-    env = type("Env", (), {})()
-    env.torch, env.lib, env.L, env.press, env.events, env.pileup, env.extend, env.contrast, env.sites = torch, _lib, _lib.lib(), press, events, pileup, extend, contrast, sites
-    return env
-
-
-def _options(env, seg=64, grid=tl.DEFAULT_GRID):
+def _options(env, seg=64, grid=DEFAULT_GRID):
     for key, v in ((b"pileup_long_seg", seg), (b"pileup_long_grid", grid)):
         env.lib.check(env.L.s5gpu_set_option(key, v), key.decode())
 
@@ -446,7 +434,7 @@ def test_the_case_list_is_exact(gpu, name):
             assert verdict.tolist() == v.tolist(), label
         up.unchanged()
     finally:
-        _options(gpu, seg=tl.DEFAULT_SEG)
+        _options(gpu, seg=DEFAULT_SEG)
 
 
 @pytest.mark.gpu
@@ -461,14 +449,14 @@ def test_the_options_do_not_change_a_byte(gpu, name):
                 want = wanted(name, label)
                 assert got.tobytes() == want.tobytes(), (seg, grid, label, _explain(got, want))
     finally:
-        _options(gpu, seg=tl.DEFAULT_SEG)
+        _options(gpu, seg=DEFAULT_SEG)
 
 
 @pytest.mark.gpu
 def test_two_calls_on_two_streams_and_a_short_work_area(gpu):
     torch = gpu.torch
-    case = tp.mixed_case(129, 200)
-    a, b = tl.relay(case.part(0, 90)), tl.relay(case.part(90, 200))
+    case = mixed_case(129, 200)
+    a, b = relay(case.part(0, 90)), relay(case.part(90, 200))
     sites = sorted(set(int(x) for x in np.linspace(0, case.R - 1, 40)))
     ua, ub = Uploaded(gpu, a), Uploaded(gpu, b)
     _options(gpu)
@@ -486,14 +474,14 @@ def test_two_calls_on_two_streams_and_a_short_work_area(gpu):
         ua.unchanged()
         ub.unchanged()
     finally:
-        _options(gpu, seg=tl.DEFAULT_SEG)
+        _options(gpu, seg=DEFAULT_SEG)
 
 
 @pytest.mark.gpu
 def test_a_fixed_pitch_batch_equals_the_ragged_call(gpu):
     torch, st = gpu.torch, gpu.sites
-    case = tp.mixed_case(129, 200)
-    ragged = tl.relay(case, seed=3)
+    case = mixed_case(129, 200)
+    ragged = relay(case, seed=3)
     sites = sorted(set(int(x) for x in np.linspace(0, case.R - 1, 40)))
     want = cells_ref(ragged, sites)
 
@@ -503,12 +491,12 @@ def test_a_fixed_pitch_batch_equals_the_ragged_call(gpu):
     got = st.cells_to_host(cells)
     assert got.tobytes() == want.tobytes(), _explain(got, want)
     assert verdict.cpu().numpy().tolist() == verdicts_ref(ragged).tolist()
-    got, _ = _cells(gpu, Uploaded(gpu, tl.relay(case)), sites)
+    got, _ = _cells(gpu, Uploaded(gpu, relay(case)), sites)
     assert got.tobytes() == want.tobytes(), _explain(got, want)
     with pytest.raises(ValueError):
         st.cells_dev(dev(case.qm), dev(case.qlen.view(np.int32)), dev(case.lo), dev(case.hi), dev(case.status), [5, 3], case.R)
     # an empty batch: a matrix of no reads
-    none = tl.long_cases()["empty batch"]
+    none = long_cases()["empty batch"]
     cells, verdict = st.cells_long_dev(dev(none.q), dev(none.first.view(np.int64)), dev(none.qlen.view(np.int32)), dev(none.lo), dev(none.hi), dev(none.status), [0, 2], none.R)
     assert tuple(cells.shape) == (2, 0, 2) and st.cells_to_host(cells).shape == (2, 0) and verdict.numel() == 0
 
@@ -586,17 +574,17 @@ def files(gpu):
     rng = np.random.default_rng(4025)
     levels = rng.normal(500.0, 110.0, 3500).astype(np.float32)
     env = type("Files", (), {})()
-    env.levels, env.ref = levels, tp.quant_ref(levels)
-    env.recs = [[tl._record(10 * s + i, tp.levels_signal(n, rng)) for i, n in enumerate(lengths)] for s, lengths in enumerate(([30000, 100, 26000, 28000], [27000, 31000, 100]))]
-    env.ids = [[tp.ob.synth_read_id(10 * s + i) for i in range(len(r))] for s, r in enumerate(env.recs)]
+    env.levels, env.ref = levels, quant_ref(levels)
+    env.recs = [[record(10 * s + i, levels_signal(n, rng)) for i, n in enumerate(lengths)] for s, lengths in enumerate(([30000, 100, 26000, 28000], [27000, 31000, 100]))]
+    env.ids = [[ob.synth_read_id(10 * s + i) for i in range(len(r))] for s, r in enumerate(env.recs)]
     env.ids = [[i if isinstance(i, bytes) else i.encode() for i in side] for side in env.ids]
     env.kw = dict(skip=2, qmax=100, qmin=20, tile_rows=64, band=128)
     return env
 
 
 def _chain_case(ref, x):
-    rows = x.rows.cpu().numpy().view(tl.EXT_ROW).reshape(-1)
-    return tl.LongCase(x.queries.cpu().numpy(), x.first.cpu().numpy().astype(np.uint64), x.qlen.cpu().numpy(), ref, x.lo.cpu().numpy(), x.hi.cpu().numpy(), rows["status"])
+    rows = x.rows.cpu().numpy().view(EXT_ROW).reshape(-1)
+    return LongCase(x.queries.cpu().numpy(), x.first.cpu().numpy().astype(np.uint64), x.qlen.cpu().numpy(), ref, x.lo.cpu().numpy(), x.hi.cpu().numpy(), rows["status"])
 
 
 def _whole(gpu, files, refine):
@@ -681,7 +669,7 @@ def test_the_chain_the_handle_and_the_tool(gpu, files, refine, tmp_path):
     ref_txt = tmp_path / "ref.txt"
     ref_txt.write_text("".join("%.9g\n" % v for v in files.levels))
     for s, name in enumerate(("ctl.blow5", "reads.blow5")):
-        tp._synth_file(tmp_path / name, files.recs[s])
+        synth_file(tmp_path / name, files.recs[s])
     sites_txt = tmp_path / "sites.txt"
     sites_txt.write_text("# unsorted, one twice\n" + "".join("%d\n" % v for v in FILE_SITES[::-1] + FILE_SITES[:1]))
     kw = files.kw

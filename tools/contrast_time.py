@@ -27,7 +27,7 @@ import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
 from pileup_long_time import paths  # noqa: E402
-from pileup_time import timed  # noqa: E402
+from devtime import timed  # noqa: E402
 
 
 def main():

@@ -26,7 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
-from extend_time import timed  # noqa: E402
+from devtime import timed  # noqa: E402
 
 EXT_ROW = np.dtype([("cost", "<u8"), ("qlen", "<u4"), ("tiles", "<u4"), ("start", "<i4"), ("end", "<i4"), ("a_last", "<i4"), ("status", "<i4")])
 

@@ -26,7 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
-from pileup_time import timed  # noqa: E402
+from devtime import timed  # noqa: E402
 
 
 def paths(n, Q, R, advance, g):

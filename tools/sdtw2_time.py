@@ -20,7 +20,7 @@ import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
 from slow5tools_amd import map as smap  # noqa: E402
-from tools.sdtw_time import timed  # noqa: E402
+from tools.devtime import timed  # noqa: E402
 
 
 def main():

@@ -13,7 +13,6 @@ The dirs pass is rated in window cells (the sum of qlen x (end - start + 1) over
 cells per second.  --wmax 0: 4 qlen.  --scratch-mb 0: a slot for every read (one group).
 One JSON object per line; --out also writes them to a file."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -24,24 +23,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
-
-
-def timed(L, fn, reps, warm=2):
-    vp = C.c_void_p
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1, t = vp(), vp(), C.c_float()
-        _lib.check(L.s5gpu_event_create(C.byref(e0))); _lib.check(L.s5gpu_event_create(C.byref(e1)))
-        _lib.check(L.s5gpu_event_record(e0, None))
-        fn()
-        _lib.check(L.s5gpu_event_record(e1, None))
-        _lib.check(L.s5gpu_event_elapsed_ms(e0, e1, C.byref(t)))
-        _lib.check(L.s5gpu_event_destroy(e0)); _lib.check(L.s5gpu_event_destroy(e1))
-        ms.append(t.value)
-    return float(np.median(ms)), float(min(ms))
+from devtime import timed  # noqa: E402
 
 
 def main():

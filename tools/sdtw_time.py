@@ -9,7 +9,6 @@ want_start.  A call is one launch per lane height that the pitch allows (--qlen 
 so the time is that of k_sdtw<4> and two empty grids.  Cells are reads x qlen x R.  The two variants' cost and end columns are compared.
 One JSON object per line; --out also writes them to a file."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -20,24 +19,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slow5tools_amd import _lib  # noqa: E402
-
-
-def timed(L, fn, reps, warm=2):
-    vp = C.c_void_p
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1, t = vp(), vp(), C.c_float()
-        _lib.check(L.s5gpu_event_create(C.byref(e0))); _lib.check(L.s5gpu_event_create(C.byref(e1)))
-        _lib.check(L.s5gpu_event_record(e0, None))
-        fn()
-        _lib.check(L.s5gpu_event_record(e1, None))
-        _lib.check(L.s5gpu_event_elapsed_ms(e0, e1, C.byref(t)))
-        _lib.check(L.s5gpu_event_destroy(e0)); _lib.check(L.s5gpu_event_destroy(e1))
-        ms.append(t.value)
-    return float(np.median(ms)), float(min(ms))
+from devtime import timed  # noqa: E402
 
 
 def main():
