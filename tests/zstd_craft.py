@@ -13,11 +13,15 @@ decoded: an offset of zero or beyond the output, literals that run out); `tags` 
 CATALOGUE lists (name, frame bytes, expected | None, tags): the smallest frames that take each route in ROUTES, and frames that
 must be refused (expected None; the tag STRICTER marks the few that the format and this project refuse but libzstd 1.4.8 accepts).  Knobs that only make INVALID frames (reserved bits, forged sizes, damaged streams) are keyword arguments marked
 "forge".
+
+For the ENCODER's tests (tests/test_zstd_encode_craft.py) the second half of the file holds parse_frame (a frame read down to its fields, RFC 8878), the
+restatement of what the device encoder must do (zenc_pieces, zenc_tokens, zenc_split) and zenc_catalogue(), the payloads that reach its edges.
 """
 import collections
 import os
 import struct
 import sys
+import types
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import gen_zstd_seq_tables as _g   # noqa: E402  (the predefined distributions and the extra bits of the length codes)
@@ -591,7 +595,12 @@ def frame(blocks, *, fcs="auto", single_segment=True, window=None, checksum=Fals
         B.ok = False
     if "cut" in forge:
         data = data[:forge["cut"]]
+    if B.ok:
+        SPECS[data] = list(blocks)
     return Crafted(data, bytes(B.out) if B.ok else None, frozenset(B.tags | set(tags)) if B.ok else frozenset())
+
+
+SPECS = {}                       # frame bytes -> the block specs frame() was given (valid frames only): what parse_frame is held to
 
 
 def walk(data):
@@ -846,3 +855,852 @@ def _catalogue():
 
 
 CATALOGUE = _catalogue()
+
+
+# ================================================================ reading frames (for the ENCODER's tests: tests/test_zstd_encode_craft.py)
+# parse_frame follows RFC 8878 section by section and keeps what it read: a test asks it WHICH block, literals form, description,
+# stream sizes and sequences a frame holds, not only what bytes come out.
+class BackReader:
+    """a stream read from its last bit down (RFC 8878 4.1): the highest set bit of the last byte is the end mark; take() never reads in
+    front of the first byte, take_padded() reads zeros there (how the end of an FSE stream of weights is found)"""
+    def __init__(self, b):
+        if not len(b) or b[-1] == 0:
+            raise ValueError("bit stream without an end mark")
+        self.b = bytes(b)
+        self.n = 8 * (len(b) - 1) + b[-1].bit_length() - 1           # bits still to read: bit n - 1 is the next one
+
+    def take(self, nb):
+        if nb > self.n:
+            raise ValueError("bit stream overrun")
+        hi = self.n
+        self.n = lo = hi - nb
+        return (int.from_bytes(self.b[lo >> 3:(hi + 7) >> 3], "little") >> (lo & 7)) & ((1 << nb) - 1)
+
+
+def read_ncount(b, max_log, max_sym):
+    """the count header of an FSE table (RFC 8878 4.1.1; the reader of ncount()) -> (norm, log, bytes read)"""
+    v, avail, pos = int.from_bytes(b, "little"), 8 * len(b), 4
+    if avail < 4:
+        raise ValueError("count header cut")
+    log = (v & 15) + 5
+    if log > max_log:
+        raise ValueError("accuracy log %d above %d" % (log, max_log))
+    remaining, threshold, nb, norm, prev0 = (1 << log) + 1, 1 << log, log + 1, [], False
+    while remaining > 1:
+        if prev0:
+            while True:
+                if pos + 2 > avail:
+                    raise ValueError("count header cut")
+                r = (v >> pos) & 3
+                pos += 2
+                norm += [0] * r
+                if r != 3:
+                    break
+        if len(norm) > max_sym:
+            raise ValueError("more symbols than the alphabet holds")
+        if pos + nb > avail + 7:                             # (a value's unread upper bits may lie in the padding of the last byte)
+            raise ValueError("count header cut")
+        maxv = 2 * threshold - 1 - remaining
+        val = (v >> pos) & (threshold - 1)
+        if val < maxv:
+            pos += nb - 1
+        else:
+            val = (v >> pos) & (2 * threshold - 1)
+            pos += nb
+            if val >= threshold:
+                val -= maxv
+        if pos > avail:
+            raise ValueError("count header cut")
+        c = val - 1
+        remaining -= abs(c)
+        if remaining < 1:
+            raise ValueError("counts exceed the table")
+        norm.append(c)
+        prev0 = c == 0
+        while remaining < threshold:
+            nb -= 1
+            threshold >>= 1
+    return norm, log, (pos + 7) // 8
+
+
+def read_tree(b):
+    """a Huffman tree description at the head of b (RFC 8878 4.2.1) -> (Huf, form, bytes, the FSE stream ended exactly)"""
+    if not len(b):
+        raise ValueError("no tree description")
+    hb, exact = b[0], True
+    if hb >= 128:
+        n = hb - 127
+        size = 1 + (n + 1) // 2
+        if size > len(b):
+            raise ValueError("tree description cut")
+        w = [(b[1 + k // 2] >> (0 if k & 1 else 4)) & 15 for k in range(n)]
+        form = "direct"
+    else:
+        size = 1 + hb
+        if hb < 2 or size > len(b):
+            raise ValueError("tree description cut")
+        norm, log, used = read_ncount(b[1:size], 6, 12)
+        t = Fse(norm, log)
+        r = BackReader(b[1 + used:size])
+        st, w, k = [r.take(log), r.take(log)], [], 0
+        while True:                                          # two states in turn; the stream is over when a state's bits are not all there
+            w.append(t.sym[st[k]])
+            if t.nb[st[k]] > r.n:
+                w.append(t.sym[st[k ^ 1]])
+                break
+            st[k] = t.base[st[k]] + r.take(t.nb[st[k]])
+            k ^= 1
+            if len(w) > 255:
+                raise ValueError("more than 255 weights")
+        exact = r.n == 0
+        form = "fse"
+    if len(w) > 255:
+        raise ValueError("more than 255 weights")
+    total = sum(1 << (x - 1) for x in w if x)
+    if total == 0 or max(w) > 11:
+        raise ValueError("weights of no tree")
+    rest = (1 << total.bit_length()) - total
+    if rest & (rest - 1) or total.bit_length() > 11:
+        raise ValueError("weights do not complete to a power of two of at most 11 bits")
+    return Huf(w + [rest.bit_length()]), form, size, exact
+
+
+def _huf_table(huf):
+    """decode table over maxbits bits: symbol | length << 8"""
+    mb = huf.maxbits
+    tab = [0] * (1 << mb)
+    for s, (c, nb) in huf.code.items():
+        lo = c << (mb - nb)
+        tab[lo:lo + (1 << (mb - nb))] = [s | (nb << 8)] * (1 << (mb - nb))
+    return tab
+
+
+def _huf_stream(tab, mb, b, count):
+    """count symbols from one Huffman stream, which must end exactly at its first bit"""
+    n = BackReader(b).n
+    mask, out, at = (1 << mb) - 1, bytearray(count), (n + 7) >> 3
+    acc, na = 0, 0                                                   # the next na bits of the stream, the first one on top
+    for i in range(count):
+        if na < mb and at:
+            lo = max(0, at - 8)
+            k = min(n, 8 * at) - 8 * lo                              # (the first refill leaves the end mark out)
+            acc = (acc << k) | (int.from_bytes(b[lo:at], "little") & ((1 << k) - 1))
+            na, at = na + k, lo
+        e = tab[(acc >> (na - mb)) & mask] if na >= mb else tab[(acc << (mb - na)) & mask]
+        na -= e >> 8
+        if na < 0:
+            raise ValueError("Huffman stream overrun")
+        acc &= (1 << na) - 1
+        out[i] = e & 255
+    if na or at:
+        raise ValueError("Huffman stream does not end on its first bit")
+    return bytes(out)
+
+
+def _read_literals(b, prev_huf):
+    """the literals section at the head of block content b -> (namespace, literals, bytes, the tree in force)"""
+    if not len(b):
+        raise ValueError("no literals section")
+    kind, sf = ("raw", "rle", "huf", "treeless")[b[0] & 3], (b[0] >> 2) & 3
+    v = int.from_bytes(b[:5], "little")
+    L = types.SimpleNamespace(kind=kind, sf=sf, csize=None, streams=0, stream_sizes=(), desc=None, desc_len=0, desc_exact=True, weights=None, lengths=None)
+    if kind in ("raw", "rle"):
+        L.hl = 1 if sf in (0, 2) else 2 if sf == 1 else 3
+        L.regen = v >> 3 & 31 if L.hl == 1 else v >> 4 & 0xFFF if L.hl == 2 else v >> 4 & 0xFFFFF
+        need = L.hl + (L.regen if kind == "raw" else 1)
+        if need > len(b) or L.regen > 131072:
+            raise ValueError("literals section cut")
+        return L, (b[L.hl:need] if kind == "raw" else b[L.hl:L.hl + 1] * L.regen), need, prev_huf
+    bits, L.hl = {0: (10, 3), 1: (10, 3), 2: (14, 4), 3: (18, 5)}[sf]
+    L.regen, L.csize, L.streams = (v >> 4) & ((1 << bits) - 1), (v >> (4 + bits)) & ((1 << bits) - 1), 1 if sf == 0 else 4
+    if L.hl + L.csize > len(b) or L.regen > 131072:
+        raise ValueError("literals section cut")
+    body = b[L.hl:L.hl + L.csize]
+    if kind == "huf":
+        huf, L.desc, L.desc_len, L.desc_exact = read_tree(body)
+        body = body[L.desc_len:]
+    else:
+        if prev_huf is None:
+            raise ValueError("treeless literals with no tree")
+        huf = prev_huf
+    L.weights = list(huf.weights)
+    L.lengths = [huf.maxbits + 1 - w if w else 0 for w in huf.weights]
+    tab = _huf_table(huf)
+    if L.streams == 1:
+        L.stream_sizes = (len(body),)
+        lits = _huf_stream(tab, huf.maxbits, body, L.regen)
+    else:
+        if len(body) < 6:
+            raise ValueError("no jump table")
+        s = struct.unpack("<3H", body[:6])
+        s += (len(body) - 6 - sum(s),)
+        if s[3] < 0:
+            raise ValueError("jump table beyond the section")
+        L.stream_sizes = s
+        per, at, parts = (L.regen + 3) // 4, 6, []
+        if 3 * per > L.regen:
+            raise ValueError("four streams for %d literals" % L.regen)
+        for k in range(4):
+            parts.append(_huf_stream(tab, huf.maxbits, body[at:at + s[k]], per if k < 3 else L.regen - 3 * per))
+            at += s[k]
+        lits = b"".join(parts)
+    return L, lits, L.hl + L.csize, huf
+
+
+def parse_frame(data):
+    """One frame, read as RFC 8878 says, with everything kept: a namespace of
+      fhd, single_segment, window_log, fcs (None: no content size field), fcs_bytes, checksum (the stored one, or None)
+      blocks     one namespace per block: type (0 raw, 1 RLE, 2 compressed), size (Block_Size), last, data (what the block regenerates) and,
+                 for a compressed block, lit (kind raw | rle | huf | treeless, sf, hl header bytes, regen, csize, streams, stream_sizes as the
+                 jump table says, desc direct | fse, desc_len, desc_exact, weights, lengths), literals, nseq, nseq_bytes, modes (the byte, None
+                 without sequences), rle_codes {"ll" | "of" | "ml": code} of the tables in RLE mode, seqs [(literal length, match length,
+                 Offset_Value)], states (the three last states, LL OF ML)
+      content    the blocks' data in a row
+      trailing   what follows the frame
+    ValueError for anything the format forbids: reserved bits and types, a window beyond 2^31, sizes that do not add up, code lengths above
+    11 bits, weights that complete no tree, streams that do not end exactly where they must, tables that are not there, offsets beyond the output,
+    a content size or checksum that is not the content's.  (A dictionary id is refused too: no dictionary is at hand.)"""
+    data = bytes(data)
+    if len(data) < 5 or data[:4] != MAGIC:
+        raise ValueError("no frame")
+    fhd = data[4]
+    single, flag = (fhd >> 5) & 1, fhd >> 6
+    if fhd & 0x08:
+        raise ValueError("reserved bit")
+    if fhd & 3:
+        raise ValueError("dictionary id")
+    F = types.SimpleNamespace(fhd=fhd, single_segment=bool(single), window_log=None, fcs=None, blocks=[], checksum=None)
+    p = 5
+    if not single:
+        if p >= len(data):
+            raise ValueError("header cut")
+        F.window_log = 10 + (data[p] >> 3)
+        if F.window_log > 31:
+            raise ValueError("window log %d" % F.window_log)
+        p += 1
+    F.fcs_bytes = {0: single, 1: 2, 2: 4, 3: 8}[flag]
+    if p + F.fcs_bytes > len(data):
+        raise ValueError("header cut")
+    if F.fcs_bytes:
+        F.fcs = int.from_bytes(data[p:p + F.fcs_bytes], "little") + (256 if F.fcs_bytes == 2 else 0)
+    p += F.fcs_bytes
+    out, rep, huf, tabs = bytearray(), [1, 4, 8], None, {"ll": None, "of": None, "ml": None}
+    while True:
+        if p + 3 > len(data):
+            raise ValueError("block header cut")
+        bh = int.from_bytes(data[p:p + 3], "little")
+        p += 3
+        B = types.SimpleNamespace(type=(bh >> 1) & 3, size=bh >> 3, last=bool(bh & 1), lit=None, literals=None, nseq=0, nseq_bytes=0, modes=None,
+                                  rle_codes={}, seqs=[], states=None)
+        if B.type == 3 or B.size > 131072:
+            raise ValueError("block type %d, size %d" % (B.type, B.size))
+        start = len(out)
+        if B.type == 0:
+            if p + B.size > len(data):
+                raise ValueError("raw block cut")
+            out += data[p:p + B.size]
+            p += B.size
+        elif B.type == 1:
+            if p + 1 > len(data):
+                raise ValueError("RLE block cut")
+            out += data[p:p + 1] * B.size
+            p += 1
+        else:
+            if B.size < 3 or p + B.size > len(data):                   # (literals header + sequence count: libzstd's MIN_CBLOCK_SIZE)
+                raise ValueError("compressed block of %d bytes" % B.size)
+            b = data[p:p + B.size]
+            p += B.size
+            B.lit, B.literals, q, huf = _read_literals(b, huf)
+            if q >= len(b):
+                raise ValueError("no sequences section")
+            n0 = b[q]
+            B.nseq_bytes = 1 if n0 < 128 else 3 if n0 == 255 else 2
+            if q + B.nseq_bytes > len(b):
+                raise ValueError("sequence count cut")
+            B.nseq = n0 if n0 < 128 else b[q + 1] + (b[q + 2] << 8) + 0x7F00 if n0 == 255 else ((n0 - 128) << 8) + b[q + 1]
+            q += B.nseq_bytes
+            li = 0
+            if B.nseq == 0:
+                if B.nseq_bytes > 1 or q != len(b):
+                    raise ValueError("no sequences, and bytes behind the count")
+            else:
+                if q >= len(b):
+                    raise ValueError("no modes byte")
+                B.modes = b[q]
+                q += 1
+                if B.modes & 3:
+                    raise ValueError("reserved bits in the modes byte")
+                for which, shift in (("ll", 6), ("of", 4), ("ml", 2)):
+                    m = (B.modes >> shift) & 3
+                    if m == 0:
+                        tabs[which] = Fse(*DEF[which])
+                    elif m == 1:
+                        if q >= len(b) or b[q] > MAX_SYM[which]:
+                            raise ValueError("RLE table of %s" % which)
+                        tabs[which] = Fse.rle(b[q])
+                        B.rle_codes[which] = b[q]
+                        q += 1
+                    elif m == 2:
+                        norm, log, used = read_ncount(b[q:], MAX_LOG[which], MAX_SYM[which])
+                        tabs[which] = Fse(norm, log)
+                        q += used
+                    elif tabs[which] is None:
+                        raise ValueError("repeat mode with no %s table" % which)
+                r = BackReader(b[q:])
+                tl, to, tm = tabs["ll"], tabs["of"], tabs["ml"]
+                sl, so, sm = r.take(tl.log), r.take(to.log), r.take(tm.log)
+                for k in range(B.nseq):
+                    ofc, mlc, llc = to.sym[so], tm.sym[sm], tl.sym[sl]
+                    ofv = (1 << ofc) + r.take(ofc)
+                    ml = ML_BASE[mlc] + r.take(ML_BITS[mlc])
+                    ll = LL_BASE[llc] + r.take(LL_BITS[llc])
+                    B.seqs.append((ll, ml, ofv))
+                    if ofv > 3:
+                        off = ofv - 3
+                        rep = [off, rep[0], rep[1]]
+                    else:
+                        idx = ofv - 1 + (ll == 0)
+                        if idx == 0:
+                            off = rep[0]
+                        else:
+                            off = rep[idx] if idx < 3 else rep[0] - 1
+                            rep = [off, rep[0], rep[1]] if idx > 1 else [off, rep[0], rep[2]]
+                    if li + ll > len(B.literals):
+                        raise ValueError("literals run out")
+                    out += B.literals[li:li + ll]
+                    li += ll
+                    if off == 0 or off > len(out):
+                        raise ValueError("offset %d at %d" % (off, len(out)))
+                    if off >= ml:
+                        out += out[len(out) - off:len(out) - off + ml]
+                    else:
+                        out += (bytes(out[-off:]) * (ml // off + 1))[:ml]
+                    if k + 1 < B.nseq:
+                        sl = tl.base[sl] + r.take(tl.nb[sl])
+                        sm = tm.base[sm] + r.take(tm.nb[sm])
+                        so = to.base[so] + r.take(to.nb[so])
+                if r.n != 0:
+                    raise ValueError("%d bits of the sequence stream left over" % r.n)
+                B.states = (sl, so, sm)
+            out += B.literals[li:]
+        B.data = bytes(out[start:])
+        F.blocks.append(B)
+        if B.last:
+            break
+    if fhd & 4:
+        if p + 4 > len(data):
+            raise ValueError("checksum cut")
+        (F.checksum,) = struct.unpack_from("<I", data, p)
+        p += 4
+        if F.checksum != xxh64(bytes(out)) & 0xFFFFFFFF:
+            raise ValueError("checksum")
+    if F.fcs is not None and F.fcs != len(out):
+        raise ValueError("content size %d, content %d" % (F.fcs, len(out)))
+    F.content, F.trailing = bytes(out), data[p:]
+    return F
+
+
+# ================================================================ the ENCODER's free choices, restated (csrc/zstd_enc_dev.h)
+# One copy of each.  What the encoder MUST do is restated here: where it cuts, which runs are sequences, when it takes them.  Its code
+# lengths are its own choice (assign_lengths_wave, build_lengths): the tests state properties of the parsed block for them, not a second encoder.
+import functools   # noqa: E402
+import re          # noqa: E402
+
+import numpy as np   # noqa: E402
+
+import deflate_craft as dc   # noqa: E402
+
+ZBLOCK = 16384                   # DEFL_BLK: the staged form cuts there; the fused kernels hold at most one block
+ZSTD_RMIN = 5                    # a run of at least this many equal bytes is a sequence
+ZMAXBITS = 11                    # ZSTD_MAXBITS
+STALE_FILL = b"\x00\x00\xe5\x00\x00\x00"    # the GPU tests fill the record slots with its first four bytes, over and over (entry stale_bytes_behind_short_block)
+
+
+def zenc_pieces(payload):
+    """the blocks of a payload: cut at every 16384 bytes; an empty payload is one empty block"""
+    return [payload[i:i + ZBLOCK] for i in range(0, len(payload), ZBLOCK)] or [b""]
+
+
+def zenc_tokens(block):
+    """(literals, [(literal length, match length)], taken) of ONE block: a run of R >= 5 equal bytes is its first byte as a literal plus one
+    match of R - 1 at offset 1; `taken` is the `use` expression of zstd_tokenise, verbatim, and False for blocks under 64 bytes.  (When it is
+    False the block's literals are the block itself.)"""
+    lits, seqs, pend = bytearray(), [], 0
+    for s, r in dc.runs_of(block):
+        if r >= ZSTD_RMIN:
+            lits.append(block[s])
+            seqs.append((pend + 1, r - 1))
+            pend = 0
+        else:
+            lits += block[s:s + r]
+            pend += r
+    blen, nlit, nseq = len(block), len(lits), len(seqs)
+    use = (nseq != 0 and not (nseq == 1 and nlit == 1) and nlit + 4 * nseq + 8 <= blen and
+           3 + nlit + 4 + ((12 * nseq + (nlit >> 2) + ((blen - nlit) >> 3) + 20) >> 3) + 1 < blen)
+    return bytes(lits), seqs, blen >= 64 and use
+
+
+def zenc_literals(block):
+    """the literals the block's literals section holds (if it is a compressed block), and its sequences"""
+    lits, seqs, taken = zenc_tokens(block)
+    return (lits, seqs) if taken else (bytes(block), [])
+
+
+def zenc_chunk(blen):
+    """K of zstd_tokenise: lane t of 256 owns bytes [t K, t K + K)"""
+    return ((blen + 255) // 256 + 3) & ~3
+
+
+def zenc_split(hdr_len, n_samples, plen):
+    """literals-only mode (option zstd_sequences = 0), fused kernel, svb-zd: the block lengths of a record — the head (raw), the key bytes,
+    then whole blocks — or None where the kernel's rule leaves the record in one piece"""
+    at = hdr_len + 12 + ((n_samples + 3) >> 2)
+    if at >= 256 and at + 256 <= plen and at <= ZBLOCK:
+        return [hdr_len + 12, at - (hdr_len + 12)] + [len(x) for x in zenc_pieces(bytes(plen - at))]
+    return None
+
+
+def ll_code(ll):
+    return _code_of(LL_BASE, ll)
+
+
+def ml_code(ml):
+    return _code_of(ML_BASE, ml)
+
+
+def histogram(data):
+    return np.bincount(np.frombuffer(bytes(data), dtype=np.uint8), minlength=256).tolist()
+
+
+def shannon_clamped(freq, limit=ZMAXBITS):
+    """min(limit, ceil(log2(N / f))) per symbol in use: where assign_lengths_wave<11> starts"""
+    return [min(limit, l) for l in dc.shannon_lengths(freq)]
+
+
+def kraft(lengths, limit=ZMAXBITS):
+    """sum of 2^(limit - l): a code iff <= 2^limit, complete iff equal"""
+    return sum(1 << (limit - l) for l in lengths if l)
+
+
+def limited_lengths(freq, limit=ZMAXBITS):
+    """optimal code lengths of at most `limit` bits (package-merge, Larmore and Hirschberg 1990): the test's own yardstick"""
+    leaves = sorted((f, (s,)) for s, f in enumerate(freq) if f)
+    n = len(leaves)
+    assert 2 <= n <= 1 << limit
+    cur = list(leaves)
+    for _ in range(limit - 1):
+        packs = [(cur[i][0] + cur[i + 1][0], cur[i][1] + cur[i + 1][1]) for i in range(0, len(cur) - 1, 2)]
+        cur = sorted(leaves + packs, key=lambda x: x[0])
+    out = [0] * len(freq)
+    for _, syms in cur[:2 * n - 2]:
+        for s in syms:
+            out[s] += 1
+    return out
+
+
+def code_bits(freq, lengths):
+    return sum(f * l for f, l in zip(freq, lengths))
+
+
+def spread(counts):
+    """bytes with counts[s] occurrences of symbol s (a dict), no two neighbours equal (the most frequent at most every other byte)"""
+    order = [s for s, c in sorted(counts.items(), key=lambda kv: (-kv[1], kv[0])) for _ in range(c)]
+    n = len(order)
+    assert 2 * max(counts.values()) <= n + 1
+    out = bytearray(n)
+    out[0::2] = bytes(order[:(n + 1) // 2])
+    out[1::2] = bytes(order[(n + 1) // 2:])
+    assert all(r == 1 for _, r in dc.runs_of(out))
+    return bytes(out)
+
+
+def low4(rng, n, alphabet=bytes(range(4))):
+    """n bytes over four small values, no run of four: a Huffman block whose tree description is three bytes"""
+    return bytes(dc.background(rng, n, alphabet))
+
+
+def zenc_payload(e, sig_method=1):
+    """the payload of an entry: a solo entry's own bytes, else the oracle's record payload (sig_method 1 svb-zd, 2 ex-zd)"""
+    if e["solo"]:
+        return e["body"]
+    return dc.enc_payload(dict(e, name="zenc:" + e["name"]), sig_method)
+
+
+ZENC_SIZES = (0, 1, 63, 64, 65, 16383, 16384, 16385, 32768, 32769)
+ZENC_KS = ((4, 1001), (32, 7999), (64, 15400))                  # (K, a block length with that K whose last lane chunk is partial)
+ZENC_NSEQ = (1, 63, 64, 65, 127, 128, 129, 3275)
+ZENC_LL_STEPS = (15, 16, 23, 24, 31, 32, 47, 48, 63, 64, 127, 128, 4097)
+ZENC_MB_STEPS = (31, 32, 39, 40, 47, 48, 63, 64, 95, 96, 127, 128, 255, 256, 16379)
+ZENC_GEO = ("runs_4_5_6", "run_from_last_byte_of_chunk", "run_from_chunk_offset_k_minus_5", "run_from_chunk_offset_k_minus_4", "run_ends_on_chunk_end",
+            "run_over_whole_chunks", "run_across_wave_boundary", "run_spans_a_wave", "run_from_position_0", "run_to_block_end", "partial_last_lane")
+ZENC_EDGES = tuple(
+    ["size_%d" % n for n in ZENC_SIZES] + ["size_16777221_carry_byte"] +
+    ["rle_block", "literal_then_run_two_raw_literals", "run_63_raw", "incompressible_raw", "flat_single_weight_raw",
+     "use_first_inequality_refuses", "use_first_inequality_takes", "use_second_inequality_refuses", "use_second_inequality_takes"] +
+    ["k%d_%s" % (K, g) for K, _ in ZENC_KS for g in ZENC_GEO] + ["stale_bytes_behind_short_second_block", "stale_bytes_behind_last_lane"] +
+    ["nseq_%d" % n for n in ZENC_NSEQ] + ["ll_%d" % n for n in ZENC_LL_STEPS] + ["mb_%d" % n for n in ZENC_MB_STEPS] +
+    ["seq_raw_literals_31", "seq_raw_literals_32", "seq_raw_literals_4095", "seq_raw_literals_4096",
+     "huf_nl_64", "huf_nl_65", "huf_nl_1023", "huf_nl_1024", "huf_nl_16383", "huf_nl_16384", "huf_csize_near_1023",
+     "distinct_2", "distinct_16", "distinct_17", "clamp_oversubscribes", "longest_code_11_exact", "longest_code_11_tree_free",
+     "maxsym_127", "maxsym_128", "maxsym_129", "weights_odd", "weights_even", "fse_gap_1", "fse_gap_3", "fse_gap_4", "fse_gap_6",
+     "normalise_gives", "normalise_takes"] +
+    ["align_phase_%d" % k for k in range(4)] +
+    ["lo_head_align_%d" % k for k in range(4)] + ["lo_at_255", "lo_at_256", "lo_tail_255", "lo_tail_256"])
+
+
+class ZView:
+    """what a property is stated on: the payload, its blocks and their restated tokens"""
+    def __init__(self, payload):
+        self.p = payload
+        self.pieces = zenc_pieces(payload)
+        self.tok = [zenc_tokens(x) for x in self.pieces]
+        self.lits = [zenc_literals(x)[0] for x in self.pieces]
+        self.runs = [dc.runs_of(x) for x in self.pieces]
+
+    def hist(self, k=0):
+        return histogram(self.lits[k])
+
+    def distinct(self, k=0):
+        return sum(1 for f in self.hist(k) if f)
+
+    def maxsym(self, k=0):
+        return max(s for s, f in enumerate(self.hist(k)) if f)
+
+    def has_run(self, start, r, k=0):
+        return (start, r) in self.runs[k]
+
+    def forced_weights(self, k=0):
+        """weights (every symbol up to the last in use) of a block whose literal frequencies are powers of two summing to one: every code no
+        larger than the Shannon start has exactly the lengths log2(N / f)"""
+        h = self.hist(k)
+        N = sum(h)
+        assert all(f == 0 or N % f == 0 and (N // f) & (N // f - 1) == 0 for f in h), "not dyadic"
+        lens = dc.shannon_lengths(h)
+        assert kraft(lens, 15) == 1 << 15
+        return [max(lens) + 1 - l if l else 0 for l in lens[:self.maxsym(k) + 1]]
+
+
+def weight_counts(weights):
+    """histogram of the LISTED weights (all but the last symbol's) — what zstd_desc_head normalises"""
+    listed = weights[:-1]
+    return [listed.count(w) for w in range(max(listed) + 1)]
+
+
+def normalise_sum(weights):
+    """the sum of the first-cut normalised counts of zstd_desc_head (floor(count * 64 / n), at least 1 for a weight in use): below 64 the
+    largest count is given the rest, above 64 the largest entries give it back"""
+    n = len(weights) - 1
+    return sum(max(1, c * 64 // n) for c in weight_counts(weights) if c)
+
+
+def weight_gaps(weights):
+    """lengths of the runs of unused weight values between used ones"""
+    used = [w for w, c in enumerate(weight_counts(weights)) if c]
+    return [b - a - 1 for a, b in zip(used, used[1:]) if b - a > 1]
+
+
+@functools.lru_cache(maxsize=None)
+def zenc_catalogue():
+    """[entry dict]: the smallest payloads that reach each edge of the zstd encoder (csrc/zstd_enc_dev.h).  An entry has name, why, solo
+    (True: whole buffers through s5gpu_solo_batch only; False: a record — the oracle's head in front, the crafted bytes as aux bytes, copied
+    verbatim — which every route takes), edges (the names of ZENC_EDGES it reaches) and prop, the stated property as a function of a ZView
+    of its payload (tests/test_zstd_encode_craft.py asserts it on the CPU for the svb-zd payload).
+
+    Branches of the encoder that no payload reaches, with the argument:
+      * RLE literals beside sequences (`lit_mode = distinct == 1 && nl >= 2`): consecutive runs hold different bytes and every run sends its
+        first byte as a literal, so literals that are all equal mean that the block is ONE run — nlit = 1, which is not >= 2 (and with
+        nseq = 1 the sequence is refused anyway).
+      * `3 * per <= nl` false: per = ceil(nl / 4), so 3 per > nl only for nl in {1, 2, 5}; the test sits behind nl >= 64.
+      * the 4-byte Huffman header for nl <= 1023 (`csize <= 1023` false while `nl <= 1023`): Huffman literals are kept only if hl + csize
+        beats the raw form, 2 + nl beside sequences and nl - 1 without, so a kept csize is below nl.  The clause decides nothing.
+      * `at <= DEFL_BLK` of the literals-only split false while the rest holds: the fused kernel holds plen <= 16384 and the rule asks
+        at + 256 <= plen.
+      * zstd_desc_pack's two "does not fit 127 bytes" returns: no payload found; a description of 255 weights over at most 12 values whose
+        counts are tied by the Kraft sum stays below 100 bytes in every block tried."""
+    E = []
+
+    def head_of(signal, read_id, fields):
+        return dc.enc_payload(dict(name="zenc-head:%r%r%r" % (tuple(signal), read_id, fields), signal=signal, read_id=read_id, fields=fields, aux=b""))
+
+    def solo(name, why, body, edges, prop):
+        E.append(dict(name=name, why=why, solo=True, body=bytes(body), edges=tuple(edges), prop=prop))
+
+    def rec(name, why, edges, prop, plen=None, runs=(), aux=None, signal=dc.SIG4, read_id=b"craft0001", fields=dc.FIELDS2, bg=None):
+        """plen and runs [(first position, length)] are in PAYLOAD positions: the aux bytes are a background of plen - head bytes (16 letters, no run
+        of four) with the runs planted in it, run i of byte RUN_BYTES[i % 16]; or aux as given (bytes, or a function of the head's length)"""
+        head = head_of(tuple(signal), read_id, fields)
+        if aux is None:
+            rng = dc._rng("zenc:" + name)
+            pay = bytearray(head) + (dc.background(rng, plen - len(head)) if bg is None else bg(rng, plen - len(head)))
+            for i, (s, r) in enumerate(runs):
+                assert s >= len(head) and s + r <= plen, (name, s, r)
+                pay[s:s + r] = bytes([dc.RUN_BYTES[i % 16]]) * r
+            aux = bytes(pay[len(head):])
+        elif callable(aux):
+            aux = aux(len(head))
+        E.append(dict(name=name, why=why, solo=False, signal=tuple(signal), read_id=read_id, fields=fields, aux=bytes(aux), edges=tuple(edges), prop=prop,
+                      hdr_len=2 + len(read_id) + 36))
+
+    bgs = lambda name, n: bytes(dc.background(dc._rng("zenc:" + name), n))
+    X, Y = b"\xe0", b"\xe1"
+
+    # ---- sizes
+    for n in (0, 1, 63, 64, 65):
+        solo("size_%d" % n, "a buffer of %d bytes%s" % (n, {0: ": one empty raw block", 63: ": below the block forms' 64", 64: ": blen >= 64, nl >= 64"}.get(n, "")),
+             low4(dc._rng("size%d" % n), n), ["size_%d" % n], lambda v, n=n: len(v.p) == n and len(v.pieces) == 1)
+    for n in (16383, 16384, 16385, 32768, 32769):
+        rec("size_%d" % n, "a payload of %d bytes: blocks of %s" % (n, " + ".join(str(len(x)) for x in zenc_pieces(bytes(n)))), ["size_%d" % n],
+            lambda v, n=n: len(v.p) == n and [len(x) for x in v.pieces] == [len(x) for x in zenc_pieces(bytes(n))], plen=n, runs=[(5000, 5)])
+    big = bytearray((1 << 24) + 5)
+    for at in (3, 9000, ZBLOCK * 700 + 5, (1 << 24) + 4):
+        big[at] = 0x55
+    solo("size_16777221", "2^24 + 5 zero bytes with four planted literals: the content size's fourth byte is 1 (z.carry = plen >> 24), 1025 blocks, most of them RLE",
+         big, ["size_16777221_carry_byte"], lambda v: len(v.p) >> 24 == 1 and len(v.pieces) == 1025 and len(v.pieces[-1]) == 5)
+    # ---- block choice
+    solo("rle_block_64", "64 equal bytes: one run, nseq == 1 && nlit == 1 refuses the sequence, and the block is an RLE block", X * 64, ["rle_block"],
+         lambda v: v.tok[0][1] == [(1, 63)] and not v.tok[0][2] and v.distinct() == 1)
+    solo("literal_then_run", "one literal and a run of 99: the sequence is taken, a compressed block with two raw literals", b"\x01" + X * 99,
+         ["literal_then_run_two_raw_literals", "nseq_1"], lambda v: v.tok[0] == (b"\x01\xe0", [(2, 98)], True))
+    solo("run_63", "63 equal bytes: below 64 neither sequences nor an RLE block, a raw block", X * 63, ["run_63_raw"], lambda v: not v.tok[0][2] and len(v.p) == 63)
+    solo("incompressible_200", "200 different byte values: an optimal code needs more than 200 bytes with its description, a raw block",
+         bytes(dc._rng("inc200").permutation(256)[:200].astype(np.uint8)), ["incompressible_raw"],
+         lambda v: v.distinct() == 200 and not v.tok[0][2] and raw_is_pinned(v.p))
+    solo("flat_256_x_32", "every byte value 32 times: all code lengths 8, ONE weight value, which the FSE form cannot say (zstd_desc_head returns 0): a raw block",
+         dc.flat_bytes(dc._rng("flat"), 8192), ["flat_single_weight_raw"],
+         lambda v: set(v.hist()) == {32} and not v.tok[0][2] and set(shannon_clamped(v.hist())) == {8} and raw_is_pinned(v.p))
+    # use = ... && nlit + 4 nseq + 8 <= blen && 3 + nlit + 4 + ((12 nseq + nlit / 4 + (blen - nlit) / 8 + 20) >> 3) + 1 < blen
+    ten = lambda last: b"".join(bytes([0xE0 + i]) * 5 for i in range(9)) + bytes([0xE9]) * last
+    solo("use_first_refuses", "ten runs, nine of 5 and one of 12, behind 143 literals: blen - nlit = 4 nseq + 7, one short of the room for the sequence records",
+         bgs("u1", 143) + ten(12), ["use_first_inequality_refuses"],
+         lambda v: len(v.tok[0][1]) == 10 and not v.tok[0][2] and len(v.p) - len(v.tok[0][0]) == 47 and use_terms(v.p) == (False, True))
+    solo("use_first_takes", "the same with a run of 13: blen - nlit = 4 nseq + 8", bgs("u1", 143) + ten(13), ["use_first_inequality_takes"],
+         lambda v: len(v.tok[0][1]) == 10 and v.tok[0][2] and len(v.p) - len(v.tok[0][0]) == 48 and use_terms(v.p) == (True, True))
+    solo("use_second_takes", "58 literals and a run of 15: 3 + 59 + 4 + (47 >> 3) + 1 = 72 < 73", bgs("u2", 58) + X * 15, ["use_second_inequality_takes"],
+         lambda v: v.tok[0][1] == [(59, 14)] and v.tok[0][2] and use_terms(v.p) == (True, True))
+    solo("use_second_refuses", "59 literals and a run of 15: 3 + 60 + 4 + (48 >> 3) + 1 = 74, not < 74", bgs("u2", 59) + X * 15, ["use_second_inequality_refuses"],
+         lambda v: v.tok[0][1] == [(60, 14)] and not v.tok[0][2] and use_terms(v.p) == (True, False))
+    # ---- tokeniser geometry
+    long_id = b"\x01" * 3 + b"craftcraf" * 28 + b"cr"                        # 257 bytes: id length 01 01, then 01 01 01: a run of 5 from position 0
+    assert len(long_id) == 257
+    for K, blen in ZENC_KS:
+        assert zenc_chunk(blen) == K and blen % K
+        c = 80 // K + 2                                                      # a lane chunk behind the head
+        g = lambda x, K=K: ["k%d_%s" % (K, x)]
+        rec("k%d_runs_4_5_6" % K, "K = %d (blen %d): runs of exactly 4, 5 and 6 — the first is no sequence" % (K, blen), g("runs_4_5_6"),
+            lambda v, c=c, K=K: [x[1] for x in v.tok[0][1][5:]] == [4, 5] and v.has_run(c * K + 1, 4) and v.has_run((c + 9) * K + 1, 5) and v.has_run((c + 18) * K + 1, 6),
+            plen=blen, runs=[(c * K + 1, 4), ((c + 9) * K + 1, 5), ((c + 18) * K + 1, 6)])
+        rec("k%d_run_from_last_byte" % K, "K = %d: a run of 6 whose first byte is the last of a lane chunk: the lane sees one break and nothing behind it" % K,
+            g("run_from_last_byte_of_chunk"), lambda v, c=c, K=K: v.has_run(c * K + K - 1, 6), plen=blen, runs=[(c * K + K - 1, 6)])
+        rec("k%d_run_from_k_minus_5" % K, "K = %d: a run of 5 from chunk offset K - 5: the last start whose RMIN - 1 followers lie inside the chunk" % K,
+            g("run_from_chunk_offset_k_minus_5") + g("run_ends_on_chunk_end"), lambda v, c=c, K=K: v.has_run(c * K + K - 5, 5),
+            plen=blen, runs=[(c * K + K - 5, 5)])
+        rec("k%d_run_from_k_minus_4" % K, "K = %d: a run of 5 from chunk offset K - 4: its last byte is the next lane's first" % K,
+            g("run_from_chunk_offset_k_minus_4"), lambda v, c=c, K=K: v.has_run(c * K + K - 4, 5), plen=blen, runs=[(c * K + K - 4, 5)])
+        rec("k%d_run_ends_on_chunk_end" % K, "K = %d: a run of 7 whose last byte is the last of a lane chunk" % K, g("run_ends_on_chunk_end"),
+            lambda v, c=c, K=K: v.has_run((c + 2) * K - 7, 7), plen=blen, runs=[((c + 2) * K - 7, 7)])
+        rec("k%d_run_over_whole_chunks" % K, "K = %d: a run from the middle of one lane chunk over three whole ones into a fifth: lanes without a break" % K,
+            g("run_over_whole_chunks"), lambda v, c=c, K=K: v.has_run(c * K + 2, 4 * K), plen=blen, runs=[(c * K + 2, 4 * K)])
+        rec("k%d_run_across_wave" % K, "K = %d: a run of 8 from lane 63 into lane 64: the break positions cross the waves through S.ws" % K,
+            g("run_across_wave_boundary"), lambda v, K=K: v.has_run(64 * K - 3, 8), plen=blen, runs=[(64 * K - 3, 8)])
+        rec("k%d_run_spans_a_wave" % K, "K = %d: a run from lane 62 to lane 130: a whole wave without a break" % K, g("run_spans_a_wave"),
+            lambda v, K=K: v.has_run(62 * K + 1, 68 * K + 1), plen=blen, runs=[(62 * K + 1, 68 * K + 1)])
+        rec("k%d_run_from_position_0" % K, "K = %d: a run of 5 from position 0 (id length 257 = 01 01, the read id starts 01 01 01)" % K, g("run_from_position_0"),
+            lambda v: v.runs[0][0] == (0, 5) and v.tok[0][1][0] == (1, 4), plen=blen, read_id=long_id)
+        rec("k%d_run_to_the_end" % K, "K = %d: a block of %d bytes — lane %d holds %d bytes, the lanes behind it none — that ends in a run of 9" %
+            (K, blen, blen // K, blen % K), g("run_to_block_end") + g("partial_last_lane"),
+            lambda v, blen=blen, K=K: len(v.p) == blen and v.has_run(blen - 9, 9) and 0 < blen % K and blen // K < 255, plen=blen, runs=[(blen - 9, 9)])
+    # bytes behind a short last block.  The staged kernel copies a block in 16-byte units, so what the tokeniser's last dword holds behind blen
+    # is never the block staged before (that would be the first thought) but the slot memory behind the parked payload: STALE_FILL is what the
+    # GPU tests put there — byte E5, the runs', right behind the payload, another value behind that.  A break bit behind blen does harm in two
+    # places: in the lane where a run starts that reaches the block's end (its `hi`), and in lane 255, whose first break the lanes in front take
+    # for the end of their run (behind any other lane an idle lane says blen)
+    def stale_aux(h):
+        pay = bytearray(h) + dc.background(dc._rng("zenc:stale"), ZBLOCK + 1030 - h)
+        pay[ZBLOCK + 100:ZBLOCK + 300] = b"\xe6" * 200
+        pay[ZBLOCK + 1025:] = b"\xe5" * 5
+        return bytes(pay[h:])
+    rec("stale_bytes_behind_short_block", "16384 + 1030 bytes (K = 8): the second block ends in a run of five E5 that starts in its last lane, two bytes short of that lane's "
+        "second dword; the two bytes behind it are whatever lies behind the parked payload (the tests fill the slots: E5, then 00).  Only the `valid` mask keeps the run at five",
+        ["stale_bytes_behind_short_second_block"],
+        lambda v: len(v.pieces[1]) == 1030 and zenc_chunk(1030) == 8 and v.runs[1][-1] == (1025, 5) and 1025 // 8 == 1029 // 8 and v.tok[1][1][-1][1] == 4 and v.tok[1][2]
+        and STALE_FILL[len(v.p) % 4:len(v.p) % 4 + 2] == b"\xe5\x00", aux=stale_aux)
+    def stale_aux(h):
+        pay = bytearray(h) + dc.background(dc._rng("zenc:stale255"), 16382 - h)
+        pay[1000:3000] = b"\xe6" * 2000
+        pay[16266:] = b"\xe5" * 116
+        return bytes(pay[h:])
+    rec("stale_bytes_behind_lane_255", "16382 bytes (K = 64): a run of 116 bytes E5 from lane 254 to the block's end in lane 255, which holds 62 bytes and no break; the "
+        "two bytes behind are the slot's (E5, then 00): a break there would be the first that the lanes in front see", ["stale_bytes_behind_last_lane"],
+        lambda v: len(v.p) == 16382 and zenc_chunk(16382) == 64 and v.runs[0][-1] == (16266, 116) and 16266 // 64 == 254 and v.tok[0][1][-1][1] == 115 and v.tok[0][2]
+        and STALE_FILL[len(v.p) % 4:len(v.p) % 4 + 2] == b"\xe5\x00", aux=stale_aux)
+    # ---- sequences
+    for n in (63, 64, 65, 127, 128, 129):
+        rec("nseq_%d" % n, "%d sequences (five of them in the head): the count's byte width, the sequences wave's passes of 64" % n, ["nseq_%d" % n],
+            lambda v, n=n: len(v.tok[0][1]) == n and v.tok[0][2], plen=80 + 13 * (n - 5), runs=[(70 + 13 * i, 5) for i in range(n - 5)])
+    most = b"".join(bytes([0xE0 + i % 16]) * 5 for i in range(3274)) + b"\x7a" + b"\x7b" * 13
+    solo("nseq_most", "3274 runs of 5, a literal and a run of 13: 3275 sequences and 3276 literals, nlit + 4 nseq + 8 = 16384 exactly — the most a block admits, the "
+         "sequence records fill the stage to its last word", most, ["nseq_3275"],
+         lambda v: len(v.p) == ZBLOCK and len(v.tok[0][1]) == 3275 and len(v.tok[0][0]) == 3276 and v.tok[0][2] and use_terms(v.p) == (True, True)
+         and not zenc_tokens(b"".join(bytes([0xE0 + i % 16]) * 5 for i in range(3276)))[2])
+    def ll_aux(h):
+        out = bytearray(X * 1500)                                            # (matched bytes enough for `use` to take the block)
+        rng = dc._rng("zenc:ll")
+        for i, ll in enumerate(ZENC_LL_STEPS):
+            out += dc.background(rng, ll - 1) + bytes([0xE1 + i % 2]) * 6
+        return bytes(out)
+    rec("ll_steps", "literal lengths %s: both sides of every step of zstd_ll_code" % ", ".join(map(str, ZENC_LL_STEPS)), ["ll_%d" % n for n in ZENC_LL_STEPS],
+        lambda v: [x[0] for x in v.tok[0][1][-len(ZENC_LL_STEPS):]] == list(ZENC_LL_STEPS) and v.tok[0][2]
+        and [ll_code(n) for n in ZENC_LL_STEPS] == [15, 16, 19, 20, 21, 22, 23, 24, 24, 25, 25, 26, 31], aux=ll_aux)
+    def ml_aux(h):
+        out = bytearray()
+        for i, mb in enumerate(ZENC_MB_STEPS[:-1]):
+            out += b"abc" + bytes([0xE0 + i % 2]) * (mb + 4)
+        return bytes(out)
+    rec("ml_steps", "match lengths of mb + 3 for mb = %s: both sides of every step of zstd_ml_code" % ", ".join(map(str, ZENC_MB_STEPS[:-1])),
+        ["mb_%d" % n for n in ZENC_MB_STEPS[:-1]],
+        lambda v: [x[1] - 3 for x in v.tok[0][1][-14:]] == list(ZENC_MB_STEPS[:-1]) and v.tok[0][2]
+        and [ml_code(n + 3) for n in ZENC_MB_STEPS[:-1]] == [31, 32, 35, 36, 37, 38, 39, 40, 41, 42, 42, 43, 43, 44], aux=ml_aux)
+    solo("ml_longest", "one literal and a run of 16383: the longest match a block can hold, 16382 = mb 16379, code 49 with 13 extra bits", b"\x01" + X * 16383,
+         ["mb_16379"], lambda v: v.tok[0] == (b"\x01\xe0", [(2, 16382)], True) and ml_code(16382) == 49 and ML_BITS[49] == 13)
+    # ---- literals section
+    for nl in (31, 32):
+        solo("seq_raw_literals_%d" % nl, "%d literals beside a sequence: nl < 64, raw literals with a %d-byte header" % (nl, 1 if nl < 32 else 2),
+             bgs("rl%d" % nl, nl - 1) + X * 40, ["seq_raw_literals_%d" % nl], lambda v, nl=nl: len(v.tok[0][0]) == nl and v.tok[0][2])
+    for nl in (4095, 4096):
+        flat = b"".join(bytes(dc._rng("rl%d" % i).permutation(256).astype(np.uint8)) for i in range(16))
+        solo("seq_raw_literals_%d" % nl, "%d literals of every value about equally often beside a sequence: no code beats 8 bits, raw literals with a %d-byte header" %
+             (nl, 2 if nl < 4096 else 3), flat[:nl - 1] + X * 300, ["seq_raw_literals_%d" % nl],
+             lambda v, nl=nl: len(v.tok[0][0]) == nl and v.tok[0][2] and len(v.tok[0][1]) == 1 and huffman_floor(v.lits[0]) >= nl + 3)
+    for nl, what in ((64, "the least the Huffman form takes: streams of 16 literals, a lane holds at most one"), (65, "streams of 17, 17, 17 and 14: an uneven last stream"),
+                     (1023, "the 3-byte header's last"), (1024, "the 4-byte header's first"), (16383, "the 4-byte header's last"), (16384, "the 5-byte header")):
+        solo("huf_nl_%d" % nl, "%d literals over four values, no run: %s" % (nl, what), low4(dc._rng("hnl%d" % nl), nl), ["huf_nl_%d" % nl],
+             lambda v, nl=nl: len(v.lits[0]) == nl and not v.tok[0][2] and v.distinct() == 4 and huffman_is_pinned(v.p))
+    near = bytes(dc._rng("near").permutation(np.repeat(np.arange(200, dtype=np.uint8), [12] * 23 + [4] * 177))[:983])
+    solo("huf_csize_near_1023", "983 literals of 200 values beside a run of 60: csize comes out near nl, far from the 1023 it would have to pass with nl below it — kept "
+         "Huffman literals have csize < nl, so that side of `csize <= 1023` cannot be reached (see the catalogue's docstring)", near + X * 60, ["huf_csize_near_1023"],
+         lambda v: len(v.tok[0][0]) == 984 and v.tok[0][2])
+    # ---- code lengths
+    solo("distinct_2", "two values, 3 and 250, no run of five: the exact construction; 250 weights of which one is not zero", bytes(dc.background(dc._rng("d2"), 3000, b"\x03\xfa")),
+         ["distinct_2"], lambda v: v.distinct() == 2 and v.maxsym() == 250)
+    for k in (16, 17):
+        p = 0.8 ** np.arange(k)
+        x = dc._rng("d%d" % k).choice(k, 3000, p=p / p.sum())
+        for i in range(3, 3000):
+            if x[i] == x[i - 1] == x[i - 2] == x[i - 3]:
+                x[i] = (x[i] + 1) % k
+        body = bytes(0x30 + int(a) for a in x)
+        solo("distinct_%d" % k, "%d values of geometric frequencies: %s" % (k, "the last alphabet of the exact construction" if k == 16 else "the first of the tree-free one"),
+             body, ["distinct_%d" % k], lambda v, k=k: v.distinct() == k and not v.tok[0][1])
+    geo = {0x10 + i: 8192 >> i for i in range(11)}
+    geo.update({0xC0 + i: 1 for i in range(8)})
+    solo("geometric_and_eight_singles", "frequencies 8192, 4096 .. 8 and eight values seen once, the last of them 199: the Shannon lengths clamped to 11 bits over-subscribe the "
+         "code space, assign_lengths_wave gives up and the exact construction repairs the Kraft sum; 199 weights, most weight values seen once: their normalised counts "
+         "sum above 64", spread(geo), ["clamp_oversubscribes", "normalise_takes"],
+         lambda v: v.distinct() == 19 and not v.tok[0][1] and kraft(shannon_clamped(v.hist())) == (1 << 11) + 7 and max(dc.shannon_lengths(v.hist())) == 14)
+    dy = {0x10 + i: 8192 >> i for i in range(11)}
+    dy[140] = 8
+    solo("dyadic_12_longest_11", "frequencies 8192, 4096 .. 8, 8 (the last for value 140): any code within the Shannon bound has lengths 1 .. 10, 11, 11; twelve values, the "
+         "exact construction; 140 weights, each weight 1 .. 11 listed once beside 129 zeros: 58 + 11 normalised counts, five to take back", spread(dy),
+         ["longest_code_11_exact", "normalise_takes"],
+         lambda v: v.distinct() == 12 and max(v.forced_weights()) == 11 and sorted(v.forced_weights())[-11:] == list(range(1, 12)) and normalise_sum(v.forced_weights()) == 69)
+    dy = {0x80 + i: 512 for i in range(16)}
+    dy.update({0x10 + i: 4096 >> i for i in range(10)})
+    dy[0x40] = 8
+    solo("dyadic_27_longest_11", "sixteen values 512 times, then 4096, 2048 .. 8, 8: 27 values, the tree-free construction with no slack to hand out, longest code 11",
+         spread(dy), ["longest_code_11_tree_free", "normalise_takes"],
+         lambda v: v.distinct() == 27 and max(v.forced_weights()) == 10 and min(w for w in v.forced_weights() if w) == 1 and normalise_sum(v.forced_weights()) == 68)
+    dy = {0x20: 8192, 250: 128}
+    dy.update({0x60 + i: 256 for i in range(20)})
+    dy.update({0x80 + i: 128 for i in range(23)})
+    solo("dyadic_45_normalise_gives", "one value of 1 bit, 20 of 6 and 24 of 7, the last of them 250: of 250 weights 206 are 0, 23 are 1, 20 are 2 and one is 7 — normalised "
+         "52 + 5 + 5 + 1 = 63, and the largest count is given the missing one", spread(dy), ["normalise_gives"],
+         lambda v: v.distinct() == 45 and weight_counts(v.forced_weights()) == [206, 23, 20, 0, 0, 0, 0, 1] and normalise_sum(v.forced_weights()) == 63)
+    # ---- tree description
+    for top in (127, 128, 129):
+        solo("maxsym_%d" % top, "four small values and value %d: %d weights listed, %s" % (top, top, "the first FSE form" if top > 128 else "direct nibbles, an %s count" %
+             ("odd" if top & 1 else "even, the last direct form")), low4(dc._rng("ms%d" % top), 400) + bytes([top, 1, top, 2]) * 8,
+             ["maxsym_%d" % top] + (["weights_odd"] if top == 127 else ["weights_even"] if top == 128 else []),
+             lambda v, top=top: v.maxsym() == top and not v.tok[0][1] and huffman_is_pinned(v.p))
+    # (one value of 1 bit and m = 2^(L - 1) of L bits: weights 0, 1 and L in use, L - 2 values between; 255 other values end that at L = 8, a gap of 6)
+    for gap, L, m in ((1, 3, 4), (3, 5, 16), (4, 6, 32), (6, 8, 128)):
+        dy = {0x20: 8192}
+        dy.update({(0xA0 if m <= 32 else 0x60) + i: 8192 // m for i in range(m)})
+        solo("fse_gap_%d" % gap, "one value half of the bytes, %d values the rest: weights 0, 1 and %d in use, %d weight values unused between: the count header's "
+             "zero-run flag %s" % (m, L, gap, {1: "0", 3: "2", 4: "3 then 0", 6: "3 then 2"}[gap]), spread(dy), ["fse_gap_%d" % gap],
+             lambda v, gap=gap: v.maxsym() > 128 and weight_gaps(v.forced_weights()) == [gap])
+    # ---- output alignment
+    for k in range(4):
+        rec("align_phase_%d" % k, "two blocks; the first is %d literals and one long run, raw literals: its size grows by one with each of these four entries, so the second "
+            "block's header, literals, jump table and sequences start at every byte phase of a word" % (33 + k), ["align_phase_%d" % k],
+            lambda v, k=k: len(v.tok[0][0]) == 33 + k and len(v.tok[0][1]) == 6 and v.tok[0][2] and v.tok[1][2] and len(v.tok[1][0]) > 2000
+            and v.tok[0][1][-1] == (9 + k + 3, ZBLOCK - 64 - k - 3) and ll_code(12) == 12 and ll_code(15) == 15 and ml_code(ZBLOCK - 70) == 49,
+            aux=lambda h, k=k: bgs("al", 5)[:k + 2] + X * (ZBLOCK - h - k - 2) + bgs("al2", 1200) + Y * 200 + bgs("al3", 1800))
+    # ---- literals-only mode (option zstd_sequences = 0): the split of an svb-zd record in the fused kernel
+    walk = lambda name, n: np.cumsum(dc._rng("zenc:" + name).integers(-9, 10, n)).astype(np.int16) + 500
+    for k in range(4):
+        rid = b"craft0001xyz"[:9 + k]
+        rec("lo_head_align_%d" % k, "an id of %d bytes: hdr_len + 12 = %d = %d mod 4 — in literals-only mode the raw head block ends, and the key and the data block "
+            "start, there in LDS" % (9 + k, 59 + k, (59 + k) % 4), ["lo_head_align_%d" % k],
+            lambda v, k=k: zenc_split(47 + k, 2000, len(v.p)) is not None and zenc_split(47 + k, 2000, len(v.p))[0] % 4 == (59 + k) % 4,
+            aux=bgs("lo%d" % k, 100), signal=walk("lo%d" % k, 2000), read_id=rid)
+    for at, ns in ((255, 784), (256, 788)):
+        rec("lo_at_%d" % at, "%d samples: the key bytes end at %d — %s" % (ns, at, "no split below 256" if at < 256 else "the first split"), ["lo_at_%d" % at],
+            lambda v, at=at, ns=ns: 59 + ((ns + 3) >> 2) == at and (zenc_split(47, ns, len(v.p)) is None) == (at < 256) and len(v.p) > at + 256,
+            aux=b"", signal=walk("lo_at", ns))
+    for tail in (255, 256):
+        rid = b"craft0001" + b"x" * 201
+        sig = walk("lo_tail", 100)
+        h = len(head_of(tuple(sig), rid, dc.FIELDS2))
+        at = 2 + 210 + 36 + 12 + 25
+        rec("lo_tail_%d" % tail, "an id of 210 bytes and 100 samples: %d bytes behind the key bytes — %s" % (tail, "no split" if tail < 256 else "the shortest data block of a split"),
+            ["lo_tail_%d" % tail], lambda v, tail=tail, at=at: len(v.p) - at == tail and (zenc_split(248, 100, len(v.p)) is None) == (tail < 256),
+            aux=bgs("lot", 300)[:tail - (h - at)], signal=sig, read_id=rid)
+    assert len({e["name"] for e in E}) == len(E)
+    return E
+
+
+def use_terms(block):
+    """the two inequalities of `use`, each on its own, for a block with sequences"""
+    lits, seqs, _ = zenc_tokens(block)
+    blen, nlit, nseq = len(block), len(lits), len(seqs)
+    return (nlit + 4 * nseq + 8 <= blen, 3 + nlit + 4 + ((12 * nseq + (nlit >> 2) + ((blen - nlit) >> 3) + 20) >> 3) + 1 < blen)
+
+
+def huffman_floor(lits):
+    """bytes that NO Huffman literals section of these literals goes below: a 3-byte header, the description (direct: 1 + ceil(n / 2) for n =
+    the largest value in use, up to 128; FSE: at least 3), the jump table, and the four streams — together at least (bits + 4) / 8 bytes for the
+    bits of an optimal 11-bit-limited code, each stream carrying its end mark"""
+    h = histogram(lits)
+    n = max(s for s, f in enumerate(h) if f)
+    bits = code_bits(h, limited_lengths(h))
+    return 3 + (1 + (n + 1) // 2 if n <= 128 else 3) + 6 + (bits + 4 + 7) // 8
+
+
+def huffman_ceiling(lits):
+    """bytes that the encoder's own Huffman literals section stays within when the clamped Shannon lengths are a code (which it only
+    shortens): a 5-byte header, the description (direct: 1 + ceil(n / 2); FSE: at most 128 bytes), the jump table, the streams at the Shannon start with a byte of rounding each"""
+    h = histogram(lits)
+    sl, n = shannon_clamped(h), max(s for s, f in enumerate(h) if f)
+    assert kraft(sl) <= 1 << ZMAXBITS
+    return 5 + (1 + (n + 1) // 2 if n <= 128 else 128) + 6 + code_bits(h, sl) // 8 + 4
+
+
+def raw_is_pinned(block):
+    """a block without sequences of which the arithmetic alone says: raw (no Huffman section could make `hl + csize + 1 < blen` true)"""
+    return len(block) < 64 or (not zenc_tokens(block)[2] and len(set(block)) > 1 and huffman_floor(block) + 1 >= len(block))
+
+
+def huffman_certain(lits, blen):
+    """a block without sequences whose own Huffman section the encoder must have found small enough (`hl + csize + 1 < blen`), whatever
+    lengths it chose"""
+    return len(lits) >= 64 and len(set(lits)) > 1 and kraft(shannon_clamped(histogram(lits))) <= 1 << ZMAXBITS and huffman_ceiling(lits) + 1 < blen
+
+
+def huffman_is_pinned(block):
+    """... and of which the arithmetic says: compressed, with Huffman literals"""
+    return not zenc_tokens(block)[2] and huffman_certain(block, len(block))
+
+
+def zenc_family(name):
+    """the name with its numbers taken out: the entries of one loop of the catalogue"""
+    return re.sub(r"\d+", "#", name)
