@@ -8,24 +8,10 @@
 //           look-ahead), the sample index is the count of commas before it (workgroup prefix sum);
 //   format: a lane owns 8 samples; their printed lengths are prefix-summed into byte offsets.
 // Both are HBM-bound byte work: ~4.2 text bytes + 2 signal bytes per sample.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/slow5gpu.h"
+#include "launch_common.h"
 #include "dev_common.h"
 
 using namespace s5;
-
-extern "C" void s5gpu_set_error(const char *fmt, ...);
-
-#define HIP_TRY(x)                                                                                   \
-    do {                                                                                             \
-        hipError_t e_ = (x);                                                                         \
-        if (e_ != hipSuccess) {                                                                      \
-            s5gpu_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return S5GPU_ERR_HIP;                                                                    \
-        }                                                                                            \
-    } while (0)
 
 constexpr int PARSE_SPAN = 16;               // characters per lane per tile
 constexpr int PARSE_AHEAD = 7;               // "-32768," started at the last owned character ends 7 characters later
@@ -170,7 +156,7 @@ __global__ __launch_bounds__(NT) void k_gather(const uint64_t *src_off, const ui
 }
 
 __global__ void k_ascii_noop(uint32_t *p) { if (p) p[0] = 0; }
-int s5ascii_warm(hipStream_t st) {             // s5gpu_warmup (kernels.hip): this file's code object
+int s5ascii_warm(hipStream_t st) {             // s5gpu_warmup (batch_kernels.hip): this file's code object
     hipLaunchKernelGGL(k_ascii_noop, dim3(1), dim3(64), 0, st, (uint32_t *)nullptr);
     return hipGetLastError() == hipSuccess ? S5GPU_OK : S5GPU_ERR_HIP;
 }

@@ -6,8 +6,6 @@
 
 // behind a kernel launch, in a function that returns a library code: the launch's own error -> the error text and S5GPU_ERR_HIP
 // (the file declares s5gpu_set_error and includes slow5gpu.h)
-// The dtw, path, refine, band and pileup kernel files use it.  diff, event, signal, fstats and skim_kernels.hip still carry a copy of
-// their own (DF_, EV_, SIG_, FS_, SKIM_LAUNCH_CHECK; skim's differs by a `const`): to be folded in here later.
 #define S5_LAUNCH_CHECK(what)                                                             \
     do {                                                                                  \
         hipError_t e_ = hipGetLastError();                                                \

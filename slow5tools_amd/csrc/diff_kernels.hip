@@ -276,15 +276,6 @@ __global__ __launch_bounds__(NT) void k_sig_diff(uint32_t n_pairs, const uint32_
     }
 }
 
-#define DF_LAUNCH_CHECK(what)                                                             \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int dfk::set_option(const char *key, long value) {
     if (!key) return S5GPU_ERR_ARG;
     if (strcmp(key, "diff_lds_bins") == 0 && (value == 0 || (value >= (long)MIN_BINS && value <= (long)MAX_BINS && (value & (value - 1)) == 0))) {
@@ -298,14 +289,14 @@ int dfk::set_option(const char *key, long value) {
 
 int dfk::launch_reset(s5gpu_diff_acc_t *acc, hipStream_t st) {
     hipLaunchKernelGGL(k_diff_acc_reset, dim3(128), dim3(NT), 0, st, reinterpret_cast<uint64_t *>(acc));
-    DF_LAUNCH_CHECK("k_diff_acc_reset");
+    S5_LAUNCH_CHECK("k_diff_acc_reset");
     return S5GPU_OK;
 }
 
 int dfk::launch_add_failed(s5gpu_diff_acc_t *acc, uint32_t k, hipStream_t st) {
     if (k == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_diff_add_failed, dim3(1), dim3(64), 0, st, acc, k);
-    DF_LAUNCH_CHECK("k_diff_add_failed");
+    S5_LAUNCH_CHECK("k_diff_add_failed");
     return S5GPU_OK;
 }
 
@@ -316,6 +307,6 @@ int dfk::launch_diff(uint32_t n_pairs, const uint32_t *pair_a, const uint32_t *p
     const uint32_t grid = n_pairs < g_grid ? n_pairs : g_grid;            // by default four resident workgroups per CU
     hipLaunchKernelGGL(k_sig_diff, dim3(grid), dim3(NT), acc ? (size_t)O.bins * COPIES * sizeof(uint32_t) : 0, st, n_pairs, pair_a, pair_b, A, B, O,
                        out, acc);
-    DF_LAUNCH_CHECK("k_sig_diff");
+    S5_LAUNCH_CHECK("k_sig_diff");
     return S5GPU_OK;
 }

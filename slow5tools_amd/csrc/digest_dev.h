@@ -1,4 +1,4 @@
-// digest_dev.h — what digest_kernels.hip, digest_api.hip and kernels.hip share: the record table k_rec_digest walks, the canonical length of a
+// digest_dev.h — what digest_kernels.hip, digest_api.hip and order_launch.hip share: the record table k_rec_digest walks, the canonical length of a
 // record (the key of its launch order) and the launcher.
 //
 // The canonical record C(r) (docs/codecs.md §4.12) is never built: it is the virtual stream
@@ -57,6 +57,6 @@ int launch_digest(const DigRecs &R, uint64_t *digest, hipStream_t st);
 
 }  // namespace digk
 
-// kernels.hip: the counting sort of order_dev.h with OrderByCanonLen as its key.  *ord = nullptr: no list (file order).  `hold` keeps the
+// order_launch.hip: the counting sort of order_dev.h with OrderByCanonLen as its key.  *ord = nullptr: no list (file order).  `hold` keeps the
 // scratch until the kernel that reads the list is enqueued.
 int s5kern_digest_order(const digk::DigRecs &R, hipStream_t st, const uint32_t **ord, std::unique_lock<std::mutex> &hold);

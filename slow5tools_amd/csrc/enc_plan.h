@@ -1,11 +1,11 @@
-// enc_plan.h — the LDS budget rules of the encode launches (kernels.hip, host_api.hip).  Plain C++, no HIP: tests/test_enc_plan.py
+// enc_plan.h — the LDS budget rules of the encode launches (encode_kernels.hip, host_api.hip).  Plain C++, no HIP: tests/test_enc_plan.py
 // compiles it on its own and compares every rule with its arithmetic restated.
 #pragma once
 #include <stdint.h>
 
 namespace s5plan {
 constexpr int SIG_SVB_ZD = 1, SIG_EX_ZD = 2;   // = S5GPU_SIG_* ...
-constexpr uint32_t BLK = 16384;                // ... and = DEFL_BLK, for callers that do not see deflate_dev.h (kernels.hip asserts all three)
+constexpr uint32_t BLK = 16384;                // ... and = DEFL_BLK, for callers that do not see deflate_dev.h (encode_kernels.hip asserts all three)
 
 // max_payload is a bound: it assumes the worst case per sample (3.25 bytes for svb-zd, 9.5 for ex-zd), real signals take ~1.27 / ~1.06.
 // The fused kernels keep room in LDS for 1.55 / 1.30 bytes per sample and a little for the record's head; everything in hundredths.

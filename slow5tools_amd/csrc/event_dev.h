@@ -1,4 +1,4 @@
-// event_dev.h — what event_kernels.hip, event_api.hip and kernels.hip share: the arguments of k_sig_events, a lane's walk over its read,
+// event_dev.h — what event_kernels.hip, event_api.hip and order_launch.hip share: the arguments of k_sig_events, a lane's walk over its read,
 // the launchers, and the launch order by sample count (docs/codecs.md §4.15).
 // With S5_EVENT_WALK_HOST defined only the walk is declared, as plain C++: tests/test_events.py compiles it for the CPU and runs the very
 // code a lane runs against the restatement, without a device.
@@ -202,7 +202,7 @@ int launch_scan(uint32_t n, const uint32_t *cnt, uint64_t *first, hipStream_t st
 }  // namespace evk
 
 #ifndef S5_EVENT_WALK_HOST
-// kernels.hip: the counting sort of order_dev.h with the reads' n_eff as its key, so that the 64 reads of a wave end together.
+// order_launch.hip: the counting sort of order_dev.h with the reads' n_eff as its key, so that the 64 reads of a wave end together.
 // *ord = nullptr: no list (file order).  `hold` keeps the scratch the list lives in until the kernel that reads it is enqueued.
 int s5kern_event_order(const sigk::SigRecs &R, hipStream_t st, const uint32_t **ord, std::unique_lock<std::mutex> &hold);
 #endif

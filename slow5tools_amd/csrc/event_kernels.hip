@@ -80,15 +80,6 @@ __global__ __launch_bounds__(NT) void k_ev_scan(uint32_t n, const uint32_t *__re
     if (threadIdx.x == 0) first[n] = carry;
 }
 
-#define EV_LAUNCH_CHECK(what)                                                             \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int evk::launch_events(const sigk::SigRecs &R, const EvArgs &A, hipStream_t st) {
     if (R.n == 0) return S5GPU_OK;
     std::unique_lock<std::mutex> hold;                                   // (the order scratch's: released when the kernel that reads the list is enqueued)
@@ -99,12 +90,12 @@ int evk::launch_events(const sigk::SigRecs &R, const EvArgs &A, hipStream_t st) 
     const size_t lds = (size_t)ring * 64 * sizeof(int16_t);              // 8 KB for w2 <= 16, 20 KB for w2 = 64
     if (A.rows) hipLaunchKernelGGL(k_sig_events<true>, grid, block, lds, st, R, A, ord, ring);
     else hipLaunchKernelGGL(k_sig_events<false>, grid, block, lds, st, R, A, ord, ring);
-    EV_LAUNCH_CHECK("k_sig_events");
+    S5_LAUNCH_CHECK("k_sig_events");
     return S5GPU_OK;
 }
 
 int evk::launch_scan(uint32_t n, const uint32_t *cnt, uint64_t *first, hipStream_t st) {
     hipLaunchKernelGGL(k_ev_scan, dim3(1), dim3(NT), 0, st, n, cnt, first);
-    EV_LAUNCH_CHECK("k_ev_scan");
+    S5_LAUNCH_CHECK("k_ev_scan");
     return S5GPU_OK;
 }

@@ -187,15 +187,6 @@ __global__ __launch_bounds__(NT) void k_read_floor(const uint4 *__restrict__ p, 
     if (lane_id() == 0) atomicXor(out, x);
 }
 
-#define FS_LAUNCH_CHECK(what)                                                             \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int fsk::set_option(const char *key, long value) {
     if (!key) return S5GPU_ERR_ARG;
     if (strcmp(key, "fstats_window_lo") == 0 && value >= -1 && value <= 65535) { g_opts.win_lo = (int32_t)value; return S5GPU_OK; }
@@ -214,20 +205,20 @@ extern "C" int s5tool_read_floor_dev(const void *p, uint64_t bytes, uint32_t *ou
     if (n16 == 0) return S5GPU_OK;
     const uint64_t blocks = (n16 + NT - 1) / NT;
     hipLaunchKernelGGL(k_read_floor, dim3((uint32_t)(blocks < 8192 ? blocks : 8192)), dim3(NT), 0, (hipStream_t)stream, (const uint4 *)p, n16, out);
-    FS_LAUNCH_CHECK("k_read_floor");
+    S5_LAUNCH_CHECK("k_read_floor");
     return S5GPU_OK;
 }
 
 int fsk::launch_reset(s5gpu_file_stats_t *acc, hipStream_t st) {
     hipLaunchKernelGGL(k_file_stats_reset, dim3(64), dim3(NT), 0, st, reinterpret_cast<uint64_t *>(acc));
-    FS_LAUNCH_CHECK("k_file_stats_reset");
+    S5_LAUNCH_CHECK("k_file_stats_reset");
     return S5GPU_OK;
 }
 
 int fsk::launch_add_failed(s5gpu_file_stats_t *acc, uint32_t k, hipStream_t st) {
     if (k == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_file_stats_add_failed, dim3(1), dim3(64), 0, st, acc, k);
-    FS_LAUNCH_CHECK("k_file_stats_add_failed");
+    S5_LAUNCH_CHECK("k_file_stats_add_failed");
     return S5GPU_OK;
 }
 
@@ -236,6 +227,6 @@ int fsk::launch_accum(const sigk::SigRecs &R, s5gpu_file_stats_t *acc, hipStream
     const Opts O = g_opts;
     const uint32_t grid = R.n < g_grid ? R.n : g_grid;                    // by default four resident workgroups per CU: the tables are emptied once per workgroup
     hipLaunchKernelGGL(k_file_stats, dim3(grid), dim3(NT), (size_t)O.bins * COPIES * sizeof(uint32_t), st, R, O, acc);
-    FS_LAUNCH_CHECK("k_file_stats");
+    S5_LAUNCH_CHECK("k_file_stats");
     return S5GPU_OK;
 }

@@ -52,7 +52,7 @@ struct DevState {
 static DevState g_dev[MAX_DEV];
 static int g_ndev = 0;
 static uint32_t g_multi_min = 1024;   // records per device below which a host batch is not split over devices
-uint32_t s5host_generation = 1;       // bumped by s5gpu_shutdown: per-thread helper streams of kernels.hip are stale after it
+uint32_t s5host_generation = 1;       // bumped by s5gpu_shutdown: the helper streams of decode_kernels.hip are stale after it
 
 static int init_devices_locked(const int *phys, int count) {
     int n = 0;
@@ -230,8 +230,8 @@ int s5host::for_each_device_range(uint32_t n, const std::function<int(int, uint3
 }
 
 using s5host::encode_and_collect;
-void s5kern_release_aux();   // kernels.hip
-void s5kern_release_order();
+void s5kern_release_aux();     // decode_kernels.hip
+void s5kern_release_order();   // order_launch.hip
 
 void s5host_stop_ticket_workers();
 extern "C" void s5gpu_shutdown(void) {
@@ -295,7 +295,7 @@ int s5host::encode_stream_resident(Ctx *c, uint32_t n, const std::vector<s5gpu_r
     // First choice: ordered single-pass output — records land in the contiguous stream directly.  It needs every read
     // to fit the LDS budget of the fused kernel; if the device reports otherwise, the slot path below redoes the batch.
     // (signal press none goes through the LZ77 matcher of the slot path instead: see s5gpu_encode_dev)
-    if (a.rec_method == S5GPU_REC_ZLIB && a.sig_method != S5GPU_SIG_NONE && (uint64_t)a.max_payload * 100 / (a.sig_method == S5GPU_SIG_EX_ZD ? 950 : 325) <= 16384) {
+    if (a.rec_method == S5GPU_REC_ZLIB && a.sig_method != S5GPU_SIG_NONE && (uint64_t)a.max_payload * 100 / s5plan::sig_rule(a.sig_method).bound <= s5plan::BLK) {
         const size_t scan_bytes = 8ull * (n + 1) + 8ull * n + 16;
         if ((rc = c->d_stream.reserve(slots_bytes + 64)) || (rc = c->d_scan.reserve(scan_bytes)) ||
             (rc = c->h_out.reserve(up(scan_bytes, 64) + 64)))
@@ -1022,12 +1022,7 @@ int s5host::decode_np_framed(Ctx *c, const char *who, uint32_t n, const uint8_t 
             max_cap = max_cap > pcap[i] ? max_cap : pcap[i];
         }
         // scratch: a slot per workgroup the decoder can use; more slots than records (and its fallback's) buy nothing
-        const uint64_t slot = ((uint64_t)max_cap + 16 + 15) & ~15ull;
-        uint64_t scratch = s5gpu_decode_scratch_bytes(max_cap);
-        const uint64_t enough = 64 + slot * ((uint64_t)n + 257), floor_ = 64 + 2 * slot, ceil_ = 1ull << 30;
-        if (scratch > enough) scratch = enough;
-        if (scratch > ceil_) scratch = ceil_;
-        if (scratch < floor_) scratch = floor_;
+        const uint64_t scratch = s5plan::np_scratch_for(s5gpu_decode_scratch_bytes(max_cap), max_cap, n);
         if ((rc = c->d_pay.reserve(scratch)) || (rc = c->d_sig2.reserve(so * 2 + 64))) return rc;
         memcpy(c->h_in.p, rd.data(), sizeof(s5gpu_rec_desc_t) * n);
         HIP_TRY(hipMemcpyAsync(c->d_desc2.p, c->h_in.p, sizeof(s5gpu_rec_desc_t) * n, hipMemcpyHostToDevice, c->st));

@@ -1,12 +1,6 @@
 // host_ctx.h — shared by every host-side translation unit of libslow5gpu.so (the *_api.hip files): error macro, grow-only workspaces, the
 // per-process context, the threaded host loop, and the resident-decode front of the analysis calls (defined in host_api.hip).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -14,21 +8,11 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/slow5gpu.h"
+#include "launch_common.h"
 #include "resident_rules.h"
 #include "signal_dev.h"
 
-extern "C" void s5gpu_set_error(const char *fmt, ...);
 extern "C" const char *s5gpu_last_error(void);
-
-#define HIP_TRY(x)                                                                                   \
-    do {                                                                                             \
-        hipError_t e_ = (x);                                                                         \
-        if (e_ != hipSuccess) {                                                                      \
-            s5gpu_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return S5GPU_ERR_HIP;                                                                    \
-        }                                                                                            \
-    } while (0)
 
 // Pinned host memory: never less than S5_PIN_MIN bytes at a time, one host thread inside the allocator at a time (host_api.hip).
 // Round 5: a SMALL pinned buffer (4.9 KB: the stream encoder's offsets) that a worker thread allocated while another worker was in its
@@ -225,25 +209,11 @@ struct ShareGather {
 }  // namespace s5host
 
 // k_qts_round over n records in order: sig_off (u64) of record i at sig_off + i * off_stride, n_samples (u32) at n_samples + i * len_stride,
-// all on the device (kernels.hip; s5gpu_qts_round_dev is its plain-array form)
+// all on the device (batch_kernels.hip; s5gpu_qts_round_dev is its plain-array form)
 int s5_qts_round_strided(int16_t *sig, uint32_t n, const void *sig_off, uint32_t off_stride, const void *n_samples, uint32_t len_stride,
                          uint32_t bits, hipStream_t st);
 
 static inline uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
-// S5GPU_TRACE=1 (tools): milliseconds since the calling thread's previous trace point, to stderr — where a chunk call's time goes
-#include <time.h>
-static inline void s5_trace(const char *what) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("S5GPU_TRACE"); on = e && atoi(e) ? 1 : 0; }
-    if (!on) return;
-    static thread_local double last = 0;
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    const double now = (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-    fprintf(stderr, "s5gpu[trace] %p +%8.3f ms  %s\n", (void *)&last, last ? 1e3 * (now - last) : 0.0, what);
-    last = now;
-}
 
 // host-side packing / unpacking of a batch is plain memcpy work: spread it over a few threads
 template <class F>

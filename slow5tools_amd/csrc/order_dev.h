@@ -3,7 +3,7 @@
 // One wave (or lane) decodes one record, so a batch ends when its longest record does — and a record of 300 k samples takes a wave ~15 ms however
 // idle the rest of the device is.  In file order it starts wherever it happens to stand: 262 144 records with the read lengths of a real
 // run decode in 23.7 ms, 16.6 ms with the longest first (tools/mixed_lengths.py: the rate per sample of a batch of equal reads).  Four lists
-// are built this way, all in the library's per-(device, stream) scratch (kernels.hip: order_scratch):
+// are built this way, all in the library's per-(device, stream) scratch (order_launch.hip: order_scratch):
 //   * the launch order of the wave-per-record decoders (round 3): records by compressed length;
 //   * the overflow list of a mixed ENCODE batch (round 4: the reads the staged kernels redo) by number of samples — a 300 k-sample read keeps
 //     one workgroup busy for most of a millisecond, and in list order (the order in which the fused kernel's workgroups happened to give
@@ -36,7 +36,7 @@ __device__ __forceinline__ uint32_t ovf_at(const uint32_t *ovf, const uint32_t *
     return ord && !ord[ORD_FLAG] ? ord[ORD_LIST + it] : ovf[1 + it];
 }
 
-// (a translation unit that only READS a list defines S5_ORDER_LIST_ONLY: the sort's kernels below live in kernels.hip alone)
+// (a translation unit that only READS a list defines S5_ORDER_LIST_ONLY: the sort's kernels below live in order_launch.hip alone)
 #ifndef S5_ORDER_LIST_ONLY
 // What is sorted: for grid index i, is there an item, which id goes on the list, and how long is it.
 struct OrderByInLen {            // the records of a decode batch by compressed length

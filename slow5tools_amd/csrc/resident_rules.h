@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/slow5gpu.h"
+#include "dec_plan.h"
 
 extern "C" void s5gpu_set_error(const char *fmt, ...);
 
@@ -17,11 +18,8 @@ inline bool methods_ok(int rec_method, int sig_method) {
     return (rec_method == S5GPU_REC_NONE || rec_method == S5GPU_REC_ZLIB || rec_method == S5GPU_REC_ZSTD) && sig_method_ok(sig_method);
 }
 
-// the decoders that keep no payload (S5GPU_DEC_NO_PAYLOAD): zlib / zstd + svb-zd and zlib + ex-zd; every other pair is decoded in full
-inline bool decodes_without_payload(int rec_method, int sig_method) {
-    return (sig_method == S5GPU_SIG_SVB_ZD && (rec_method == S5GPU_REC_ZLIB || rec_method == S5GPU_REC_ZSTD)) ||
-           (sig_method == S5GPU_SIG_EX_ZD && rec_method == S5GPU_REC_ZLIB);
-}
+// the decoders that keep no payload (S5GPU_DEC_NO_PAYLOAD; the pairs are dec_plan.h's); every other pair is decoded in full
+inline bool decodes_without_payload(int rec_method, int sig_method) { return s5plan::np_served(rec_method, sig_method); }
 
 // Every item [pos[i], pos[i] + len[i]) lies inside the chunk, or S5GPU_ERR_ARG and a message that names who, the noun and i.  [*b0, *e1) is the
 // part of the chunk the items span, b0 rounded down to 16 bytes (the alignment the decoders' loads want); n = 0: an empty span at 0.

@@ -321,20 +321,11 @@ __global__ __launch_bounds__(NT) void k_sig_windows(sigk::SigRecs R, sigk::WinAr
     }
 }
 
-#define SIG_LAUNCH_CHECK(what)                                                            \
-    do {                                                                                  \
-        hipError_t e_ = hipGetLastError();                                                \
-        if (e_ != hipSuccess) {                                                           \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));         \
-            return S5GPU_ERR_HIP;                                                         \
-        }                                                                                 \
-    } while (0)
-
 int sigk::launch_stats(const SigRecs &R, const Quantiles &Q, s5gpu_sig_stats_t *stats, hipStream_t st) {
     if (R.n == 0) return S5GPU_OK;
     const uint32_t grid = R.n < 8192u ? R.n : 8192u;                  // eight workgroups per CU and a few rounds of them: reads vary in length
     hipLaunchKernelGGL(k_sig_stats, dim3(grid), dim3(NT), 0, st, R, Q, stats);
-    SIG_LAUNCH_CHECK("k_sig_stats");
+    S5_LAUNCH_CHECK("k_sig_stats");
     return S5GPU_OK;
 }
 
@@ -346,6 +337,6 @@ int sigk::launch_windows(const SigRecs &R, const WinArgs &A, int dtype, hipStrea
     const bool dbl = A.mode == S5GPU_NORM_PA || A.mode == S5GPU_NORM_QUANT, half = dtype == S5GPU_SIG_F16;
     if (dbl) { if (half) hipLaunchKernelGGL((k_sig_windows<true, true>), grid, block, 0, st, R, A); else hipLaunchKernelGGL((k_sig_windows<true, false>), grid, block, 0, st, R, A); }
     else { if (half) hipLaunchKernelGGL((k_sig_windows<false, true>), grid, block, 0, st, R, A); else hipLaunchKernelGGL((k_sig_windows<false, false>), grid, block, 0, st, R, A); }
-    SIG_LAUNCH_CHECK("k_sig_windows");
+    S5_LAUNCH_CHECK("k_sig_windows");
     return S5GPU_OK;
 }

@@ -291,5 +291,5 @@ int s5_skim_measure(const skim::SkimArgs &a, hipStream_t st);
 int s5_skim_write(const skim::SkimArgs &a, hipStream_t st);
 // len[host_idx[j]] = host_len[j] for the n_host host-printed lines (before the scan)
 int s5_skim_patch_len(uint32_t *len, uint32_t n_host, const uint32_t *host_idx, const uint32_t *host_len, hipStream_t st);
-// off[i] = len[0] + ... + len[i-1], off[n] = the total (kernels.hip: the scan of s5gpu_compact_dev); tmp: 8 * (n / 1024 + 2) bytes
+// off[i] = len[0] + ... + len[i-1], off[n] = the total (batch_kernels.hip: the scan of s5gpu_compact_dev); tmp: 8 * (n / 1024 + 2) bytes
 int s5_scan_lengths(const uint32_t *len, uint32_t n, uint64_t *off, uint64_t *tmp, hipStream_t st);

@@ -2,8 +2,9 @@
 //
 // One lane per record: every record of a file has the same fields in the same order (the header's), so the lanes of a wave walk the
 // same role list and stay together; what differs — id length, digits, string lengths — is a few bytes.  Pass 1 measures each line,
-// an exclusive scan of the lengths (the record-stream scan of kernels.hip) places them back to back, pass 2 writes them there, gathered
+// an exclusive scan of the lengths (the record-stream scan of batch_kernels.hip) places them back to back, pass 2 writes them there, gathered
 // into aligned 8-byte stores.  The signal is never decoded: its sample count sits in the blob's first bytes (skim_dev.h).
+#include "dev_common.h"
 #include "skim_dev.h"
 
 extern "C" void s5gpu_set_error(const char *fmt, ...);
@@ -69,30 +70,21 @@ __global__ void k_skim_patch_len(uint32_t *len, uint32_t n_host, const uint32_t 
 
 }  // namespace
 
-#define SKIM_LAUNCH_CHECK(what)                                                          \
-    do {                                                                                 \
-        const hipError_t e_ = hipGetLastError();                                         \
-        if (e_ != hipSuccess) {                                                          \
-            s5gpu_set_error("%s launch failed: %s", what, hipGetErrorString(e_));        \
-            return S5GPU_ERR_HIP;                                                        \
-        }                                                                                \
-    } while (0)
-
 int s5_skim_measure(const skim::SkimArgs &a, hipStream_t st) {
     if (a.n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_skim_format_measure, dim3((a.n + SKIM_NT - 1) / SKIM_NT), dim3(SKIM_NT), 0, st, a);
-    SKIM_LAUNCH_CHECK("k_skim_format (measure)");
+    S5_LAUNCH_CHECK("k_skim_format (measure)");
     return S5GPU_OK;
 }
 int s5_skim_write(const skim::SkimArgs &a, hipStream_t st) {
     if (a.n == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_skim_format_write, dim3((a.n + SKIM_NT - 1) / SKIM_NT), dim3(SKIM_NT), 0, st, a);
-    SKIM_LAUNCH_CHECK("k_skim_format (write)");
+    S5_LAUNCH_CHECK("k_skim_format (write)");
     return S5GPU_OK;
 }
 int s5_skim_patch_len(uint32_t *len, uint32_t n_host, const uint32_t *host_idx, const uint32_t *host_len, hipStream_t st) {
     if (n_host == 0) return S5GPU_OK;
     hipLaunchKernelGGL(k_skim_patch_len, dim3((n_host + 255) / 256), dim3(256), 0, st, len, n_host, host_idx, host_len);
-    SKIM_LAUNCH_CHECK("k_skim_patch_len");
+    S5_LAUNCH_CHECK("k_skim_patch_len");
     return S5GPU_OK;
 }

@@ -6,5 +6,9 @@ name=$1; shift
 V=slow5tools_amd/_variants
 mkdir -p $V
 C=slow5tools_amd/csrc
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-sched-strategy=max-memory-clause "$@" -c $C/kernels.hip -o $V/kernels_$name.o || exit 1
-hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libs5_$name.so $V/kernels_$name.o $C/host_api.o $C/ascii_kernels.o $C/ascii_api.o $C/slow5_compat.o $C/blow5_file.o && ls -la $V/libs5_$name.so
+objs=
+for u in encode_kernels decode_kernels batch_kernels order_launch; do   # the -D flags reach all four units of the press path
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-sched-strategy=max-memory-clause "$@" -c $C/$u.hip -o $V/${u}_$name.o || exit 1
+    objs="$objs $V/${u}_$name.o"
+done
+hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libs5_$name.so $objs $C/host_api.o $C/ascii_kernels.o $C/ascii_api.o $C/slow5_compat.o $C/blow5_file.o && ls -la $V/libs5_$name.so

@@ -6,6 +6,10 @@ name=$1; shift
 V=slow5tools_amd/_variants
 mkdir -p $V
 C=slow5tools_amd/csrc
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $C/kernels.hip -o $V/kernels_$name.o || exit 1
-hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libs5_$name.so $V/kernels_$name.o $C/host_api.o $C/ascii_kernels.o $C/ascii_api.o $C/slow5_compat.o $C/blow5_file.o && ls -la $V/libs5_$name.so
-rm -f $V/kernels_$name.o
+objs=
+for u in encode_kernels decode_kernels batch_kernels order_launch; do   # the flags reach all four units of the press path
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $C/$u.hip -o $V/${u}_$name.o || exit 1
+    objs="$objs $V/${u}_$name.o"
+done
+hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libs5_$name.so $objs $C/host_api.o $C/ascii_kernels.o $C/ascii_api.o $C/slow5_compat.o $C/blow5_file.o && ls -la $V/libs5_$name.so
+rm -f $objs
