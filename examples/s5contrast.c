@@ -15,6 +15,12 @@
  *   --refine [--iters N] [--slope LO,HI]: every read of both files is first put into the reference's units by the rounds of
  *   s5extend --refine (docs/codecs.md §4.24; s5gpu_contrast_set_refine): a per-read scale error no longer shows as a level difference.  A
  *   read whose fit is refused is left out and counts as skipped; how many there were goes to stderr behind each file's totals.
+ *   s5contrast ... --fasta ref.fa --model kmer.model [--fwd-only] [--by-kmer] a.blow5 b.blow5 : the reference is made from the sequences and
+ *   the k-mer level table as in s5map --fasta (no ref.txt then); ref_pos is the reference column.  --by-kmer (docs/codecs.md §4.26): both
+ *   files' tables and histograms are folded onto the 4^k k-mers on the GPU before they are compared (s5gpu_contrast_close_folded), one line
+ *   per k-mer in rank order, the same thirteen columns: the k-mer stands where ref_pos stood and the table's quantised level for it where
+ *   ref_level stood; depth and events are the sums over the columns that show the k-mer.  A shift that no single position has the depth
+ *   to show can show here.
  *   Exit 0; 1 when a record is corrupt (its file and number go to stderr; the other reads are counted); 2 on any other error.
  *
  * One handle (s5gpu_contrast_open), one s5gpu_contrast_add_batch per K records (default 4096) of a.blow5, then of b.blow5, and one
@@ -64,8 +70,8 @@ int main(int argc, char **argv) {
     long K = 4096, skip = 0, qmax = 250, qmin = 50, min_depth = 1, tile = 256, band = 512, emax = 1l << 20, q0 = -128, shift = 2;
     long iters = 2;
     double a_lo = 0.5, a_hi = 2.0;
-    int rna = 0, bad = 0, refine = 0;
-    const char *ref_path = NULL, *path[2] = {NULL, NULL};
+    int rna = 0, bad = 0, refine = 0, fwd_only = 0, by_kmer = 0;
+    const char *ref_path = NULL, *path[2] = {NULL, NULL}, *fasta = NULL, *model = NULL;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "-K") && i + 1 < argc) K = atol(argv[++i]);
         else if (!strcmp(argv[i], "--skip") && i + 1 < argc) skip = atol(argv[++i]);
@@ -81,6 +87,10 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--refine")) refine = 1;
         else if (!strcmp(argv[i], "--iters") && i + 1 < argc) iters = atol(argv[++i]);
         else if (!strcmp(argv[i], "--slope") && i + 1 < argc) { if (sscanf(argv[++i], "%lf,%lf", &a_lo, &a_hi) != 2) bad = 1; }
+        else if (!strcmp(argv[i], "--fasta") && i + 1 < argc) fasta = argv[++i];
+        else if (!strcmp(argv[i], "--model") && i + 1 < argc) model = argv[++i];
+        else if (!strcmp(argv[i], "--fwd-only")) fwd_only = 1;
+        else if (!strcmp(argv[i], "--by-kmer")) by_kmer = 1;
         else if (argv[i][0] != '-' && !ref_path) ref_path = argv[i];
         else if (argv[i][0] != '-' && !path[0]) path[0] = argv[i];
         else if (argv[i][0] != '-' && !path[1]) path[1] = argv[i];
@@ -90,6 +100,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "s5contrast: --iters N (1 .. 4), --slope LO,HI (0 < LO <= HI)\n");
         return EXIT_ERROR;
     }
+    if (fasta || model) {                                                  /* the reference is made here: the two positional arguments are the files */
+        if (!fasta || !model || path[1]) bad = 1;
+        path[1] = path[0]; path[0] = ref_path; ref_path = NULL;
+    } else if (fwd_only || by_kmer) bad = 1;
     if (tile != 64 && tile != 128 && tile != 256 && tile != 512 && tile != 1024) bad = 1;
     if (band < 64 || band > 4096 || band % 64 || emax < qmin || emax > (1l << 20)) bad = 1;
     if (q0 < -32768 || q0 > 32767 || shift < 0 || shift > 10) bad = 1;
@@ -98,24 +112,52 @@ int main(int argc, char **argv) {
         fprintf(stderr, "usage: s5contrast [-K batch] [--rna] [--skip S] [--events Q (1 .. 1024)] [--min-events M (1 .. Q)] [--tile T (64, 128, 256, 512, 1024)]\n"
                         "                  [--band B (a multiple of 64 in 64 .. 4096)] [--max-events N (M .. 2^20)] [--min-depth D (>= 1)]\n"
                         "                  [--q0 V (-32768 .. 32767)] [--shift S (0 .. 10)]\n"
-                        "                  [--refine [--iters N (1 .. 4)] [--slope LO,HI (0 < LO <= HI)]] ref.txt a.blow5 b.blow5\n");
+                        "                  [--refine [--iters N (1 .. 4)] [--slope LO,HI (0 < LO <= HI)]] ref.txt a.blow5 b.blow5\n"
+                        "       s5contrast [...] --fasta ref.fa --model kmer.model [--fwd-only] [--by-kmer] a.blow5 b.blow5\n");
         return EXIT_ERROR;
     }
     const s5gpu_map_params_t M = {(uint32_t)skip, (uint32_t)qmax, (uint32_t)qmin, 32.0, 127, 1};
     size_t R = 0;
-    float *levels = read_reference(ref_path, 1u << 22, "too many numbers (at most 2^22)", &R);
-    if (!levels) return EXIT_ERROR;
-    int16_t *ref = (int16_t *)malloc(sizeof(int16_t) * R);
-    if (!ref) return die("out of memory");
-    if (s5gpu_quantise_host(levels, R, M.scale, M.clip, ref) != S5GPU_OK) return die("the reference cannot be quantised");
-    free(levels);
+    int16_t *ref = NULL;
+    void *rs = NULL;
+    if (fasta) {
+        rs = s5gpu_refseq_open(fasta, model, fwd_only ? 1 : 2, rna, M.scale, M.clip);
+        if (!rs) return die("no reference from the sequences and the model");
+        uint32_t R32 = 0;
+        const int16_t *r = s5gpu_refseq_ref(rs, &R32);
+        if (R32 > (1u << 22)) return die("the reference has more than 2^22 columns");
+        R = R32;
+        ref = (int16_t *)malloc(sizeof(int16_t) * R);
+        if (!ref) return die("out of memory");
+        memcpy(ref, r, sizeof(int16_t) * R);
+    } else {
+        float *levels = read_reference(ref_path, 1u << 22, "too many numbers (at most 2^22)", &R);
+        if (!levels) return EXIT_ERROR;
+        ref = (int16_t *)malloc(sizeof(int16_t) * R);
+        if (!ref) return die("out of memory");
+        if (s5gpu_quantise_host(levels, R, M.scale, M.clip, ref) != S5GPU_OK) return die("the reference cannot be quantised");
+        free(levels);
+    }
+    /* --by-kmer: a class per column, and what is printed has a row per class */
+    uint32_t n4 = 0, kk = 0, *cls = NULL;
+    int16_t *kmer_q = NULL;
+    if (by_kmer) {
+        cls = (uint32_t *)malloc(sizeof(uint32_t) * R);
+        if (!cls) return die("out of memory");
+        if (s5gpu_refseq_classes(rs, cls, &n4) != S5GPU_OK || s5gpu_refseq_params(rs, &kk, NULL, NULL) != S5GPU_OK) return die("the reference has no classes");
+        kmer_q = (int16_t *)calloc(n4, sizeof(int16_t));                     /* the quantised level of a k-mer: that of any column that shows it */
+        if (!kmer_q) return die("out of memory");
+        for (size_t j = 0; j < R; j++)
+            if (cls[j] < n4) kmer_q[cls[j]] = ref[j];
+    }
+    const size_t N = by_kmer ? n4 : R;                                     /* the rows that come back */
     if (s5gpu_init(0) != S5GPU_OK) return die("no GPU");
     const s5gpu_band_params_t B = {(uint32_t)skip, (uint32_t)qmin, (uint32_t)emax, (uint32_t)tile, (uint32_t)band, M.clip, M.scale};
     big_stdout();
 
     int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)K);
-    uint8_t *acc[2] = {(uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R)), (uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)R))};
-    s5gpu_pile_contrast_t *rows = (s5gpu_pile_contrast_t *)malloc(sizeof *rows * R);
+    uint8_t *acc[2] = {(uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)N)), (uint8_t *)malloc(s5gpu_pileup_bytes((uint32_t)N))};
+    s5gpu_pile_contrast_t *rows = (s5gpu_pile_contrast_t *)malloc(sizeof *rows * N);
     if (!st || !acc[0] || !acc[1] || !rows) return die("out of memory");
     void *h = s5gpu_contrast_open(event_params(rna), &M, &B, 0, ref, (uint32_t)R, (int32_t)q0, (uint32_t)shift);
     if (!h) return die("the tables cannot be opened");
@@ -128,12 +170,22 @@ int main(int argc, char **argv) {
         if (c == EXIT_ERROR) return EXIT_ERROR;
         if (c) code = c;
     }
-    if (s5gpu_contrast_close(h, acc[0], acc[1], rows) != S5GPU_OK) return die("the rows cannot be fetched");
+    if ((by_kmer ? s5gpu_contrast_close_folded(h, cls, n4, acc[0], acc[1], rows) : s5gpu_contrast_close(h, acc[0], acc[1], rows)) != S5GPU_OK)
+        return die("the rows cannot be fetched");
     const s5gpu_pile_col_t *ca = (const s5gpu_pile_col_t *)(acc[0] + sizeof(s5gpu_pile_total_t)), *cb = (const s5gpu_pile_col_t *)(acc[1] + sizeof(s5gpu_pile_total_t));
-    for (size_t j = 0; j < R; j++) {
+    for (size_t j = 0; j < N; j++) {
         const s5gpu_pile_contrast_t *r = &rows[j];
         if (r->depth_a < (uint64_t)min_depth || r->depth_b < (uint64_t)min_depth) continue;
         const double nn = (double)r->n_a * (double)r->n_b;
+        if (by_kmer) {
+            char kmer[16];
+            for (uint32_t b = 0; b < kk; b++) kmer[b] = "ACGT"[(j >> (2 * (kk - 1 - b))) & 3u];
+            kmer[kk] = 0;
+            printf("%s\t%d\t%u\t%u\t%u\t%u\t%.6g\t%.6g\t%.6g\t%ld\t%.6g\t%ld\t%ld\n", kmer, (int)kmer_q[j], r->depth_a, r->depth_b, ca[j].n_events, cb[j].n_events,
+                   (double)ca[j].sum_q / (double)ca[j].n_events, (double)cb[j].sum_q / (double)cb[j].n_events, (double)r->ks_num / nn, q0 + ((long)r->ks_bin << shift),
+                   1.0 - (double)r->ov_num / nn, q0 + ((long)r->med_a << shift), q0 + ((long)r->med_b << shift));
+            continue;
+        }
         printf("%zu\t%d\t%u\t%u\t%u\t%u\t%.6g\t%.6g\t%.6g\t%ld\t%.6g\t%ld\t%ld\n", j, (int)ref[j], r->depth_a, r->depth_b, ca[j].n_events, cb[j].n_events,
                (double)ca[j].sum_q / (double)ca[j].n_events, (double)cb[j].sum_q / (double)cb[j].n_events, (double)r->ks_num / nn, q0 + ((long)r->ks_bin << shift),
                1.0 - (double)r->ov_num / nn, q0 + ((long)r->med_a << shift), q0 + ((long)r->med_b << shift));
@@ -145,6 +197,7 @@ int main(int argc, char **argv) {
         if (refine) fprintf(stderr, "s5contrast: %s: reads refused by the fit %" PRIu64 " (they count as skipped)\n", path[side], n_refused[side]);
     }
     if (fflush(stdout) != 0 || ferror(stdout)) { fprintf(stderr, "s5contrast: write failed\n"); return EXIT_ERROR; }
-    free(st); free(acc[0]); free(acc[1]); free(rows); free(ref);
+    free(st); free(acc[0]); free(acc[1]); free(rows); free(ref); free(cls); free(kmer_q);
+    if (rs) s5gpu_refseq_close(rs);
     return code;
 }

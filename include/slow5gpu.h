@@ -1256,6 +1256,62 @@ int s5gpu_sites_add_batch(void *handle, uint32_t n, const void *const *rec, cons
 /* Downloads the control histogram to hist_out where not NULL (HOST memory, s5gpu_pile_hist_bytes(R)) and ends the handle, whatever it returns. */
 int s5gpu_sites_close(void *handle, void *hist_out);
 
+/* ---- model: the pileup folded onto k-mers, and a level table re-estimated from it (docs/codecs.md §4.26) ----
+ * A fold adds the columns of a table of "pileup", or of a histogram of "contrast", that share a class: cls[j] is the class of input column
+ * j, and column j is KEPT iff cls[j] < K.  Every member of output column c is the sum over the kept j with cls[j] = c (min_q and max_q the
+ * minimum and maximum over those j that are not empty), so the result is an ordinary table (histogram) of K columns: to_host, the line
+ * printers and s5gpu_pile_contrast_dev take it as it stands.  The head's reads are the input's; its cells and cost are the sums over the
+ * kept columns only, so cells = sum of n_events and cost = sum of sum_cost hold on the output.  All integer: the bytes do not depend on
+ * the launch shape or on the order of the adds. */
+#define S5GPU_FOLD_NONE 0xFFFFFFFFu    /* cls[j]: the column belongs to no class (any value >= K is dropped the same way) */
+#define S5GPU_FOLD_REFUSED 1u          /* reserved[0] of the output's head: a fold added nothing (see below) */
+/* the mean and the standard deviation "quant" takes of m[0 .. L) (double, left to right): with scale they invert s5gpu_quantise_host.
+ * S5GPU_ERR_ARG: a NULL pointer or L = 0. */
+int s5gpu_quant_stats_host(const float *m, size_t L, double *mu_out, double *sd_out);
+/* One class per column of a reference of s5gpu_refseq_build / _open, cls_out[0 .. R): the base-4 rank of the k-mer the column shows, which
+ * is the rank whose model level the column took -- on a forward segment, on a reverse-complement segment (the k-mer of the reverse-
+ * complement sequence) and under the RNA rule (the columns are reversed, the ranks are not); S5GPU_FOLD_NONE for a wall column and for a
+ * k-mer that holds a letter other than ACGT.  *K_out = 4^k.  Either output may be NULL. */
+int s5gpu_refseq_classes(const void *h, uint32_t *cls_out, uint32_t *K_out);
+/* mu and sd of the levels of all segments together, as the reference's quantiser took them, and its scale: a quantised level q stands for
+ * mu + (sd / scale) q.  Any output may be NULL. */
+int s5gpu_refseq_quant(const void *h, double *mu_out, double *sd_out, double *scale_out);
+/* Adds the fold of acc_in (R columns) to acc_out, which s5gpu_pileup_reset_dev wrote for K columns; cls[0 .. R) and both tables DEVICE
+ * memory.  Asynchronous on hip_stream.  The fold ADDS: several inputs may go into one output.  depth and n_events are 32-bit: the kernel
+ * reads the input's total cells, and where that is 2^32 or more (or a head's R is not the R or K of the call) it adds nothing and sets
+ * S5GPU_FOLD_REFUSED; otherwise every sum of this call fits.  The caller answers for the sums over several calls into one output.
+ * S5GPU_ERR_ARG (nothing launched): a NULL or misaligned pointer (tables: 16 bytes; cls: 4), R or K outside 1 .. 2^26, acc_out = acc_in.
+ * s5gpu_set_option (tests, tools): "pile_fold_lds" (0 / 1): for K <= 1024 a workgroup keeps the whole class table in LDS and adds its
+ * non-empty classes to the output at its end (1), or every merge is a global atomic (0); "pile_fold_grid" (1 .. 1024): the most
+ * workgroups of a launch.  Neither changes the result. */
+int s5gpu_pileup_fold_dev(const void *acc_in, uint32_t R, const uint32_t *cls, uint32_t K, void *acc_out, void *hip_stream);
+/* The same for a histogram of "contrast": hist_out was written by s5gpu_pile_hist_reset_dev for K columns.  q0, shift and bins of the two
+ * heads are compared on the device: where they disagree, or the input's cells are 2^32 or more, nothing is added and S5GPU_FOLD_REFUSED is
+ * set in reserved[0] of hist_out's head.  S5GPU_ERR_ARG as above, with R and K in 1 .. 2^22. */
+int s5gpu_pile_hist_fold_dev(const void *hist_in, uint32_t R, const uint32_t *cls, uint32_t K, void *hist_out, void *hip_stream);
+/* s5gpu_pileup_close for a handle of either kind, folded: cls_host[0 .. R) (HOST memory) is uploaded, the table folded onto K columns
+ * on the device, and 64 + 48 K bytes come to acc_out (HOST memory).  Ends the handle, whatever it returns. */
+int s5gpu_pileup_close_folded(void *handle, const uint32_t *cls_host, uint32_t K, void *acc_out);
+/* s5gpu_contrast_close, folded: both sides' table and histogram folded onto K columns, s5gpu_pile_contrast_dev over the K rows; rows_out
+ * [K], acc_a_out and acc_b_out (64 + 48 K bytes each, may be NULL).  Ends the handle, whatever it returns. */
+int s5gpu_contrast_close_folded(void *handle, const uint32_t *cls_host, uint32_t K, void *acc_a_out, void *acc_b_out,
+                                s5gpu_pile_contrast_t *rows_out);
+typedef struct s5gpu_kmer_row {    /* 40 bytes: a k-mer of a re-estimated table */
+    double level, stdv;            /* in the units of the table that made the reference */
+    double dwell;                  /* n_samples / cells: samples per event (0 when no event lengths were given) */
+    uint32_t cells;                /* n_events of the class */
+    uint32_t kept;                 /* 1: fewer than min_cells cells; level is levels_in's, stdv and dwell are 0 */
+    uint64_t zero;
+} s5gpu_kmer_row_t;
+/* The estimate, on the host, from a folded table (HOST memory, 64 + 48 K bytes) and s5gpu_refseq_quant's mu, sd and scale.  For a class
+ * with n = n_events >= min_cells: mean_q = sum_q / n, var_q = max(0, sumsq_q / n - mean_q^2), level = mu + (sd / scale) mean_q,
+ * stdv = (sd / scale) sqrt(var_q), dwell = n_samples / n; double, left to right, without contraction.  A class below min_cells keeps
+ * levels_in[c] (kept = 1).  Two limits: queries are clamped to +-clip, so a k-mer whose level lies near +-clip / scale standard deviations
+ * is biased inwards; and the estimate is in the units of the table that made the reference, so a round changes the table's shape, not
+ * its overall scale.  S5GPU_ERR_ARG: a NULL pointer, K = 0, a head whose R is not K, sd or scale not finite or <= 0. */
+int s5gpu_kmer_model_solve(const void *acc_folded, uint32_t K, double mu, double sd, double scale, uint32_t min_cells, const float *levels_in,
+                           s5gpu_kmer_row_t *rows_out);
+
 #ifdef __cplusplus
 }
 #endif

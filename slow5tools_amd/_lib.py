@@ -135,6 +135,10 @@ assert PileHistHead.itemsize == 64 and PileContrast.itemsize == 40
 SiteCell = np.dtype([("sum_q", "<i8"), ("cells", "<u4"), ("row0", "<u4")])
 SiteScore = np.dtype([("level", "<i2"), ("flags", "<u2"), ("below", "<u4"), ("above", "<u4"), ("n", "<u4")])
 assert SiteCell.itemsize == 16 and SiteScore.itemsize == 16
+# s5gpu_kmer_row_t: a k-mer of a re-estimated level table (slow5tools_amd/model.py)
+KmerRow = np.dtype([("level", "<f8"), ("stdv", "<f8"), ("dwell", "<f8"), ("cells", "<u4"), ("kept", "<u4"), ("zero", "<u8")])
+assert KmerRow.itemsize == 40
+FOLD_NONE, FOLD_REFUSED = 0xFFFFFFFF, 1
 STATUS_FIT_FLAT, STATUS_FIT_RANGE = 21, 22
 # s5gpu_fit_t: the fit of "refine" (slow5tools_amd/refine.py)
 Fit = np.dtype([("a", "<f8"), ("b", "<f8"), ("n", "<i8"), ("sq", "<i8"), ("sr", "<i8"), ("sqq", "<i8"), ("sqr", "<i8"), ("srr", "<i8")])
@@ -358,6 +362,15 @@ def lib():
     L.s5gpu_sites_set_control.argtypes = [vp, vp]
     L.s5gpu_sites_add_batch.argtypes = [vp, u32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.s5gpu_sites_close.argtypes = [vp, vp]
+    # model: a reference's classes and quantiser, the fold of a table and a histogram onto classes, the folded closes, and the estimate
+    L.s5gpu_quant_stats_host.argtypes = [vp, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.s5gpu_refseq_classes.argtypes = [vp, vp, C.POINTER(u32)]
+    L.s5gpu_refseq_quant.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.s5gpu_pileup_fold_dev.argtypes = [vp, u32, vp, u32, vp, vp]
+    L.s5gpu_pile_hist_fold_dev.argtypes = [vp, u32, vp, u32, vp, vp]
+    L.s5gpu_pileup_close_folded.argtypes = [vp, vp, u32, vp]
+    L.s5gpu_contrast_close_folded.argtypes = [vp, vp, u32, vp, vp, vp]
+    L.s5gpu_kmer_model_solve.argtypes = [vp, u32, C.c_double, C.c_double, C.c_double, u32, vp, vp]
     _LIB = L
     return L
 
@@ -396,4 +409,6 @@ EXPORTS = [
     "s5gpu_pileup_set_refine", "s5gpu_contrast_set_refine",
     "s5gpu_site_cells_long_dev", "s5gpu_site_score_dev", "s5gpu_sites_open", "s5gpu_sites_set_refine", "s5gpu_sites_add_control", "s5gpu_sites_set_control",
     "s5gpu_sites_add_batch", "s5gpu_sites_close",
+    "s5gpu_quant_stats_host", "s5gpu_refseq_classes", "s5gpu_refseq_quant", "s5gpu_pileup_fold_dev", "s5gpu_pile_hist_fold_dev", "s5gpu_pileup_close_folded",
+    "s5gpu_contrast_close_folded", "s5gpu_kmer_model_solve",
 ]

@@ -10,9 +10,9 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libslow5gpu.so")
 S5VIEW = os.path.join(HERE, "s5view")
 
-HIP_SOURCES = ["encode_kernels.hip", "decode_kernels.hip", "batch_kernels.hip", "order_launch.hip", "host_api.hip", "ascii_kernels.hip", "ascii_api.hip", "skim_kernels.hip", "skim_api.hip", "signal_kernels.hip", "signal_api.hip", "digest_kernels.hip", "digest_api.hip", "fstats_kernels.hip", "fstats_api.hip", "diff_kernels.hip", "diff_api.hip", "event_kernels.hip", "event_api.hip", "dtw_kernels.hip", "dtw_api.hip", "dtw_path_kernels.hip", "dtw_path_api.hip", "pileup_kernels.hip", "pileup_api.hip", "refine_kernels.hip", "refine_api.hip", "refine_long_api.hip", "refine_long_kernels.hip", "band_kernels.hip", "band_api.hip", "contrast_kernels.hip", "contrast_api.hip", "sites_kernels.hip", "sites_api.hip"]
+HIP_SOURCES = ["encode_kernels.hip", "decode_kernels.hip", "batch_kernels.hip", "order_launch.hip", "host_api.hip", "ascii_kernels.hip", "ascii_api.hip", "skim_kernels.hip", "skim_api.hip", "signal_kernels.hip", "signal_api.hip", "digest_kernels.hip", "digest_api.hip", "fstats_kernels.hip", "fstats_api.hip", "diff_kernels.hip", "diff_api.hip", "event_kernels.hip", "event_api.hip", "dtw_kernels.hip", "dtw_api.hip", "dtw_path_kernels.hip", "dtw_path_api.hip", "pileup_kernels.hip", "pileup_api.hip", "refine_kernels.hip", "refine_api.hip", "refine_long_api.hip", "refine_long_kernels.hip", "band_kernels.hip", "band_api.hip", "contrast_kernels.hip", "contrast_api.hip", "sites_kernels.hip", "sites_api.hip", "fold_kernels.hip", "fold_api.hip"]
 C_SOURCES = ["slow5_compat.c", "blow5_file.c", "refseq.c"]
-DEPS = ["dev_common.h", "deflate_dev.h", "deflate2_dev.h", "lz_dev.h", "inflate_dev.h", "inflate_simt_dev.h", "inflate_par_dev.h", "svb_dev.h", "exzd_dev.h", "zstd_dev.h", "zstd_enc_dev.h", "host_ctx.h", "skim_dev.h", "signal_dev.h", "digest_dev.h", "fstats_dev.h", "diff_dev.h", "event_dev.h", "dtw_dev.h", "dtw_host.h", "pileup_dev.h", "ragged_dev.h", "pileup_host.h", "sites_dev.h", "refine_dev.h", "refine_host.h", "band_dev.h", "band_host.h", "order_dev.h", "enc_plan.h", "dec_plan.h", "launch_common.h", "resident_rules.h", "event_host.h",
+DEPS = ["dev_common.h", "deflate_dev.h", "deflate2_dev.h", "lz_dev.h", "inflate_dev.h", "inflate_simt_dev.h", "inflate_par_dev.h", "svb_dev.h", "exzd_dev.h", "zstd_dev.h", "zstd_enc_dev.h", "host_ctx.h", "skim_dev.h", "signal_dev.h", "digest_dev.h", "fstats_dev.h", "diff_dev.h", "event_dev.h", "dtw_dev.h", "dtw_host.h", "pileup_dev.h", "ragged_dev.h", "pileup_host.h", "fold_dev.h", "sites_dev.h", "refine_dev.h", "refine_host.h", "band_dev.h", "band_host.h", "order_dev.h", "enc_plan.h", "dec_plan.h", "launch_common.h", "resident_rules.h", "event_host.h",
         os.path.join(ROOT, "include", "slow5gpu.h"), os.path.join(ROOT, "include", "slow5_compat.h"), os.path.join(ROOT, "include", "slow5gpu_hooks.h")]
 
 
@@ -60,9 +60,9 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
-    # the view / get / merge / skim / sum / stats / diff / events / map / align / pileup / refine / extend / contrast / sites loop examples = the end-to-end harnesses (plain C against the public headers)
+    # the view / get / merge / skim / sum / stats / diff / events / map / align / pileup / refine / extend / contrast / sites / model loop examples = the end-to-end harnesses (plain C against the public headers)
     tool_h = os.path.join(ROOT, "examples", "s5tool.h")    # what the tools share: each of them includes it
-    for name in ("s5view", "s5get", "s5merge", "s5skim", "s5sum", "s5stats", "s5diff", "s5events", "s5map", "s5align", "s5pileup", "s5refine", "s5extend", "s5contrast", "s5sites"):
+    for name in ("s5view", "s5get", "s5merge", "s5skim", "s5sum", "s5stats", "s5diff", "s5events", "s5map", "s5align", "s5pileup", "s5refine", "s5extend", "s5contrast", "s5sites", "s5model"):
         ex = os.path.join(ROOT, "examples", name + ".c")
         exe = os.path.join(HERE, name)
         if os.path.exists(ex) and (force or _newer(exe, [ex, tool_h, LIB] + deps)):

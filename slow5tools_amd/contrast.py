@@ -13,7 +13,8 @@ column j's two histograms: D = ks_num / (n_a n_b), total variation = 1 - ov_num 
   hist_to_host        : a histogram tensor -> (head, counts [R, 64])
   contrast_dev        : two histograms (and the two tables) -> a device tensor of rows; rows_to_host views it as CONTRAST_ROW
   contrast_whole_dev  : two DecodedDev -> extend, both accumulates and the comparison; nothing but the rows need come to the host
-  Contrast            : records -> a per-file handle with two sides (s5gpu_contrast_add_batch); close() -> rows and both tables
+  Contrast            : records -> a per-file handle with two sides (s5gpu_contrast_add_batch); close() -> rows and both tables;
+                        close_folded(cls, K) -> the same over K classes, such as k-mers (§4.26, model.py)
   file_contrast       : two .blow5 files and a reference file -> a CONTRAST_LINE array through the s5contrast tool
 """
 import ctypes as C
@@ -217,6 +218,23 @@ class Contrast:
         rows = np.zeros(self.R, dtype=CONTRAST_ROW)
         h, self._h = self._h, None
         check(_lib.lib().s5gpu_contrast_close(h, a.ctypes.data_as(vp), b.ctypes.data_as(vp), rows.ctypes.data_as(vp)), "s5gpu_contrast_close")
+        return rows, _pileup.from_bytes(a), _pileup.from_bytes(b)
+
+    def close_folded(self, cls, K):
+        """close(), with both sides' table and histogram folded onto K classes on the device first and the comparison made over the K rows
+        (s5gpu_contrast_close_folded, §4.26): cls a uint32 class per reference column (RefSeq.classes()).  The handle ends whatever happens."""
+        if self._h is None:
+            raise _lib.S5GpuError("contrast handle: already closed")
+        vp = C.c_void_p
+        c = np.ascontiguousarray(cls, dtype=np.uint32)
+        h, self._h = self._h, None
+        if c.shape != (self.R,) or hist_bytes(K) == 0:
+            _lib.lib().s5gpu_contrast_close(h, None, None, None)
+            raise ValueError("close_folded: cls holds a class per column (%d), K is 1 .. 2^22" % self.R)
+        a, b = (np.zeros(_pileup.acc_bytes(K), dtype=np.uint8) for _ in range(2))
+        rows = np.zeros(int(K), dtype=CONTRAST_ROW)
+        check(_lib.lib().s5gpu_contrast_close_folded(h, c.ctypes.data_as(vp), int(K), a.ctypes.data_as(vp), b.ctypes.data_as(vp), rows.ctypes.data_as(vp)),
+              "s5gpu_contrast_close_folded")
         return rows, _pileup.from_bytes(a), _pileup.from_bytes(b)
 
     def abandon(self):

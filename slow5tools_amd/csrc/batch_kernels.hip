@@ -340,13 +340,15 @@ namespace pilek { int set_option(const char *key, long value); }   // pileup_ker
 namespace pilek { int hist_set_option(const char *key, long value); }   // contrast_kernels.hip: the level histograms' window and grid
 namespace pilek { int site_set_option(const char *key, long value); }   // sites_kernels.hip: which passes the site call launches
 namespace refk { int long_set_option(const char *key, long value); }   // refine_long_kernels.hip: which passes the whole-read refine launches
+namespace pilek { int fold_set_option(const char *key, long value); }   // fold_kernels.hip: the fold's class table in LDS, and its grid
 namespace bandk { int set_option(const char *key, long value); }   // band_kernels.hip: which passes the band call launches
 // every unit owns its options; a key nobody takes, or a value outside its key's range, is unknown
 extern "C" int s5gpu_set_option(const char *key, long value) {
     if (deck::set_option(key, value) == S5GPU_OK || enck::set_option(key, value) == S5GPU_OK || ordk::set_option(key, value) == S5GPU_OK ||
         s5host_set_option(key, value) == S5GPU_OK || fsk::set_option(key, value) == S5GPU_OK || dfk::set_option(key, value) == S5GPU_OK ||
         dtwk::path_set_option(key, value) == S5GPU_OK || pilek::set_option(key, value) == S5GPU_OK || pilek::hist_set_option(key, value) == S5GPU_OK ||
-        pilek::site_set_option(key, value) == S5GPU_OK || refk::long_set_option(key, value) == S5GPU_OK || bandk::set_option(key, value) == S5GPU_OK)
+        pilek::site_set_option(key, value) == S5GPU_OK || refk::long_set_option(key, value) == S5GPU_OK || bandk::set_option(key, value) == S5GPU_OK ||
+        pilek::fold_set_option(key, value) == S5GPU_OK)
         return S5GPU_OK;
     s5gpu_set_error("s5gpu_set_option: unknown option");
     return S5GPU_ERR_ARG;

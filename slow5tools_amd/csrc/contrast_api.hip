@@ -3,6 +3,7 @@
 // s5gpu_pileup_add_batch_whole (pilek::add_batch_whole) into the side's table and histogram, s5gpu_contrast_close runs k_pile_contrast and
 // makes the downloads.
 #include "pileup_host.h"
+#include "fold_dev.h"
 
 namespace {
 
@@ -118,5 +119,47 @@ extern "C" int s5gpu_contrast_close(void *handle, void *acc_a_out, void *acc_b_o
     const int rc = rows_out ? fetch() : S5GPU_OK;
     if (d_rows) (void)hipFree(d_rows);
     free_handle(h);                                                        // whatever the downloads did: the handle ends here
+    return rc;
+}
+
+// §4.26: both sides' table and histogram folded onto K classes on the device, the unchanged k_pile_contrast over the K rows
+extern "C" int s5gpu_contrast_close_folded(void *handle, const uint32_t *cls_host, uint32_t K, void *acc_a_out, void *acc_b_out, s5gpu_pile_contrast_t *rows_out) {
+    const char *who = "s5gpu_contrast_close_folded";
+    Handle *h = (Handle *)handle;
+    if (!h) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
+    const uint32_t R = (uint32_t)h->c.ref.size();
+    void *d_cls = nullptr, *d_rows = nullptr, *d_acc[2] = {nullptr, nullptr}, *d_hist[2] = {nullptr, nullptr};
+    auto fetch = [&]() -> int {
+        if (!cls_host || !rows_out) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+        if (K == 0 || K > pilek::HIST_RMAX) { s5gpu_set_error("%s: %u classes (1 .. 2^22)", who, K); return S5GPU_ERR_ARG; }
+        s5host::CtxHold hold;
+        int r;
+        if ((r = hold.acquire(0))) return r;
+        Ctx *c = hold.c;
+        s5gpu_pile_hist_head_t head;                                       // q0 and shift: the sides' own
+        HIP_TRY(hipMemcpy(&head, h->d_hist[0], sizeof head, hipMemcpyDeviceToHost));
+        const size_t row_bytes = sizeof(s5gpu_pile_contrast_t) * (size_t)K;
+        HIP_TRY(hipMalloc(&d_cls, sizeof(uint32_t) * (size_t)R));
+        HIP_TRY(hipMalloc(&d_rows, row_bytes));
+        HIP_TRY(hipMemcpyAsync(d_cls, cls_host, sizeof(uint32_t) * (size_t)R, hipMemcpyHostToDevice, c->st));
+        for (int s = 0; s < 2; s++) {
+            HIP_TRY(hipMalloc(&d_acc[s], s5gpu_pileup_bytes(K)));
+            HIP_TRY(hipMalloc(&d_hist[s], s5gpu_pile_hist_bytes(K)));
+            if ((r = pilek::launch_reset(d_acc[s], K, c->st))) return r;
+            if ((r = pilek::launch_hist_reset(d_hist[s], K, head.q0, head.shift, c->st))) return r;
+            if ((r = pilek::fold_checked(who, h->d_acc[s], R, (const uint32_t *)d_cls, K, d_acc[s], c->st))) return r;
+            if ((r = pilek::hist_fold_checked(who, h->d_hist[s], R, (const uint32_t *)d_cls, K, d_hist[s], c->st))) return r;
+        }
+        if ((r = pilek::launch_contrast(d_hist[0], d_hist[1], d_acc[0], d_acc[1], K, (s5gpu_pile_contrast_t *)d_rows, c->st))) return r;
+        HIP_TRY(hipMemcpyAsync(rows_out, d_rows, row_bytes, hipMemcpyDeviceToHost, c->st));
+        if (acc_a_out) HIP_TRY(hipMemcpyAsync(acc_a_out, d_acc[0], s5gpu_pileup_bytes(K), hipMemcpyDeviceToHost, c->st));
+        if (acc_b_out) HIP_TRY(hipMemcpyAsync(acc_b_out, d_acc[1], s5gpu_pileup_bytes(K), hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        return S5GPU_OK;
+    };
+    const int rc = fetch();
+    for (void *p : {d_cls, d_rows, d_acc[0], d_acc[1], d_hist[0], d_hist[1]})
+        if (p) (void)hipFree(p);
+    free_handle(h);                                                        // whatever the fold did: the handle ends here
     return rc;
 }

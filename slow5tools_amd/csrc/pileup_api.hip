@@ -6,6 +6,7 @@
 // and adds the ragged paths it leaves on the device.  The checks of a ragged call and that add are shared with contrast_api.hip and
 // sites_api.hip (pileup_host.h), which feed a level histogram (§4.23) and the site matrix (§4.25) from the same run.
 #include "pileup_host.h"
+#include "fold_dev.h"
 
 namespace {
 
@@ -105,6 +106,37 @@ extern "C" int s5gpu_pileup_close(void *handle, void *acc_out) {
     if (!h) return S5GPU_OK;
     // (straight into the caller's buffer: a table may be gigabytes, too much for the pinned staging buffer)
     const int rc = s5host::acc_close(h->d_acc, s5gpu_pileup_bytes((uint32_t)h->c.ref.size()), acc_out, true);
+    delete h;
+    return rc;
+}
+
+// §4.26: the table folded onto K classes on the device, and only the K columns downloaded
+extern "C" int s5gpu_pileup_close_folded(void *handle, const uint32_t *cls_host, uint32_t K, void *acc_out) {
+    const char *who = "s5gpu_pileup_close_folded";
+    Handle *h = (Handle *)handle;
+    if (!h) { s5gpu_set_error("%s: NULL handle", who); return S5GPU_ERR_ARG; }
+    const uint32_t R = (uint32_t)h->c.ref.size();
+    void *d_cls = nullptr, *d_out = nullptr;
+    auto fetch = [&]() -> int {
+        if (!cls_host || !acc_out) { s5gpu_set_error("%s: NULL argument", who); return S5GPU_ERR_ARG; }
+        if (K == 0 || K > pilek::RMAX) { s5gpu_set_error("%s: %u classes (1 .. 2^26)", who, K); return S5GPU_ERR_ARG; }
+        s5host::CtxHold hold;
+        int r;
+        if ((r = hold.acquire(0))) return r;
+        Ctx *c = hold.c;
+        HIP_TRY(hipMalloc(&d_cls, sizeof(uint32_t) * (size_t)R));
+        HIP_TRY(hipMalloc(&d_out, s5gpu_pileup_bytes(K)));
+        HIP_TRY(hipMemcpyAsync(d_cls, cls_host, sizeof(uint32_t) * (size_t)R, hipMemcpyHostToDevice, c->st));
+        if ((r = pilek::launch_reset(d_out, K, c->st))) return r;
+        if ((r = pilek::fold_checked(who, h->d_acc, R, (const uint32_t *)d_cls, K, d_out, c->st))) return r;
+        HIP_TRY(hipMemcpyAsync(acc_out, d_out, s5gpu_pileup_bytes(K), hipMemcpyDeviceToHost, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        return S5GPU_OK;
+    };
+    const int rc = fetch();
+    if (d_cls) (void)hipFree(d_cls);
+    if (d_out) (void)hipFree(d_out);
+    if (h->d_acc) (void)hipFree(h->d_acc);                                 // whatever the fold did: the handle ends here
     delete h;
     return rc;
 }

@@ -20,6 +20,8 @@ typedef struct refseq {
     uint64_t *len;
     uint32_t *Lk;
     s5gpu_refseq_segment_t *seg;
+    uint32_t *cls;                                                         /* [R]: the rank of each column's k-mer, or S5GPU_FOLD_NONE (§4.26) */
+    double mu, sd, scale;                                                  /* the quantiser's: over all segments' levels together */
 } refseq_t;
 
 /* A, C, G, T (U) = 0 .. 3 without case; anything else -1 */
@@ -112,11 +114,26 @@ static void levels_of(const int8_t *codes, size_t L, const float *model, uint32_
     }
 }
 
+/* ... and their ranks: the rank levels_of took the level of, S5GPU_FOLD_NONE where it took the mean */
+static void classes_of(const int8_t *codes, size_t L, uint32_t k, uint32_t *out) {
+    const size_t maskk = ((size_t)1 << (2 * k)) - 1;
+    size_t rank = 0;
+    long long last_bad = -1;
+    for (size_t p = 0; p < L; p++) {
+        if (codes[p] < 0) last_bad = (long long)p;
+        rank = ((rank << 2) | (size_t)(codes[p] < 0 ? 0 : codes[p])) & maskk;
+        if (p + 1 >= k) {
+            const size_t s = p + 1 - k;
+            out[s] = last_bad >= (long long)s ? S5GPU_FOLD_NONE : (uint32_t)rank;
+        }
+    }
+}
+
 static void refseq_free(refseq_t *h) {
     if (!h) return;
     if (h->names)
         for (uint32_t i = 0; i < h->n_contigs; i++) free(h->names[i]);
-    free(h->names); free(h->len); free(h->Lk); free(h->seg); free(h->ref); free(h);
+    free(h->names); free(h->len); free(h->Lk); free(h->seg); free(h->ref); free(h->cls); free(h);
 }
 
 void *s5gpu_refseq_build(uint32_t n_contigs, const char *const *names, const char *const *seqs, const size_t *lens, const float *model, uint32_t k,
@@ -141,6 +158,7 @@ void *s5gpu_refseq_build(uint32_t n_contigs, const char *const *names, const cha
     float *lev = NULL;
     int8_t *codes = NULL;
     int16_t *q = NULL;
+    uint32_t *cls = NULL;
     if (!h->names || !h->len || !h->Lk || !h->seg) goto nomem;
     uint64_t total = 0, longest = 0;
     for (uint32_t i = 0; i < n_contigs; i++) {
@@ -163,7 +181,8 @@ void *s5gpu_refseq_build(uint32_t n_contigs, const char *const *names, const cha
     lev = (float *)malloc(sizeof(float) * total);
     codes = (int8_t *)malloc(longest);
     q = (int16_t *)malloc(sizeof(int16_t) * total);
-    if (!lev || !codes || !q) goto nomem;
+    cls = (uint32_t *)malloc(sizeof(uint32_t) * total);
+    if (!lev || !codes || !q || !cls) goto nomem;
     uint64_t at = 0;
     for (uint32_t i = 0; i < n_contigs; i++) {
         const uint32_t Lk = h->Lk[i];
@@ -171,38 +190,47 @@ void *s5gpu_refseq_build(uint32_t n_contigs, const char *const *names, const cha
         if (!Lk) continue;
         for (size_t p = 0; p < L; p++) codes[p] = (int8_t)base_code(seqs[i][p]);
         levels_of(codes, L, model, k, mean, lev + at);
+        classes_of(codes, L, k, cls + at);
         if (rna)
-            for (uint32_t a = 0, b = Lk - 1; a < b; a++, b--) { const float t = lev[at + a]; lev[at + a] = lev[at + b]; lev[at + b] = t; }
+            for (uint32_t a = 0, b = Lk - 1; a < b; a++, b--) {
+                const float t = lev[at + a]; lev[at + a] = lev[at + b]; lev[at + b] = t;
+                const uint32_t u = cls[at + a]; cls[at + a] = cls[at + b]; cls[at + b] = u;
+            }
         s5gpu_refseq_segment_t *s = &h->seg[h->n_seg++];
         s->contig = i; s->strand = '+'; s->Lk = Lk; s->reversed = rna ? 1 : 0; s->name = h->names[i];
         at += Lk;
         if (per == 2) {
             for (size_t p = 0; p < L; p++) { const int c = base_code(seqs[i][L - 1 - p]); codes[p] = (int8_t)(c < 0 ? -1 : 3 - c); }
             levels_of(codes, L, model, k, mean, lev + at);
+            classes_of(codes, L, k, cls + at);
             s = &h->seg[h->n_seg++];
             s->contig = i; s->strand = '-'; s->Lk = Lk; s->reversed = 1; s->name = h->names[i];
             at += Lk;
         }
     }
     if (s5gpu_quantise_host(lev, (size_t)total, scale, clip, q) != S5GPU_OK) goto fail;
+    if (s5gpu_quant_stats_host(lev, (size_t)total, &h->mu, &h->sd) != S5GPU_OK) goto fail;
+    h->scale = scale;
     h->R = (uint32_t)(total + (uint64_t)W * (h->n_seg - 1));
     h->ref = (int16_t *)malloc(sizeof(int16_t) * h->R);
-    if (!h->ref) goto nomem;
+    h->cls = (uint32_t *)malloc(sizeof(uint32_t) * h->R);
+    if (!h->ref || !h->cls) goto nomem;
     uint32_t col = 0;
     at = 0;
     for (uint32_t s = 0; s < h->n_seg; s++) {
         if (s)
-            for (uint32_t w = 0; w < W; w++) h->ref[col++] = INT16_MIN;
+            for (uint32_t w = 0; w < W; w++) { h->cls[col] = S5GPU_FOLD_NONE; h->ref[col++] = INT16_MIN; }
         h->seg[s].offset = col;
         memcpy(h->ref + col, q + at, sizeof(int16_t) * h->seg[s].Lk);
+        memcpy(h->cls + col, cls + at, sizeof(uint32_t) * h->seg[s].Lk);
         col += h->seg[s].Lk; at += h->seg[s].Lk;
     }
-    free(lev); free(codes); free(q);
+    free(lev); free(codes); free(q); free(cls);
     return h;
 nomem:
     s5gpu_set_error("%s: out of memory", who);
 fail:
-    free(lev); free(codes); free(q);
+    free(lev); free(codes); free(q); free(cls);
     refseq_free(h);
     return NULL;
 }
@@ -310,6 +338,23 @@ int s5gpu_refseq_locate(const void *hv, uint32_t col, s5gpu_refseq_loc_t *loc) {
     if (p >= s->Lk) { loc->contig = 0xFFFFFFFFu; loc->strand = 0; loc->pos = 0; return S5GPU_REFSEQ_WALL; }
     loc->contig = s->contig; loc->strand = s->strand;
     loc->pos = s->reversed ? s->Lk - 1 - p : p;
+    return S5GPU_OK;
+}
+
+int s5gpu_refseq_classes(const void *hv, uint32_t *cls_out, uint32_t *K_out) {
+    const refseq_t *h = (const refseq_t *)hv;
+    if (!h) { s5gpu_set_error("s5gpu_refseq_classes: NULL handle"); return S5GPU_ERR_ARG; }
+    if (cls_out) memcpy(cls_out, h->cls, sizeof(uint32_t) * h->R);
+    if (K_out) *K_out = 1u << (2 * h->k);
+    return S5GPU_OK;
+}
+
+int s5gpu_refseq_quant(const void *hv, double *mu_out, double *sd_out, double *scale_out) {
+    const refseq_t *h = (const refseq_t *)hv;
+    if (!h) { s5gpu_set_error("s5gpu_refseq_quant: NULL handle"); return S5GPU_ERR_ARG; }
+    if (mu_out) *mu_out = h->mu;
+    if (sd_out) *sd_out = h->sd;
+    if (scale_out) *scale_out = h->scale;
     return S5GPU_OK;
 }
 

@@ -213,6 +213,8 @@ class RefSeq:
       .segments   a list of (contig, name, strand, offset, Lk), strand '+' or '-'
       .contigs    a list of (name, bases, Lk); Lk = 0: shorter than k, no segment
       .k, .wall, .clip
+      .classes()  the k-mer rank of every column, and 4^k: what model.fold_dev and close_folded take (§4.26)
+      .quant      (mu, sd, scale): the way back from a quantised level to the model's units
     """
 
     def __init__(self, fasta=None, model=None, contigs=None, levels=None, strands=2, rna=False, scale=SCALE, clip=CLIP):
@@ -263,6 +265,20 @@ class RefSeq:
                 check(rc, "s5gpu_refseq_locate")
                 out.append((loc.contig, chr(loc.strand), loc.pos))
         return out
+
+    def classes(self):
+        """(cls, K): a uint32 class per column of .ref, the base-4 rank of the k-mer the column shows (the rank whose level it took), and
+        K = 4^k; 0xFFFFFFFF for a wall column and for a k-mer that holds a letter other than ACGT (s5gpu_refseq_classes, §4.26)"""
+        cls, K = np.zeros(len(self.ref), dtype=np.uint32), C.c_uint32()
+        check(_lib.lib().s5gpu_refseq_classes(self._h, cls.ctypes.data_as(C.c_void_p), C.byref(K)), "s5gpu_refseq_classes")
+        return cls, K.value
+
+    @property
+    def quant(self):
+        """(mu, sd, scale) of the quantiser over all segments' levels: a quantised level q stands for mu + (sd / scale) q"""
+        mu, sd, sc = C.c_double(), C.c_double(), C.c_double()
+        check(_lib.lib().s5gpu_refseq_quant(self._h, C.byref(mu), C.byref(sd), C.byref(sc)), "s5gpu_refseq_quant")
+        return mu.value, sd.value, sc.value
 
     def spans(self, rows):
         """the (start, end) of MAP_ROW rows -> a list of (contig, strand, pos_lo, pos_hi), pos_lo <= pos_hi the first and last k-mer start on

@@ -19,6 +19,8 @@ Whole reads (§4.22): the same table from all of a read's events, over the ragge
   pileup_whole_dev : a DecodedDev -> extend.extend_dev(host=False), then accum_long_dev
   PileupWhole      : records -> a per-file handle (s5gpu_pileup_add_batch_whole)
   file_pileup(whole=True) : s5pileup --whole
+
+Folded (§4.26, model.py): Pileup.close_folded and PileupWhole.close_folded fold the table onto classes on the device before the download.
 """
 import ctypes as C
 import os
@@ -222,6 +224,20 @@ class Pileup:
         out = np.zeros(acc_bytes(self.R), dtype=np.uint8)
         h, self._h = self._h, None
         check(_lib.lib().s5gpu_pileup_close(h, out.ctypes.data_as(C.c_void_p)), "s5gpu_pileup_close")
+        return from_bytes(out)
+
+    def close_folded(self, cls, K):
+        """close(), with the table folded onto K classes on the device first (s5gpu_pileup_close_folded, §4.26): cls a uint32 class per
+        reference column (RefSeq.classes()); -> (total, cols) of K columns.  The handle ends whatever happens."""
+        if self._h is None:
+            raise _lib.S5GpuError("pileup handle: already closed")
+        c = np.ascontiguousarray(cls, dtype=np.uint32)
+        h, self._h = self._h, None
+        if c.shape != (self.R,) or acc_bytes(K) == 0:
+            _lib.lib().s5gpu_pileup_close(h, None)
+            raise ValueError("close_folded: cls holds a class per column (%d), K is 1 .. 2^26" % self.R)
+        out = np.zeros(acc_bytes(K), dtype=np.uint8)
+        check(_lib.lib().s5gpu_pileup_close_folded(h, c.ctypes.data_as(C.c_void_p), int(K), out.ctypes.data_as(C.c_void_p)), "s5gpu_pileup_close_folded")
         return from_bytes(out)
 
     def abandon(self):
