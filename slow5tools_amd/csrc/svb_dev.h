@@ -38,7 +38,8 @@ __device__ __forceinline__ void svb_tile_classify(const int16_t *__restrict__ si
     // (and the one in front of each lane) lies in [-16384, 16384), every delta fits 16 bits and so does its zig-zag value: the packed 16-bit
     // forms of subtract / shift / min do two samples each, the key bits come out of two accumulators, the byte count is a population count (a
     // value takes one byte or two).  Lanes without samples ride along on zeros.  Anything else — a sample outside that range, a lane with 1 .. 15
-    // samples — sends the whole wave down the general path below: same results, bit for bit (tests/test_gpu_parity.py, tests/test_full_size.py).
+    // samples — sends the whole wave down the general path below: same results, bit for bit (tests/test_gpu_parity.py, tests/test_full_size.py; tests/test_signal_encode_craft.py
+    // holds both paths to blobs written field by field, one sample outside the range at the seams of a wave).
     {
         typedef unsigned short us2 __attribute__((ext_vector_type(2)));
         typedef short ss2 __attribute__((ext_vector_type(2)));

@@ -27,154 +27,12 @@ import pytest
 
 import oracle_bind as ob
 import test_svbzd_decode as sv
+from signal_craft import M32, WIDTH_END, WIDTH_LO, _balance, _decode, _gaps, _min_codes, _svb32_read, exzd_blob, fields, svb32   # noqa: F401  (the builders: tests/signal_craft.py)
+from signal_craft import exzd_ref_decode as ref_decode
 from test_svbzd_decode import RUN_AUX, SENT, _aux, _interleave, _np_cap, _opt, press   # noqa: F401  (press: the fixture)
 
 HDR_ARGS = sv.HDR_ARGS
 SIG_EX_ZD = 2
-WIDTH_LO = (0, 1 << 8, 1 << 16, 1 << 24)
-WIDTH_END = (1 << 8, 1 << 16, 1 << 24, 1 << 32)
-M32 = 0xFFFFFFFF
-
-
-# ---------------------------------------------------------------- blob builder and reference (no GPU, no encoder)
-
-def _min_codes(v):
-    v = np.asarray(v, dtype=np.uint64)
-    return ((v > 0xFF).astype(np.uint8) + (v > 0xFFFF) + (v > 0xFFFFFF)).astype(np.uint8)
-
-
-def svb32(vals, codes=None):
-    """ceil(len/4) key bytes (2 bits per value, LSB first) | code + 1 little-endian bytes of each value, as given: a value must
-    fit its width, a wider width than needed is allowed"""
-    vals = np.asarray(vals, dtype=np.uint64)
-    codes = _min_codes(vals) if codes is None else np.asarray(codes, dtype=np.uint8)
-    assert codes.shape == vals.shape and (codes <= 3).all()
-    assert (vals < np.array(WIDTH_END, dtype=np.uint64)[codes]).all()
-    n = len(vals)
-    padded = np.zeros(4 * ((n + 3) // 4), dtype=np.uint8)
-    padded[:n] = codes
-    keys = padded[0::4] | (padded[1::4] << 2) | (padded[2::4] << 4) | (padded[3::4] << 6)
-    vb = vals.astype("<u4").view(np.uint8).reshape(-1, 4)
-    data = vb[np.arange(4)[None, :] <= codes[:, None]]
-    return keys.astype(np.uint8).tobytes() + data.tobytes()
-
-
-def exzd_blob(N, q, z0, gaps, vals, rest, gap_codes=None, val_codes=None, nex=None, slack=(b"", b""), version=0):
-    """docs/codecs.md §4.4, written as given: u8 version | u64 N | u8 q | (nothing more for N == 0 without lists and rest) u16 z0 |
-    u32 nex | [u32 len | svb32(gaps) + slack[0] | u32 len | svb32(vals) + slack[1]] when there are lists | rest.
-    gaps = first position, then gap - 1; vals = z - 256.  nex overrides the count field; slack sits behind a section's data,
-    inside its length."""
-    out = struct.pack("<BQB", version, N, q)
-    rest = bytes(rest)
-    if N == 0 and not len(gaps) and not len(vals) and not rest and nex is None:
-        return out
-    out += struct.pack("<HI", z0, len(gaps) if nex is None else nex)
-    if len(gaps) or len(vals):
-        for lst, codes, sl in ((gaps, gap_codes, slack[0]), (vals, val_codes, slack[1])):
-            sec = svb32(lst, codes) + bytes(sl)
-            out += struct.pack("<I", len(sec)) + sec
-    return out + rest
-
-
-def _svb32_read(sec, n):
-    """the n values of a section that must be consumed exactly, or None"""
-    nk = (n + 3) // 4
-    if nk > len(sec):
-        return None
-    keys = np.frombuffer(sec[:nk], dtype=np.uint8)
-    codes = ((keys[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:n].astype(np.int64)
-    end = np.cumsum(codes + 1)
-    if nk + int(end[-1]) != len(sec):
-        return None
-    data = np.frombuffer(sec[nk:], dtype=np.uint8)
-    start = end - (codes + 1)
-    v = np.zeros(n, dtype=np.int64)
-    for k in range(4):
-        m = codes >= k
-        v[m] |= data[start[m] + k].astype(np.int64) << (8 * k)
-    return v
-
-
-def _decode(blob):
-    """(int16 samples, largest |y|) of a well-formed blob, None for a malformed one"""
-    b = bytes(blob)
-    L = len(b)
-    if L < 10 or b[0] != 0:
-        return None
-    N, q = struct.unpack_from("<QB", b, 1)
-    if N == 0:
-        return (np.zeros(0, np.int16), 0) if L == 10 else None
-    if q > 15 or L < 16 or N > 0xFFFFFFF0:
-        return None
-    z0, nex = struct.unpack_from("<HI", b, 10)
-    if nex > N - 1:
-        return None
-    p = 16
-    lists = []
-    if nex:
-        for _ in range(2):
-            if p + 4 > L:
-                return None
-            sl = struct.unpack_from("<I", b, p)[0]
-            p += 4
-            if sl > L - p:
-                return None
-            v = _svb32_read(b[p:p + sl], nex)
-            if v is None:
-                return None
-            lists.append(v)
-            p += sl
-    if L - p != N - 1 - nex:       # from here on N - 1 <= L - 16: nothing below is sized by an impossible count
-        return None
-    np_ = N - 1
-    z = np.zeros(np_, dtype=np.int64)
-    plain = np.ones(np_, dtype=bool)
-    if nex:
-        pos = -1
-        where = []
-        for g in lists[0].tolist():          # Python integers: no wrap
-            pos += 1 + g
-            if pos >= np_:
-                return None
-            where.append(pos)
-        where = np.array(where, dtype=np.int64)
-        plain[where] = False
-        z[where] = (lists[1] + 256) & M32
-    z[plain] = np.frombuffer(b[p:], dtype=np.uint8)
-    d = (z >> 1) ^ -(z & 1)
-    y0 = (z0 >> 1) ^ -(z0 & 1)
-    y = np.concatenate([[y0], y0 + np.cumsum(d)]).astype(np.int64)
-    return ((y << q) & 0xFFFF).astype(np.uint16).view(np.int16), int(np.abs(y).max())
-
-
-def ref_decode(blob):
-    """int16 samples of a well-formed blob, None for a malformed one: every section consumed exactly, positions summed in Python
-    integers and below N - 1, z = val + 256 modulo 2^32, output (y << q) & 0xFFFF"""
-    r = _decode(blob)
-    return None if r is None else r[0]
-
-
-def fields(x, q=None):
-    """(N, q, z0, gaps, vals, rest) of a signal; q = None: the encoders' choice, the trailing zero bits common to all samples"""
-    x = np.asarray(x, dtype=np.int16)
-    n = len(x)
-    if q is None:
-        acc = int(np.bitwise_or.reduce(x.view(np.uint16))) if n else 0
-        q = (acc & -acc).bit_length() - 1 if acc else 0
-    if n == 0:
-        return 0, q, 0, [], [], b""
-    y = x.astype(np.int64) >> q
-    d = np.diff(y)
-    z = ((d << 1) ^ (d >> 63)) & M32
-    ex = np.flatnonzero(z > 255)
-    gaps = np.diff(np.concatenate([[-1], ex])) - 1
-    z0 = int((y[0] << 1) ^ (y[0] >> 63)) & 0xFFFF
-    return n, q, z0, gaps, z[ex] - 256, z[z <= 255].astype(np.uint8).tobytes()
-
-
-def _gaps(pos):
-    pos = np.asarray(pos, dtype=np.int64)
-    return np.diff(np.concatenate([[-1], pos])) - 1
 
 
 def _full_width(rng, codes, top=1 << 31):
@@ -183,18 +41,6 @@ def _full_width(rng, codes, top=1 << 31):
     lo = np.array(WIDTH_LO, dtype=np.float64)[codes]
     hi = np.minimum(np.array(WIDTH_END, dtype=np.float64)[codes], top)
     return np.minimum(lo + np.floor(rng.random(len(codes)) * (hi - lo)), hi - 1).astype(np.uint64)
-
-
-def _balance(vals):
-    """set the low bit of every val (the sign of its delta: val and z = val + 256 have the same parity) against the running sum
-    of the exceptions' deltas, so that |y| stays far below 2^31 (the oracle accumulates in int32)"""
-    out, run = [], 0
-    for v in np.asarray(vals, dtype=np.uint64).tolist():
-        v = (v & ~1) | (1 if run > 0 else 0)
-        z = (v + 256) & M32
-        run += (z >> 1) ^ -(z & 1)
-        out.append(v)
-    return np.array(out, dtype=np.uint64)
 
 
 def _vals(rng, k):

@@ -22,61 +22,10 @@ import pytest
 
 import oracle_bind as ob
 from deflate_craft import Bits
+from signal_craft import WIDTH_END, WIDTH_LO, _interleave, svb_blob   # noqa: F401  (the builders: tests/signal_craft.py)
+from signal_craft import svb_full_width as _full_width, svb_ref_decode as ref_decode
 
 HDR_ARGS = (8192.0, 23.0, 1467.61, 4000.0)
-WIDTH_LO = np.array([0, 1 << 8, 1 << 16, 1 << 24], dtype=np.uint64)      # smallest z that needs code + 1 bytes
-WIDTH_END = np.array([1 << 8, 1 << 16, 1 << 24, 1 << 32], dtype=np.uint64)
-
-
-# ---------------------------------------------------------------- blob builder and reference (no GPU, no encoder)
-
-def svb_blob(codes, zs, count=None, tail=b""):
-    """u32 count | ceil(len/4) key bytes (2 bits per value, LSB first) | code + 1 little-endian bytes of each z.  The pairs
-    (codes[i], zs[i]) are written as given: z must fit its width, a wider width than needed is allowed.  count overrides the
-    count field (malformed blobs); tail is appended behind the data."""
-    codes = np.asarray(codes, dtype=np.uint8)
-    zs = np.asarray(zs, dtype=np.uint64)
-    assert codes.shape == zs.shape and (codes <= 3).all()
-    assert (zs < WIDTH_END[codes]).all()
-    n = len(codes)
-    padded = np.zeros(4 * ((n + 3) // 4), dtype=np.uint8)
-    padded[:n] = codes
-    keys = padded[0::4] | (padded[1::4] << 2) | (padded[2::4] << 4) | (padded[3::4] << 6)
-    zb = zs.astype("<u4").view(np.uint8).reshape(-1, 4)
-    data = zb[np.arange(4)[None, :] <= codes[:, None]]
-    return struct.pack("<I", n if count is None else count) + keys.astype(np.uint8).tobytes() + data.tobytes() + bytes(tail)
-
-
-def ref_decode(blob):
-    """int16 samples of a well-formed blob, None for a malformed one (count, keys and data bytes must add up to the length)"""
-    b = np.frombuffer(bytes(blob), dtype=np.uint8)
-    if len(b) < 4:
-        return None
-    n = int.from_bytes(bytes(b[:4]), "little")
-    nk = (n + 3) // 4
-    if 4 + nk > len(b):
-        return None
-    codes = ((b[4:4 + nk, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:n].astype(np.int64)
-    end = np.cumsum(codes + 1)
-    if 4 + nk + (int(end[-1]) if n else 0) != len(b):
-        return None
-    data = b[4 + nk:]
-    start = end - (codes + 1)
-    z = np.zeros(n, dtype=np.int64)
-    for k in range(4):
-        m = codes >= k
-        z[m] |= data[start[m] + k].astype(np.int64) << (8 * k)
-    d = (z >> 1) ^ -(z & 1)
-    return (np.cumsum(d) & 0xFFFF).astype(np.uint16).view(np.int16)
-
-
-def _full_width(rng, codes):
-    """a z for every code that needs all of its bytes (any byte for code 0)"""
-    codes = np.asarray(codes, dtype=np.int64)
-    lo = WIDTH_LO[codes].astype(np.float64)
-    hi = WIDTH_END[codes].astype(np.float64)
-    return np.minimum(lo + np.floor(rng.random(len(codes)) * (hi - lo)), hi - 1).astype(np.uint64)
-
 
 def _small(rng, n, code3_at=()):
     """mostly one-byte deltas, a few two-byte ones; code-3 values at the given positions"""
@@ -158,14 +107,6 @@ def _guards(k):
     """valid, short blobs that sit between the corpus entries of a batch"""
     rng = np.random.default_rng(0x6A5D + k)
     return [svb_blob(*_small(rng, int(rng.integers(200, 900)))) for _ in range(k)]
-
-
-def _interleave(items, guards):
-    """guard, item, guard, item, ..., guard: every item has valid neighbours on both sides"""
-    out = [guards[0]]
-    for it, g in zip(items, guards[1:]):
-        out += [it, g]
-    return out
 
 
 # ---------------------------------------------------------------- CPU: the reference against the oracle
